@@ -26,6 +26,9 @@ multi-party call, no collective on the data path), weak scaling.
 
 The parts live in tools/benchkit/: workloads.py (the named workloads, algorithmic bytes), host.py (ranks, CPU budget,
 cpu_baseline), stream.py (the timed legs), tilesplit_bench.py (configs[4]), report.py (the roofline object).
+
+--dump-outputs DIR: after the timed steps, what the headline leg computed in its last step goes to DIR/<name>.npy (float32 / float64, 64 MB
+at most; stream.py step_outputs names them).  The synthetic clip is seeded, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import ctypes as C
@@ -92,7 +95,11 @@ def parse_args():
     ap.add_argument("--gpu-entropy", action="store_true", help="gpu-entropy=1: the arithmetic coder on the GPU (k_cabac_rows) instead of the host pool")
     ap.add_argument("--sao", action="store_true", help="kvazaar sao=full (off at the ultrafast preset the headline workload uses)")
     ap.add_argument("--owf", type=int, default=6, help="uvgComm setting video/OWF (kvazaar owf): pictures in flight in the encoder")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the headline leg's last timed step to DIR/<name>.npy (rank 0's stream)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.host_io or a.workload == "8k-tilesplit"):
+        ap.error("--dump-outputs: the resident path of a one-stream workload only (no --host-io, no 8k-tilesplit)")
     if a.no_host_boundary or a.host_io:
         a.no_latency = a.no_bounds = True
     return a
@@ -268,6 +275,13 @@ def valu_roofline(args, m):
             "peak": round(peak / 1e12, 2), "unit": "T sample-differences/s", "frac": round(sads / me_s / peak, 4)}
 
 
+def write_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.cpu_worker:
@@ -287,11 +301,14 @@ def main():
     headline_1080p = single and args.workload == "1080p" and not args.no_secondary
 
     # ---- the headline leg
+    dump = {} if args.dump_outputs and rank == 0 else None
     if args.host_io:
         args.no_host_boundary = True
         m = run_stream(args, wl, args.steps, args.warmup, ranks, rank, world, quality=False, host_io=True, extra_custom=HOST_CUSTOM)
     else:
-        m = run_stream(args, wl, args.steps, args.warmup, ranks, rank, world, quality=(rank == 0), extra_custom=RESIDENT)
+        m = run_stream(args, wl, args.steps, args.warmup, ranks, rank, world, quality=(rank == 0), extra_custom=RESIDENT, dump=dump)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     npic = args.steps * PERIOD
     fps = world * npic / m["elapsed"]
 

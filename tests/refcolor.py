@@ -1,4 +1,4 @@
-"""ctypes access to the reference's own yuvconversions.cpp, compiled from where it lies by __graft_entry__.build()
+"""ctypes access to the reference's own yuvconversions.cpp, compiled from where it lies by __graft_entry__.build() (oracle/reference.py)
 into oracle/_ref/libyuvconversions_ref.so (never copied into the repo), plus a numpy restatement of the two
 arithmetics it contains (src/media/processing/yuvconversions.cpp:72-420 SIMD converters, :423-493 scalar fallback).
 Test infrastructure only."""

@@ -19,7 +19,7 @@ def test_numpy_restatement_matches_the_golden_vectors(case):
     assert np.array_equal(refcolor.restatement(variant, GOLD[case + "_in"], w, h), GOLD[case + "_out"])
 
 
-@pytest.mark.skipif(not refcolor.available(), reason="oracle/_ref not built (needs /root/reference at build time)")
+@pytest.mark.skipif(not refcolor.available(), reason="oracle/_ref not built (needs the reference tree at build time)")
 def test_reference_object_code_matches_the_golden_vectors_and_its_simd_variants_agree():
     for case in CASES:
         w, h = (int(x) for x in GOLD[case + "_dims"])
@@ -45,7 +45,7 @@ def test_rgb2yuv_numpy_restatement_matches_the_golden_vectors(case):
     assert np.array_equal(refcolor.restatement_rgb2yuv("sse41" if case.startswith("sse41") else "c", GOLD2[case + "_in"], w, h), GOLD2[case + "_out"])
 
 
-@pytest.mark.skipif(not refcolor.available(), reason="oracle/_ref not built (needs /root/reference at build time)")
+@pytest.mark.skipif(not refcolor.available(), reason="oracle/_ref not built (needs the reference tree at build time)")
 def test_rgb2yuv_reference_object_code_matches_the_golden_vectors():
     for case in CASES2:
         w, h = (int(x) for x in GOLD2[case + "_dims"])

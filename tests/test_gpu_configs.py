@@ -2,7 +2,7 @@
   configs[0]  1080p all-intra (period = 1), 30 pictures through the filter pipeline
   configs[1]  plain 1080p / period 64 / QP 32 against the checker, and a 130-picture run (two IDRs, POC wrap at 256 is in test_long_run)
   configs[3]  several independent streams at once (two pipelines on the one GPU of the test box)
-  configs[4]  7680x4320 with 8 tile rows in band mode against the checker; 8 ranks sharing the GPU with the halo exchange
+  configs[4]  7680x4320 with 8 tile rows in band mode against the checker; 4 ranks sharing the GPU with the halo exchange
 plus the pipelined encoder (owf 3) with SAO on the device path (the ordering the source-set events protect)."""
 import os
 import subprocess
@@ -229,10 +229,12 @@ def test_config4_8k_eight_tile_rows_band_mode(gpu):
 
 
 @pytest.mark.gpu
-def test_config4_eight_ranks_share_the_gpu(gpu):
-    """8 ranks (gloo, all on the test box's one GPU), one tile row each, with the halo exchange: 1920x1088, tiles 1x8"""
+def test_config4_four_ranks_share_the_gpu(gpu):
+    """4 ranks (gloo, all on the test box's one GPU), two tile rows each, with the halo exchange: 1920x1088, tiles 1x8.  Two of the ranks
+    exchange halos on both sides.  (Four, not eight: with this test process the GPU is then open in five processes, the most a shared
+    test box allows is six.)"""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="1")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", "29871", os.path.join(ROOT, "tests", "run_tilesplit.py"), "1920", "1088", "8", "4"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])

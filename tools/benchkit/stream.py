@@ -15,7 +15,8 @@ from .workloads import PERIOD, CLIP_FRAMES, DeviceClip, algorithmic_bytes, strea
 from .host import cpu_budget, _throttled_us, _thread_cpu
 
 
-def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=False, extra_custom=(), extra_settings=None, kind=0, bare=False, repeats=None):
+def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=False, extra_custom=(), extra_settings=None, kind=0, bare=False, repeats=None,
+               dump=None):
     """K = steps intra periods of one stream through KvazaarFilter' -> WireAdapter -> OpenHEVCFilter' on this rank's GPU, timed
     args.repeats times (median of 3 runs); every repetition starts and ends on an empty, flushed pipeline.
     host_io: the reference's own boundary -- pictures enter as HOST I420 through kvz_api->encoder_encode(kvz_picture*) (the filter's
@@ -23,6 +24,7 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
     host memory (openhevcfilter.cpp:192-239): PCIe both ways inside the timed region.
     kind: the synthetic clip (0 moving objects, 1 flat, 2 noise -- SURVEY 8(d)'s bounds).  bare: NO custom parameter at all reaches the encoder (uvgComm's
     INI list "parameters" empty: the workload's search range and device are the defaults anyway) -- what an unmodified uvgComm.ini gets.
+    dump (a dict, resident input only): filled with the outputs of the last timed step (step_outputs).
     Returns a dict of measurements.  sync(value=None) = barrier / max over ranks."""
     from kvazzup_amd.pipeline import Pipeline
     import ctypes as C
@@ -61,8 +63,11 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
                         custom=(("me-range", args.me_range), ("gpu", dev_index)) + ((("sao", "full"),) if args.sao else ()) + ((("me-early-termination", "off"),) if args.full_search else ()) + ((("intra-satd", "0"),) if args.intra_sad else ()) + ((("gpu-entropy", "1"),) if args.gpu_entropy else ()) + ((("subme", str(args.subme)),) if args.subme else ()) + tuple(tuple(kv.split("=", 1)) for kv in args.custom) + tuple(extra_custom),
                         loopback=True, keep_outputs=keep)
 
-    # source -> KvazaarFilter -> WireAdapter -> OpenHEVCFilter -> sink, one thread per filter (csrc/filters.hip)
-    pl = make(False, host_io)
+    # source -> KvazaarFilter -> WireAdapter -> OpenHEVCFilter -> sink, one thread per filter (csrc/filters.hip).  With a dump the pipeline keeps
+    # what it hands out (the access units are copied for the sink either way; the decoded pictures are device pointers) until drain() below.
+    if dump is not None and host_io:
+        raise RuntimeError("outputs are dumped from the resident path only")
+    pl = make(dump is not None, host_io)
     lib = pl.lib
     enc_h, dec_h = pl.encoder_handle(), pl.decoder_handle()
     cw, ch = C.c_int(), C.c_int()
@@ -95,6 +100,18 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
             out[name] = (a[0] + ms[i], a[1] + n[i])
         return out
 
+    def drain():
+        """the access units (bytes, pts) the pipeline kept since the last call, in coding order; the decoded pictures it kept are dropped"""
+        aus = []
+        while True:
+            a = pl.pop_encoded()
+            if a is None:
+                break
+            aus.append(a)
+        while pl.pop_decoded() is not None:
+            pass
+        return aus
+
     run(max(1, warmup) * PERIOD if warmup > 0 else 8)         # warm-up: whole periods, so that the first timed picture is an IDR (8 pictures when --warmup 0: the pipeline must at least be built)
     if pl.pushed % PERIOD:
         run(PERIOD - pl.pushed % PERIOD)
@@ -109,6 +126,9 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
     _sampler = None
     if os.environ.get("CPU_SAMPLER_REGION"):                  # tools/cpu_sampler.c preloaded: sample the timed regions only
         _sampler = C.CDLL(None)
+    if dump is not None:
+        drain()                                                # (the warm-up's)
+    last_step = []
     reps = []
     for rep in range(max(1, repeats or args.repeats)):
         device_sync()                                          # the pipeline is empty: everything pushed so far has been decoded
@@ -130,6 +150,8 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
         ru1 = resource.getrusage(resource.RUSAGE_SELF)
         reps.append({"elapsed": sync(el), "throttled_ms": (_throttled_us() - thr0) / 1e3, "host_cores": (time.process_time() - cpu0) / el,
                      "minflt": (ru1.ru_minflt - ru0.ru_minflt) / (steps * PERIOD), "sys_share": (ru1.ru_stime - ru0.ru_stime) / max(1e-9, (ru1.ru_stime - ru0.ru_stime) + (ru1.ru_utime - ru0.ru_utime))})
+        if dump is not None:
+            last_step = drain()[-PERIOD:]
     if _thr0 is not None:                                       # KVAZZUP_BENCH_THREADS=1: CPU time per thread over the timed regions (stderr)
         _thr1 = _thread_cpu()
         tot = sum(r["elapsed"] for r in reps)
@@ -148,6 +170,8 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
     if st["decoded_pictures"] != pl.pushed or st["dropped"] or st["encoded_pictures"] - st0["encoded_pictures"] != nall:
         raise RuntimeError("pipeline lost pictures: %r" % (st,))
     pl.close()
+    if dump is not None:
+        dump.update(step_outputs(make(True, True), last_step, w, h))
 
     out = {"elapsed": elapsed, "pictures": npic, "cw": cw, "ch": ch, "kt": kt, "busy": busy, "bytes_per_picture": nbytes / nall, "D": D,
            "host_cores": host_cores, "budget": budget, "throttled_ms": throttled_ms, "psnr_y": None, "minflt": med["minflt"], "sys_share": med["sys_share"],
@@ -173,6 +197,56 @@ def run_stream(args, wl, steps, warmup, ranks, rank, world, quality, host_io=Fal
         out["psnr_y"] = round(sum(ps) / len(ps), 3)
     dclip.close()
     return out
+
+
+DUMP_BYTES = (64 << 20) - (1 << 16)      # what bench.py --dump-outputs writes at most: 64 MB, less room for the .npy headers
+
+
+def _fixed_sample(n, k, seed):
+    """k of the positions 0 .. n-1, ascending, the same in every run (seeded); all of them when k >= n"""
+    import numpy as np
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def step_outputs(q, aus, w, h):
+    """What a caller of the timed path received in its last step, as float arrays for bench.py --dump-outputs (DUMP_BYTES at most together):
+      access_units          the step's access units byte by byte, back to back (a fixed sample of 4 M bytes when they are longer)
+      access_unit_bytes     the length of each access unit
+      decoded_sample        [picture, k]: the decoded I420 samples at k fixed positions (decoded_sample_index) of every picture of the step
+      decoded_plane_sums    [picture, (Y, Cb, Cr)]: the sum over each whole decoded plane
+    The timed path leaves its decoded pictures in HBM, each valid for a few more decode calls only.  The pictures here come out of a fresh
+    receiving side (q: WireAdapter -> OpenHEVCFilter', the timed path's settings, pictures downloaded) fed the same access units."""
+    import numpy as np
+    try:
+        if len(aus) != PERIOD:
+            raise RuntimeError("dump: the last timed step handed out %d access units, not %d" % (len(aus), PERIOD))
+        for au, pts in aus:
+            if not q.push_encoded(au, pts):
+                raise RuntimeError("dump: the decoder did not take access unit %d" % pts)
+        q.push_encoded(None)
+        if not q.wait(PERIOD, 120000):
+            raise RuntimeError("dump: the decoder did not deliver %d pictures: %r" % (PERIOD, q.stats()))
+        au_max = 4 << 20
+        stream = np.frombuffer(b"".join(au for au, _ in aus), dtype=np.uint8)
+        au_samples = stream[_fixed_sample(stream.size, au_max, 1)].astype(np.float32)
+        n, y, c = w * h * 3 // 2, w * h, w * h // 4
+        k = min(n, (DUMP_BYTES - 4 * au_max - 4 * 8 * PERIOD) // (4 * PERIOD + 8))       # (positions by picture size alone, whatever the bits)
+        idx = _fixed_sample(n, k, 2)
+        sample = np.empty((PERIOD, k), dtype=np.float32)
+        sums = np.empty((PERIOD, 3), dtype=np.float64)
+        for t, (_, pts) in enumerate(aus):
+            d = q.pop_decoded()
+            if d is None or d["pts"] != pts or d["i420"].size != n:
+                raise RuntimeError("dump: decoded picture %d is missing or out of order" % t)
+            pic = d["i420"]
+            sample[t] = pic[idx]
+            sums[t] = [pic[:y].sum(dtype=np.int64), pic[y:y + c].sum(dtype=np.int64), pic[y + c:].sum(dtype=np.int64)]
+    finally:
+        q.close()
+    return {"access_units": au_samples, "access_unit_bytes": np.array([len(au) for au, _ in aus], dtype=np.float64),
+            "decoded_sample": sample, "decoded_sample_index": idx.astype(np.float64), "decoded_plane_sums": sums}
 
 
 def latency_run(args, wl, ranks, settings, custom, source_fps, npic, drop_tail):

@@ -91,6 +91,7 @@ class OrderedPool {
     gen_.fetch_add(1, std::memory_order_acq_rel); futex_wake_all(gen_);
     for (auto &t : workers_) t.join();
   }
+  int threads() const { return (int)workers_.size() + 1; }           // (the caller included)
   // Runs fn(0) .. fn(n - 1); returns when all have finished.
   void run(int n, const std::function<void(int)> &fn)
   {

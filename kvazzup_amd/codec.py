@@ -119,6 +119,9 @@ class Encoder:
         for k in ("cu_log2", "cu_intra", "cu_flags", "cu_merge_idx", "cu_mvp_idx", "cu_intra_mode", "cu_cbf"):
             d[k] = self.debug(k, np.uint8, b8)
         d["cu_mv"] = self.debug("cu_mv", np.int16, b8 + (2,))
+        # ref_idx_l0 per 8x8 block: an array of its own only with lp-refs >= 2, else every block refers to reference 0
+        d["cu_ref"] = np.zeros(b8, dtype=np.uint8)
+        self.lib.kvzx_encoder_debug_copy(self.enc, b"cu_ref", d["cu_ref"].ctypes.data, d["cu_ref"].nbytes)
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             d["coef%d" % c] = self.debug("coef%d" % c, np.int16, shp)

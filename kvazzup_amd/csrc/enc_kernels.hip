@@ -25,6 +25,7 @@
 //   k_tok_compact   restores coding order per CTU, dense copy to host-mapped memory for the host arithmetic coder
 // (the decoder's kernels live in dec_kernels.hip, the fractional-sample search in subpel_kernels.hip, rate control in rc_kernels.hip)
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "hevc_core.h"
 #include "enc_kernels.h"
 #include "kernel_common.h"
@@ -48,11 +49,18 @@ namespace kvzx {
 // to at most 65280), and each window row read from LDS serves both candidates of the pair.
 // (Measured on MI355X: v_qsad_pk_u16_u8 issues at ~24 cycles per wave, v_sad_u8 at ~4.7; the quad form
 // still wins because it needs no v_alignbyte to line the window up with the candidate.)
+// MR (lp-refs, f.nref references): the window of every reference in turn, and the minimum over (reference, candidate) pairs of the 64-bit key
+// cost << 16 | ref << 13 | candidate -- ties to the lower reference, then the lower candidate; cost includes ref_bins(ref).
+// One reference: the 32-bit key cost << 13 | candidate (the same order).
+template <bool MR>
 __global__ __launch_bounds__(256) void k_me(EncFrame f)
 {
+  using Key = typename std::conditional<MR, unsigned long long, uint32_t>::type;
+  constexpr int KS = MR ? 16 : 13;                                     // cost field's shift
+  constexpr Key KMAX = ~(Key)0;
   __shared__ __attribute__((aligned(16))) uint8_t win[(32 + 2 * ME_MAXR + 1) * ME_WPITCH + 16];
   __shared__ __attribute__((aligned(16))) uint32_t cur[32 * 8];
-  __shared__ uint32_t red[5];
+  __shared__ Key red[5];
   const int tid = threadIdx.x, nthreads = blockDim.x;
   int bx_, by_; xcd_block_2d(bx_, by_);
   const int x0 = bx_ * 32, y0 = by_ * 32 + f.row0 * 64;
@@ -72,7 +80,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
       cur[i] = c;
       if (f.me_early) s0 = __builtin_amdgcn_sad_u8(c, *reinterpret_cast<const uint32_t *>(ref + g), s0);
     }
-    if (f.me_early) { s0 = wave_sum_u32(s0); if ((tid & 63) == 0) atomicAdd(&red[0], s0); }
+    if (f.me_early) { s0 = wave_sum_u32(s0); if ((tid & 63) == 0) atomicAdd(&red[0], (Key)s0); }
   }
   __syncthreads();
   if (f.me_early && red[0] <= 64u * lam) {
@@ -80,15 +88,21 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
       const int i = b8idx(f, x0 + (tid & 3) * 8, y0 + (tid >> 2) * 8);
       f.cu_log2[i] = 5; f.cu_intra[i] = 0; f.cu_mv[i * 2] = 0; f.cu_mv[i * 2 + 1] = 0;
       f.cu_mvp_idx[i] = 0;                               // mark for k_subpel: not searched (k_inter_signal writes the real value later)
+      if (MR) f.cu_ref[i] = 0;                           // (the co-located block of reference 0)
     }
     if (f.intra_p && tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = 0;      // never an intra candidate
     return;
   }
-  __syncthreads();                                                     // (red[] is about to be re-initialised)
+  Key best[5] = {KMAX, KMAX, KMAX, KMAX, KMAX};
+  const int nr = MR ? f.nref : 1;
+#pragma unroll 1
+  for (int rf = 0; rf < nr; rf++) {                                    // (MR: one reference after the other through the same LDS window)
+  const uint8_t *refp = MR ? f.me_refs[rf] : ref;
+  __syncthreads();                                                     // (red[] is about to be re-initialised; MR: the previous reference's window is done with)
   for (int i = tid; i < (WW + 1) * (ME_WPITCH / 4); i += nthreads) {   // four window samples per thread; columns >= WW and row WW are padding
     const int wy = i / (ME_WPITCH / 4), wx = (i - wy * (ME_WPITCH / 4)) * 4;
     const int gy = clip3(0, f.ch - 1, y0 - R + wy), gx = x0 - R + wx;
-    const uint8_t *row = ref + (size_t)gy * f.cw;
+    const uint8_t *row = refp + (size_t)gy * f.cw;
     uint32_t v;
     if (gx >= 0 && gx + 7 < f.cw) {
       const uint32_t *q = (const uint32_t *)(row + (gx & ~3));
@@ -99,9 +113,9 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     }
     *(uint32_t *)&win[wy * ME_WPITCH + wx] = v;
   }
-  if (tid < 5) red[tid] = 0xffffffffu;
+  if (rf == 0 && tid < 5) red[tid] = KMAX;
   __syncthreads();
-  uint32_t best[5] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+  const uint32_t rbins = MR ? (uint32_t)ref_bins(rf, nr) : 0u;
   // tile constraint (statement: me_block32() in oracle/hevc_enc.c): the displaced 32x32 block, plus 4 rows each side for
   // the chroma half-sample taps when the displacement is odd, stays inside its tile -- except across the picture's own edges
   int ty0 = 0, ty1 = f.ch, tx0 = 0, tx1 = f.cw;
@@ -159,43 +173,46 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
         if (dxi >= W) continue;
         { const int dx = dxi - R, m = (dx & 1) ? 4 : 0; if ((tx0 > 0 && x0 + dx - m < tx0) || (tx1 < f.cw && x0 + dx + 32 + m > tx1)) continue; }
         if (f.mv_frame) { const int dx = dxi - R, mx = (f.mv_frame == 2 && (dx & 1)) ? 4 : 0; if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > f.cw) continue; }
-        const uint32_t cand = (uint32_t)(dyi * W + dxi);
-        const uint32_t rate = (lam * (uint32_t)(mvd_bits((dxi - R) * 4) + ry)) >> 4;
+        const Key cand = (Key)(dyi * W + dxi) | ((Key)rf << 13);
+        const uint32_t rate = (lam * (uint32_t)(mvd_bits((dxi - R) * 4) + ry + rbins)) >> 4;
         uint32_t sq[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) sq[k] = (uint32_t)(acc[e][k] >> (16 * k4)) & 0xffffu;
 #pragma unroll
-        for (int k = 0; k < 4; k++) best[k] = min(best[k], ((sq[k] + rate) << 13) | cand);
-        best[4] = min(best[4], ((sq[0] + sq[1] + sq[2] + sq[3] + rate) << 13) | cand);
+        for (int k = 0; k < 4; k++) best[k] = min(best[k], ((Key)(sq[k] + rate) << KS) | cand);
+        best[4] = min(best[4], ((Key)(sq[0] + sq[1] + sq[2] + sq[3] + rate) << KS) | cand);
       }
     }
   }
+  }
 #pragma unroll
   for (int k = 0; k < 5; k++) {
-    uint32_t v = best[k];
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    Key v = best[k];
+    if constexpr (MR) { for (int o = 32; o > 0; o >>= 1) v = min(v, (Key)__shfl_xor((unsigned long long)v, o)); }
+    else { for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o)); }
     if ((tid & 63) == 0) atomicMin(&red[k], v);
   }
   __syncthreads();
   if (tid < 16) {
     uint32_t pen = (lam * SPLIT_BITS) >> 4;
-    uint32_t csplit = pen + (red[0] >> 13) + (red[1] >> 13) + (red[2] >> 13) + (red[3] >> 13);
-    bool split = csplit < (red[4] >> 13);
+    uint32_t csplit = pen + (uint32_t)(red[0] >> KS) + (uint32_t)(red[1] >> KS) + (uint32_t)(red[2] >> KS) + (uint32_t)(red[3] >> KS);
+    bool split = csplit < (uint32_t)(red[4] >> KS);
     int bx = tid & 3, by = tid >> 2;                     // 8x8 block inside the 32x32 block
     int k = (by >> 1) * 2 + (bx >> 1);
-    uint32_t ci = (split ? red[k] : red[4]) & 0x1fff;
+    uint32_t ci = (uint32_t)(split ? red[k] : red[4]) & 0x1fff;
     int i = b8idx(f, x0 + bx * 8, y0 + by * 8);
     f.cu_log2[i] = split ? 4 : 5;
     f.cu_intra[i] = 0;
     f.cu_mvp_idx[i] = 1;                                 // mark for k_subpel: searched
+    if (MR) f.cu_ref[i] = (uint8_t)(((split ? red[k] : red[4]) >> 13) & 7);
     f.cu_mv[i * 2] = (int16_t)(((int)(ci % W) - R) * 4);
     f.cu_mv[i * 2 + 1] = (int16_t)(((int)(ci / W) - R) * 4);
     // intra-in-P: the inter cost of the block's 16x16 quarters -- what the search found for a quarter, or a quarter of the 32x32 block's cost
-    if (f.intra_p && tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = split ? red[tid] >> 13 : ((red[4] >> 13) + 2) >> 2;
+    if (f.intra_p && tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = split ? (uint32_t)(red[tid] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2;
     if (f.intra_p && tid == 0) {
       // ... and the block joins the list k_intra_analyse<P> works through when a quarter is above the gate (f.me_cand: count, then block indices)
       bool any = false;
-      for (int k = 0; k < 4; k++) any |= (split ? red[k] >> 13 : ((red[4] >> 13) + 2) >> 2) > (uint32_t)INTRA_P_GATE * lam;
+      for (int k = 0; k < 4; k++) any |= (split ? (uint32_t)(red[k] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2) > (uint32_t)INTRA_P_GATE * lam;
       if (any) f.me_cand[1 + atomicAdd(&f.me_cand[0], 1u)] = (uint32_t)((y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
     }
   }
@@ -253,6 +270,7 @@ struct InterLds {
   alignas(16) uint8_t win[2][4][11 * 12];  // chroma reference windows: plane x 8x8 sub-block, 11 x 11 samples each
   uint32_t nz[2];
   int mv[4][2];
+  uint8_t rf[4];                           // lp-refs: ref_idx of each quarter
   int intra_q[4];                          // intra-in-P: the 16x16 quarter is an intra unit
   int rc_qp, rc_last; uint32_t rc_part[4]; // rate control v2 inside the launch (k_inter_recon<.., RC>)
   alignas(16) int8_t M8[2][32 * 32];       // the 32-point matrix and its transpose as int8: MFMA B operands
@@ -547,6 +565,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
   if (tid < 4) {
     int bi = b8idx(f, x0 + (tid & 1) * 16, y0 + (tid >> 1) * 16);
     s.mv[tid][0] = f.cu_mv[bi * 2]; s.mv[tid][1] = f.cu_mv[bi * 2 + 1];
+    s.rf[tid] = (uint8_t)cu_ref_at(f, bi);                            // lp-refs: the quarter's reference
     // intra-in-P: a quarter that is an intra unit gets no residual here (levels, cbf and reconstruction are k_intra_recon's, which runs behind this kernel)
     s.intra_q[tid] = (!DEC && f.intra_p && split) ? f.cu_intra[bi] : 0;
   }
@@ -557,7 +576,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
     for (int i = tid; i < 4 * 23 * 23; i += 256) {
       const int k = i / 529, r = i - k * 529, wy = r / 23, wx = r - wy * 23;
       const int gx = x0 + (k & 1) * 16 + (s.mv[k][0] >> 2) - 3 + wx, gy = y0 + (k >> 1) * 16 + (s.mv[k][1] >> 2) - 3 + wy;
-      fr->lwin[k][wy * 24 + wx] = f.ref[0][(size_t)clip3(0, f.ch - 1, gy) * f.cw + clip3(0, f.cw - 1, gx)];
+      fr->lwin[k][wy * 24 + wx] = ref_plane(f, s.rf[k], 0)[(size_t)clip3(0, f.ch - 1, gy) * f.cw + clip3(0, f.cw - 1, gx)];
     }
     __syncthreads();
     for (int i = tid; i < 4 * 23 * 16; i += 256) {
@@ -587,7 +606,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
         } else v = xf ? tp[3 * 16 + i] : tp[3 * 16 + i] * 64;
         p4 |= (uint32_t)clip8((v + 32) >> 6) << (8 * i);
       }
-    } else p4 = mc_luma4(f.ref[0], f.cw, f.ch, x0 + x, y0 + y, s.mv[k][0], s.mv[k][1]);
+    } else p4 = mc_luma4(ref_plane(f, s.rf[k], 0), f.cw, f.ch, x0 + x, y0 + y, s.mv[k][0], s.mv[k][1]);
     const size_t g = (size_t)(y0 + y) * f.cw + x0 + x;
     if (!coded) *(uint32_t *)&f.rec[0][g] = p4;
     *(uint32_t *)&s.px[y * 32 + x] = p4;
@@ -617,7 +636,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
     for (int i = tid; i < 8 * 121; i += 256) {
       const int w8 = i / 121, r = i - w8 * 121, wy = r / 11, wx = r - wy * 11, pl = w8 >> 2, sub = w8 & 3, k = split ? sub : 0;
       const int xi = (x0 >> 1) + (sub & 1) * 8 + (s.mv[k][0] >> 3) + wx - 1, yi = (y0 >> 1) + (sub >> 1) * 8 + (s.mv[k][1] >> 3) + wy - 1;
-      s.win[pl][sub][wy * 12 + wx] = f.ref[1 + pl][(size_t)clip3(0, ch2 - 1, yi) * cw2 + clip3(0, cw2 - 1, xi)];
+      s.win[pl][sub][wy * 12 + wx] = ref_plane(f, s.rf[k], 1 + pl)[(size_t)clip3(0, ch2 - 1, yi) * cw2 + clip3(0, cw2 - 1, xi)];
     }
   };
   // RC: everything chroma reads from memory is fetched in front of the luma transform, where a workgroup may wait for its QP -- behind the wait it is on the
@@ -1497,7 +1516,7 @@ __global__ __launch_bounds__(256) void k_deblock_tile(EncFrame f)
   __shared__ __attribute__((aligned(16))) uint8_t tc_[2][34 * PC];
   // the CU records of the tile's 8x8 cells and one ring around them (cells -1 .. 8 in both directions): everything the boundary
   // strength needs, fetched in one go beside the samples instead of per edge segment
-  __shared__ uint8_t r_log2[100], r_intra[100], r_cbf[100]; __shared__ uint32_t r_mv[100];
+  __shared__ uint8_t r_log2[100], r_intra[100], r_cbf[100], r_ref[100]; __shared__ uint32_t r_mv[100];
   const int tid = threadIdx.x, wc = f.cw >> 6, hc = f.ch >> 6;
   if (f.me_cand && blockIdx.x == 0 && tid == 0) { f.me_cand[0] = 0; f.sync[(size_t)3 * wc * hc + 1] = 0; }      // intra-in-P: the next picture's k_me starts its list of candidate blocks from nothing, its "has intra units" word from zero
   const int lin = xcd_contiguous((int)blockIdx.x, (int)gridDim.x), tx = lin % wc, tyi = lin / wc;
@@ -1505,18 +1524,19 @@ __global__ __launch_bounds__(256) void k_deblock_tile(EncFrame f)
   const int TW = tx == wc - 1 ? 68 : 64, TH = tyi == hc - 1 ? 68 : 64;
   if (tid < 100) {
     const int bx = tx * 8 - 1 + tid % 10, by = tyi * 8 - 1 + tid / 10;
-    uint32_t l2 = 6, in = 0, cb = 0, mv = 0;
+    uint32_t l2 = 6, in = 0, cb = 0, mv = 0, rf = 0;
     if (bx >= 0 && by >= 0 && bx < f.b8w && by < f.b8h) {
       const int i = by * f.b8w + bx;
-      l2 = f.cu_log2[i]; in = f.cu_intra[i]; cb = f.cu_cbf[i]; mv = *(const uint32_t *)&f.cu_mv[i * 2];
+      l2 = f.cu_log2[i]; in = f.cu_intra[i]; cb = f.cu_cbf[i]; mv = *(const uint32_t *)&f.cu_mv[i * 2]; rf = (uint32_t)cu_ref_at(f, i);
     }
-    r_log2[tid] = (uint8_t)l2; r_intra[tid] = (uint8_t)in; r_cbf[tid] = (uint8_t)cb; r_mv[tid] = mv;
+    r_log2[tid] = (uint8_t)l2; r_intra[tid] = (uint8_t)in; r_cbf[tid] = (uint8_t)cb; r_mv[tid] = mv; r_ref[tid] = (uint8_t)rf;
   }
   __syncthreads();
   auto cell = [&](int x, int y) { return ((y >> 3) - (tyi * 8 - 1)) * 10 + ((x >> 3) - (tx * 8 - 1)); };
   auto bs_of = [&](int cp, int cq) -> int {
     if (r_intra[cp] | r_intra[cq]) return 2;
     if ((r_cbf[cp] | r_cbf[cq]) & 1) return 1;
+    if (r_ref[cp] != r_ref[cq]) return 1;                              // different reference pictures (lp-refs)
     const uint32_t a = r_mv[cp], b = r_mv[cq];
     if (iabs((int)(int16_t)(a & 0xffff) - (int)(int16_t)(b & 0xffff)) >= 4 || iabs((int)(int16_t)(a >> 16) - (int)(int16_t)(b >> 16)) >= 4) return 1;
     return 0;
@@ -1893,12 +1913,12 @@ __device__ __forceinline__ void tok_unit(const EncFrame &f, TokWave &W, const in
   const int bx0 = ux * 2 - 1, by0 = uy * 2 - 1;
   if (lane < 9) {
     int bx = bx0 + lane % 3, by = by0 + lane / 3;
-    CuRec r; r.log2 = 0; r.intra = 0; r.flags = 0; r.merge_idx = 0; r.mvp_idx = 0; r.intra_mode = 0; r.cbf = 0; r.pad = 0; r.mvdx = 0; r.mvdy = 0;
+    CuRec r; r.log2 = 0; r.intra = 0; r.flags = 0; r.merge_idx = 0; r.mvp_idx = 0; r.intra_mode = 0; r.cbf = 0; r.ref = 0; r.mvdx = 0; r.mvdy = 0;
     if (bx >= 0 && by >= 0) {
       int g = by * f.b8w + bx;
       r.log2 = f.cu_log2[g]; r.intra = f.cu_intra[g]; r.flags = f.cu_flags[g]; r.merge_idx = f.cu_merge_idx[g];
       r.mvp_idx = f.cu_mvp_idx[g]; r.intra_mode = f.cu_intra_mode[g]; r.cbf = f.cu_cbf[g];
-      r.mvdx = f.cu_mvd[g * 2]; r.mvdy = f.cu_mvd[g * 2 + 1];
+      r.mvdx = f.cu_mvd[g * 2]; r.mvdy = f.cu_mvd[g * 2 + 1]; r.ref = (uint8_t)cu_ref_at(f, g);
     }
     tile[lane] = r;
   }
@@ -1933,7 +1953,7 @@ __device__ __forceinline__ void tok_unit(const EncFrame &f, TokWave &W, const in
         enc_sao(t, f.sao[ctu], hl ? &f.sao[ctu - 1] : nullptr, hu ? &f.sao[ctu - wc] : nullptr);     // (read where they lie: a local copy indexed at run time would live in scratch memory)
       }
       enc_split_flags(v, t, f.cw, f.chp, x0, y0, z, cu.log2);
-      enc_cu_header(v, t, f.cw, f.chp, f.is_intra != 0, x0, y0, cu, f.lossless != 0);
+      enc_cu_header(v, t, f.cw, f.chp, f.is_intra != 0, x0, y0, cu, f.lossless != 0, f.cu_ref ? f.nref : 1);
       // the quantisation group's (= CTU's) delta QP goes with its first CU that has residual, right after the cbf flags
       if (f.ctu_qy && !(cu.flags & CU_SKIP) && cu.cbf && z == f.ctu_first[ctu]) enc_cu_qp_delta(t, f.ctu_delta[ctu]);
       hdr_n = t.n;
@@ -2445,7 +2465,8 @@ void launch_me(const EncFrame &f, hipStream_t st)
 {
   const int W = 2 * f.range + 1, items = ((W + 3) / 4) * ((W + 1) / 2);          // quads x pairs; R = 16: 153 items -> 192 threads
   const int threads = items >= 256 ? 256 : ((items + 63) / 64) * 64;
-  hipLaunchKernelGGL(k_me, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
+  if (f.cu_ref) hipLaunchKernelGGL(k_me<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // lp-refs
+  else hipLaunchKernelGGL(k_me<false>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
 }
 void launch_inter_recon(const EncFrame &f, hipStream_t st)
 {

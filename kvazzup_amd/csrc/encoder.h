@@ -56,6 +56,8 @@ struct EncoderConfig {
   int signhide = 0;           // kvazaar "signhide": sign_data_hiding_enabled_flag; the quantiser makes the parity of every eligible coefficient group say the hidden sign
   int hash = 0;               // kvazaar "hash": 1 checksum, 2 md5 -- a decoded picture hash SEI (D.2.19) behind every picture's slices, from the reconstruction downloaded for it
   int entropy_gpu = 0;        // arithmetic coder: 1 = on the GPU (k_cabac_rows, cabac_kernels.hip), 0 = host thread pool (entropy_host.h); band mode always uses the host pool
+  int lp_refs = 1;            // "lp-refs" (extension, "uvgx multi-reference v1"): references per P picture, 1..4 -- picture t refers to pictures
+                              // t - 1 .. t - min(lp_refs, pictures since the IDR picture), all in list 0; 1 = one reference (the encoder of before); not in band mode
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -155,9 +157,9 @@ class Encoder {
   // the input stage of picture t waited for the reconstruction of t - 2, and the calling thread with it: the main stream ran dry between pictures)
   static constexpr int kSets = 8;
   uint8_t *src_[kSets][3] = {};         // padded source planes
-  // reconstruction ring: the picture being coded, its reference, and (owf >= 2) the one still waiting to be output
+  // reconstruction ring: the picture being coded, its reference(s) (lp-refs), and (owf >= 2) the one still waiting to be output
   static constexpr int kMaxDepth = 16;    // pictures in flight behind the one being submitted (owf), at most
-  uint8_t *rec_[kMaxDepth + 4][3] = {};
+  uint8_t *rec_[kMaxDepth + 2 + KVZ_MAX_LP_REFS][3] = {};
   bool spin_wait_ = false;      // KVAZZUP_AMD_SPIN: poll the GPU instead of napping between queries
   int rc_delay_ = 3;            // rate control: pictures between a picture and the access unit size booked before it (3 .. 7)
   int nrec_ = 3;                // reconstruction ring: the picture being written, its reference, and the ones whose output is still owed (owf)
@@ -167,6 +169,7 @@ class Encoder {
   int16_t *coef_[kSets][3] = {};
   uint8_t *cu_bytes_[kSets] = {};          // 7 byte arrays back to back
   int16_t *cu_mv_[kSets] = {}, *cu_mvd_[kSets] = {};
+  uint8_t *cu_ref_[kSets] = {};            // lp-refs >= 2: ref_idx_l0 per 8x8 block (EncFrame::cu_ref)
   int set_ = 0, out_set_ = 0;
   char prio_[3] = {'h', 'n', 'n'};                      // priority levels of the main, tokenizer and input streams (stream_pool.h keys)
   std::vector<int8_t> roi_; int roi_w_ = 0, roi_h_ = 0;           // as set by the caller (set_roi)

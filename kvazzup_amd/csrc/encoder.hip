@@ -38,6 +38,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.band_rows > 0) cfg.intra_in_p = 0;               // (intra-in-P runs behind the whole picture's inter reconstruction: not in band mode, where a picture is coded in parts by several instances)
   if (cfg.rc_bands > 0) cfg.qp_in_cu = 1;                  // ... and so do the steps of rate control v2
   if (cfg.band_rows > 0) cfg.me_source = 0;                // (a band's search window reaches into the neighbouring bands' rows: the halo carries reconstruction rows, not source rows)
+  if (cfg.lp_refs < 1 || cfg.lp_refs > KVZ_MAX_LP_REFS) { if (error) *error = "lp-refs out of range (0 .. 4)"; return false; }
+  if (cfg.lp_refs > 1 && cfg.band_rows > 0) { if (error) *error = "lp-refs >= 2 is not available in band mode (the halo exchange carries one reference picture's rows)"; return false; }
 
   const char *prio = getenv("KVAZZUP_AMD_PRIO"); if (!prio || strlen(prio) < 4) prio = "hnnn";   // main, tokenizer, input, decoder: the chain the next picture waits for is the urgent one (+6 % at 1080p; any explicit priority also gives the stream a hardware queue of its own)
 
@@ -77,7 +79,10 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   // a pipelined encoder then decides exactly like a synchronous one with the same delay (oracle/hevc_enc.c rate_control, "rc-delay").
   depth_ = cfg.owf >= 3 ? (cfg.bitrate == 0 ? (cfg.owf > kMaxDepth ? kMaxDepth : cfg.owf) : (cfg.owf > 6 ? 6 : cfg.owf)) : (cfg.owf >= 2 ? 2 : (cfg.owf == 1 ? 1 : 0));
   rc_delay_ = cfg.bitrate > 0 && depth_ + 1 > 3 && cfg.band_rows == 0 ? depth_ + 1 : 3;
-  nrec_ = depth_ + 2 < 3 ? 3 : depth_ + 2;              // (+ 1: an intra picture is written ahead of its turn, beside the P pictures in front of it, which still read theirs)
+  // the picture being written, the lp_refs pictures before it, and the depth_ pictures in flight in front of it -- none of whose references may be
+  // overwritten (the oldest, t - depth_, reads t - depth_ - lp_refs); + 1 (at least): an intra picture is written ahead of its turn, beside the P pictures
+  // in front of it, which still read theirs
+  nrec_ = depth_ + 1 + cfg.lp_refs < 2 + cfg.lp_refs ? 2 + cfg.lp_refs : depth_ + 1 + cfg.lp_refs;
   prio_[0] = prio[0]; prio_[1] = prio[1]; prio_[2] = prio[2];
   HIP_OK(stream_acquire(&stream_, cfg.device, 'M', prio_[0]));
   const size_t npx = (size_t)cw_ * ch_, nb8 = npx / 64, in_bytes = (size_t)cfg.width * cfg.height * 3 / 2;
@@ -92,6 +97,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     HIP_OK(hipMalloc(&cu_bytes_[k], nb8 * 7)); HIP_OK(hipMemset(cu_bytes_[k], 0, nb8 * 7));
     HIP_OK(hipMalloc(&cu_mv_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mv_[k], 0, nb8 * 2 * sizeof(int16_t)));
     HIP_OK(hipMalloc(&cu_mvd_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mvd_[k], 0, nb8 * 2 * sizeof(int16_t)));
+    if (cfg.lp_refs > 1) { HIP_OK(hipMalloc(&cu_ref_[k], nb8)); HIP_OK(hipMemset(cu_ref_[k], 0, nb8)); }
     HIP_OK(hipEventCreateWithFlags(&ev_tok_done_[k], kDeviceEvent));
   }
   if (cfg.qp_in_cu) {
@@ -237,6 +243,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   f_.sync = sync_; f_.err = err_; f_.trace = trace_; f_.intra_order = intra_order_;
 
   sp_.cw = cw_; sp_.ch = ch_; sp_.width = cfg.width; sp_.height = cfg.height; sp_.qp = cfg.qp; sp_.wpp = cfg.wpp; sp_.tile_rows = cfg.tile_rows; sp_.tile_cols = cfg.tile_cols; sp_.qp_in_cu = cfg.qp_in_cu; sp_.sao = cfg.sao; sp_.slices = cfg.slices; sp_.signhide = cfg.signhide; sp_.scaling_list = cfg.scaling_list; sp_.tq_bypass = cfg.lossless;
+  sp_.lp_refs = cfg.lp_refs > 1 ? cfg.lp_refs : 0;
   sp_.deblock = cfg.deblock; sp_.fps_num = cfg.fps_num; sp_.fps_den = cfg.fps_den;
   HIP_OK(hipStreamSynchronize(stream_));
   HIP_OK(hipDeviceSynchronize());
@@ -258,6 +265,7 @@ void Encoder::bind_set(int k)
   f_.cu_log2 = cu; f_.cu_intra = cu + nb8; f_.cu_flags = cu + 2 * nb8; f_.cu_merge_idx = cu + 3 * nb8;
   f_.cu_mvp_idx = cu + 4 * nb8; f_.cu_intra_mode = cu + 5 * nb8; f_.cu_cbf = cu + 6 * nb8;
   f_.cu_mv = cu_mv_[k]; f_.cu_mvd = cu_mvd_[k];
+  f_.cu_ref = cu_ref_[k];                              // NULL with one reference
   f_.sao = sao_[k];                                    // NULL without SAO
   f_.ctu_qt = ctu_qt_[k]; f_.ctu_qy = ctu_qy_[k]; f_.ctu_delta = ctu_delta_[k]; f_.ctu_first = ctu_first_[k];     // all NULL without qp_in_cu
 }
@@ -303,10 +311,10 @@ Encoder::~Encoder()
   if (stream_h2d_ && stream_h2d_ != stream_in_) stream_release(stream_h2d_, cfg_.device, 'H', 'l');
   for (int k = 0; k < kInRing; k++) { hipFree(d_in_[k]); if (h_in_[k]) hipHostFree(h_in_[k]); if (ev_h2d_[k]) hipEventDestroy(ev_h2d_[k]); if (ev_pad_[k]) hipEventDestroy(ev_pad_[k]); }
   stream_release(stream_rec_, cfg_.device, 'R', 'n');
-  for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kMaxDepth + 4; b++) hipFree(rec_[b][c]); }
+  for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kMaxDepth + 2 + KVZ_MAX_LP_REFS; b++) hipFree(rec_[b][c]); }
   hipFree(vaq_act_); hipFree(vaq_sum_); hipFree(rc_state_);
   for (int k = 0; k < kSets; k++) { hipFree(ctu_qt_[k]); hipFree(ctu_qy_[k]); hipFree(ctu_delta_[k]); hipFree(ctu_first_[k]); if (h_ctu_qt_[k]) hipHostFree(h_ctu_qt_[k]); hipFree(ctu_roi_[k]); }
-  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
+  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
   for (int c = 0; c < 3; c++) { hipFree(work_[c]); hipFree(work_idr_[c]); }
   hipFree(sync_idr_); hipFree(edge_col_idr_); hipFree(edge_row_); hipFree(edge_row_idr_);
   for (int k = 0; k < kSets; k++) hipFree(sao_[k]);
@@ -591,6 +599,17 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
   // gone through the input stream, behind this picture's k_me), and what the search and the intra pricing behind it write is the set's own
   const bool ahead = me_ahead_ && !intra;
   f_.me_ref = ahead ? src_[prev_set_][0] : f_.ref[0];
+  // lp-refs: reference k is the picture k + 1 before this one -- ring slot cur_idx_ - 1 - k -- as far as pictures since the IDR picture go (poc_); the search
+  // looks at its reconstruction or (me-source) at its input picture, which is still in the working set it was padded into (set_ - 1 - k: a set is padded
+  // into again kSets pictures later, behind this picture's search on the input stream)
+  if (f_.cu_ref) {
+    f_.nref = intra ? 1 : (poc_ < cfg_.lp_refs ? poc_ : cfg_.lp_refs);
+    for (int k = 0; k < KVZ_MAX_LP_REFS; k++) {
+      const int slot = (cur_idx_ + nrec_ - 1 - (k < f_.nref ? k : 0)) % nrec_;
+      for (int c = 0; c < 3; c++) f_.refs[k][c] = rec_[slot][c];
+      f_.me_refs[k] = ahead ? src_[(set_ + kSets - 1 - (k < f_.nref ? k : 0)) % kSets][0] : f_.refs[k][0];
+    }
+  }
   auto bind_me_block = [&](uint32_t *base, uint32_t *sy) {
     const size_t n16 = (size_t)(cw_ / 16) * (ch_ / 16);
     f_.me_cost16 = base; f_.me_cand = base ? base + n16 : nullptr; f_.sync = sy;
@@ -1051,6 +1070,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   for (int i = 0; i < 7; i++) if (w == names[i]) { src = cu_bytes_[out_set_] + i * nb8; have = nb8; }
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
+  if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }
   if (w == "trace" && trace_) { src = trace_; have = sizeof(unsigned long long) * (rows_ * (cw_ / 64) * 72); }
   for (int c = 0; c < 3; c++) {
     size_t n = c ? npx / 4 : npx;

@@ -57,6 +57,7 @@ KVZ_HD int scaling_offset(int log2n, int plane, int inter)
 // (`decided` is polled by every waiting workgroup and acc[g] takes an atomic from every workgroup of group g: each on a 128-byte line of its own --
 // with all of them in one line the polls queued in front of the atomics and the launch took 130 us instead of 90.)
 #define KVZ_RC_ACC_STRIDE 16
+#define KVZ_MAX_LP_REFS 4
 struct RcState {
   uint32_t ratio_q8, ratio_valid, cost_sofar; uint32_t cost[8], cost_valid[8];
   alignas(128) uint32_t decided;
@@ -123,7 +124,19 @@ struct EncFrame {
   RcState *pb_rc; int8_t *pb_qt; const int8_t *pb_roi; uint32_t pb_bits3; int pb_nctu; int8_t pb_on, pb_slot3, pb_have3, pb_pad;
   RcState *rc; long long rc_target; int rc_nb, rc_slot;      // rc_target: bits for the picture; rc_slot: where the picture's level cost is filed (picture index & 7)
   unsigned long long *trace;    // KVAZZUP_AMD_INTRA_TRACE: per (CTU, plane) 8 words {start, first block, end, time in border waits, blocks, stores, publishes, number of blocks} of k_intra_recon, 100 MHz ticks; else NULL
+  // "lp-refs" (extension, "uvgx multi-reference v1"): the picture's active references in list 0 -- reference k is the picture k + 1
+  // before this one (POC distance k + 1).  A zeroed frame means one reference: nref 0 / 1, cu_ref NULL, and ref[] / me_ref are what the kernels read.
+  int nref;
+  uint8_t *cu_ref;              // [b8] ref_idx_l0 of the CU (NULL: every CU refers to reference 0)
+  const uint8_t *refs[KVZ_MAX_LP_REFS][3];   // reconstruction planes of reference k (refs[0] = ref)
+  const uint8_t *me_refs[KVZ_MAX_LP_REFS];   // the luma plane k_me searches for reference k (me_refs[0] = me_ref; me-source: input picture t - 1 - k)
 };
+
+// the reference planes of ref_idx k (one reference: ref[])
+KVZ_HD const uint8_t *ref_plane(const EncFrame &f, int k, int c) { return f.cu_ref ? f.refs[k][c] : f.ref[c]; }
+KVZ_HD int cu_ref_at(const EncFrame &f, int i) { return f.cu_ref ? f.cu_ref[i] : 0; }
+// length of the truncated-unary ref_idx_l0 codeword of reference k with n active references (cMax = n - 1); 0 with one reference
+KVZ_HD int ref_bins(int k, int n) { return n <= 1 ? 0 : (k < n - 1 ? k + 1 : n - 1); }
 
 enum { CU_SKIP = 1, CU_MERGE = 2 };
 
@@ -715,6 +728,17 @@ KVZ_HD void enc_mvd(S &c, int dx, int dy)
   }
 }
 
+// ref_idx_l0 (7.3.8.6): truncated rice, cMax = nref - 1, cRice 0; bins 0 and 1 context coded, the rest bypass (9.3.4.2, Table 9-41)
+template <class S>
+KVZ_HD void enc_ref_idx(S &c, int r, int nref)
+{
+  for (int i = 0; i < nref - 1; i++) {
+    const int b = r > i;
+    if (i < 2) cabac_bin(c, CTX_REF_IDX + i, b); else cabac_bypass(c, b);
+    if (!b) break;
+  }
+}
+
 template <class S>
 KVZ_HD void enc_merge_idx(S &c, int idx)
 {
@@ -726,7 +750,7 @@ KVZ_HD void enc_merge_idx(S &c, int idx)
 // for any luma position of the current CTU and its left / above neighbours: FrameView reads the
 // per-8x8 arrays directly (host tests), the entropy kernel uses a tile staged in LDS.
 struct CuRec {
-  uint8_t log2, intra, flags, merge_idx, mvp_idx, intra_mode, cbf, pad;
+  uint8_t log2, intra, flags, merge_idx, mvp_idx, intra_mode, cbf, ref;     // ref: ref_idx_l0
   int16_t mvdx, mvdy;
 };
 struct FrameView {
@@ -736,7 +760,7 @@ struct FrameView {
     int i = b8idx(*f, x, y);
     CuRec r;
     r.log2 = f->cu_log2[i]; r.intra = f->cu_intra[i]; r.flags = f->cu_flags[i]; r.merge_idx = f->cu_merge_idx[i];
-    r.mvp_idx = f->cu_mvp_idx[i]; r.intra_mode = f->cu_intra_mode[i]; r.cbf = f->cu_cbf[i]; r.pad = 0;
+    r.mvp_idx = f->cu_mvp_idx[i]; r.intra_mode = f->cu_intra_mode[i]; r.cbf = f->cu_cbf[i]; r.ref = (uint8_t)cu_ref_at(*f, i);
     r.mvdx = f->cu_mvd[i * 2]; r.mvdy = f->cu_mvd[i * 2 + 1];
     return r;
   }
@@ -777,7 +801,7 @@ KVZ_HD void enc_split_flags(const V &v, S &c, int cw, int ch, int x0, int y0, in
 // coding_unit() up to and including the cbf flags of its single transform unit (7.3.8.5-7.3.8.10).
 // Returns the cbf bits (bit0 Y, bit1 Cb, bit2 Cr) whose residual_coding() must follow, 0 if none.
 template <class V, class S>
-KVZ_HD int enc_cu_header(const V &v, S &c, int cw, int ch, bool pic_intra, int x0, int y0, const CuRec &cu, bool bypass = false)
+KVZ_HD int enc_cu_header(const V &v, S &c, int cw, int ch, bool pic_intra, int x0, int y0, const CuRec &cu, bool bypass = false, int nref = 1)
 {
   const int intra = cu.intra, flags = cu.flags, cbf = cu.cbf, log2 = cu.log2;
   if (bypass) cabac_bin(c, CTX_TQ_BYPASS, 1);                  // cu_transquant_bypass_flag (`lossless`: the PPS enables it and every coding unit sets it), first in the coding unit
@@ -810,6 +834,7 @@ KVZ_HD int enc_cu_header(const V &v, S &c, int cw, int ch, bool pic_intra, int x
     cabac_bin(c, CTX_MERGE_FLAG, (flags & CU_MERGE) ? 1 : 0);
     if (flags & CU_MERGE) enc_merge_idx(c, cu.merge_idx);
     else {
+      if (nref > 1) enc_ref_idx(c, cu.ref, nref);                 // (num_ref_idx_l0_active_minus1 > 0)
       enc_mvd(c, cu.mvdx, cu.mvdy);
       cabac_bin(c, CTX_MVP_FLAG, cu.mvp_idx);
       cabac_bin(c, CTX_RQT_ROOT_CBF, cbf != 0);
@@ -848,9 +873,10 @@ KVZ_HD void enc_ctu(const EncFrame &f, CabacEnc &c, int cx, int cy)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Merge / AMVP signalling of one inter 2Nx2N CU from the final motion field of a P picture with
-// one reference picture and no intra CUs... (intra neighbours are treated as unavailable).
-// H.265 8.5.3.2.2-8.5.3.2.7 specialised: Log2ParMrgLevel = 2, MaxNumMergeCand = 5, no TMVP.
+// Merge / AMVP signalling of one inter 2Nx2N CU from the final motion field of a P picture (intra
+// neighbours are treated as unavailable).  H.265 8.5.3.2.2-8.5.3.2.8 specialised: Log2ParMrgLevel = 2,
+// MaxNumMergeCand = 5, no TMVP, list 0 only.  With lp-refs the vectors carry a ref_idx; reference k is
+// the picture k + 1 before the current one, so the POC distance of ref_idx k is k + 1.
 // ---------------------------------------------------------------------------------------------
 KVZ_HD int mvd_bits(int q)
 {
@@ -862,12 +888,12 @@ KVZ_HD int mvd_bits(int q)
   return 2 + len + 1 + k + 1;
 }
 
-struct NbMv { bool ok; int mx, my; };
+struct NbMv { bool ok; int mx, my, ref; };
 // where the derivations below read a CU's record from: the frame's arrays (host tests, band encoder) or a tile of them staged in LDS (k_inter_signal)
-struct MvRec { int intra, mx, my, cbf; };
+struct MvRec { int intra, mx, my, cbf, ref; };
 struct FrameMvView {
   const EncFrame &f;
-  KVZ_HD MvRec at(int x, int y) const { const int i = b8idx(f, x, y); MvRec r; r.intra = f.cu_intra[i]; r.mx = f.cu_mv[i * 2]; r.my = f.cu_mv[i * 2 + 1]; r.cbf = f.cu_cbf[i]; return r; }
+  KVZ_HD MvRec at(int x, int y) const { const int i = b8idx(f, x, y); MvRec r; r.intra = f.cu_intra[i]; r.mx = f.cu_mv[i * 2]; r.my = f.cu_mv[i * 2 + 1]; r.cbf = f.cu_cbf[i]; r.ref = cu_ref_at(f, i); return r; }
 };
 template <class V>
 KVZ_HD NbMv nb_mv(const V &v, int cw, int chp, int xc, int yc, int xn, int yn)
@@ -876,10 +902,11 @@ KVZ_HD NbMv nb_mv(const V &v, int cw, int chp, int xc, int yc, int xn, int yn)
   // all five neighbours of a CU are in flight together instead of ten dependent round trips (k_inter_signal: 4K 24 -> 9 us).
   const bool av = avail64(cw, chp, xc, yc, xn, yn);
   const MvRec m = v.at(av ? xn : xc, av ? yn : yc);
-  NbMv r; r.ok = av && !m.intra; r.mx = r.ok ? m.mx : 0; r.my = r.ok ? m.my : 0;
+  NbMv r; r.ok = av && !m.intra; r.mx = r.ok ? m.mx : 0; r.my = r.ok ? m.my : 0; r.ref = r.ok ? m.ref : 0;
   return r;
 }
-KVZ_HD bool same_mv(const NbMv &a, const NbMv &b) { return a.mx == b.mx && a.my == b.my; }
+// same motion: vector and reference (8.5.3.2.3's pruning compares both)
+KVZ_HD bool same_mv(const NbMv &a, const NbMv &b) { return a.mx == b.mx && a.my == b.my && a.ref == b.ref; }
 
 // the five spatial neighbours of the 2Nx2N PU at (x0, y0), size n, that both the merge and the AMVP derivation read (8.5.3.2.3, 8.5.3.2.7)
 struct FiveNb { NbMv A0, A1, B0, B1, B2; };
@@ -891,8 +918,8 @@ KVZ_HD FiveNb five_neighbours(const V &v, int cw, int chp, int x0, int y0, int n
   q.B0 = nb_mv(v, cw, chp, x0, y0, x0 + n, y0 - 1); q.A0 = nb_mv(v, cw, chp, x0, y0, x0 - 1, y0 + n); q.B2 = nb_mv(v, cw, chp, x0, y0, x0 - 1, y0 - 1);
   return q;
 }
-// the five merge candidates (8.5.3.2.2-8.5.3.2.5)
-KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5])
+// the five merge candidates (8.5.3.2.2-8.5.3.2.5); nref: active references (zero candidates take refIdx 0, 1, .. nref - 1, then 0)
+KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5], int cref[5], int nref = 1)
 {
   const NbMv &A1 = q.A1, &B1 = q.B1, &B0 = q.B0, &A0 = q.A0, &B2 = q.B2;
   bool fA1 = A1.ok;
@@ -901,45 +928,68 @@ KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5])
   bool fA0 = A0.ok && !(A1.ok && same_mv(A1, A0));
   bool fB2 = B2.ok && !(A1.ok && same_mv(A1, B2)) && !(B1.ok && same_mv(B1, B2)) && !(fA0 && fA1 && fB0 && fB1);
   int nc = 0;
-  if (fA1) { cmx[nc] = A1.mx; cmy[nc] = A1.my; nc++; }
-  if (fB1) { cmx[nc] = B1.mx; cmy[nc] = B1.my; nc++; }
-  if (fB0) { cmx[nc] = B0.mx; cmy[nc] = B0.my; nc++; }
-  if (fA0) { cmx[nc] = A0.mx; cmy[nc] = A0.my; nc++; }
-  if (fB2 && nc < 5) { cmx[nc] = B2.mx; cmy[nc] = B2.my; nc++; }
-  while (nc < 5) { cmx[nc] = 0; cmy[nc] = 0; nc++; }        // zero candidates (refIdx 0 for one reference)
+  if (fA1) { cmx[nc] = A1.mx; cmy[nc] = A1.my; cref[nc] = A1.ref; nc++; }
+  if (fB1) { cmx[nc] = B1.mx; cmy[nc] = B1.my; cref[nc] = B1.ref; nc++; }
+  if (fB0) { cmx[nc] = B0.mx; cmy[nc] = B0.my; cref[nc] = B0.ref; nc++; }
+  if (fA0) { cmx[nc] = A0.mx; cmy[nc] = A0.my; cref[nc] = A0.ref; nc++; }
+  if (fB2 && nc < 5) { cmx[nc] = B2.mx; cmy[nc] = B2.my; cref[nc] = B2.ref; nc++; }
+  for (int z = 0; nc < 5; z++) { cmx[nc] = 0; cmy[nc] = 0; cref[nc] = z < nref ? z : 0; nc++; }     // zero candidates (8.5.3.2.5)
 }
+KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5]) { int cref[5]; merge_cand_list(q, cmx, cmy, cref, 1); }
 KVZ_HD void merge_cand_list(const EncFrame &f, int x0, int y0, int n, int cmx[5], int cmy[5]) { FrameMvView v{f}; merge_cand_list(five_neighbours(v, f.cw, f.chp, x0, y0, n), cmx, cmy); }
-// the two AMVP candidates (8.5.3.2.6-8.5.3.2.7); every neighbour refers to the same picture
-KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2])
+// 8.5.3.2.8: a neighbour's vector for reference td - 1 scaled to reference tb - 1 (td, tb: POC distances; short-term references only)
+KVZ_HD int mv_scale(int mv, int td, int tb)
 {
-  const NbMv &A1 = q.A1, &B1 = q.B1, &B0 = q.B0, &A0 = q.A0, &B2 = q.B2;
-  bool haveA = A0.ok || A1.ok, haveB = B0.ok || B1.ok || B2.ok;
-  NbMv a = A0.ok ? A0 : A1, b = B0.ok ? B0 : (B1.ok ? B1 : B2);
-  if (!haveA && haveB) { a = b; haveA = true; }          // isScaledFlag == 0: A takes B's vector
+  if (td == tb) return mv;
+  const int tx = (16384 + (iabs(td) >> 1)) / td;
+  const int dsf = clip3(-4096, 4095, (tb * tx + 32) >> 6);
+  const int p = dsf * mv;
+  return clip3(-32768, 32767, p < 0 ? -((-p + 127) >> 8) : ((p + 127) >> 8));
+}
+// the two AMVP candidates for ref_idx `ref` (8.5.3.2.6-8.5.3.2.7): A from A0 / A1 referring to the same picture, else (scaled) from the first of
+// them that is available; B from B0 / B1 / B2 referring to the same picture, and when neither A0 nor A1 is available (isScaledFlag 0) A takes that
+// B and B becomes the first available of B0 / B1 / B2, scaled
+KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0)
+{
+  const NbMv *An[2] = {&q.A0, &q.A1}, *Bn[3] = {&q.B0, &q.B1, &q.B2};
+  bool haveA = false, haveB = false;
+  int ax = 0, ay = 0, bx = 0, by = 0;
+  for (int k = 0; k < 2 && !haveA; k++) if (An[k]->ok && An[k]->ref == ref) { haveA = true; ax = An[k]->mx; ay = An[k]->my; }
+  for (int k = 0; k < 2 && !haveA; k++)
+    if (An[k]->ok) { haveA = true; ax = mv_scale(An[k]->mx, An[k]->ref + 1, ref + 1); ay = mv_scale(An[k]->my, An[k]->ref + 1, ref + 1); }
+  const bool scaled = q.A0.ok || q.A1.ok;                  // isScaledFlagLX
+  for (int k = 0; k < 3 && !haveB; k++) if (Bn[k]->ok && Bn[k]->ref == ref) { haveB = true; bx = Bn[k]->mx; by = Bn[k]->my; }
+  if (!scaled && haveB) { haveA = true; ax = bx; ay = by; }          // isScaledFlag == 0: A takes B's vector ...
+  if (!scaled) {                                                       // ... and B is derived again, from any reference
+    haveB = false;
+    for (int k = 0; k < 3 && !haveB; k++)
+      if (Bn[k]->ok) { haveB = true; bx = mv_scale(Bn[k]->mx, Bn[k]->ref + 1, ref + 1); by = mv_scale(Bn[k]->my, Bn[k]->ref + 1, ref + 1); }
+  }
   int np = 0;
-  if (haveA) { px[np] = a.mx; py[np] = a.my; np++; }
-  if (haveB && !(haveA && a.mx == b.mx && a.my == b.my)) { px[np] = b.mx; py[np] = b.my; np++; }
+  if (haveA) { px[np] = ax; py[np] = ay; np++; }
+  if (haveB && !(haveA && ax == bx && ay == by)) { px[np] = bx; py[np] = by; np++; }
   while (np < 2) { px[np] = 0; py[np] = 0; np++; }
 }
-KVZ_HD void amvp_cand_list(const EncFrame &f, int x0, int y0, int n, int px[2], int py[2]) { FrameMvView v{f}; amvp_cand_list(five_neighbours(v, f.cw, f.chp, x0, y0, n), px, py); }
+KVZ_HD void amvp_cand_list(const EncFrame &f, int x0, int y0, int n, int px[2], int py[2]) { FrameMvView v{f}; amvp_cand_list(five_neighbours(v, f.cw, f.chp, x0, y0, n), px, py, 0); }
 
-// the signalling of the inter CU at (x0, y0): merge (+ skip) with the first candidate that equals its vector, else AMVP with the cheaper predictor
+// the signalling of the inter CU at (x0, y0): merge (+ skip) with the first candidate that equals its (vector, reference), else AMVP for its
+// reference with the cheaper predictor.  nref: the slice's active references.
 struct CuSignal { int flags, midx, mvp, mvdx, mvdy; };
 template <class V>
-KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, int y0, int log2)
+KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, int y0, int log2, int nref = 1)
 {
   const int n = 1 << log2;
   const MvRec own = v.at(x0, y0);
-  const int mvx = own.mx, mvy = own.my;
+  const int mvx = own.mx, mvy = own.my, ref = own.ref;
   const FiveNb q = five_neighbours(v, cw, chp, x0, y0, n);      // (once for both derivations: ten availability tests and record fetches were most of k_inter_signal's code)
-  int cmx[5], cmy[5];
-  merge_cand_list(q, cmx, cmy);
+  int cmx[5], cmy[5], cref[5];
+  merge_cand_list(q, cmx, cmy, cref, nref);
   CuSignal r; r.flags = 0; r.midx = 0; r.mvp = 0; r.mvdx = 0; r.mvdy = 0;
-  for (int k = 4; k >= 0; k--) if (cmx[k] == mvx && cmy[k] == mvy) { r.flags = CU_MERGE; r.midx = k; }      // (the first match wins)
+  for (int k = 4; k >= 0; k--) if (cmx[k] == mvx && cmy[k] == mvy && cref[k] == ref) { r.flags = CU_MERGE; r.midx = k; }      // (the first match wins)
   if (r.flags && own.cbf == 0) r.flags |= CU_SKIP;
   if (!r.flags) {
     int px[2], py[2];
-    amvp_cand_list(q, px, py);
+    amvp_cand_list(q, px, py, ref);
     int b0 = mvd_bits(mvx - px[0]) + mvd_bits(mvy - py[0]);
     int b1 = mvd_bits(mvx - px[1]) + mvd_bits(mvy - py[1]);
     r.mvp = b1 < b0;
@@ -947,7 +997,7 @@ KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, in
   }
   return r;
 }
-KVZ_HD CuSignal decide_signalling_values(const EncFrame &f, int x0, int y0, int log2) { FrameMvView v{f}; return decide_signalling_values(v, f.cw, f.chp, x0, y0, log2); }
+KVZ_HD CuSignal decide_signalling_values(const EncFrame &f, int x0, int y0, int log2) { FrameMvView v{f}; return decide_signalling_values(v, f.cw, f.chp, x0, y0, log2, f.cu_ref && f.nref > 1 ? f.nref : 1); }
 KVZ_HD void decide_signalling(const EncFrame &f, int x0, int y0, int log2)
 {
   const int n = 1 << log2;
@@ -1110,6 +1160,7 @@ KVZ_HD int edge_bs(const EncFrame &f, int xp, int yp, int xq, int yq)
   int ip = b8idx(f, xp, yp), iq = b8idx(f, xq, yq);
   if (f.cu_intra[ip] || f.cu_intra[iq]) return 2;
   if ((f.cu_cbf[ip] & 1) || (f.cu_cbf[iq] & 1)) return 1;
+  if (cu_ref_at(f, ip) != cu_ref_at(f, iq)) return 1;               // different reference pictures
   if (iabs(f.cu_mv[ip * 2] - f.cu_mv[iq * 2]) >= 4 || iabs(f.cu_mv[ip * 2 + 1] - f.cu_mv[iq * 2 + 1]) >= 4) return 1;
   return 0;
 }

@@ -36,7 +36,13 @@ struct StreamParams {
   int scaling_list = 0;     // scaling_list_enabled_flag = 1, no sps_scaling_list_data: the default lists
   int tq_bypass = 0;        // transquant_bypass_enabled_flag (`lossless`: every coding unit sets cu_transquant_bypass_flag)
   int slices = 0;           // kvazaar slices: 1 = "wpp", a dependent slice segment per CTU row (dependent_slice_segments_enabled_flag); 2 = "tiles", a slice per tile
+  int lp_refs = 0;          // "lp-refs" n >= 2: n short-term RPS sets (set i: pictures -1 .. -(i + 1)), n references by default, DPB of n + 1 pictures; 0 / 1: one reference
 };
+
+// pictures the DPB holds beside the current one: sps/vps_max_dec_pic_buffering_minus1
+inline int dpb_minus1(const StreamParams &s) { return s.lp_refs > 1 ? s.lp_refs : 1; }
+// active references of a P picture `poc` pictures after its IDR picture
+inline int active_refs(const StreamParams &s, int poc) { const int n = s.lp_refs > 1 ? s.lp_refs : 1; return poc < n ? (poc < 1 ? 1 : poc) : n; }
 
 inline int level_idc_for(int w, int h)
 {
@@ -57,7 +63,7 @@ inline void write_vps(BitWriter &w, const StreamParams &s)
 {
   w.put(0, 4); w.put(3, 2); w.put(0, 6); w.put(0, 3); w.bit(1); w.put(0xffff, 16);
   write_ptl(w, level_idc_for(s.cw, s.ch));
-  w.bit(1); w.ue(1); w.ue(0); w.ue(0);                           // ordering info: dpb 2, no reorder
+  w.bit(1); w.ue((uint32_t)dpb_minus1(s)); w.ue(0); w.ue(0);     // ordering info: dpb 2 (lp-refs n: n + 1), no reorder
   w.put(0, 6); w.ue(0);
   w.bit(1); w.put((uint32_t)s.fps_den, 32); w.put((uint32_t)s.fps_num, 32); w.bit(0); w.ue(0);
   w.bit(0);
@@ -73,12 +79,19 @@ inline void write_sps(BitWriter &w, const StreamParams &s)
   w.bit(crop);
   if (crop) { w.ue(0); w.ue((uint32_t)(s.cw - s.width) / 2); w.ue(0); w.ue((uint32_t)(s.ch - s.height) / 2); }
   w.ue(0); w.ue(0); w.ue(4);                                     // 8-bit, log2_max_poc_lsb 8
-  w.bit(1); w.ue(1); w.ue(0); w.ue(0);
+  w.bit(1); w.ue((uint32_t)dpb_minus1(s)); w.ue(0); w.ue(0);
   w.ue(0); w.ue(3); w.ue(0); w.ue(3);                            // CB 8..64, TB 4..32
   w.ue(0); w.ue(0);                                              // transform hierarchy depths
   w.bit(s.scaling_list != 0); if (s.scaling_list) w.bit(0);       // scaling_list_enabled_flag (sps_scaling_list_data_present_flag = 0: Tables 7-5 / 7-6)
   w.bit(0); w.bit(s.sao != 0); w.bit(0);                          // amp, sao, pcm
-  w.ue(1); w.ue(1); w.ue(0); w.ue(0); w.bit(1);                  // one short-term RPS: previous picture
+  if (s.lp_refs > 1) {                                           // lp-refs n: set i = the i + 1 previous pictures, all used
+    w.ue((uint32_t)s.lp_refs);
+    for (int i = 0; i < s.lp_refs; i++) {
+      if (i) w.bit(0);                                             // inter_ref_pic_set_prediction_flag
+      w.ue((uint32_t)i + 1); w.ue(0);
+      for (int j = 0; j <= i; j++) { w.ue(0); w.bit(1); }          // delta_poc_s0_minus1 = 0 (each one picture further back), used_by_curr_pic_s0_flag
+    }
+  } else { w.ue(1); w.ue(1); w.ue(0); w.ue(0); w.bit(1); }       // one short-term RPS: previous picture
   w.bit(0); w.bit(0); w.bit(1);                                  // long-term, tmvp, strong intra smoothing
   w.bit(1);                                                      // VUI: timing only
   w.put(0, 8);
@@ -92,7 +105,7 @@ inline void write_pps(BitWriter &w, const StreamParams &s)
 {
   w.ue(0); w.ue(0);
   w.bit(s.slices == 1); w.bit(0); w.put(0, 3); w.bit(s.signhide != 0); w.bit(0);   // dependent_slice_segments_enabled_flag, output_flag_present, extra header bits, sign_data_hiding_enabled_flag, cabac_init_present
-  w.ue(0); w.ue(0);
+  w.ue((uint32_t)dpb_minus1(s) - 1); w.ue(0);                   // num_ref_idx_l0 / l1_default_active_minus1
   w.se(s.qp - 26);
   w.bit(0); w.bit(0); w.bit(s.qp_in_cu != 0);                    // constrained intra, transform skip, cu_qp_delta
   if (s.qp_in_cu) w.ue(0);                                       // diff_cu_qp_delta_depth
@@ -141,9 +154,17 @@ inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, in
   }
   if (!dependent) {
     w.ue(idr ? 2 : 1);
-    if (!idr) { w.put((uint32_t)poc & 255, 8); w.bit(1); }
+    const int nact = active_refs(s, poc);
+    if (!idr) {
+      w.put((uint32_t)poc & 255, 8); w.bit(1);
+      if (s.lp_refs > 1) { int bits = 0; while ((1 << bits) < s.lp_refs) bits++; w.put((uint32_t)nact - 1, bits); }     // short_term_ref_pic_set_idx
+    }
     if (s.sao) { w.bit(1); w.bit(1); }                             // slice_sao_luma_flag, slice_sao_chroma_flag
-    if (!idr) { w.bit(0); w.ue(0); }                               // num_ref_idx override, five_minus_max_num_merge_cand
+    if (!idr) {
+      const int ndef = dpb_minus1(s);
+      w.bit(nact != ndef); if (nact != ndef) w.ue((uint32_t)nact - 1);   // num_ref_idx_active_override_flag (fewer pictures since the IDR picture than lp-refs)
+      w.ue(0);                                                     // five_minus_max_num_merge_cand
+    }
     w.se(slice_qp_delta);                                          // against the PPS init_qp (= the configured QP)
     // (deblocking override not enabled; slice_loop_filter_across_slices_enabled_flag present when deblocking or SAO is on)
     if (s.deblock || s.sao) w.bit(1);

@@ -198,6 +198,7 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
   INT_OPT("gpu", gpu_device, 0, 64)
   BOOL_OPT("recon-output", recon_output)
   BOOL_OPT("intra-chain", intra_chain) BOOL_OPT("me-source", me_source) BOOL_OPT("input-hold", input_hold) INT_OPT("intra-in-p", intra_in_p, 0, 2)
+  INT_OPT("lp-refs", lp_refs, 0, 4)              // (extension: references per P picture, "uvgx multi-reference v1"; "ref" keeps accepting 1 only)
   if (n == "null-input") {
     if (!strcmp(value, "drain")) { cfg->null_input_poll = 0; return 1; }
     if (!strcmp(value, "poll")) { cfg->null_input_poll = 1; return 1; }
@@ -341,6 +342,7 @@ kvz_encoder *encoder_open(const kvz_config *cfg)
   // kvz_config.lossless (uvgComm writes the field itself, kvazaarfilter.cpp:244): cu_transquant_bypass in every coding unit (round 4, second half)
   ec.lossless = cfg->lossless != 0;
   ec.rdoq = cfg->rdoq_enable != 0; ec.signhide = cfg->signhide_enable != 0; ec.intra_in_p = cfg->intra_in_p; ec.me_source = cfg->me_source != 0;
+  ec.lp_refs = cfg->lp_refs > 1 ? cfg->lp_refs : 1;
   ec.hash = cfg->hash == KVZ_HASH_MD5 ? 2 : (cfg->hash == KVZ_HASH_CHECKSUM ? 1 : 0);
   ec.vaq = cfg->vaq > 0 ? cfg->vaq : 0;
   ec.qp_in_cu = (cfg->set_qp_in_cu || ec.vaq > 0) ? 1 : 0;

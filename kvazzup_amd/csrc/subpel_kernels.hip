@@ -172,6 +172,7 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
   const int X = x0 + (w & 1) * 16, Y = y0 + (w >> 1) * 16;  // this wave's quadrant
   const int bq = b8idx(f, X, Y);
   const int mvx0 = f.cu_mv[bq * 2], mvy0 = f.cu_mv[bq * 2 + 1], ix = mvx0 >> 2, iy = mvy0 >> 2;    // integer vector (multiples of 4)
+  const uint8_t *rp = ref_plane(f, cu_ref_at(f, bq), 0);   // lp-refs: the reference the search chose (the refinement never changes it)
   const int ux = split ? X : x0, uy = split ? Y : y0, un = split ? 16 : 32;                          // the coding unit the quadrant belongs to
   int ty0 = 0, ty1 = f.ch;
   if (f.tile_rows > 1) {
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
     if (wx0 >= 0 && wx0 + 24 <= f.cw && wy0 >= 0 && wy0 + 24 <= f.ch) {
       for (int i = l2; i < 144; i += 128) {
         const int wy = i / 6, k = i - wy * 6;
-        const uint8_t *p = f.ref[0] + (size_t)(wy0 + wy) * f.cw + wx0 + 4 * k;
+        const uint8_t *p = rp + (size_t)(wy0 + wy) * f.cw + wx0 + 4 * k;
         const uint32_t *q = (const uint32_t *)((uintptr_t)p & ~(uintptr_t)3);
         const uint32_t sh = (uint32_t)((uintptr_t)p & 3);
         *(uint32_t *)&win[wy * 24 + 4 * k] = sh ? __builtin_amdgcn_alignbyte(q[1], q[0], sh) : q[0];
@@ -199,7 +200,7 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
     } else {
       for (int i = l2; i < 24 * 24; i += 128) {
         const int wy = i / 24, wx = i - wy * 24;
-        win[i] = f.ref[0][(size_t)clip3(0, f.ch - 1, wy0 + wy) * f.cw + clip3(0, f.cw - 1, wx0 + wx)];
+        win[i] = rp[(size_t)clip3(0, f.ch - 1, wy0 + wy) * f.cw + clip3(0, f.cw - 1, wx0 + wx)];
       }
     }
   }

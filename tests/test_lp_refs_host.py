@@ -1,0 +1,242 @@
+"""CPU side of "uvgx multi-reference v1" (kvazaar.h lp-refs): the option's parsing, the parameter sets and slice headers with n
+references read back by tests/pyhevc.py, the reference-aware merge / AMVP derivation of hevc_core.h (host build: tests/hostrefs) against pyhevc's, and the
+numpy restatement of the search (tests/lp_refs_model.py) pinned to the checker's single-reference encoder."""
+import ctypes as C
+import fcntl
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import orc
+import pyhevc
+import lp_refs_model
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = None
+
+
+def hr():
+    global _LIB
+    if _LIB is None:
+        d = os.path.join(ROOT, "tests", "hostrefs")
+        with open(os.path.join(d, ".build.lock"), "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
+        L = C.CDLL(os.path.join(d, "build", "libhostrefs.so"))
+        P = C.c_void_p
+        L.hr_header.argtypes = [C.c_int] * 4 + [P, C.c_int]
+        L.hr_cands.argtypes = [C.c_int] * 5 + [P] * 5 + [C.c_int] * 3 + [P] * 3
+        L.hr_ref_idx_tokens.argtypes = [C.c_int, C.c_int, P, C.c_int]
+        _LIB = L
+    return _LIB
+
+
+def header(which, n, poc=0, sao=0):
+    buf = np.zeros(512, np.uint8)
+    k = hr().hr_header(which, n, poc, sao, buf.ctypes.data, len(buf))
+    assert k > 0
+    return bytes(buf[:k])
+
+
+# ---- 1. config_parse
+@pytest.fixture(scope="module")
+def api():
+    from kvazzup_amd import _native
+    if not os.path.exists(_native.library_path()):
+        _native.build_library()
+    lib = _native.load_library()
+    return lib.kvz_api_get(8).contents
+
+
+def test_config_parse_lp_refs(api):
+    cfg = api.config_alloc()
+    api.config_init(cfg)
+    ok = lambda k, v: api.config_parse(cfg, k.encode(), v.encode())
+    assert cfg.contents.lp_refs == 0
+    for v in range(5):
+        assert ok("lp-refs", str(v)) == 1 and cfg.contents.lp_refs == v
+    for bad in ("5", "-1", "x", ""):
+        assert ok("lp-refs", bad) == 0, bad
+    assert cfg.contents.lp_refs == 4
+    assert ok("ref", "3") == 0 and ok("ref", "1") == 1                  # "ref" keeps its meaning
+    assert ok("gop", "lp-g4d3t1") == 1 and cfg.contents.lp_refs == 4    # ... and "gop" its "accepted, no effect"
+    assert ok("preset", "veryfast") == 1 and cfg.contents.lp_refs == 4  # no preset touches it
+    api.config_destroy(cfg)
+
+
+# ---- 2. parameter sets and slice headers
+def test_one_reference_headers_are_unchanged():
+    """lp-refs 0 and 1 write the bytes of the one-reference writers, which the checker's encoder writes too"""
+    for which in range(3):
+        assert header(which, 0) == header(which, 1)
+    for poc in range(5):
+        assert header(3, 0, poc) == header(3, 1, poc)
+    oe = orc.OracleEncoder(256, 128, qp=32, period=64, me_range=8)
+    nals = [n for n in orc.split_nals(oe.encode(orc.synth_frame(0, 1, 256, 128, 0)))]
+    oe.close()
+    got = {32: header(0, 0), 33: header(1, 0), 34: header(2, 0)}
+    for nal in nals:
+        t = (nal[0] >> 1) & 63
+        if t in got:
+            assert pyhevc.unescape(nal)[2:] == got[t], t
+
+
+@pytest.mark.parametrize("n", [2, 3, 4])
+def test_reference_sets_and_counts(n):
+    sps = pyhevc.parse_sps(b"\x42\x01" + header(1, n))
+    assert [[d for d, used in s] for s in sps["rps"]] == [[-(j + 1) for j in range(i + 1)] for i in range(n)]
+    assert all(used for s in sps["rps"] for _, used in s)
+    pps = pyhevc.parse_pps(b"\x44\x01" + header(2, n))
+    assert pps["nref_default"] == n
+    # max_dec_pic_buffering_minus1 = n in the VPS (ordering info right behind the profile / level) and in the SPS
+    r = pyhevc.Bits(header(0, n))
+    r.u(32)
+    pyhevc.parse_ptl(r, 0)
+    r.u(1)
+    assert r.ue() == n
+    r = pyhevc.Bits(header(1, n))
+    r.u(8)
+    pyhevc.parse_ptl(r, 0)
+    for _ in range(4):
+        r.ue()                                          # id, chroma format, width, height
+    r.u(1); r.ue(); r.ue(); r.ue(); r.u(1)              # no cropping, bit depths, POC bits, ordering info present
+    assert r.ue() == n
+    # slice headers: the set index and override of the pictures 1 .. n + 1 after the IDR picture give 1, 2, .., n, n references
+    for poc in range(1, n + 2):
+        r = pyhevc.Bits(header(3, n, poc))
+        assert r.u(1) == 1                              # first_slice_segment_in_pic_flag
+        assert r.ue() == 0 and r.ue() == 1              # pps id, slice_type P
+        assert r.u(8) == poc and r.u(1) == 1            # POC LSBs, the set comes from the SPS
+        idx = r.u((n - 1).bit_length())
+        assert len(sps["rps"][idx]) == min(n, poc)
+        over = r.u(1)
+        nact = r.ue() + 1 if over else pps["nref_default"]
+        assert nact == min(n, poc) and over == (poc < n)
+        assert r.ue() == 0                              # five_minus_max_num_merge_cand
+
+
+def test_ref_idx_binarisation():
+    out = np.zeros(8, np.uint16)
+    for n in range(2, 5):
+        for r in range(n):
+            k = hr().hr_ref_idx_tokens(r, n, out.ctypes.data, 8)
+            bins = [int(t) & 1 for t in out[:k]]
+            assert bins == [1] * r + ([0] if r < n - 1 else []), (n, r, bins)
+            ctx = [(int(t) >> 1) for t in out[:k] if not (int(t) & 0x8000)]
+            assert ctx == [24, 25][:min(k, 2)], (n, r)          # CTX_REF_IDX + 0 / + 1, later bins bypass
+            assert lp_refs_model.ref_bins(r, n) == k
+
+
+# ---- 3. merge / AMVP with reference indices against pyhevc's derivation
+class _Pic:
+    pass
+
+
+class _Ref:
+    def __init__(self, poc):
+        self.poc, self.is_lt = poc, False
+
+
+class _Stub:
+    """the state pyhevc.SliceDecoder's merge / AMVP derivations read, filled from one motion field"""
+    merge_candidates = pyhevc.SliceDecoder.merge_candidates
+    amvp_candidates = pyhevc.SliceDecoder.amvp_candidates
+    pb_avail = pyhevc.SliceDecoder.pb_avail
+    avail = pyhevc.SliceDecoder.avail
+    zaddr = pyhevc.SliceDecoder.zaddr
+    motion = pyhevc.SliceDecoder.motion
+    temporal = pyhevc.SliceDecoder.temporal
+    scale = staticmethod(pyhevc.SliceDecoder.scale)
+
+    def __init__(self, cw, ch, tr, tc, nref, intra, mv, ref, poc=10):
+        self.w, self.h, self.ctb_log2, self.ctb, self.wc = cw, ch, 6, 64, cw // 64
+        rows, cols = ch // 64, cw // 64
+        self.tile_of_row = [next(i for i in range(tr) if (i * rows) // tr <= y < ((i + 1) * rows) // tr) for y in range(rows)]
+        self.tile_of_col = [next(i for i in range(tc) if (i * cols) // tc <= x < ((i + 1) * cols) // tc) for x in range(cols)]
+        self.ctb_slice = [-1] * (rows * cols)
+        self.sps = {"min_cb": 3}
+        self.pps = {"par_mrg": 2}
+        self.cu_pred = intra.astype(np.int32)
+        self.pic = _Pic()
+        self.pic.mv = np.zeros((ch // 4, cw // 4, 2, 2), np.int32)
+        self.pic.mv[:, :, 0, :] = np.repeat(np.repeat(mv, 2, 0), 2, 1)
+        self.pic.ref_idx = np.full((ch // 4, cw // 4, 2), -1, np.int32)
+        self.pic.ref_idx[:, :, 0] = np.repeat(np.repeat(ref, 2, 0), 2, 1)
+        self.refs = [[_Ref(poc - 1 - k) for k in range(nref)], []]
+        self.sh = {"poc": poc, "max_merge": 5, "b": False, "nref": nref, "tmvp": False}
+
+
+def _motion_field(rng, cw, ch, nref):
+    """a random quadtree of 32x32 / 16x16 / 8x8 units: some intra, vectors from a small set (so that neighbours often agree), random references"""
+    b8h, b8w = ch // 8, cw // 8
+    log2 = np.zeros((b8h, b8w), np.uint8); intra = np.zeros_like(log2); ref = np.zeros_like(log2); cbf = np.zeros_like(log2)
+    mv = np.zeros((b8h, b8w, 2), np.int16)
+    pool = [(0, 0), (4, 0), (-8, 4), (12, -4), (4, 0), (3, -1), (-33, 17), (100, -60)]
+    for y in range(0, ch, 32):
+        for x in range(0, cw, 32):
+            l = rng.choice((5, 4, 4, 3))
+            for yy in range(y, y + 32, 1 << l):
+                for xx in range(x, x + 32, 1 << l):
+                    sl = (slice(yy // 8, (yy + (1 << l)) // 8), slice(xx // 8, (xx + (1 << l)) // 8))
+                    log2[sl] = l
+                    intra[sl] = rng.random() < 0.12
+                    mv[sl] = pool[rng.randrange(len(pool))] if rng.random() < 0.8 else (rng.randrange(-200, 200), rng.randrange(-120, 120))
+                    ref[sl] = rng.randrange(nref)
+                    cbf[sl] = rng.random() < 0.5
+    return log2, intra, mv, ref, cbf
+
+
+@pytest.mark.parametrize("seed", range(12))
+def test_merge_and_amvp_match_pyhevc(seed):
+    rng = random.Random(seed)
+    cw, ch = rng.choice(((256, 128), (192, 192), (320, 128)))
+    tr, tc = rng.choice(((1, 1), (2, 1), (1, 2), (2, 2)))
+    nref = rng.choice((1, 2, 3, 4))
+    log2, intra, mv, ref, cbf = _motion_field(rng, cw, ch, nref)
+    stub = _Stub(cw, ch, tr, tc, nref, intra, mv, ref)
+    merge = np.zeros(15, np.int32); amvp = np.zeros(4, np.int32); sig = np.zeros(5, np.int32)
+    a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
+    scaled = 0
+    for y in range(0, ch, 8):
+        for x in range(0, cw, 8):
+            l = int(log2[y // 8, x // 8])
+            if intra[y // 8, x // 8] or (x | y) & ((1 << l) - 1):
+                continue
+            hr().hr_cands(cw, ch, tr, tc, nref, *[v.ctypes.data for v in a], x, y, l, merge.ctypes.data, amvp.ctypes.data, sig.ctypes.data)
+            n = 1 << l
+            want_m = [(c[0], c[1], c[2]) for c in stub.merge_candidates(x, y, n, x, y, n, n, 0, 0)]
+            assert [tuple(merge[3 * k:3 * k + 3]) for k in range(5)] == want_m, (seed, x, y)
+            r = int(ref[y // 8, x // 8])
+            want_a = [tuple(c) for c in stub.amvp_candidates(x, y, n, x, y, n, n, 0, 0, r)]
+            assert [tuple(amvp[2 * k:2 * k + 2]) for k in range(2)] == want_a, (seed, x, y, r)
+            own = (int(mv[y // 8, x // 8, 0]), int(mv[y // 8, x // 8, 1]))
+            scaled += any(c not in [tuple(v) for v in mv.reshape(-1, 2).tolist()] for c in want_a)
+            # the signalling: merge with the first candidate equal in vector AND reference, else AMVP for the own reference
+            first = next((k for k, c in enumerate(want_m) if (c[0], c[1], c[2]) == own + (r,)), None)
+            if first is not None:
+                assert sig[0] & 2 and sig[1] == first
+            else:
+                assert sig[0] == 0 and (own[0] - sig[3], own[1] - sig[4]) == want_a[sig[2]]
+    if nref > 1:
+        assert scaled > 0 or seed % 3, "no scaled AMVP candidate came up"
+
+
+# ---- 4. the search model, pinned to the checker with one reference
+@pytest.mark.parametrize("w,h,qp,me_range,kind,me_early", [(256, 128, 32, 8, 0, 1), (192, 128, 27, 6, 2, 0), (256, 192, 37, 8, 0, 0)])
+def test_search_model_reproduces_the_checker_with_one_reference(w, h, qp, me_range, kind, me_early):
+    oe = orc.OracleEncoder(w, h, qp=qp, period=64, me_range=me_range, me_early=me_early, subme=0)
+    prev = None
+    for t in range(3):
+        f = orc.synth_frame(kind, 0x5EED0000, w, h, t)
+        oe.encode(f)
+        d = oe.debug()
+        if prev is not None:
+            log2, mv, rf = lp_refs_model.search(f[:w * h].reshape(h, w), [prev], qp, me_range, me_early=me_early)
+            assert np.array_equal(log2, d["cu_log2"]), t
+            assert np.array_equal(mv, d["cu_mv"]), t
+            assert not rf.any()
+        prev = oe.recon()[:w * h].reshape(h, w)
+    oe.close()

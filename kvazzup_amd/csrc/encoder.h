@@ -132,6 +132,13 @@ class Encoder {
   bool submit(const uint8_t *d_i420, int in_ring);   // in_ring >= 0: the picture is being uploaded into d_in_[in_ring] (encode_host)
   bool collect(EncodedPicture *out);
   struct Slot;
+  // submit() in stages: plan (sets set_, POC, rate control), the picture's frame, then the input stage, its chain and the hand-off, in this order
+  struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; };   // side: the chain on stream_idr_; ahead: me-source search on the input stream; ms: the chain's stream
+  Plan plan(int set);
+  EncFrame picture_frame(const Plan &p, const Slot &sl, uint32_t chain_gen) const;
+  bool input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i420, int in_ring);
+  bool chain_stage(const EncFrame &f, const Plan &p);
+  bool hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring);
   bool finish_slot(Slot &sl, EncodedPicture *out, int worker = 0);   // wait for the slot's kernels, arithmetic coding, access unit
   void background(int worker);
   void timed(KernelId id, hipStream_t st, const std::function<void()> &launch);
@@ -139,19 +146,17 @@ class Encoder {
   EncoderConfig cfg_;
   int cw_ = 0, ch_ = 0, rows_ = 0;
   hipStream_t stream_ = nullptr;
-  EncFrame f_{};
-  // Host pictures (kvz_api->encoder_encode, kvazaarfilter.cpp:435-438): a ring of packed device buffers filled by the copy engine on a
-  // stream of its own -- picture t + 1 travels over PCIe while the kernels of picture t run -- and, for callers whose planes are not
+  EncFrame base_{};                      // what does not change from picture to picture: geometry, options, scratch, tokenizer buffers, the main chain's arrays (written by init only)
+  // Host pictures (kvz_api->encoder_encode, kvazaarfilter.cpp:435-438): a ring of packed device buffers filled by the copy engine ahead of
+  // each picture's input stage -- picture t + 1 travels over PCIe while the kernels of picture t run -- and, for callers whose planes are not
   // page-locked, a ring of pinned staging buffers (allocated on first use).  Twelve entries: more than the pictures that can be in flight
   // (owf <= 8 plus the submitter's hand), so a copy never waits in the copy engine's queue for its buffer's previous reader.
   static constexpr int kInRing = 20;
   uint8_t *d_in_[kInRing] = {};          // packed input (device)
   uint8_t *h_in_[kInRing] = {};          // pinned host staging
-  hipStream_t stream_h2d_ = nullptr;
   hipEvent_t ev_h2d_[kInRing] = {}, ev_pad_[kInRing] = {}; bool pad_pending_[kInRing] = {}, h2d_pending_[kInRing] = {};
   long in_count_ = 0;
   hipStream_t stream_rec_ = nullptr;     // download of reconstructions the caller asks for (encoder_encode's pic_out)
-  uint32_t *probe_words_ = nullptr;      // KVAZZUP_AMD_PARSE_PROBE: {wrong bins, bins} of k_cabac_decode_probe
   // Per-picture working sets (padded source planes, level planes, CU arrays, per-CTU QP arrays, SAO parameters): kSets of them take turns, so the
   // host can queue kSets - 1 pictures' kernels ahead of the one the GPU is working on without waiting for a set to come free (with two sets
   // the input stage of picture t waited for the reconstruction of t - 2, and the calling thread with it: the main stream ran dry between pictures)
@@ -181,12 +186,12 @@ class Encoder {
   const int8_t *roi_dev_ = nullptr;
   int *vaq_act_ = nullptr, *vaq_sum_ = nullptr; // VAQ: activity of every CTU, its sum over the picture
   uint32_t next_chain_gen();
-  bool picture_begin(hipStream_t qt_stream, EncFrame *fold = nullptr, bool zero = false);     // fold: a P picture without VAQ -- the work rides in the picture's k_me launch (EncFrame::pb_*) instead of a launch of its own   // launch_picture_begin: the rate control state on the main stream (picture order), the per-CTU targets on the picture's own stream (+ the VAQ kernels)
+  bool picture_begin(const EncFrame &f, hipStream_t qt_stream, EncFrame *fold = nullptr, bool zero = false);     // fold: a P picture without VAQ -- the work rides in the picture's k_me launch (EncFrame::pb_*) instead of a launch of its own   // launch_picture_begin: the rate control state on the main stream (picture order), the per-CTU targets on the picture's own stream (+ the VAQ kernels)
   int qp_cur_ = 0; int64_t rc_debt_ = 0; uint32_t rc_bytes_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint32_t rc_known_ = 0;   // rate control state (calling thread)
   void rate_control();
   RcState *rc_state_ = nullptr;                 // rate control v2: device-side state
   bool band_picture_setup();
-  bool band_intra_ = false;
+  EncFrame band_f_{};                    // band mode: the frame of the picture between band_phase1 and band_phase2b
   hipStream_t stream_tok_ = nullptr;     // signalling decisions, tokenizer, compaction
   hipStream_t stream_in_ = nullptr;      // input padding (runs ahead of the previous picture's kernels)
   hipEvent_t ev_src_free_[kSets] = {}; bool src_busy_[kSets] = {};
@@ -200,7 +205,6 @@ class Encoder {
   // pictures, per-CTU QPs and rate control v2 -- uvgComm's default mode): progress counters + ticket word, the CTUs' edge columns, the SAO work picture
   uint32_t *sync_idr_ = nullptr; uint32_t *edge_col_idr_ = nullptr; uint32_t chain_gen_ = 0; unsigned long long *edge_row_ = nullptr, *edge_row_idr_ = nullptr; uint8_t *work_idr_[3] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_signalled_ = nullptr, ev_tok_done_[kSets] = {}; bool tok_pending_[kSets] = {};
-  void bind_set(int k);
   uint8_t *intra_scratch_ = nullptr;
   uint8_t *d_scaling_ = nullptr;          // scaling-list default: KVZ_SCALING_BYTES scaling factors
   uint16_t *tok_buf_ = nullptr; int tok_cap_ = 0; int32_t *tok_count_ = nullptr; uint32_t *tok_seg_ = nullptr; uint32_t *tok_list_ = nullptr; int tok_nctu_ = 0;

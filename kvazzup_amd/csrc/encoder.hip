@@ -14,11 +14,27 @@ namespace kvzx {
 
 // Events that only order this library's streams among themselves (never waited for or queried by the host): no system-scope fence when they complete --
 // the default makes every record write back and invalidate the caches for the host's benefit, a bubble of its own in a chain of 10-50 us kernels.
-// KVAZZUP_AMD_EVENT_FENCE=1 restores the default (measurement aid).
-static const unsigned kDeviceEvent = hipEventDisableTiming | (getenv("KVAZZUP_AMD_EVENT_FENCE") ? 0u : (unsigned)hipEventDisableSystemFence);
+static const unsigned kDeviceEvent = hipEventDisableTiming | hipEventDisableSystemFence;
 
 #define HIP_OK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { if (error) *error = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } } while (0)
 #define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fprintf(stderr, "kvazzup_amd: %s failed: %s\n", #expr, hipGetErrorString(e_)); return false; } } while (0)
+
+// the me-source block of one working set, or the shared one: k_me's 16x16 costs, the candidate list with the intra pricing's arrival counters and scratch
+static void point_me_block(EncFrame &f, uint32_t *block)
+{
+  const size_t n16 = (size_t)(f.cw / 16) * (f.ch / 16);
+  f.me_cost16 = block; f.me_cand = block + n16;
+  f.ip_arrive = f.me_cand + 1 + n16 / 4; f.ip_scratch = (uint64_t *)(block + ((n16 + 1 + n16 / 4 + n16 / 4 + 1) & ~(size_t)1));      // (8-byte aligned)
+}
+
+// the arrays of one intra chain: progress counters, and per plane the CTUs' right columns and bottom rows
+static void point_chain(EncFrame &f, uint32_t *sync, uint32_t *col, unsigned long long *row)
+{
+  const size_t nctu = (size_t)(f.cw / 64) * (f.ch / 64);
+  f.sync = sync;
+  f.edge_col[0] = col; f.edge_col[1] = col + nctu * 64; f.edge_col[2] = col + nctu * 96;
+  f.edge_row[0] = row; f.edge_row[1] = row + nctu * 16; f.edge_row[2] = row + nctu * 24;
+}
 
 Encoder *Encoder::create(const EncoderConfig &cfg, std::string *error)
 {
@@ -58,7 +74,6 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
                     tile_row_ends_at(hc, T, cfg.band_row0 + cfg.band_rows - 1) && !cfg.sao && cfg.vaq == 0;
     if (!ok) { if (error) *error = "a band must consist of whole tile rows (and SAO and VAQ are not available in band mode)"; return false; }
   }
-  if (const char *e = getenv("KVAZZUP_AMD_ENTROPY")) cfg.entropy_gpu = strcmp(e, "gpu") == 0;    // A/B knob: host | gpu
   if (cfg.band_rows > 0) cfg.entropy_gpu = 0;               // (band mode hands its substreams to the caller from the host pool)
   if (cfg.band_rows > 0) cfg.hash = 0;                      // (a band encoder holds a part of the picture only)
   cfg_ = cfg;
@@ -124,11 +139,11 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   // progress counters, edge columns and SAO work picture; VAQ still does: its activity scratch is shared)
   // (not when every picture is an intra picture: then the chains ARE the main stream's work, and the next picture's analysis belongs beside them on the
   // input stream, not behind them -- all-intra 1080p 940 -> 1 300 frames/s)
-  idr_side_ = depth_ >= 2 && cfg.vaq == 0 && cfg.band_rows == 0 && cfg.intra_period != 1 && !getenv("KVAZZUP_AMD_IDR_INLINE");
+  idr_side_ = depth_ >= 2 && cfg.vaq == 0 && cfg.band_rows == 0 && cfg.intra_period != 1;
   // Every picture an intra picture (BASELINE configs[0]): no picture depends on another, and one chain keeps a few dozen compute units busy for 0.7 ms --
   // the pictures ALTERNATE between the main stream with its arrays and a second stream with the side chain's (round 5: all-intra 1080p was bound by
   // one chain after the other, 1 / (0.67 + 0.03 ms)).  The second stream is one of its own here: the input stream carries every picture's analysis.
-  all_intra_alt_ = depth_ >= 2 && cfg.vaq == 0 && cfg.band_rows == 0 && cfg.intra_period == 1 && !getenv("KVAZZUP_AMD_IDR_INLINE");
+  all_intra_alt_ = depth_ >= 2 && cfg.vaq == 0 && cfg.band_rows == 0 && cfg.intra_period == 1;
   if (idr_side_ || all_intra_alt_) {
     const size_t nsync = ((size_t)rows_ * (cw_ / 64) * 3 + 2 + 3) & ~(size_t)3, nctu_ = (size_t)(cw_ / 64) * rows_;
     HIP_OK(hipMalloc(&sync_idr_, sizeof(uint32_t) * nsync)); HIP_OK(hipMemset(sync_idr_, 0, sizeof(uint32_t) * nsync));
@@ -137,9 +152,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     if (cfg.sao) { const size_t npx_ = (size_t)cw_ * ch_; for (int c = 0; c < 3; c++) HIP_OK(hipMalloc(&work_idr_[c], c ? npx_ / 4 : npx_)); }
     // ... which is the INPUT stream: the pictures behind an intra picture need it anyway, so their input stages lose nothing by queueing behind
     // its chain, and a further stream would share a hardware queue with one that matters (HIP spreads a priority level's streams over four;
-    // measured with a stream of its own: no gain at the default level, half the rate at any other -- KVAZZUP_AMD_IDR_PRIO)
-    const char *lv = getenv("KVAZZUP_AMD_IDR_PRIO");
-    if (lv || all_intra_alt_) HIP_OK(stream_acquire(&stream_idr_, cfg.device, 'X', lv ? lv[0] : prio_[0])); else stream_idr_ = stream_in_;
+    // measured with a stream of its own: no gain at the default level, half the rate at any other)
+    if (all_intra_alt_) HIP_OK(stream_acquire(&stream_idr_, cfg.device, 'X', prio_[0])); else stream_idr_ = stream_in_;
     HIP_OK(hipEventCreateWithFlags(&ev_idr_done_, kDeviceEvent));
   }
   // intra scratch: ic8 (nb8 u32) | ic16 (nb8/4 u32) | ic32 (nb8/16 u32) | im8 | im16 | im32
@@ -201,8 +215,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     // dispatch order of the intra reconstruction's workgroups: the CTUs of the rows this instance codes, by anti-diagonal cx + 2 cy
     const int wc = cw_ / 64, r0 = cfg.band_rows > 0 ? cfg.band_row0 : 0, nr = cfg.band_rows > 0 ? cfg.band_rows : rows_;
     std::vector<uint32_t> order;
-    const int slope = getenv("KVAZZUP_AMD_INTRA_SLOPE") ? atoi(getenv("KVAZZUP_AMD_INTRA_SLOPE")) : 2;
-    for (int d = 0; d < wc + slope * nr; d++) for (int cy = 0; cy < nr; cy++) { const int cx = d - slope * cy; if (cx >= 0 && cx < wc) order.push_back((uint32_t)((r0 + cy) * wc + cx)); }
+    for (int d = 0; d < wc + 2 * nr; d++) for (int cy = 0; cy < nr; cy++) { const int cx = d - 2 * cy; if (cx >= 0 && cx < wc) order.push_back((uint32_t)((r0 + cy) * wc + cx)); }
     HIP_OK(hipMalloc(&intra_order_, sizeof(uint32_t) * order.size()));
     HIP_OK(hipMemcpy(intra_order_, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice));
   }
@@ -218,66 +231,50 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     entropy2_ = new EntropyHost(eth / 2 < rows_ ? eth / 2 : rows_);
   } else entropy_ = new EntropyHost(eth < rows_ ? eth : rows_);
 
-  memset(&f_, 0, sizeof(f_));
-  f_.cw = cw_; f_.ch = ch_; f_.b8w = cw_ / 8; f_.b8h = ch_ / 8;
-  f_.tile_rows = cfg.tile_rows; f_.tile_cols = cfg.tile_cols; f_.chp = pack_height(ch_, cfg.tile_rows, cfg.tile_cols);
-  f_.row0 = cfg.band_rows > 0 ? cfg.band_row0 : 0; f_.nrows = cfg.band_rows > 0 ? cfg.band_rows : 0;
-  f_.qp = cfg.qp; f_.qpc = kChromaQp[cfg.qp]; f_.lambda_q4 = kLambdaQ4[cfg.qp]; f_.range = cfg.me_range;
   if (cfg.scaling_list) {                                 // `scaling-list default`: the default lists' factors, once
     uint8_t tab[KVZ_SCALING_BYTES];
     scaling_factors(scaling_defaults(), tab);
     HIP_OK(hipMalloc(&d_scaling_, KVZ_SCALING_BYTES)); HIP_OK(hipMemcpy(d_scaling_, tab, KVZ_SCALING_BYTES, hipMemcpyHostToDevice));
   }
-  f_.scaling = d_scaling_; f_.intra_chain = cfg.intra_chain;
-  f_.lossless = cfg.lossless; f_.rdoq = cfg.rdoq; f_.signhide = cfg.signhide; f_.intra_p = cfg.intra_in_p; f_.me_cost16 = me_cost16_; f_.me_cand = me_cost16_ ? me_cost16_ + (size_t)(cw_ / 16) * (ch_ / 16) : nullptr;
-  if (me_cost16_) { const size_t n16 = (size_t)(cw_ / 16) * (ch_ / 16); f_.ip_arrive = f_.me_cand + 1 + n16 / 4; f_.ip_scratch = (uint64_t *)(me_cost16_ + ((n16 + 1 + n16 / 4 + n16 / 4 + 1) & ~(size_t)1)); }      // (8-byte aligned)
-  f_.wpp = cfg.wpp; f_.mv_frame = cfg.mv_frame; f_.me_early = cfg.me_early; f_.satd = cfg.satd; f_.subme = cfg.subme; f_.slices = cfg.slices;
-  bind_set(0);
+  // what every picture's frame starts from (picture_frame)
+  EncFrame &b = base_;
+  b.cw = cw_; b.ch = ch_; b.b8w = cw_ / 8; b.b8h = ch_ / 8;
+  b.tile_rows = cfg.tile_rows; b.tile_cols = cfg.tile_cols; b.chp = pack_height(ch_, cfg.tile_rows, cfg.tile_cols);
+  b.row0 = cfg.band_rows > 0 ? cfg.band_row0 : 0; b.nrows = cfg.band_rows > 0 ? cfg.band_rows : 0;
+  b.range = cfg.me_range; b.scaling = d_scaling_; b.intra_chain = cfg.intra_chain;
+  b.lossless = cfg.lossless; b.rdoq = cfg.rdoq; b.signhide = cfg.signhide; b.intra_p = cfg.intra_in_p;
+  if (me_cost16_) point_me_block(b, me_cost16_);
+  b.wpp = cfg.wpp; b.mv_frame = cfg.mv_frame; b.me_early = cfg.me_early; b.satd = cfg.satd; b.subme = cfg.subme; b.slices = cfg.slices;
   uint8_t *p = intra_scratch_;
-  f_.ic8 = (uint32_t *)p; p += nb8 * 4; f_.ic16 = (uint32_t *)p; p += nb8; f_.ic32 = (uint32_t *)p; p += nb8 / 4;
-  f_.im8 = p; p += nb8; f_.im16 = p; p += nb8 / 4; f_.im32 = p;
-  f_.tok_buf = tok_buf_; f_.tok_cap = tok_cap_; f_.tok_cursor = (uint32_t *)tok_count_; f_.tok_cursor_next = (uint32_t *)tok_count_ + tok_nctu_; f_.tok_seg = tok_seg_; f_.tok_list = tok_list_;
-  f_.tok_dense_cap = (uint32_t)tok_dense_cap_;
-  { const size_t nctu = (size_t)(cw_ / 64) * rows_; f_.edge_col[0] = edge_col_; f_.edge_col[1] = edge_col_ + nctu * 64; f_.edge_col[2] = edge_col_ + nctu * 96;
-    f_.edge_row[0] = edge_row_; f_.edge_row[1] = edge_row_ + nctu * 16; f_.edge_row[2] = edge_row_ + nctu * 24; }
-  f_.sync = sync_; f_.err = err_; f_.trace = trace_; f_.intra_order = intra_order_;
+  b.ic8 = (uint32_t *)p; p += nb8 * 4; b.ic16 = (uint32_t *)p; p += nb8; b.ic32 = (uint32_t *)p; p += nb8 / 4;
+  b.im8 = p; p += nb8; b.im16 = p; p += nb8 / 4; b.im32 = p;
+  b.tok_buf = tok_buf_; b.tok_cap = tok_cap_; b.tok_seg = tok_seg_; b.tok_list = tok_list_; b.tok_dense_cap = (uint32_t)tok_dense_cap_;
+  point_chain(b, sync_, edge_col_, edge_row_);
+  b.err = err_; b.trace = trace_; b.intra_order = intra_order_;
+  // (a synchronous encoder: the cap that keeps the search from holding every wave slot protects nobody -- 185 -> 142 us of an intra picture's encoding delay
+  // at 1080p; band mode keeps the cap)
+  b.analyse_alone = depth_ < 2 && cfg.band_rows == 0 ? 1 : 0;
+  // (two pictures' chains side by side: two anti-diagonals of workgroups each -- all-intra 2 030 -> 2 110 frames/s; a lone chain is 2.5 % slower with two,
+  // 670 -> 687 us: profiles/r05_intra_diags.txt)
+  b.chain_diags = all_intra_alt_ ? 2 : 0;
 
   sp_.cw = cw_; sp_.ch = ch_; sp_.width = cfg.width; sp_.height = cfg.height; sp_.qp = cfg.qp; sp_.wpp = cfg.wpp; sp_.tile_rows = cfg.tile_rows; sp_.tile_cols = cfg.tile_cols; sp_.qp_in_cu = cfg.qp_in_cu; sp_.sao = cfg.sao; sp_.slices = cfg.slices; sp_.signhide = cfg.signhide; sp_.scaling_list = cfg.scaling_list; sp_.tq_bypass = cfg.lossless;
   sp_.lp_refs = cfg.lp_refs > 1 ? cfg.lp_refs : 0;
   sp_.deblock = cfg.deblock; sp_.fps_num = cfg.fps_num; sp_.fps_den = cfg.fps_den;
   HIP_OK(hipStreamSynchronize(stream_));
   HIP_OK(hipDeviceSynchronize());
-  tok_deferred_ = depth_ >= 2 && cfg.sao && !cfg.entropy_gpu && cfg.band_rows == 0 && cfg.owf <= kSets - 1 && !getenv("KVAZZUP_AMD_TOK_INLINE");
+  tok_deferred_ = depth_ >= 2 && cfg.sao && !cfg.entropy_gpu && cfg.band_rows == 0 && cfg.owf <= kSets - 1;
   HIP_OK(hipDeviceSynchronize());                        // (every clear above ran on the null stream: done before anything is queued on the encoder's non-blocking streams)
   if (tok_deferred_) tok_thread_ = std::thread([this] { name_this_thread("kvzx-enc-tok"); tok_launcher(); });
   if (depth_ >= 2) { bg_[0] = std::thread([this] { name_this_thread("kvzx-enc-bg0"); background(0); }); if (entropy2_) bg_[1] = std::thread([this] { name_this_thread("kvzx-enc-bg1"); background(1); }); }
-  if (depth_ >= 2 && cfg.band_rows == 0 && !getenv("KVAZZUP_AMD_SYNC_SUBMIT")) sub_thread_ = std::thread([this] { name_this_thread("kvzx-enc-sub"); submitter(); });
+  if (depth_ >= 2 && cfg.band_rows == 0) sub_thread_ = std::thread([this] { name_this_thread("kvzx-enc-sub"); submitter(); });
   return true;
 }
 
 namespace { struct Tick { std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } }; }
 
-void Encoder::bind_set(int k)
-{
-  const size_t nb8 = (size_t)cw_ * ch_ / 64;
-  uint8_t *cu = cu_bytes_[k];
-  for (int c = 0; c < 3; c++) { f_.coef[c] = coef_[k][c]; f_.src[c] = src_[k][c]; }
-  f_.cu_log2 = cu; f_.cu_intra = cu + nb8; f_.cu_flags = cu + 2 * nb8; f_.cu_merge_idx = cu + 3 * nb8;
-  f_.cu_mvp_idx = cu + 4 * nb8; f_.cu_intra_mode = cu + 5 * nb8; f_.cu_cbf = cu + 6 * nb8;
-  f_.cu_mv = cu_mv_[k]; f_.cu_mvd = cu_mvd_[k];
-  f_.cu_ref = cu_ref_[k];                              // NULL with one reference
-  f_.sao = sao_[k];                                    // NULL without SAO
-  f_.ctu_qt = ctu_qt_[k]; f_.ctu_qy = ctu_qy_[k]; f_.ctu_delta = ctu_delta_[k]; f_.ctu_first = ctu_first_[k];     // all NULL without qp_in_cu
-}
-
 Encoder::~Encoder()
 {
-  if (probe_words_) {
-    uint32_t w[2] = {0, 0};
-    hipDeviceSynchronize(); hipMemcpy(w, probe_words_, sizeof(w), hipMemcpyDeviceToHost);
-    fprintf(stderr, "kvazzup_amd parse probe: %u bins decoded on the GPU, %u differ from the token list\n", w[1], w[0]);
-    hipFree(probe_words_);
-  }
   if (getenv("KVAZZUP_AMD_TRACE")) fprintf(stderr, "kvazzup_amd encoder thread ms: submit %.1f  wait_gpu %.1f  arith %.1f  assemble %.1f  wait_input %.1f  (pictures %ld)\n", t_submit_, t_wait_, t_arith_, t_asm_, t_in_, collected_);
   { std::lock_guard<std::mutex> l(sm_); squit_ = true; }
   scv_.notify_all();
@@ -308,7 +305,6 @@ Encoder::~Encoder()
     if (sl.rec_done) hipEventDestroy(sl.rec_done);
   }
   if (in_done_) hipEventDestroy(in_done_);
-  if (stream_h2d_ && stream_h2d_ != stream_in_) stream_release(stream_h2d_, cfg_.device, 'H', 'l');
   for (int k = 0; k < kInRing; k++) { hipFree(d_in_[k]); if (h_in_[k]) hipHostFree(h_in_[k]); if (ev_h2d_[k]) hipEventDestroy(ev_h2d_[k]); if (ev_pad_[k]) hipEventDestroy(ev_pad_[k]); }
   stream_release(stream_rec_, cfg_.device, 'R', 'n');
   for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kMaxDepth + 2 + KVZ_MAX_LP_REFS; b++) hipFree(rec_[b][c]); }
@@ -322,7 +318,7 @@ Encoder::~Encoder()
   for (int k = 0; k < kSets; k++) if (ev_src_free_[k]) hipEventDestroy(ev_src_free_[k]);
   stream_release(stream_tok_, cfg_.device, 'T', prio_[1]);
   stream_release(stream_in_, cfg_.device, 'I', prio_[2]);
-  if (stream_idr_ && stream_idr_ != stream_in_) { const char *lv = getenv("KVAZZUP_AMD_IDR_PRIO"); stream_release(stream_idr_, cfg_.device, 'X', lv ? lv[0] : (all_intra_alt_ ? prio_[0] : 'n')); }
+  if (stream_idr_ && stream_idr_ != stream_in_) stream_release(stream_idr_, cfg_.device, 'X', prio_[0]);
   if (ev_idr_done_) hipEventDestroy(ev_idr_done_);
   hipFree(intra_scratch_); hipFree(d_scaling_);
   delete entropy_; delete entropy2_;
@@ -354,8 +350,8 @@ void Encoder::get_kernel_times(double *ms, uint64_t *launches, bool reset)
 // encode = submit the picture's kernels, then finish ("collect") the oldest picture in flight.  With
 // owf == 0 that is the picture just submitted; with owf >= 1 it is the previous one, whose arithmetic
 // coding on the host then runs while the GPU works on the new picture.
-// Host picture in: the copy engine moves it into device buffer k = t mod kInRing on the upload stream while earlier pictures' kernels
-// run; the input stage of picture t (stream_in_) waits for that copy.  The ring is longer than the pictures that can be in flight, so the
+// Host picture in: the copy engine moves it into device buffer k = t mod kInRing on the input stream while earlier pictures' kernels
+// run; the input stage of picture t (stream_in_) follows that copy.  The ring is longer than the pictures that can be in flight, so the
 // buffer's previous reader (the input stage of picture t - kInRing) has long finished and the copy command carries no dependency: the copy
 // engine takes it at once.  (A copy waiting inside the engine's queue holds up every copy behind it, the decoder's included; the input
 // kernel reading the host picture itself across PCIe -- tried -- slows the kernels running beside it 2-10x, tools/measure/pcie_copy_vs_kernels.hip.)
@@ -367,10 +363,8 @@ bool Encoder::upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_
   // The copy rides on the input stream itself, ahead of the picture's input kernel.  HIP spreads the streams of one priority level over four
   // hardware queues, and at the default level those are taken (tokenizer, input, decoder, decoder transfers): a fifth stream there shares a
   // queue with one of them and is serialised behind that stream's event waits (measured: the input stream behind the tokenizer's, 3700 instead
-  // of 5200 frames/s at 1080p); a stream at the lowest level (KVAZZUP_AMD_H2D=own) has a queue to itself and measured no better for the
-  // encoder alone, worse with the decoder beside it.
-  static const bool h2d_on_in = [] { const char *e = getenv("KVAZZUP_AMD_H2D"); return !e || strcmp(e, "own"); }();
-  if (!stream_h2d_) { if (h2d_on_in) stream_h2d_ = stream_in_; else HIP_CHECK(stream_acquire(&stream_h2d_, cfg_.device, 'H', 'l')); }
+  // of 5200 frames/s at 1080p); a stream at the lowest level has a queue to itself and measured no better for the encoder alone, worse with
+  // the decoder beside it.
   if (!d_in_[k]) {
     HIP_CHECK(hipMalloc(&d_in_[k], bytes));
     HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[k], hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ev_pad_[k], hipEventDisableTiming));
@@ -383,12 +377,11 @@ bool Encoder::upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_
     src = h_in_[k];
   }
   if (pad_pending_[k]) {                             // d_in_[k]'s last reader: done long ago, normally
-    if (hipEventQuery(ev_pad_[k]) != hipSuccess) HIP_CHECK(hipStreamWaitEvent(stream_h2d_, ev_pad_[k], 0));
+    if (hipEventQuery(ev_pad_[k]) != hipSuccess) HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_pad_[k], 0));
     pad_pending_[k] = false;
   }
-  HIP_CHECK(hipMemcpyAsync(d_in_[k], src, bytes, hipMemcpyHostToDevice, stream_h2d_));
-  HIP_CHECK(hipEventRecord(ev_h2d_[k], stream_h2d_)); h2d_pending_[k] = true;
-  if (stream_h2d_ != stream_in_) HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_h2d_[k], 0));
+  HIP_CHECK(hipMemcpyAsync(d_in_[k], src, bytes, hipMemcpyHostToDevice, stream_in_));
+  HIP_CHECK(hipEventRecord(ev_h2d_[k], stream_in_)); h2d_pending_[k] = true;
   { Tick tk; if (!submit(d_in_[k], k)) return false; t_submit_ += tk.ms(); }
   in_pending_ = false;                               // (nobody but this ring reads d_in_[k])
   return true;
@@ -536,7 +529,7 @@ uint32_t Encoder::next_chain_gen()
   return chain_gen_;
 }
 
-bool Encoder::picture_begin(hipStream_t qt_stream, EncFrame *fold, bool zero)
+bool Encoder::picture_begin(const EncFrame &f, hipStream_t qt_stream, EncFrame *fold, bool zero)
 {
   const bool have = frame_idx_ >= rc_delay_;
   const uint32_t bits3 = have ? 8u * rc_bytes_[(frame_idx_ - rc_delay_) & 7] : 0u;
@@ -549,8 +542,8 @@ bool Encoder::picture_begin(hipStream_t qt_stream, EncFrame *fold, bool zero)
   }
   // (an intra picture, `zero`: the launch also takes the chain's two arrays back to zero -- the ticket counter's array with the "has intra units" word of the
   // P pictures behind it, which no P picture has pending while an intra picture starts on these arrays, and the CU cbf bits)
-  void *za = zero ? (void *)f_.sync : nullptr, *zb = zero ? (void *)f_.cu_cbf : nullptr;
-  const size_t na = zero ? sizeof(uint32_t) * (((size_t)rows_ * (cw_ / 64) * 3 + 2 + 3) & ~(size_t)3) : 0, nb = zero ? (size_t)f_.b8w * f_.b8h : 0;
+  void *za = zero ? (void *)f.sync : nullptr, *zb = zero ? (void *)f.cu_cbf : nullptr;
+  const size_t na = zero ? sizeof(uint32_t) * (((size_t)rows_ * (cw_ / 64) * 3 + 2 + 3) & ~(size_t)3) : 0, nb = zero ? (size_t)f.b8w * f.b8h : 0;
   if (qt_stream == stream_) launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, qt, roi_dev_, n, qp_cur_, cfg_.vaq > 0 ? 1 : 0, stream_, za, na, zb, nb);
   else {
     // an intra picture on its side stream: the rate control state is updated in PICTURE ORDER on the main stream (between the P pictures' row groups, which
@@ -558,7 +551,7 @@ bool Encoder::picture_begin(hipStream_t qt_stream, EncFrame *fold, bool zero)
     launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, nullptr, nullptr, 0, qp_cur_, 0, stream_);
     launch_picture_begin(nullptr, 0, 0, 0, qt, roi_dev_, n, qp_cur_, 0, qt_stream, za, na, zb, nb);
   }
-  if (cfg_.qp_in_cu && cfg_.vaq > 0) launch_vaq(f_, cfg_.vaq, vaq_act_, vaq_sum_, stream_);          // (f_.qp, f_.src and f_.ctu_qt of this picture are set; the source is padded: stream_ waits for in_done_)
+  if (cfg_.qp_in_cu && cfg_.vaq > 0) launch_vaq(f, cfg_.vaq, vaq_act_, vaq_sum_, stream_);          // (reads f.qp, f.src and f.ctu_qt; the source is padded: stream_ waits for in_done_)
   return true;
 }
 
@@ -575,9 +568,68 @@ void Encoder::rate_control()
   qp_cur_ = clip3(10, 51, qp_cur_ + step);
 }
 
+// What is decided for a picture before anything is queued: its working set, intra picture or not (POC), its QP (rate control), where its chain runs
+Encoder::Plan Encoder::plan(int set)
+{
+  Plan p;
+  set_ = set;
+  const int period = cfg_.intra_period;
+  p.intra = (frame_idx_ == 0) || (period > 0 && (frame_idx_ % period) == 0);
+  if (p.intra) poc_ = 0; else poc_++;
+  rate_control();
+  p.ahead = me_ahead_ && !p.intra;
+  // the stream this picture's chain runs on: an intra picture's own (encoder.h stream_idr_), else the main stream -- behind the last intra picture's chain
+  p.side = p.intra && (idr_side_ || (all_intra_alt_ && (frame_idx_ & 1)));
+  p.ms = p.side ? stream_idr_ : stream_;
+  return p;
+}
+
+// The frame every kernel of the planned picture gets: base_ with the working set set_, the arrays of the chain it runs on, the set's me-source block, its
+// references, the slot's outputs, and its QP, POC and tokenizer cursors.  Reads the encoder's state and changes none of it.
+EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_gen) const
+{
+  EncFrame f = base_;
+  const int k = set_;
+  const size_t nb8 = (size_t)cw_ * ch_ / 64;
+  uint8_t *cu = cu_bytes_[k];
+  for (int c = 0; c < 3; c++) { f.coef[c] = coef_[k][c]; f.src[c] = src_[k][c]; }
+  f.cu_log2 = cu; f.cu_intra = cu + nb8; f.cu_flags = cu + 2 * nb8; f.cu_merge_idx = cu + 3 * nb8;
+  f.cu_mvp_idx = cu + 4 * nb8; f.cu_intra_mode = cu + 5 * nb8; f.cu_cbf = cu + 6 * nb8;
+  f.cu_mv = cu_mv_[k]; f.cu_mvd = cu_mvd_[k];
+  f.cu_ref = cu_ref_[k];                              // NULL with one reference
+  f.sao = sao_[k];                                    // NULL without SAO
+  f.ctu_qt = ctu_qt_[k]; f.ctu_qy = ctu_qy_[k]; f.ctu_delta = ctu_delta_[k]; f.ctu_first = ctu_first_[k];     // all NULL without qp_in_cu
+  f.qp = qp_cur_; f.qpc = kChromaQp[qp_cur_]; f.lambda_q4 = kLambdaQ4[qp_cur_];
+  f.is_intra = p.intra; f.poc = poc_;
+  for (int c = 0; c < 3; c++) { f.rec[c] = cfg_.sao ? work_[c] : rec_[cur_idx_][c]; f.sao_out[c] = rec_[cur_idx_][c]; f.ref[c] = rec_[ref_idx_][c]; }
+  // me-source: the search looks at the previous input picture (still in its working set: the set is not padded into again before kSets - 1 more pictures have
+  // gone through the input stream, behind this picture's k_me), and what the search and the intra pricing behind it write is the set's own
+  f.me_ref = p.ahead ? src_[prev_set_][0] : f.ref[0];
+  // lp-refs: reference r is the picture r + 1 before this one -- ring slot cur_idx_ - 1 - r -- as far as pictures since the IDR picture go (poc_); the search
+  // looks at its reconstruction or (me-source) at its input picture, which is still in the working set it was padded into (set_ - 1 - r: a set is padded
+  // into again kSets pictures later, behind this picture's search on the input stream)
+  if (f.cu_ref) {
+    f.nref = p.intra ? 1 : (poc_ < cfg_.lp_refs ? poc_ : cfg_.lp_refs);
+    for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
+      const int back = r < f.nref ? r : 0, slot = (cur_idx_ + nrec_ - 1 - back) % nrec_;
+      for (int c = 0; c < 3; c++) f.refs[r][c] = rec_[slot][c];
+      f.me_refs[r] = p.ahead ? src_[(k + kSets - 1 - back) % kSets][0] : f.refs[r][0];
+    }
+  }
+  if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
+  f.tok_dense = sl.d_tok_dense; f.tok_count_out = sl.d_tok_count; f.tok_off_out = sl.d_tok_off; f.err_out = sl.d_err; f.ent_cursors = sl.g_cursors;
+  f.tok_cursor = (uint32_t *)tok_count_ + (size_t)(frame_idx_ & 1) * tok_nctu_; f.tok_cursor_next = (uint32_t *)tok_count_ + (size_t)((frame_idx_ + 1) & 1) * tok_nctu_;
+  f.chain_gen = chain_gen;
+  if (p.side) {                                       // beside the P pictures still on the main stream: nothing of theirs is touched
+    point_chain(f, sync_idr_, edge_col_idr_, edge_row_idr_);
+    f.me_cand = nullptr;                              // (me_cand NULL: the picture's deblocking kernel leaves the P pictures' candidate list and "has intra units" word alone)
+    if (cfg_.sao) for (int c = 0; c < 3; c++) f.rec[c] = work_idr_[c];
+  }
+  return f;
+}
+
 bool Encoder::submit(const uint8_t *d_i420, int in_ring)
 {
-  const int w = cfg_.width, h = cfg_.height;
   Slot &sl = slot_[submitted_ % nslots_];
   cur_slot_ = &sl;
   prof_now_ = profiling_ && (frame_idx_ % prof_every_) == 0;
@@ -586,73 +638,28 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
   //   stream_:     motion search / intra decisions, reconstruction, deblocking: the chain picture t + 1 depends on.
   //   stream_tok_: merge/AMVP signalling, tokenizer, compaction, which only feed the host; they read set t & 1 of the
   //                level / CU arrays while stream_ already fills the other set for t + 1.
-  set_ = (int)(submitted_ % kSets);
-  bind_set(set_);
-  const int period = cfg_.intra_period;
-  const bool intra = (frame_idx_ == 0) || (period > 0 && (frame_idx_ % period) == 0);
-  if (intra) poc_ = 0; else poc_++;
-  rate_control();
-  f_.qp = qp_cur_; f_.qpc = kChromaQp[qp_cur_]; f_.lambda_q4 = kLambdaQ4[qp_cur_];
-  f_.is_intra = intra; f_.poc = poc_;
-  for (int c = 0; c < 3; c++) { f_.rec[c] = cfg_.sao ? work_[c] : rec_[cur_idx_][c]; f_.sao_out[c] = rec_[cur_idx_][c]; f_.ref[c] = rec_[ref_idx_][c]; }
-  // me-source: the search looks at the previous input picture (still in its working set: the set is not padded into again before kSets - 1 more pictures have
-  // gone through the input stream, behind this picture's k_me), and what the search and the intra pricing behind it write is the set's own
-  const bool ahead = me_ahead_ && !intra;
-  f_.me_ref = ahead ? src_[prev_set_][0] : f_.ref[0];
-  // lp-refs: reference k is the picture k + 1 before this one -- ring slot cur_idx_ - 1 - k -- as far as pictures since the IDR picture go (poc_); the search
-  // looks at its reconstruction or (me-source) at its input picture, which is still in the working set it was padded into (set_ - 1 - k: a set is padded
-  // into again kSets pictures later, behind this picture's search on the input stream)
-  if (f_.cu_ref) {
-    f_.nref = intra ? 1 : (poc_ < cfg_.lp_refs ? poc_ : cfg_.lp_refs);
-    for (int k = 0; k < KVZ_MAX_LP_REFS; k++) {
-      const int slot = (cur_idx_ + nrec_ - 1 - (k < f_.nref ? k : 0)) % nrec_;
-      for (int c = 0; c < 3; c++) f_.refs[k][c] = rec_[slot][c];
-      f_.me_refs[k] = ahead ? src_[(set_ + kSets - 1 - (k < f_.nref ? k : 0)) % kSets][0] : f_.refs[k][0];
-    }
-  }
-  auto bind_me_block = [&](uint32_t *base, uint32_t *sy) {
-    const size_t n16 = (size_t)(cw_ / 16) * (ch_ / 16);
-    f_.me_cost16 = base; f_.me_cand = base ? base + n16 : nullptr; f_.sync = sy;
-    if (base) { f_.ip_arrive = f_.me_cand + 1 + n16 / 4; f_.ip_scratch = (uint64_t *)(base + ((n16 + 1 + n16 / 4 + n16 / 4 + 1) & ~(size_t)1)); }
-  };
-  if (ahead && me_block_[set_]) bind_me_block(me_block_[set_], sync_set_[set_]);
-  f_.tok_dense = sl.d_tok_dense; f_.tok_count_out = sl.d_tok_count; f_.tok_off_out = sl.d_tok_off; f_.err_out = sl.d_err; f_.ent_cursors = sl.g_cursors;
-  f_.tok_cursor = (uint32_t *)tok_count_ + (size_t)(frame_idx_ & 1) * tok_nctu_; f_.tok_cursor_next = (uint32_t *)tok_count_ + (size_t)((frame_idx_ + 1) & 1) * tok_nctu_;
-  // the stream this picture's chain runs on: an intra picture's own (encoder.h stream_idr_), else the main stream -- behind the last intra picture's chain
-  const bool side = intra && (idr_side_ || (all_intra_alt_ && (frame_idx_ & 1)));
-  const hipStream_t ms = side ? stream_idr_ : stream_;
-  f_.chain_gen = next_chain_gen();
-  f_.analyse_alone = depth_ < 2 ? 1 : 0;                     // (a synchronous encoder: the cap that keeps the search from holding every wave slot protects nobody -- 185 -> 142 us of an intra picture's encoding delay at 1080p)
-  f_.chain_diags = all_intra_alt_ ? 2 : 0;                  // (two pictures' chains side by side: two anti-diagonals of workgroups each -- all-intra 2 030 -> 2 110 frames/s; a lone chain is 2.5 % slower with two, 670 -> 687 us: profiles/r05_intra_diags.txt)
-  if (side) {                                               // beside the P pictures still on the main stream: nothing of theirs is touched
-    const size_t nctu = (size_t)(cw_ / 64) * rows_;
-    f_.sync = sync_idr_; f_.me_cand = nullptr;              // (me_cand NULL: the picture's deblocking kernel leaves the P pictures' candidate list and "has intra units" word alone)
-    f_.edge_col[0] = edge_col_idr_; f_.edge_col[1] = edge_col_idr_ + nctu * 64; f_.edge_col[2] = edge_col_idr_ + nctu * 96;
-    f_.edge_row[0] = edge_row_idr_; f_.edge_row[1] = edge_row_idr_ + nctu * 16; f_.edge_row[2] = edge_row_idr_ + nctu * 24;
-    if (cfg_.sao) for (int c = 0; c < 3; c++) f_.rec[c] = work_idr_[c];
-  }
-  const EncFrame f = f_;
-  if (ahead && me_block_[set_]) bind_me_block(me_cost16_, sync_);      // (f_ goes back to the shared arrays: intra pictures, band mode)
-  if (side) {                                               // (f_ goes back to the shared arrays for the pictures that follow)
-    const size_t nctu = (size_t)(cw_ / 64) * rows_;
-    f_.sync = sync_; f_.me_cand = me_cost16_ ? me_cost16_ + (size_t)(cw_ / 16) * (ch_ / 16) : nullptr;
-    f_.edge_col[0] = edge_col_; f_.edge_col[1] = edge_col_ + nctu * 64; f_.edge_col[2] = edge_col_ + nctu * 96;
-    f_.edge_row[0] = edge_row_; f_.edge_row[1] = edge_row_ + nctu * 16; f_.edge_row[2] = edge_row_ + nctu * 24;
-  }
+  const Plan p = plan((int)(submitted_ % kSets));
+  const EncFrame f = picture_frame(p, sl, next_chain_gen());
   if (all_intra_alt_) idr_pending_ = false;                 // (alternating intra pictures: the main stream's next picture has nothing to do with the side stream's last)
-  if (!side && idr_pending_) { HIP_CHECK(hipStreamWaitEvent(stream_, ev_idr_done_, 0)); idr_pending_ = false; }
+  if (!p.side && idr_pending_) { HIP_CHECK(hipStreamWaitEvent(stream_, ev_idr_done_, 0)); idr_pending_ = false; }
+  return input_stage(f, p, d_i420, in_ring) && chain_stage(f, p) && hand_off(f, p, sl, in_ring);
+}
+
+// stream_in_: the picture padded into its set, and what needs the source pictures only; in_done_ behind it
+bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i420, int in_ring)
+{
   if (src_busy_[set_]) { HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_src_free_[set_], 0)); src_busy_[set_] = false; }   // the last picture that used this set (t - kSets) has been reconstructed
-  timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, w, h, src_[set_][0], src_[set_][1], src_[set_][2], cw_, ch_, stream_in_); });
+  timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[set_][0], src_[set_][1], src_[set_][2], cw_, ch_, stream_in_); });
   if (in_ring >= 0) { HIP_CHECK(hipEventRecord(ev_pad_[in_ring], stream_in_)); pad_pending_[in_ring] = true; }
   // The tokenizer of the set's previous picture must be done with the set's CU arrays before this picture writes them: the INPUT stream waits for it (the
   // event is long past when it gets there), so that the main stream's one wait for in_done_ says both -- a wait of its own in front of every picture's chain
   // cost the chain a barrier packet, a few microseconds with nothing running.
   if (tok_pending_[set_]) { HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_tok_done_[set_], 0)); tok_pending_[set_] = false; }
-  if (intra) {
+  if (p.intra) {
     // The intra decisions need the source picture only: they run on the input stream, beside what is left of picture t - 1 on the main stream.
     timed(K_INTRA_ANALYSE, stream_in_, [&] { launch_intra_analyse(f, stream_in_); });
   }
-  if (ahead) {
+  if (p.ahead) {
     // "uvgx search pipelining v1": the search needs the two input pictures only, the pricing of its expensive quarters as intra blocks the search and the source --
     // both run HERE, on the input stream, beside what the main stream still has of the pictures in front (k_me 31-34 us and k_intra_analyse<P> 19-24 us at
     // 1080p leave the chain the next picture waits for; the head of the chain, when there is one, is a launch of its own on the main stream)
@@ -661,17 +668,24 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
   }
   if (!stage_roi(stream_in_)) return false;
   HIP_CHECK(hipEventRecord(in_done_, stream_in_)); in_pending_ = true;
+  return true;
+}
+
+// the picture's chain on p.ms: decisions, reconstruction, loop filters; ev_src_free_ behind it
+bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
+{
+  const hipStream_t ms = p.ms;
   HIP_CHECK(hipStreamWaitEvent(ms, in_done_, 0));      // (measured by leaving it out: 8 of the ~28 us between a picture's last kernel and the next one's first; the rest is the record behind k_sao that two other streams wait for)
   EncFrame fm = f;                                               // (the picture's first kernel may carry the head of the chain)
-  if (intra) { const uint32_t *keep = f_.sync; f_.sync = f.sync; const bool ok = picture_begin(ms, nullptr, true); f_.sync = const_cast<uint32_t *>(keep); if (!ok) return false; }      // (f.sync: the side stream's array when the picture runs there; f_ is back on the shared one)
-  else if (!picture_begin(ms, ahead && cfg_.subme == 0 ? nullptr : &fm)) return false;      // (the search ahead on the input stream: the chain's head rides in k_subpel, or is a launch of its own without one)
-  if (intra) {
+  if (p.intra) { if (!picture_begin(f, ms, nullptr, true)) return false; }
+  else if (!picture_begin(f, ms, p.ahead && cfg_.subme == 0 ? nullptr : &fm)) return false;      // (the search ahead on the input stream: the chain's head rides in k_subpel, or is a launch of its own without one)
+  if (p.intra) {
     timed(K_INTRA_RECON, ms, [&] { launch_intra_recon(f, ms); });
   } else {
-    if (!ahead) timed(K_ME, stream_, [&] { launch_me(fm, stream_); });
+    if (!p.ahead) timed(K_ME, stream_, [&] { launch_me(fm, stream_); });
     // intra-in-P: quarters whose inter cost is high are priced as intra blocks and may become intra units (the launch leaves at once where none is)
-    if (cfg_.intra_in_p && !ahead) timed(K_INTRA_ANALYSE_P, stream_, [&] { launch_intra_analyse(f, stream_); });
-    if (cfg_.subme > 0) timed(K_SUBPEL, stream_, [&] { launch_subpel(ahead ? fm : f, stream_); });
+    if (cfg_.intra_in_p && !p.ahead) timed(K_INTRA_ANALYSE_P, stream_, [&] { launch_intra_analyse(f, stream_); });
+    if (cfg_.subme > 0) timed(K_SUBPEL, stream_, [&] { launch_subpel(p.ahead ? fm : f, stream_); });
     if (rc_state_) {
       // rate control v2: the CTU rows in groups inside the one launch, the next group's QP decided on the device from the levels of the groups before
       EncFrame fb = f;
@@ -693,14 +707,20 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
   // Last reader of this set on the main stream: k_sao reads the source picture for its statistics, deblocking the CU records.
   // Input padding and intra analysis of the next picture with this set (input stream) overwrite both and wait for this event.
   HIP_CHECK(hipEventRecord(ev_src_free_[set_], ms)); src_busy_[set_] = true;
-  if (side) { HIP_CHECK(hipEventRecord(ev_idr_done_, ms)); idr_pending_ = true; }
+  if (p.side) { HIP_CHECK(hipEventRecord(ev_idr_done_, ms)); idr_pending_ = true; }
+  return true;
+}
+
+// the picture handed on: tokenizer, GPU arithmetic coder, copy of the reconstruction into the caller's picture, the slot to the workers
+bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
+{
+  const hipStream_t ms = p.ms;
   sl.set = set_;
   if (tok_deferred_) { sl.f_tok = f; sl.prof = prof_now_; }          // (encoder.h tok_deferred_: the launcher thread makes these launches when the chain is done)
-  else if (!launch_tokenizer(sl, f, intra, true, prof_now_)) return false;
+  else if (!launch_tokenizer(sl, f, p.intra, true, prof_now_)) return false;
   tok_pending_[set_] = true;
   // the slot is complete when both streams are: the tokens (stream_tok_) and the reconstruction (stream_)
-  if (tok_deferred_) { }
-  else if (cfg_.entropy_gpu) {
+  if (cfg_.entropy_gpu) {
     // arithmetic coding on the slot's own stream, behind the compaction: the coders of several pictures run side by side
     HIP_CHECK(hipEventRecord(sl.tok_ev, stream_tok_));
     HIP_CHECK(hipStreamWaitEvent(sl.ent_stream, sl.tok_ev, 0));
@@ -709,18 +729,10 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
     a.tok = sl.g_tok; a.count = sl.g_count; a.off = sl.g_off; a.stage = sl.g_stage; a.stage_cap = (uint32_t)stage_cap_; a.out = sl.d_out; a.out_cap = (uint32_t)out_cap_;
     a.cursors = sl.g_cursors; a.sub_off = sl.d_sub; a.sub_len = sl.d_sub + rows_; a.sub_bins = sl.d_sub + 2 * rows_;
     a.ctx_save = sl.g_ctx_save; a.ctx_ready = sl.g_ctx_ready; a.gen = ++sl.gen; a.err = err_;
-    a.wc = cw_ / 64; a.hc = rows_; a.wpp = cfg_.wpp; a.tile_rows = cfg_.tile_rows; a.init_type = intra ? 0 : 1; a.qp = qp_cur_; a.first_sub = 0;
+    a.wc = cw_ / 64; a.hc = rows_; a.wpp = cfg_.wpp; a.tile_rows = cfg_.tile_rows; a.init_type = p.intra ? 0 : 1; a.qp = qp_cur_; a.first_sub = 0;
     timed(K_CABAC_ROWS, sl.ent_stream, [&] { launch_cabac_rows(a, nsub, sl.ent_stream); });
-    // measurement aid (KVAZZUP_AMD_PARSE_PROBE=1): the decoder's mirror of the coder over the substreams just written -- what arithmetic DECODING costs a wave
-    // per bin on this GPU, the lower bound of a slice-data parser there (cabac_kernels.hip k_cabac_decode_probe; the count of wrong bins must stay 0)
-    static const bool parse_probe = getenv("KVAZZUP_AMD_PARSE_PROBE") != nullptr;
-    if (parse_probe) {
-      if (!probe_words_) { HIP_CHECK(hipMalloc(&probe_words_, 2 * sizeof(uint32_t))); HIP_CHECK(hipMemset(probe_words_, 0, 2 * sizeof(uint32_t))); }
-      launch_cabac_decode_probe(a, nsub, probe_words_, sl.ent_stream);
-    }
     HIP_CHECK(hipEventRecord(sl.done, sl.ent_stream));
-  } else
-  HIP_CHECK(hipEventRecord(sl.done, stream_tok_));
+  } else if (!tok_deferred_) HIP_CHECK(hipEventRecord(sl.done, stream_tok_));      // (tok_deferred_: launch_tokenizer records it)
   // reconstruction final: with SAO the tokenizer's stream waited for the filter -- the chain's last kernel --, so sl.done already says it (and a record the
   // host can inspect ends with a system-scope fence: one fewer at the end of every picture's chain)
   if (!cfg_.sao) HIP_CHECK(hipEventRecord(sl.rec_done, ms));
@@ -731,7 +743,7 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
     if (!sl.sink_done) HIP_CHECK(hipEventCreateWithFlags(&sl.sink_done, hipEventDisableTiming));
     HIP_CHECK(hipStreamWaitEvent(stream_rec_, cfg_.sao ? ev_src_free_[set_] : sl.rec_done, 0));
     for (int c = 0; c < 3; c++) {
-      const int pw = c ? w / 2 : w, ph = c ? h / 2 : h, cp = c ? cw_ / 2 : cw_;
+      const int pw = c ? cfg_.width / 2 : cfg_.width, ph = c ? cfg_.height / 2 : cfg_.height, cp = c ? cw_ / 2 : cw_;
       if (pw == cp) HIP_CHECK(hipMemcpyAsync(sink_sub_[c], rec_[cur_idx_][c], (size_t)pw * ph, hipMemcpyDeviceToHost, stream_rec_));
       else HIP_CHECK(hipMemcpy2DAsync(sink_sub_[c], (size_t)pw, rec_[cur_idx_][c], (size_t)cp, (size_t)pw, (size_t)ph, hipMemcpyDeviceToHost, stream_rec_));
     }
@@ -739,8 +751,8 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
     sl.has_sink = true;
   }
   sink_sub_[0] = sink_sub_[1] = sink_sub_[2] = nullptr;
-  sl.pic_idx = submitted_; sl.poc = poc_; sl.intra = intra; sl.rec_idx = cur_idx_; sl.set = set_; sl.qp = qp_cur_; sl.write_ps = false;
-  if (intra) {
+  sl.pic_idx = submitted_; sl.poc = poc_; sl.intra = p.intra; sl.rec_idx = cur_idx_; sl.qp = qp_cur_; sl.write_ps = false;
+  if (p.intra) {
     sl.write_ps = (intra_count_ == 0) || (cfg_.vps_period > 0 && (intra_count_ % cfg_.vps_period) == 0);
     intra_count_++;
   }
@@ -911,27 +923,18 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
 bool Encoder::band_picture_setup()
 {
   HIP_CHECK(hipSetDevice(cfg_.device));
-  set_ = 0; bind_set(0);
   cur_slot_ = &slot_[0];
   prof_now_ = false;
-  const int period = cfg_.intra_period;
-  band_intra_ = (frame_idx_ == 0) || (period > 0 && (frame_idx_ % period) == 0);
-  if (band_intra_) poc_ = 0; else poc_++;
   // rate control: every band's encoder runs the same controller on the same access-unit sizes (band_report_au), so all of them
   // arrive at the same QP without talking to each other
   if (cfg_.bitrate > 0 && frame_idx_ >= 3 && !(rc_known_ & (1u << ((frame_idx_ - 3) & 7)))) {
     fprintf(stderr, "kvazzup_amd: band mode with rate control: the size of access unit %d has not been reported (kvzx_encoder_band_report_au)\n", frame_idx_ - 3);
     return false;
   }
-  rate_control();
+  const Plan p = plan(0);
   if (frame_idx_ >= 3) rc_known_ &= ~(1u << ((frame_idx_ - 3) & 7));
-  f_.qp = qp_cur_; f_.qpc = kChromaQp[qp_cur_]; f_.lambda_q4 = kLambdaQ4[qp_cur_];
-  f_.is_intra = band_intra_; f_.poc = poc_;
-  for (int c = 0; c < 3; c++) { f_.rec[c] = rec_[cur_idx_][c]; f_.ref[c] = rec_[ref_idx_][c]; }
-  f_.me_ref = f_.ref[0];
-  Slot &sl = slot_[0];
-  f_.tok_dense = sl.d_tok_dense; f_.tok_count_out = sl.d_tok_count; f_.tok_off_out = sl.d_tok_off; f_.err_out = sl.d_err;
-  f_.tok_cursor = (uint32_t *)tok_count_ + (size_t)(frame_idx_ & 1) * tok_nctu_; f_.tok_cursor_next = (uint32_t *)tok_count_ + (size_t)((frame_idx_ + 1) & 1) * tok_nctu_;
+  band_f_ = picture_frame(p, slot_[0], 0);                 // (chain_gen: band_phase1)
+  for (int c = 0; c < 3; c++) band_f_.sao_out[c] = nullptr;          // (no SAO in band mode)
   return true;
 }
 
@@ -943,14 +946,14 @@ bool Encoder::band_phase1(const uint8_t *d_i420)
   if (cfg_.band_rows <= 0 || !d_i420) return false;
   if (!band_picture_setup()) return false;
   roi_sub_ = roi_; roi_sub_w_ = roi_w_; roi_sub_h_ = roi_h_;
-  if (!stage_roi(stream_) || !picture_begin(stream_)) return false;
-  f_.chain_gen = next_chain_gen();
-  const EncFrame f = f_;
+  if (!stage_roi(stream_) || !picture_begin(band_f_, stream_)) return false;
+  band_f_.chain_gen = next_chain_gen();                   // (drawn behind the picture's head: the clears of a wrap keep their place)
+  const EncFrame &f = band_f_;
   launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[0][0], src_[0][1], src_[0][2], cw_, ch_, stream_);
-  if (band_intra_) {
+  if (f.is_intra) {
     launch_intra_analyse(f, stream_);
     HIP_CHECK(hipMemsetAsync(sync_, 0, sizeof(uint32_t) * (rows_ * (cw_ / 64) * 3 + 1), stream_));
-    HIP_CHECK(hipMemsetAsync(f_.cu_cbf + (size_t)f.row0 * 8 * f.b8w, 0, (size_t)f.b8w * 8 * band_rows(f), stream_));
+    HIP_CHECK(hipMemsetAsync(f.cu_cbf + (size_t)f.row0 * 8 * f.b8w, 0, (size_t)f.b8w * 8 * band_rows(f), stream_));
     launch_intra_recon(f, stream_);
   } else {
     launch_me(f, stream_);
@@ -969,17 +972,18 @@ size_t Encoder::halo_bytes() const { return (size_t)cw_ * 4 + (size_t)(cw_ / 2) 
 
 bool Encoder::band_export_halo(uint8_t *d_up, uint8_t *d_down)
 {
-  const int Y0 = f_.row0 * 64, Y1 = (f_.row0 + band_rows(f_)) * 64, b8w = f_.b8w, cw2 = cw_ / 2;
+  const EncFrame &f = band_f_;
+  const int Y0 = f.row0 * 64, Y1 = (f.row0 + band_rows(f)) * 64, b8w = f.b8w, cw2 = cw_ / 2;
   for (int side = 0; side < 2; side++) {
     uint8_t *dst = side ? d_down : d_up;
     if (!dst) continue;
     const int y = side ? Y1 - 4 : Y0, b8y = side ? Y1 / 8 - 1 : Y0 / 8;        // first luma row of the 4-row strip; CU row
     size_t o = 0;
-    HIP_CHECK(hipMemcpyAsync(dst + o, f_.rec[0] + (size_t)y * cw_, (size_t)cw_ * 4, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw_ * 4;
-    for (int c = 1; c < 3; c++) { HIP_CHECK(hipMemcpyAsync(dst + o, f_.rec[c] + (size_t)(y / 2) * cw2, (size_t)cw2 * 2, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw2 * 2; }
-    const uint8_t *arr[3] = {f_.cu_log2, f_.cu_intra, f_.cu_cbf};
+    HIP_CHECK(hipMemcpyAsync(dst + o, f.rec[0] + (size_t)y * cw_, (size_t)cw_ * 4, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw_ * 4;
+    for (int c = 1; c < 3; c++) { HIP_CHECK(hipMemcpyAsync(dst + o, f.rec[c] + (size_t)(y / 2) * cw2, (size_t)cw2 * 2, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw2 * 2; }
+    const uint8_t *arr[3] = {f.cu_log2, f.cu_intra, f.cu_cbf};
     for (int k = 0; k < 3; k++) { HIP_CHECK(hipMemcpyAsync(dst + o, arr[k] + (size_t)b8y * b8w, (size_t)b8w, hipMemcpyDeviceToDevice, stream_)); o += (size_t)b8w; }
-    HIP_CHECK(hipMemcpyAsync(dst + o, f_.cu_mv + (size_t)b8y * b8w * 2, (size_t)b8w * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(dst + o, f.cu_mv + (size_t)b8y * b8w * 2, (size_t)b8w * 4, hipMemcpyDeviceToDevice, stream_));
   }
   HIP_CHECK(hipStreamSynchronize(stream_));
   return true;
@@ -987,7 +991,8 @@ bool Encoder::band_export_halo(uint8_t *d_up, uint8_t *d_down)
 
 bool Encoder::band_import_halo(const uint8_t *d_from_up, const uint8_t *d_from_down)
 {
-  const int Y0 = f_.row0 * 64, Y1 = (f_.row0 + band_rows(f_)) * 64, b8w = f_.b8w, cw2 = cw_ / 2;
+  const EncFrame &f = band_f_;
+  const int Y0 = f.row0 * 64, Y1 = (f.row0 + band_rows(f)) * 64, b8w = f.b8w, cw2 = cw_ / 2;
   for (int side = 0; side < 2; side++) {
     const uint8_t *src = side ? d_from_down : d_from_up;
     if (!src) continue;
@@ -995,11 +1000,11 @@ bool Encoder::band_import_halo(const uint8_t *d_from_up, const uint8_t *d_from_d
     const int y = side ? Y1 : Y0 - 4, b8y = side ? Y1 / 8 : Y0 / 8 - 1;
     if (y < 0 || y + 4 > ch_) return false;
     size_t o = 0;
-    HIP_CHECK(hipMemcpyAsync(f_.rec[0] + (size_t)y * cw_, src + o, (size_t)cw_ * 4, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw_ * 4;
-    for (int c = 1; c < 3; c++) { HIP_CHECK(hipMemcpyAsync(f_.rec[c] + (size_t)(y / 2) * cw2, src + o, (size_t)cw2 * 2, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw2 * 2; }
-    uint8_t *arr[3] = {f_.cu_log2, f_.cu_intra, f_.cu_cbf};
+    HIP_CHECK(hipMemcpyAsync(f.rec[0] + (size_t)y * cw_, src + o, (size_t)cw_ * 4, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw_ * 4;
+    for (int c = 1; c < 3; c++) { HIP_CHECK(hipMemcpyAsync(f.rec[c] + (size_t)(y / 2) * cw2, src + o, (size_t)cw2 * 2, hipMemcpyDeviceToDevice, stream_)); o += (size_t)cw2 * 2; }
+    uint8_t *arr[3] = {f.cu_log2, f.cu_intra, f.cu_cbf};
     for (int k = 0; k < 3; k++) { HIP_CHECK(hipMemcpyAsync(arr[k] + (size_t)b8y * b8w, src + o, (size_t)b8w, hipMemcpyDeviceToDevice, stream_)); o += (size_t)b8w; }
-    HIP_CHECK(hipMemcpyAsync(f_.cu_mv + (size_t)b8y * b8w * 2, src + o, (size_t)b8w * 4, hipMemcpyDeviceToDevice, stream_));
+    HIP_CHECK(hipMemcpyAsync(f.cu_mv + (size_t)b8y * b8w * 2, src + o, (size_t)b8w * 4, hipMemcpyDeviceToDevice, stream_));
   }
   HIP_CHECK(hipStreamSynchronize(stream_));
   return true;
@@ -1012,7 +1017,7 @@ bool Encoder::band_phase2a()
 {
   if (cfg_.band_rows <= 0) return false;
   HIP_CHECK(hipSetDevice(cfg_.device));
-  const EncFrame f = f_;
+  const EncFrame &f = band_f_;
   Slot &sl = slot_[0];
   if (cfg_.deblock) launch_deblock_h(f, stream_, 1);
   launch_tokenize(f, stream_); launch_tok_compact(f, stream_);
@@ -1021,7 +1026,7 @@ bool Encoder::band_phase2a()
   const int wc = cw_ / 64;
   for (int i = f.row0 * wc; i < (f.row0 + band_rows(f)) * wc; i++) if (sl.h_tok_count[i] < 0) { fprintf(stderr, "kvazzup_amd: token array overflow (CTU %d)\n", i); return false; }
   band_bins_ = 0;
-  entropy_->code_band(sl.h_tok_dense, sl.h_tok_count, sl.h_tok_off, wc, rows_, cfg_.wpp != 0, cfg_.tile_rows, band_intra_ ? 0 : 1, qp_cur_,
+  entropy_->code_band(sl.h_tok_dense, sl.h_tok_count, sl.h_tok_off, wc, rows_, cfg_.wpp != 0, cfg_.tile_rows, f.is_intra ? 0 : 1, qp_cur_,
                       f.row0, band_rows(f), band_subs_, &band_bins_);
   band_coded_ = true;
   return true;
@@ -1031,12 +1036,12 @@ bool Encoder::band_phase2b(std::vector<std::vector<uint8_t>> *substreams, Encode
 {
   if (cfg_.band_rows <= 0 || !substreams || !band_coded_) return false;
   HIP_CHECK(hipSetDevice(cfg_.device));
-  if (cfg_.deblock) { launch_deblock_h(f_, stream_, 2); HIP_CHECK(hipStreamSynchronize(stream_)); }
+  if (cfg_.deblock) { launch_deblock_h(band_f_, stream_, 2); HIP_CHECK(hipStreamSynchronize(stream_)); }
   substreams->swap(band_subs_);
   band_coded_ = false;
-  if (info) { info->valid = true; info->poc = poc_; info->qp = qp_cur_; info->is_intra = band_intra_; info->bins = band_bins_; info->au.clear(); }
+  if (info) { info->valid = true; info->poc = poc_; info->qp = qp_cur_; info->is_intra = band_f_.is_intra; info->bins = band_bins_; info->au.clear(); }
   frame_idx_++;
-  if (band_intra_) intra_count_++;
+  if (band_f_.is_intra) intra_count_++;
   ref_idx_ = cur_idx_; cur_idx_ = (cur_idx_ + 1) % nrec_; out_idx_ = ref_idx_;
   return true;
 }

@@ -97,7 +97,7 @@ typedef struct kvz_config {
   int32_t threads;            /* "threads": host threads of the arithmetic-coding stage (-1 / "auto": 16; 0: the calling thread only) */
   int32_t cpuid;
   int32_t lossless;           /* must be 0 */
-  int32_t tmvp_enable;
+  int32_t tmvp_enable;        /* "tmvp": temporal motion vector prediction, collocated picture = the previous picture.  0 (default, also at every preset, unlike Kvazaar): off, the streams of before.  Not in band mode (encoder_open fails) */
   int32_t rdoq_skip, implicit_rdpcm;
   int32_t mv_rdo;
   int32_t calc_psnr;

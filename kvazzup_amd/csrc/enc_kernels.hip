@@ -735,6 +735,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
 // (510 of them, a wave or two on every compute unit, each fetching the code for itself) 31 us, in workgroups of 256 13.8 - 21 us, 512 10.9, 1024 10.0
 // (profiles/r05_inter_signal_variants.txt; one box, isolated).  Round 4's form (a thread per 16x16 block, 128 workgroups of 64): 22 us; staging the records
 // in LDS, one workgroup per CTU: 28 - 32 us (twice the waves, a barrier) -- it was never the round trips to memory.
+// TMVP ("tmvp"): the temporal candidates come from the previous picture's collocated record (f.col_prev, NULL right after the IDR
+// picture), and the thread at each 16x16 origin files this picture's (f.col_out).  Both on the tokenizer's stream in picture order, which orders the write
+// of picture t - 1 before the read of picture t, and the read of t before the write of t + kSets - 1 into the same set's record.  A separate
+// instantiation: without tmvp the launch runs the code of before.
+template <bool TMVP>
 __global__ __launch_bounds__(1024) void k_inter_signal(EncFrame f)
 {
   const int w8 = f.cw >> 3, h8 = band_rows(f) * 8;
@@ -746,10 +751,19 @@ __global__ __launch_bounds__(1024) void k_inter_signal(EncFrame f)
   int flags = 0;
   if (valid && !intra) {
     const int n = 1 << cl;
-    const CuSignal r = decide_signalling_values(f, x & ~(n - 1), y & ~(n - 1), cl);
+    CuSignal r;
+    // (inlined on purpose: left to itself the compiler makes the longer TMVP derivation a call, with a 1 KB stack frame in scratch memory per thread)
+    if constexpr (TMVP) { FrameMvView v{f}; [[clang::always_inline]] r = decide_signalling_values(v, f.cw, f.chp, x & ~(n - 1), y & ~(n - 1), cl, f.cu_ref && f.nref > 1 ? f.nref : 1, f.col_prev); }
+    else r = decide_signalling_values(f, x & ~(n - 1), y & ~(n - 1), cl);
     flags = r.flags;
     f.cu_flags[g] = (uint8_t)r.flags; f.cu_merge_idx[g] = (uint8_t)r.midx; f.cu_mvp_idx[g] = (uint8_t)r.mvp;
     *reinterpret_cast<uint32_t *>(&f.cu_mvd[g * 2]) = ((uint32_t)r.mvdx & 0xffffu) | ((uint32_t)r.mvdy << 16);
+  }
+  if constexpr (TMVP) {
+    if (valid && !((x | y) & 15)) {
+      ColMv c; c.mx = intra ? 0 : f.cu_mv[g * 2]; c.my = intra ? 0 : f.cu_mv[g * 2 + 1]; c.dist = intra ? 0 : (int16_t)(cu_ref_at(f, g) + 1); c.pad = 0;
+      f.col_out[(y >> 4) * (f.cw >> 4) + (x >> 4)] = c;
+    }
   }
   // The tokenizer's work list (EncFrame::tok_list): of a P picture's 4 x units (unit, role) pairs nine in ten have nothing to say -- units inside a 32x32 coding
   // unit that starts elsewhere, colour components without residual -- and a wave each to find that out WAS k_tokenize's launch (32 640 waves at 1080p, 130 000
@@ -2489,7 +2503,8 @@ void launch_inter_recon(const EncFrame &f, hipStream_t st)
 void launch_inter_signal(const EncFrame &f, hipStream_t st)
 {
   const int n = (f.cw / 8) * (band_rows(f) * 8);
-  hipLaunchKernelGGL(k_inter_signal, dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
+  if (f.col_out) hipLaunchKernelGGL(k_inter_signal<true>, dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
+  else hipLaunchKernelGGL(k_inter_signal<false>, dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
 }
 void launch_intra_analyse(const EncFrame &f, hipStream_t st)
 {

@@ -56,6 +56,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.band_rows > 0) cfg.me_source = 0;                // (a band's search window reaches into the neighbouring bands' rows: the halo carries reconstruction rows, not source rows)
   if (cfg.lp_refs < 1 || cfg.lp_refs > KVZ_MAX_LP_REFS) { if (error) *error = "lp-refs out of range (0 .. 4)"; return false; }
   if (cfg.lp_refs > 1 && cfg.band_rows > 0) { if (error) *error = "lp-refs >= 2 is not available in band mode (the halo exchange carries one reference picture's rows)"; return false; }
+  if (cfg.tmvp && cfg.band_rows > 0) { if (error) *error = "tmvp is not available in band mode"; return false; }
 
   const char *prio = getenv("KVAZZUP_AMD_PRIO"); if (!prio || strlen(prio) < 4) prio = "hnnn";   // main, tokenizer, input, decoder: the chain the next picture waits for is the urgent one (+6 % at 1080p; any explicit priority also gives the stream a hardware queue of its own)
 
@@ -113,6 +114,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     HIP_OK(hipMalloc(&cu_mv_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mv_[k], 0, nb8 * 2 * sizeof(int16_t)));
     HIP_OK(hipMalloc(&cu_mvd_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mvd_[k], 0, nb8 * 2 * sizeof(int16_t)));
     if (cfg.lp_refs > 1) { HIP_OK(hipMalloc(&cu_ref_[k], nb8)); HIP_OK(hipMemset(cu_ref_[k], 0, nb8)); }
+    if (cfg.tmvp) { HIP_OK(hipMalloc(&col_[k], nb8 / 4 * sizeof(ColMv))); HIP_OK(hipMemset(col_[k], 0, nb8 / 4 * sizeof(ColMv))); }
     HIP_OK(hipEventCreateWithFlags(&ev_tok_done_[k], kDeviceEvent));
   }
   if (cfg.qp_in_cu) {
@@ -260,6 +262,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
 
   sp_.cw = cw_; sp_.ch = ch_; sp_.width = cfg.width; sp_.height = cfg.height; sp_.qp = cfg.qp; sp_.wpp = cfg.wpp; sp_.tile_rows = cfg.tile_rows; sp_.tile_cols = cfg.tile_cols; sp_.qp_in_cu = cfg.qp_in_cu; sp_.sao = cfg.sao; sp_.slices = cfg.slices; sp_.signhide = cfg.signhide; sp_.scaling_list = cfg.scaling_list; sp_.tq_bypass = cfg.lossless;
   sp_.lp_refs = cfg.lp_refs > 1 ? cfg.lp_refs : 0;
+  sp_.tmvp = cfg.tmvp;
   sp_.deblock = cfg.deblock; sp_.fps_num = cfg.fps_num; sp_.fps_den = cfg.fps_den;
   HIP_OK(hipStreamSynchronize(stream_));
   HIP_OK(hipDeviceSynchronize());
@@ -310,7 +313,7 @@ Encoder::~Encoder()
   for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kMaxDepth + 2 + KVZ_MAX_LP_REFS; b++) hipFree(rec_[b][c]); }
   hipFree(vaq_act_); hipFree(vaq_sum_); hipFree(rc_state_);
   for (int k = 0; k < kSets; k++) { hipFree(ctu_qt_[k]); hipFree(ctu_qy_[k]); hipFree(ctu_delta_[k]); hipFree(ctu_first_[k]); if (h_ctu_qt_[k]) hipHostFree(h_ctu_qt_[k]); hipFree(ctu_roi_[k]); }
-  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
+  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
   for (int c = 0; c < 3; c++) { hipFree(work_[c]); hipFree(work_idr_[c]); }
   hipFree(sync_idr_); hipFree(edge_col_idr_); hipFree(edge_row_); hipFree(edge_row_idr_);
   for (int k = 0; k < kSets; k++) hipFree(sao_[k]);
@@ -616,6 +619,9 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
       f.me_refs[r] = p.ahead ? src_[(k + kSets - 1 - back) % kSets][0] : f.refs[r][0];
     }
   }
+  // tmvp: the previous picture -- set k - 1 -- filed its record on the tokenizer's stream, where this picture's k_inter_signal reads it; right after the IDR
+  // picture (which files none) the slice says slice_temporal_mvp_enabled_flag = 0 (hevc_headers.h slice_tmvp) and nothing is read
+  if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
   if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
   f.tok_dense = sl.d_tok_dense; f.tok_count_out = sl.d_tok_count; f.tok_off_out = sl.d_tok_off; f.err_out = sl.d_err; f.ent_cursors = sl.g_cursors;
   f.tok_cursor = (uint32_t *)tok_count_ + (size_t)(frame_idx_ & 1) * tok_nctu_; f.tok_cursor_next = (uint32_t *)tok_count_ + (size_t)((frame_idx_ + 1) & 1) * tok_nctu_;
@@ -1076,6 +1082,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
   if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }
+  if (w == "col") { src = col_[out_set_]; have = col_[out_set_] ? nb8 / 4 * sizeof(ColMv) : 0; }
   if (w == "trace" && trace_) { src = trace_; have = sizeof(unsigned long long) * (rows_ * (cw_ / 64) * 72); }
   for (int c = 0; c < 3; c++) {
     size_t n = c ? npx / 4 : npx;

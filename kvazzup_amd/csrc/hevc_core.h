@@ -63,6 +63,10 @@ struct RcState {
   alignas(128) uint32_t decided;
   alignas(128) unsigned long long acc[8 * KVZ_RC_ACC_STRIDE];
 };
+// "tmvp" (DESIGN.md section 9b): the collocated record of a P picture, one entry per 16x16 block in raster order (pitch cw / 16) -- the motion of the block's
+// top-left 8x8 unit, the storage 8.5.3.2.8 reads ((x >> 4) << 4, (y >> 4) << 4).  dist: POC distance of the reference the vector points into (ref_idx + 1);
+// 0: an intra unit, no vector.
+struct ColMv { int16_t mx, my, dist, pad; };
 struct EncFrame {
   int cw, ch, b8w, b8h;
   int qp, qpc, lambda_q4, range;
@@ -130,6 +134,10 @@ struct EncFrame {
   uint8_t *cu_ref;              // [b8] ref_idx_l0 of the CU (NULL: every CU refers to reference 0)
   const uint8_t *refs[KVZ_MAX_LP_REFS][3];   // reconstruction planes of reference k (refs[0] = ref)
   const uint8_t *me_refs[KVZ_MAX_LP_REFS];   // the luma plane k_me searches for reference k (me_refs[0] = me_ref; me-source: input picture t - 1 - k)
+  // "tmvp" (P pictures, NULL otherwise): col_out = this picture's collocated record, written by k_inter_signal<true>; col_prev = the previous
+  // picture's, which the temporal candidates read (NULL: slice_temporal_mvp_enabled_flag 0 -- the previous picture is the IDR picture)
+  ColMv *col_out;
+  const ColMv *col_prev;
 };
 
 // the reference planes of ref_idx k (one reference: ref[])
@@ -874,9 +882,11 @@ KVZ_HD void enc_ctu(const EncFrame &f, CabacEnc &c, int cx, int cy)
 
 // ---------------------------------------------------------------------------------------------
 // Merge / AMVP signalling of one inter 2Nx2N CU from the final motion field of a P picture (intra
-// neighbours are treated as unavailable).  H.265 8.5.3.2.2-8.5.3.2.8 specialised: Log2ParMrgLevel = 2,
-// MaxNumMergeCand = 5, no TMVP, list 0 only.  With lp-refs the vectors carry a ref_idx; reference k is
-// the picture k + 1 before the current one, so the POC distance of ref_idx k is k + 1.
+// neighbours are treated as unavailable).  H.265 8.5.3.2.2-8.5.3.2.9 specialised: Log2ParMrgLevel = 2,
+// MaxNumMergeCand = 5, list 0 only.  With lp-refs the vectors carry a ref_idx; reference k is
+// the picture k + 1 before the current one, so the POC distance of ref_idx k is k + 1.  With tmvp the
+// collocated picture is the previous picture (ref_idx 0), read through its ColMv record; every
+// reference is short-term.
 // ---------------------------------------------------------------------------------------------
 KVZ_HD int mvd_bits(int q)
 {
@@ -918,8 +928,9 @@ KVZ_HD FiveNb five_neighbours(const V &v, int cw, int chp, int x0, int y0, int n
   q.B0 = nb_mv(v, cw, chp, x0, y0, x0 + n, y0 - 1); q.A0 = nb_mv(v, cw, chp, x0, y0, x0 - 1, y0 + n); q.B2 = nb_mv(v, cw, chp, x0, y0, x0 - 1, y0 - 1);
   return q;
 }
-// the five merge candidates (8.5.3.2.2-8.5.3.2.5); nref: active references (zero candidates take refIdx 0, 1, .. nref - 1, then 0)
-KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5], int cref[5], int nref = 1)
+// the five merge candidates (8.5.3.2.2-8.5.3.2.5); nref: active references (zero candidates take refIdx 0, 1, .. nref - 1, then 0); tcol: the temporal
+// candidate for refIdx 0 (temporal_cand), which follows the (at most four) spatial ones; NULL: no temporal candidate
+KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5], int cref[5], int nref = 1, const NbMv *tcol = nullptr)
 {
   const NbMv &A1 = q.A1, &B1 = q.B1, &B0 = q.B0, &A0 = q.A0, &B2 = q.B2;
   bool fA1 = A1.ok;
@@ -933,6 +944,7 @@ KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5], int cref[5]
   if (fB0) { cmx[nc] = B0.mx; cmy[nc] = B0.my; cref[nc] = B0.ref; nc++; }
   if (fA0) { cmx[nc] = A0.mx; cmy[nc] = A0.my; cref[nc] = A0.ref; nc++; }
   if (fB2 && nc < 5) { cmx[nc] = B2.mx; cmy[nc] = B2.my; cref[nc] = B2.ref; nc++; }
+  if (tcol && tcol->ok) { cmx[nc] = tcol->mx; cmy[nc] = tcol->my; cref[nc] = 0; nc++; }        // Col (8.5.3.2.2 step 4): refIdxL0Col = 0
   for (int z = 0; nc < 5; z++) { cmx[nc] = 0; cmy[nc] = 0; cref[nc] = z < nref ? z : 0; nc++; }     // zero candidates (8.5.3.2.5)
 }
 KVZ_HD void merge_cand_list(const FiveNb &q, int cmx[5], int cmy[5]) { int cref[5]; merge_cand_list(q, cmx, cmy, cref, 1); }
@@ -946,10 +958,30 @@ KVZ_HD int mv_scale(int mv, int td, int tb)
   const int p = dsf * mv;
   return clip3(-32768, 32767, p < 0 ? -((-p + 127) >> 8) : ((p + 127) >> 8));
 }
+// 8.5.3.2.8 / 8.5.3.2.9 for the 2Nx2N PU at (x0, y0), size n: the collocated block -- bottom right when that lies in the PU's CTB row and inside the picture
+// (cw x ch, the coded size = pic_width / pic_height_in_luma_samples), else the centre; an intra block at the bottom right falls back to the centre too --
+// as read from the previous picture's record.  dist 0: no candidate (intra at both positions, or no record).
+KVZ_HD ColMv col_block(const ColMv *col, int cw, int ch, int x0, int y0, int n)
+{
+  ColMv c; c.mx = 0; c.my = 0; c.dist = 0; c.pad = 0;
+  if (!col) return c;
+  const int w16 = cw >> 4, xb = x0 + n, yb = y0 + n;
+  if ((yb >> 6) == (y0 >> 6) && yb < ch && xb < cw) c = col[(yb >> 4) * w16 + (xb >> 4)];
+  if (c.dist == 0) c = col[((y0 + (n >> 1)) >> 4) * w16 + ((x0 + (n >> 1)) >> 4)];
+  return c;
+}
+// ... and the temporal candidate it gives for ref_idx `ref`: the vector scaled from the collocated block's POC distance to this reference's (ref + 1)
+KVZ_HD NbMv temporal_cand(const ColMv &c, int ref)
+{
+  NbMv r; r.ok = c.dist != 0; r.ref = ref;
+  r.mx = r.ok ? mv_scale(c.mx, c.dist, ref + 1) : 0; r.my = r.ok ? mv_scale(c.my, c.dist, ref + 1) : 0;
+  return r;
+}
 // the two AMVP candidates for ref_idx `ref` (8.5.3.2.6-8.5.3.2.7): A from A0 / A1 referring to the same picture, else (scaled) from the first of
 // them that is available; B from B0 / B1 / B2 referring to the same picture, and when neither A0 nor A1 is available (isScaledFlag 0) A takes that
-// B and B becomes the first available of B0 / B1 / B2, scaled
-KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0)
+// B and B becomes the first available of B0 / B1 / B2, scaled.  tcol: the temporal candidate for `ref` (temporal_cand), taken when A and B do not give two
+// different vectors (8.5.3.2.6); NULL: none
+KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0, const NbMv *tcol = nullptr)
 {
   const NbMv *An[2] = {&q.A0, &q.A1}, *Bn[3] = {&q.B0, &q.B1, &q.B2};
   bool haveA = false, haveB = false;
@@ -968,28 +1000,32 @@ KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0)
   int np = 0;
   if (haveA) { px[np] = ax; py[np] = ay; np++; }
   if (haveB && !(haveA && ax == bx && ay == by)) { px[np] = bx; py[np] = by; np++; }
+  if (np < 2 && tcol && tcol->ok) { px[np] = tcol->mx; py[np] = tcol->my; np++; }
   while (np < 2) { px[np] = 0; py[np] = 0; np++; }
 }
 KVZ_HD void amvp_cand_list(const EncFrame &f, int x0, int y0, int n, int px[2], int py[2]) { FrameMvView v{f}; amvp_cand_list(five_neighbours(v, f.cw, f.chp, x0, y0, n), px, py, 0); }
 
 // the signalling of the inter CU at (x0, y0): merge (+ skip) with the first candidate that equals its (vector, reference), else AMVP for its
-// reference with the cheaper predictor.  nref: the slice's active references.
+// reference with the cheaper predictor.  nref: the slice's active references; col: the collocated record (tmvp; NULL: no temporal candidates).
 struct CuSignal { int flags, midx, mvp, mvdx, mvdy; };
 template <class V>
-KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, int y0, int log2, int nref = 1)
+KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, int y0, int log2, int nref = 1, const ColMv *col = nullptr)
 {
   const int n = 1 << log2;
   const MvRec own = v.at(x0, y0);
   const int mvx = own.mx, mvy = own.my, ref = own.ref;
   const FiveNb q = five_neighbours(v, cw, chp, x0, y0, n);      // (once for both derivations: ten availability tests and record fetches were most of k_inter_signal's code)
+  const ColMv cb = col_block(col, cw, chp & 0xfffff, x0, y0, n);  // (one collocated block for both: merge scales it to ref_idx 0, AMVP to the CU's own)
+  const NbMv t0 = temporal_cand(cb, 0);
   int cmx[5], cmy[5], cref[5];
-  merge_cand_list(q, cmx, cmy, cref, nref);
+  merge_cand_list(q, cmx, cmy, cref, nref, col ? &t0 : nullptr);
   CuSignal r; r.flags = 0; r.midx = 0; r.mvp = 0; r.mvdx = 0; r.mvdy = 0;
   for (int k = 4; k >= 0; k--) if (cmx[k] == mvx && cmy[k] == mvy && cref[k] == ref) { r.flags = CU_MERGE; r.midx = k; }      // (the first match wins)
   if (r.flags && own.cbf == 0) r.flags |= CU_SKIP;
   if (!r.flags) {
     int px[2], py[2];
-    amvp_cand_list(q, px, py, ref);
+    const NbMv tr = temporal_cand(cb, ref);
+    amvp_cand_list(q, px, py, ref, col ? &tr : nullptr);
     int b0 = mvd_bits(mvx - px[0]) + mvd_bits(mvy - py[0]);
     int b1 = mvd_bits(mvx - px[1]) + mvd_bits(mvy - py[1]);
     r.mvp = b1 < b0;

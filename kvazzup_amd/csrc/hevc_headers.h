@@ -37,12 +37,16 @@ struct StreamParams {
   int tq_bypass = 0;        // transquant_bypass_enabled_flag (`lossless`: every coding unit sets cu_transquant_bypass_flag)
   int slices = 0;           // kvazaar slices: 1 = "wpp", a dependent slice segment per CTU row (dependent_slice_segments_enabled_flag); 2 = "tiles", a slice per tile
   int lp_refs = 0;          // "lp-refs" n >= 2: n short-term RPS sets (set i: pictures -1 .. -(i + 1)), n references by default, DPB of n + 1 pictures; 0 / 1: one reference
+  int tmvp = 0;             // sps_temporal_mvp_enabled_flag; the slices: slice_temporal_mvp_enabled_flag (slice_tmvp), collocated_ref_idx 0
 };
 
 // pictures the DPB holds beside the current one: sps/vps_max_dec_pic_buffering_minus1
 inline int dpb_minus1(const StreamParams &s) { return s.lp_refs > 1 ? s.lp_refs : 1; }
 // active references of a P picture `poc` pictures after its IDR picture
 inline int active_refs(const StreamParams &s, int poc) { const int n = s.lp_refs > 1 ? s.lp_refs : 1; return poc < n ? (poc < 1 ? 1 : poc) : n; }
+// slice_temporal_mvp_enabled_flag of the picture `poc` pictures after its IDR picture: 1 but where the collocated picture (ref_idx_l0 0, the previous
+// picture) is the IDR picture -- an intra picture, which gives no temporal candidate and files no collocated record
+inline bool slice_tmvp(const StreamParams &s, bool idr, int poc) { return s.tmvp && !idr && poc != 1; }
 
 inline int level_idc_for(int w, int h)
 {
@@ -92,7 +96,7 @@ inline void write_sps(BitWriter &w, const StreamParams &s)
       for (int j = 0; j <= i; j++) { w.ue(0); w.bit(1); }          // delta_poc_s0_minus1 = 0 (each one picture further back), used_by_curr_pic_s0_flag
     }
   } else { w.ue(1); w.ue(1); w.ue(0); w.ue(0); w.bit(1); }       // one short-term RPS: previous picture
-  w.bit(0); w.bit(0); w.bit(1);                                  // long-term, tmvp, strong intra smoothing
+  w.bit(0); w.bit(s.tmvp != 0); w.bit(1);                        // long-term, sps_temporal_mvp_enabled_flag, strong intra smoothing
   w.bit(1);                                                      // VUI: timing only
   w.put(0, 8);
   w.bit(1); w.put((uint32_t)s.fps_den, 32); w.put((uint32_t)s.fps_num, 32); w.bit(0); w.bit(0);
@@ -158,11 +162,13 @@ inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, in
     if (!idr) {
       w.put((uint32_t)poc & 255, 8); w.bit(1);
       if (s.lp_refs > 1) { int bits = 0; while ((1 << bits) < s.lp_refs) bits++; w.put((uint32_t)nact - 1, bits); }     // short_term_ref_pic_set_idx
+      if (s.tmvp) w.bit(slice_tmvp(s, idr, poc));                  // slice_temporal_mvp_enabled_flag
     }
     if (s.sao) { w.bit(1); w.bit(1); }                             // slice_sao_luma_flag, slice_sao_chroma_flag
     if (!idr) {
       const int ndef = dpb_minus1(s);
       w.bit(nact != ndef); if (nact != ndef) w.ue((uint32_t)nact - 1);   // num_ref_idx_active_override_flag (fewer pictures since the IDR picture than lp-refs)
+      if (slice_tmvp(s, idr, poc) && nact > 1) w.ue(0);             // collocated_ref_idx: the previous picture (P slice: collocated_from_l0_flag inferred 1)
       w.ue(0);                                                     // five_minus_max_num_merge_cand
     }
     w.se(slice_qp_delta);                                          // against the PPS init_qp (= the configured QP)

@@ -199,6 +199,7 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
   BOOL_OPT("recon-output", recon_output)
   BOOL_OPT("intra-chain", intra_chain) BOOL_OPT("me-source", me_source) BOOL_OPT("input-hold", input_hold) INT_OPT("intra-in-p", intra_in_p, 0, 2)
   INT_OPT("lp-refs", lp_refs, 0, 4)              // (extension: references per P picture, "uvgx multi-reference v1"; "ref" keeps accepting 1 only)
+  BOOL_OPT("tmvp", tmvp_enable)                  // (temporal motion vector prediction; off by default and at every preset, unlike Kvazaar)
   if (n == "null-input") {
     if (!strcmp(value, "drain")) { cfg->null_input_poll = 0; return 1; }
     if (!strcmp(value, "poll")) { cfg->null_input_poll = 1; return 1; }
@@ -210,7 +211,7 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
   // Tools this encoder does not have: switching one ON is rejected -- config_parse's return value is all uvgComm's custom-parameter list
   // reports back (kvazaarfilter.cpp:363-367) --, switching it off is accepted.
 #define OFF_ONLY(key, field) if (n == key) { if (!parse_bool(value, &iv)) return 0; cfg->field = 0; return iv ? 0 : 1; }
-  OFF_ONLY("smp", smp_enable) OFF_ONLY("amp", amp_enable) OFF_ONLY("bipred", bipred) OFF_ONLY("tmvp", tmvp_enable) OFF_ONLY("transform-skip", trskip_enable)
+  OFF_ONLY("smp", smp_enable) OFF_ONLY("amp", amp_enable) OFF_ONLY("bipred", bipred) OFF_ONLY("transform-skip", trskip_enable)
   OFF_ONLY("full-intra-search", full_intra_search) OFF_ONLY("mv-rdo", mv_rdo) OFF_ONLY("implicit-rdpcm", implicit_rdpcm) OFF_ONLY("intra-rdo-et", intra_rdo_et)
 #undef OFF_ONLY
   BOOL_OPT("rdoq-skip", rdoq_skip) BOOL_OPT("early-skip", early_skip)       // (recorded: the zero-out of "uvgx RDOQ v1" and the skip decision do not depend on them)
@@ -343,6 +344,7 @@ kvz_encoder *encoder_open(const kvz_config *cfg)
   ec.lossless = cfg->lossless != 0;
   ec.rdoq = cfg->rdoq_enable != 0; ec.signhide = cfg->signhide_enable != 0; ec.intra_in_p = cfg->intra_in_p; ec.me_source = cfg->me_source != 0;
   ec.lp_refs = cfg->lp_refs > 1 ? cfg->lp_refs : 1;
+  ec.tmvp = cfg->tmvp_enable != 0;
   ec.hash = cfg->hash == KVZ_HASH_MD5 ? 2 : (cfg->hash == KVZ_HASH_CHECKSUM ? 1 : 0);
   ec.vaq = cfg->vaq > 0 ? cfg->vaq : 0;
   ec.qp_in_cu = (cfg->set_qp_in_cu || ec.vaq > 0) ? 1 : 0;

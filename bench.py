@@ -8,7 +8,10 @@ each on its own thread as in the reference's filter graph.  The clock starts on 
 last timed picture has left the decoder (the pipeline is flushed again): nothing is in flight across either end.
 `value` = frames/s of that region (median of --repeats runs); `config.pictures_per_step` = 64.
 
-What the one JSON line carries besides `value` (every leg can be switched off):
+A plain run is the headline leg alone: set-up, warm-up, the timed steps, --dump-outputs, the JSON line with what those steps give
+(`roofline`: the dominant kernel against the HBM peak + every kernel's fraction, `kernels_us`, `kernel_share_of_step`); the legs below
+are null.  --full adds them (each can still be switched off) and `config.psnr_y` (one untimed period through a second pipeline,
+decoded pictures against the source):
   host_boundary    the same steps through the reference's own boundary: host I420 in, decoded I420 out into host memory
   streams_per_gpu  K pipelines at once in this process on the one GPU (a K-party call): aggregate frames/s, the decoders'
                    batched launches (csrc/batch.h)
@@ -18,7 +21,9 @@ What the one JSON line carries besides `value` (every leg can be switched off):
   uvgcomm_defaults the same boundary with NO custom parameter and uvgComm's default OWF / threads (what an unmodified uvgComm.ini gets)
   latency_us       encoding delay and total delay per picture (p50 / p99) at a camera-paced source, at uvgComm's defaults and at the throughput setting
   bounds           the flat and noise clips of SURVEY 8(d): frames/s, bits per picture
-  roofline         the dominant kernel against the HBM peak (+ every kernel's fraction), cpu_baseline: oracle/ on all host cores
+  cpu_baseline     oracle/ on all host cores
+
+--full with --workload 8k-tilesplit adds the split decoder's leg (`secondary`).
 
 --gpus N (N > 1) without a torch.distributed environment: this process launches N fresh rank processes (before anything
 here touches torch or the GPU) and forwards rank 0's line.  N > 1 runs one independent stream per GPU (BASELINE configs[3]:
@@ -58,7 +63,7 @@ VALUE_IS = (
     "median run of `repeats`; pictures enter RESIDENT IN HBM and the decoded pictures stay there (the bench contract: inputs in HBM "
     "when the timed region starts) -- the rate through the reference's own host-in / host-out boundary (BASELINE.md: upload included) "
     "is `host_boundary.value`, and the rate an unmodified uvgComm.ini gets (no custom parameter, default OWF / threads) `uvgcomm_defaults.value`: the "
-    "three stand side by side in `rates`, all measured by this one command")
+    "three stand side by side in `rates`, all measured by this one command with --full")
 
 
 def parse_args():
@@ -97,9 +102,15 @@ def parse_args():
     ap.add_argument("--owf", type=int, default=6, help="uvgComm setting video/OWF (kvazaar owf): pictures in flight in the encoder")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the outputs of the headline leg's last timed step to DIR/<name>.npy (rank 0's stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="run the side legs too (host boundary, streams per GPU, 4K, default mode, all-intra, latency, bounds, CPU baseline, the split "
+                         "decoder, config.psnr_y); without it only the headline leg runs and the --no-* options have nothing to skip")
     a = ap.parse_args()
     if a.dump_outputs and (a.host_io or a.workload == "8k-tilesplit"):
         ap.error("--dump-outputs: the resident path of a one-stream workload only (no --host-io, no 8k-tilesplit)")
+    if not a.full:                                   # a plain run: the headline leg alone
+        a.no_host_boundary = a.no_preset_line = a.no_cpu_baseline = a.no_secondary = a.no_split_decode = True
+        a.streams_per_gpu = ""
     if a.no_host_boundary or a.host_io:
         a.no_latency = a.no_bounds = True
     return a
@@ -306,7 +317,7 @@ def main():
         args.no_host_boundary = True
         m = run_stream(args, wl, args.steps, args.warmup, ranks, rank, world, quality=False, host_io=True, extra_custom=HOST_CUSTOM)
     else:
-        m = run_stream(args, wl, args.steps, args.warmup, ranks, rank, world, quality=(rank == 0), extra_custom=RESIDENT, dump=dump)
+        m = run_stream(args, wl, args.steps, args.warmup, ranks, rank, world, quality=(rank == 0 and args.full), extra_custom=RESIDENT, dump=dump)
     if dump is not None:
         write_outputs(args.dump_outputs, dump)
     npic = args.steps * PERIOD

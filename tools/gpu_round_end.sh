@@ -1,11 +1,11 @@
 #!/bin/bash
 # the way the driver ends a round: the full GPU suite (serial, as the driver runs it), then the driver's bench line -- kept under profiles/
-R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; mkdir -p gpurun_out; r=${ROUND:-r05}
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R; out=${OUT_DIR:-$(mktemp -d)}; mkdir -p "$out"; r=${ROUND:-r05}; echo "bench line: $out/${r}_bench_driver_line.json"
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -4
-cd $R; timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${r}_bench_driver_line.json 2> gpurun_out/${r}_bench_driver_line.err; echo "bench rc $?"; tail -c 400 gpurun_out/${r}_bench_driver_line.err
+cd $R; timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$out/${r}_bench_driver_line.json" 2> "$out/${r}_bench_driver_line.err"; echo "bench rc $?"; tail -c 400 "$out/${r}_bench_driver_line.err"
 python - <<PY
 import json
-d=json.load(open('gpurun_out/${r}_bench_driver_line.json'))
+d=json.load(open('$out/${r}_bench_driver_line.json'))
 print('value',d['value'],'rates',{k:v for k,v in d['rates'].items() if k!='note'})
 l=d.get('latency_us') or {}
 for k in ('uvgcomm_default_owf0','uvgcomm_owf2','throughput_setting'):

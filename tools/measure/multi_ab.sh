@@ -2,7 +2,7 @@
 # several pipelines in one process on one GPU.  MODES: space-separated "share,batch" pairs -- KVAZZUP_AMD_SHARE_STREAMS (0: one set of HIP streams per
 # instance, round 3) and KVAZZUP_AMD_BATCH (0: every decoder launches its own pictures) -- run alternately, REPS times
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; mkdir -p gpurun_out
-B="python bench.py --steps ${STEPS:-8} --warmup 2 --repeats 1 --no-secondary --no-host-boundary --no-cpu-baseline --no-preset-line --streams-per-gpu ${KS:-2,4}"
+B="python bench.py --full --steps ${STEPS:-8} --warmup 2 --repeats 1 --no-secondary --no-host-boundary --no-cpu-baseline --no-preset-line --streams-per-gpu ${KS:-2,4}"
 for rep in $(seq 1 ${REPS:-2}); do
   for mode in ${MODES:-1,1 1,0}; do
     share=${mode%,*}; batch=${mode#*,}

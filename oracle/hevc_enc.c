@@ -18,6 +18,7 @@
 #define INTRA_P_BITS 16       /* ... and goes intra when the intra cost plus this many bins is below the inter cost */
 #define SPLIT_BITS 8          /* rate charged for splitting a CU one level, in bins */
 #define ME_PAD 64             /* padding of the reference copy used by the motion search */
+#define ORC_MAX_LP_REFS 4     /* lp-refs: references per P picture at most */
 
 const uint16_t orc_lambda_q4[52] = {
   3, 3, 4, 4, 5, 5, 6, 7, 8, 9, 10, 11, 12, 14, 15, 17, 19, 22, 24, 27, 30, 34, 38, 43, 48, 54,
@@ -35,12 +36,17 @@ struct orc_encoder {
    * last eight pictures and whether they were P pictures coded in groups */
   uint32_t rc_ratio_q8; int rc_ratio_valid; uint32_t rc_cost[8]; uint8_t rc_cost_valid[8];
   orc_vps vps; orc_sps sps; orc_pps pps;
-  orc_pic pics[2]; orc_pic *cur, *ref;
+  /* the picture being coded and its references: refs[k] = the picture coded k + 1 pictures before (lp-refs: nref = n of them, else 1); the
+   * pictures rotate through pics[] (orc_enc_encode's end) */
+  orc_pic pics[1 + ORC_MAX_LP_REFS]; orc_pic *cur, *refs[ORC_MAX_LP_REFS];
+  int nref;                            /* max(lp_refs, 1): references kept */
+  int nact;                            /* m: active references of the picture being coded (P: min(nref, pictures since the IDR picture)) */
   pixel *src[3];
-  pixel *prev_src;                     /* cfg.me_source: the luma plane of the previous input picture (padded to the coded size), NULL until the option is set */
+  pixel *prev_src[ORC_MAX_LP_REFS];    /* cfg.me_source: the luma planes of the previous input pictures, [k] = picture t-1-k (padded to the coded size), NULL until needed */
   int16_t *coef[3];
   pixel *predeblock[3];
-  pixel *refpad; int refpad_stride;
+  pixel *refpad[ORC_MAX_LP_REFS]; int refpad_stride;   /* the plane the integer search looks at, per reference (build_refpad) */
+  uint8_t *cu_ref;                     /* per 8x8 block: ref_idx_l0 of the search's choice */
   uint8_t *cu_log2, *cu_intra, *cu_flags, *cu_merge_idx, *cu_mvp_idx, *cu_intra_mode, *cu_cbf;
   int16_t *cu_mv, *cu_mvd;
   uint8_t *bs_v, *bs_h;
@@ -102,13 +108,14 @@ orc_encoder *orc_enc_open(const orc_enc_config *c)
   e->b8w = e->cw / 8; e->b8h = e->ch / 8;
   size_t nb8 = (size_t)e->b8w * e->b8h, npx = (size_t)e->cw * e->ch;
   for (int i = 0; i < 2; i++) if (orc_pic_alloc(&e->pics[i], e->cw, e->ch)) return NULL;
-  e->cur = &e->pics[0]; e->ref = &e->pics[1];
+  e->cur = &e->pics[0]; e->refs[0] = &e->pics[1]; e->nref = 1;
   for (int i = 0; i < 3; i++) {
     size_t n = i ? npx / 4 : npx;
     e->src[i] = (pixel *)malloc(n); e->coef[i] = (int16_t *)calloc(n, sizeof(int16_t)); e->predeblock[i] = (pixel *)malloc(n);
   }
   e->refpad_stride = e->cw + 2 * ME_PAD;
-  e->refpad = (pixel *)malloc((size_t)e->refpad_stride * (e->ch + 2 * ME_PAD));
+  e->refpad[0] = (pixel *)malloc((size_t)e->refpad_stride * (e->ch + 2 * ME_PAD));
+  e->cu_ref = (uint8_t *)calloc(nb8, 1);
   e->cu_log2 = (uint8_t *)calloc(nb8, 1); e->cu_intra = (uint8_t *)calloc(nb8, 1); e->cu_flags = (uint8_t *)calloc(nb8, 1);
   e->cu_merge_idx = (uint8_t *)calloc(nb8, 1); e->cu_mvp_idx = (uint8_t *)calloc(nb8, 1); e->cu_intra_mode = (uint8_t *)calloc(nb8, 1);
   e->cu_cbf = (uint8_t *)calloc(nb8, 1); e->cu_mv = (int16_t *)calloc(nb8 * 2, sizeof(int16_t)); e->cu_mvd = (int16_t *)calloc(nb8 * 2, sizeof(int16_t));
@@ -167,9 +174,10 @@ orc_encoder *orc_enc_open(const orc_enc_config *c)
 void orc_enc_close(orc_encoder *e)
 {
   if (!e) return;
-  for (int i = 0; i < 2; i++) orc_pic_free(&e->pics[i]);
+  for (int i = 0; i < 1 + e->nref; i++) orc_pic_free(&e->pics[i]);
   for (int i = 0; i < 3; i++) { free(e->src[i]); free(e->coef[i]); free(e->predeblock[i]); }
-  free(e->refpad); free(e->prev_src); free(e->sao); for (int i = 0; i < 3; i++) free(e->sao_in[i]);
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) { free(e->refpad[k]); free(e->prev_src[k]); }
+  free(e->cu_ref); free(e->sao); for (int i = 0; i < 3; i++) free(e->sao_in[i]);
   free(e->cu_log2); free(e->cu_intra); free(e->cu_flags); free(e->cu_merge_idx); free(e->cu_mvp_idx);
   free(e->cu_intra_mode); free(e->cu_cbf); free(e->cu_mv); free(e->cu_mvd); free(e->bs_v); free(e->bs_h);
   free(e->im8); free(e->im16); free(e->im32); free(e->ic8); free(e->ic16); free(e->ic32);
@@ -402,14 +410,15 @@ static void encode_intra_picture(orc_encoder *e)
  * INPUT picture: then the search of picture t + 1 depends on nothing picture t's reconstruction loop produces and the two run side by side (what hardware
  * encoders do).  Only the search moves: early termination, the 32x32 / 16x16 costs and the intra-in-P gate are priced on that picture; fractional
  * refinement (subme), motion compensation and everything behind them use the reconstruction as before. */
-static void build_refpad(orc_encoder *e)
+static void build_refpad(orc_encoder *e, int k)
 {
   int st = e->refpad_stride;
-  const pixel *plane = e->cfg.me_source && e->prev_src ? e->prev_src : e->ref->plane[0];
-  const int pstride = e->cfg.me_source && e->prev_src ? e->cw : e->ref->stride[0];
+  const pixel *plane = e->cfg.me_source && e->prev_src[k] ? e->prev_src[k] : e->refs[k]->plane[0];      /* reference k: picture t-1-k */
+  const int pstride = e->cfg.me_source && e->prev_src[k] ? e->cw : e->refs[k]->stride[0];
+  if (!e->refpad[k]) e->refpad[k] = (pixel *)malloc((size_t)st * (e->ch + 2 * ME_PAD));
   for (int y = -ME_PAD; y < e->ch + ME_PAD; y++) {
     const pixel *srow = plane + (size_t)orc_clip3(0, e->ch - 1, y) * pstride;
-    pixel *drow = e->refpad + (size_t)(y + ME_PAD) * st;
+    pixel *drow = e->refpad[k] + (size_t)(y + ME_PAD) * st;
     for (int x = -ME_PAD; x < e->cw + ME_PAD; x++) drow[x + ME_PAD] = srow[orc_clip3(0, e->cw - 1, x)];
   }
 }
@@ -420,6 +429,9 @@ static inline uint32_t sad16(const pixel *a, int as, const pixel *b, int bs)
   for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) s += (uint32_t)orc_abs(a[y * as + x] - b[y * bs + x]);
   return s;
 }
+
+/* lp-refs: bins of ref_idx_l0 = k in a slice with m active references -- truncated unary with cMax m - 1 (none with one reference) */
+static int ref_bins(int k, int m) { return m <= 1 ? 0 : (k < m - 1 ? k + 1 : m - 1); }
 
 /* "uvgx subme v1" (kvazaar subme 1..4): fractional-sample refinement of one CU's vector after the integer search.  Two steps
  * of eight neighbours each -- half-sample positions around the integer vector, then quarter-sample positions around the best
@@ -447,7 +459,7 @@ static int subme_allowed(const orc_encoder *e, int x0, int y0, int n, int mvx, i
 static uint32_t subme_cost(orc_encoder *e, int x0, int y0, int n, int mvx, int mvy)
 {
   int16_t tmp[32 * 32]; pixel pred[32 * 32];
-  orc_pic *r = e->ref;
+  const orc_pic *r = e->refs[e->cu_ref[b8i(e, x0, y0)]];          /* the CU's own reference: the refinement never changes it */
   orc_mc_luma(r->plane[0], r->stride[0], r->w, r->h, x0, y0, n, n, mvx, mvy, tmp, 32);
   orc_pred_uni(tmp, 32, pred, 32, n, n);
   uint32_t rate = ((uint32_t)orc_lambda_q4[e->qp] * (uint32_t)(orc_mvd_bits(mvx) + orc_mvd_bits(mvy))) >> 4;
@@ -473,22 +485,22 @@ static void subme_refine(orc_encoder *e, int x0, int y0, int n, int ty0, int ty1
   for (int y = y0; y < y0 + n; y += 8) for (int x = x0; x < x0 + n; x += 8) { e->cu_mv[b8i(e, x, y) * 2] = (int16_t)cx; e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)cy; }
 }
 
-/* Full search for one 32x32 block: candidates in raster order (dy outer, dx inner),
- * cost = SAD + (lambda * bits(mv as mvd from zero)) >> 4, key = cost << 13 | candidate index. */
+/* Full search for one 32x32 block over the m active references (reference k: refpad[k]), each with candidates in raster order (dy outer,
+ * dx inner), cost = SAD + (lambda * (bits(mv as mvd from zero) + ref_bins(k, m))) >> 4, key = cost << 16 | k << 13 | candidate index:
+ * lower cost, then lower reference, then lower candidate (with one reference the order of cost << 13 | candidate). */
 static void me_block32(orc_encoder *e, int x0, int y0)
 {
-  int R = e->cfg.search_range, st = e->refpad_stride;
+  int R = e->cfg.search_range, st = e->refpad_stride, m = e->nact;
   uint32_t lam = orc_lambda_q4[e->qp];
-  uint32_t best16[4] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu }, best32 = 0xffffffffu;
-  int idx = 0;
-  if (e->cfg.me_early) {                              /* early termination: static content is not searched */
+  uint64_t best16[4] = { UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX }, best32 = UINT64_MAX;
+  if (e->cfg.me_early) {                              /* early termination: static content is not searched (against reference 0, which it then takes) */
     uint32_t s0 = 0;
     for (int k = 0; k < 4; k++) {
       int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16;
-      s0 += sad16(e->src[0] + by * e->cw + bx, e->cw, e->refpad + (size_t)(by + ME_PAD) * st + bx + ME_PAD, st);
+      s0 += sad16(e->src[0] + by * e->cw + bx, e->cw, e->refpad[0] + (size_t)(by + ME_PAD) * st + bx + ME_PAD, st);
     }
     if (s0 <= 64u * lam) {
-      set_cu(e, e->cu_log2, x0, y0, 32, 5); set_cu(e, e->cu_intra, x0, y0, 32, 0);
+      set_cu(e, e->cu_log2, x0, y0, 32, 5); set_cu(e, e->cu_intra, x0, y0, 32, 0); set_cu(e, e->cu_ref, x0, y0, 32, 0);
       for (int y = y0; y < y0 + 32; y += 8) for (int x = x0; x < x0 + 32; x += 8) { e->cu_mv[b8i(e, x, y) * 2] = 0; e->cu_mv[b8i(e, x, y) * 2 + 1] = 0; }
       return;
     }
@@ -499,42 +511,49 @@ static void me_block32(orc_encoder *e, int x0, int y0)
   for (int i = 0; i < e->cfg.tile_rows; i++) if ((y0 >> 6) >= e->tile_row_bd[i] && (y0 >> 6) < e->tile_row_bd[i + 1]) { ty0 = e->tile_row_bd[i] * 64; ty1 = e->tile_row_bd[i + 1] * 64; }
   int tx0 = 0, tx1 = e->cw;                                      /* ... and the same in x with tile columns */
   for (int j = 0; j < e->cfg.tile_cols; j++) if ((x0 >> 6) >= e->tile_col_bd[j] && (x0 >> 6) < e->tile_col_bd[j + 1]) { tx0 = e->tile_col_bd[j] * 64; tx1 = e->tile_col_bd[j + 1] * 64; }
+  for (int rk = 0; rk < m; rk++) {
+    const pixel *refpad = e->refpad[rk];
+    const uint32_t rb = (uint32_t)ref_bins(rk, m);
+    int idx = 0;
   for (int dy = -R; dy <= R; dy++)
     for (int dx = -R; dx <= R; dx++, idx++) {
-      int m = (dy & 1) ? 4 : 0, mxt = (dx & 1) ? 4 : 0;
-      if ((ty0 > 0 && y0 + dy - m < ty0) || (ty1 < e->ch && y0 + dy + 32 + m > ty1)) continue;
+      int myt = (dy & 1) ? 4 : 0, mxt = (dx & 1) ? 4 : 0;
+      if ((ty0 > 0 && y0 + dy - myt < ty0) || (ty1 < e->ch && y0 + dy + 32 + myt > ty1)) continue;
       if ((tx0 > 0 && x0 + dx - mxt < tx0) || (tx1 < e->cw && x0 + dx + 32 + mxt > tx1)) continue;
       if (e->cfg.mv_frame) {                                   /* mv-constraint frame: the displaced block stays inside the picture */
         int my = (e->cfg.mv_frame == 2 && (dy & 1)) ? 4 : 0, mx = (e->cfg.mv_frame == 2 && (dx & 1)) ? 4 : 0;
         if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > e->cw || y0 + dy - my < 0 || y0 + dy + 32 + my > e->ch) continue;
       }
-      uint32_t rate = (lam * (uint32_t)(orc_mvd_bits(dx * 4) + orc_mvd_bits(dy * 4))) >> 4;
+      uint32_t rate = (lam * (uint32_t)(orc_mvd_bits(dx * 4) + orc_mvd_bits(dy * 4) + rb)) >> 4;
+      const uint64_t cand = ((uint64_t)rk << 13) | (uint64_t)idx;
       uint32_t s32 = 0;
       for (int k = 0; k < 4; k++) {
         int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16;
-        uint32_t s = sad16(e->src[0] + by * e->cw + bx, e->cw, e->refpad + (size_t)(by + dy + ME_PAD) * st + bx + dx + ME_PAD, st);
+        uint32_t s = sad16(e->src[0] + by * e->cw + bx, e->cw, refpad + (size_t)(by + dy + ME_PAD) * st + bx + dx + ME_PAD, st);
         s32 += s;
-        uint32_t key = ((s + rate) << 13) | (uint32_t)idx;
+        uint64_t key = ((uint64_t)(s + rate) << 16) | cand;
         if (key < best16[k]) best16[k] = key;
       }
-      uint32_t key = ((s32 + rate) << 13) | (uint32_t)idx;
+      uint64_t key = ((uint64_t)(s32 + rate) << 16) | cand;
       if (key < best32) best32 = key;
     }
+  }
   uint32_t pen = (lam * SPLIT_BITS) >> 4;
   uint32_t csplit = pen;
-  for (int k = 0; k < 4; k++) csplit += best16[k] >> 13;
+  for (int k = 0; k < 4; k++) csplit += (uint32_t)(best16[k] >> 16);
+  const uint32_t c32 = (uint32_t)(best32 >> 16);
   int W = 2 * R + 1;
-  if (csplit < (best32 >> 13)) {
+  if (csplit < c32) {
     for (int k = 0; k < 4; k++) {
       int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16, ci = (int)(best16[k] & 0x1fff);
-      set_cu(e, e->cu_log2, bx, by, 16, 4);
+      set_cu(e, e->cu_log2, bx, by, 16, 4); set_cu(e, e->cu_ref, bx, by, 16, (int)((best16[k] >> 13) & 7));      /* quarters keep their own reference */
       for (int y = by; y < by + 16; y += 8) for (int x = bx; x < bx + 16; x += 8) {
         e->cu_mv[b8i(e, x, y) * 2] = (int16_t)(((ci % W) - R) * 4); e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)(((ci / W) - R) * 4);
       }
     }
   } else {
     int ci = (int)(best32 & 0x1fff);
-    set_cu(e, e->cu_log2, x0, y0, 32, 5);
+    set_cu(e, e->cu_log2, x0, y0, 32, 5); set_cu(e, e->cu_ref, x0, y0, 32, (int)((best32 >> 13) & 7));
     for (int y = y0; y < y0 + 32; y += 8) for (int x = x0; x < x0 + 32; x += 8) {
       e->cu_mv[b8i(e, x, y) * 2] = (int16_t)(((ci % W) - R) * 4); e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)(((ci / W) - R) * 4);
     }
@@ -547,7 +566,7 @@ static void me_block32(orc_encoder *e, int x0, int y0)
      * units (the inter ones keep their vectors; an intra quarter is one 16x16 or four 8x8 intra units). */
     uint32_t ic[4]; int any = 0, cand[4];
     for (int k = 0; k < 4; k++) {
-      ic[k] = csplit < (best32 >> 13) ? best16[k] >> 13 : ((best32 >> 13) + 2) >> 2;
+      ic[k] = csplit < c32 ? (uint32_t)(best16[k] >> 16) : (c32 + 2) >> 2;      /* (the chosen costs: reference bins included) */
       cand[k] = ic[k] > INTRA_P_GATE * lam; any |= cand[k];
     }
     if (any) {
@@ -600,7 +619,8 @@ static void me_block32(orc_encoder *e, int x0, int y0)
 
 static void inter_recon_cu(orc_encoder *e, int x0, int y0, int log2)
 {
-  orc_pic *p = e->cur, *r = e->ref;
+  const int rk = e->cu_ref[b8i(e, x0, y0)];
+  orc_pic *p = e->cur; const orc_pic *r = e->refs[rk];            /* luma and chroma from the CU's own reference */
   int n = 1 << log2;
   int16_t mv[2] = { e->cu_mv[b8i(e, x0, y0) * 2], e->cu_mv[b8i(e, x0, y0) * 2 + 1] };
   int16_t tmp[32 * 32];
@@ -608,7 +628,7 @@ static void inter_recon_cu(orc_encoder *e, int x0, int y0, int log2)
   mark_cu(e, x0, y0, log2, MODE_INTER);
   for (int y = y0; y < y0 + n; y += 4) for (int x = x0; x < x0 + n; x += 4) {
     orc_mvinfo *m = &p->mvf[(y >> 2) * p->b4_w + (x >> 2)];
-    m->mv[0] = mv[0]; m->mv[1] = mv[1]; m->ref_idx = 0;
+    m->mv[0] = mv[0]; m->mv[1] = mv[1]; m->ref_idx = (int8_t)rk;
   }
   orc_mc_luma(r->plane[0], r->stride[0], r->w, r->h, x0, y0, n, n, mv[0], mv[1], tmp, 32);
   orc_pred_uni(tmp, 32, p->plane[0] + y0 * p->stride[0] + x0, p->stride[0], n, n);
@@ -624,22 +644,29 @@ static void inter_recon_cu(orc_encoder *e, int x0, int y0, int log2)
   set_cu(e, e->cu_intra, x0, y0, n, 0);
 }
 
+/* tmvp: slice_temporal_mvp_enabled_flag of the picture being coded -- 1 on every P picture but the one right after an IDR picture, whose
+ * collocated picture (the previous one) is intra and gives no candidate */
+static int slice_tmvp(const orc_encoder *e) { return e->cfg.tmvp && !e->is_intra && e->poc != 1; }
+
 /* merge / skip / AMVP signalling decided from the FINAL motion field of the picture */
 static void inter_decide_signalling(orc_encoder *e, int x0, int y0, int log2)
 {
   orc_pic *p = e->cur; int n = 1 << log2, bi = b8i(e, x0, y0);
   orc_mvpred_ctx mc; memset(&mc, 0, sizeof(mc)); mc.collocated_from_l0 = 1;
-  mc.pic = p; mc.av = e->av; mc.log2_par_mrg_level = 2; mc.max_num_merge_cand = 5; mc.num_ref_idx = 1;
-  mc.cur_poc = e->poc; mc.ref_poc[0] = e->poc - 1;
+  mc.pic = p; mc.av = e->av; mc.log2_par_mrg_level = 2; mc.max_num_merge_cand = 5; mc.num_ref_idx = e->nact;
+  mc.cur_poc = e->poc;
+  for (int k = 0; k < e->nact; k++) mc.ref_poc[k] = e->poc - 1 - k;          /* reference k: POC distance k + 1 */
+  if (slice_tmvp(e)) mc.col = e->refs[0];                                       /* collocated_ref_idx 0: the previous picture */
+  const int rk = e->cu_ref[bi];
   int16_t mvx = e->cu_mv[bi * 2], mvy = e->cu_mv[bi * 2 + 1];
   orc_mvcand cand[5];
   orc_merge_candidates(&mc, x0, y0, n, x0, y0, n, n, 0, PART_2Nx2N, cand);
   int flags = 0, midx = 0, mvp = 0; int16_t mvdx = 0, mvdy = 0;
-  for (int k = 0; k < 5; k++) if (cand[k].ref_idx == 0 && cand[k].mv[0] == mvx && cand[k].mv[1] == mvy) { flags = 2; midx = k; break; }
+  for (int k = 0; k < 5; k++) if (cand[k].ref_idx == rk && cand[k].mv[0] == mvx && cand[k].mv[1] == mvy) { flags = 2; midx = k; break; }   /* equal in vector and reference */
   if (flags && e->cu_cbf[bi] == 0) flags |= 1;
   if (!flags) {
     int16_t ac[2][2];
-    orc_amvp_candidates(&mc, x0, y0, n, x0, y0, n, n, 0, 0, ac);
+    orc_amvp_candidates(&mc, x0, y0, n, x0, y0, n, n, 0, rk, ac);
     int b0 = orc_mvd_bits(mvx - ac[0][0]) + orc_mvd_bits(mvy - ac[0][1]);
     int b1 = orc_mvd_bits(mvx - ac[1][0]) + orc_mvd_bits(mvy - ac[1][1]);
     mvp = b1 < b0;
@@ -695,7 +722,7 @@ static void rc_picture_start(orc_encoder *e)
 static void intra_recon_tree(orc_encoder *e, int x0, int y0, int log2);
 static void encode_inter_picture(orc_encoder *e)
 {
-  build_refpad(e);
+  for (int k = 0; k < e->nact; k++) build_refpad(e, k);
   e->intra_p_ready = 0;
   for (int y = 0; y < e->ch; y += 32) for (int x = 0; x < e->cw; x += 32) me_block32(e, x, y);
   /* Reconstruction, in rc_bands groups of CTU rows when rate control v2 is on: after each group the level cost so far is priced
@@ -951,6 +978,14 @@ static void enc_cu(orc_encoder *e, orc_cabac_enc *c, int x0, int y0, int log2)
       orc_cenc_bin(c, CTX_MERGE_IDX, idx > 0);
       if (idx > 0) for (int i = 1; i < 4; i++) { orc_cenc_bypass(c, idx > i); if (idx <= i) break; }
     } else {
+      if (e->nact > 1) {                             /* ref_idx_l0 (7.3.8.6): truncated rice, cMax m - 1; bins 0 and 1 on contexts, the rest bypass (9.3.4.2) */
+        const int r = e->cu_ref[bi];
+        for (int i = 0; i < e->nact - 1; i++) {
+          const int b = r > i;
+          if (i < 2) orc_cenc_bin(c, CTX_REF_IDX + i, b); else orc_cenc_bypass(c, b);
+          if (!b) break;
+        }
+      }
       enc_mvd(c, e->cu_mvd[bi * 2], e->cu_mvd[bi * 2 + 1]);
       orc_cenc_bin(c, CTX_MVP_FLAG, e->cu_mvp_idx[bi]);
       orc_cenc_bin(c, CTX_RQT_ROOT_CBF, cbf != 0);
@@ -1046,7 +1081,9 @@ static void write_picture(orc_encoder *e, int write_ps)
   sh.slice_type = e->is_intra ? SLICE_I : SLICE_P; sh.pic_output_flag = 1;
   sh.slice_qp_delta = e->qp - e->cfg.qp;            /* PPS init_qp is the configured QP */
   sh.poc_lsb = e->poc & 255; sh.short_term_ref_pic_set_sps_flag = 1;
-  sh.num_ref_idx_l0 = 1; sh.num_ref_idx_l1 = 1; sh.max_num_merge_cand = 5; sh.collocated_from_l0 = 1;
+  sh.num_ref_idx_l0 = e->is_intra ? 1 : e->nact; sh.num_ref_idx_l1 = 1; sh.max_num_merge_cand = 5; sh.collocated_from_l0 = 1;
+  sh.short_term_rps_idx = e->is_intra ? 0 : e->nact - 1;          /* set m - 1: the m previous pictures; num_ref_idx_active_override when m < n */
+  sh.slice_temporal_mvp_enabled = slice_tmvp(e); sh.collocated_ref_idx = 0;
   sh.slice_deblocking_disabled = !e->cfg.deblock;
   sh.loop_filter_across_slices = 1;
   sh.sao_luma = sh.sao_chroma = e->cfg.sao ? 1 : 0;
@@ -1170,12 +1207,14 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
   int period = e->cfg.intra_period;
   e->is_intra = (e->frame_idx == 0) || (period > 0 && (e->frame_idx % period) == 0);
   if (e->is_intra) e->poc = 0; else e->poc++;
+  e->nact = e->is_intra ? 0 : (e->poc < e->nref ? e->poc : e->nref);
   rate_control(e);
   rc_picture_start(e);
   load_input(e, y, u, v);
   roi_targets(e);
   orc_pic_reset_side(e->cur);
-  for (int i = 0; i < 16; i++) e->cur->ref_poc_list[i] = e->poc - 1;       /* one reference picture */
+  e->cur->poc = e->poc;
+  for (int i = 0; i < 16; i++) e->cur->ref_poc_list[i] = e->poc - 1 - (i < e->nref ? i : 0);      /* reference k = picture t-1-k (bS compares these, TMVP scales by them) */
   for (int c = 0; c < 3; c++) memset(e->coef[c], 0, sizeof(int16_t) * (size_t)(c ? e->cw * e->ch / 4 : e->cw * e->ch));
   if (e->is_intra) encode_intra_picture(e); else encode_inter_picture(e);
   roi_resolve(e);
@@ -1223,10 +1262,17 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
   }
   e->rc_bytes[e->frame_idx & 7] = (uint32_t)e->au.len;
   e->frame_idx++;
-  orc_pic *t = e->cur; e->cur = e->ref; e->ref = t;     /* e->ref now holds the picture just coded */
-  if (e->cfg.me_source) {                               /* the next picture's search looks at this input picture */
-    if (!e->prev_src) e->prev_src = (pixel *)malloc((size_t)e->cw * e->ch);
-    memcpy(e->prev_src, e->src[0], (size_t)e->cw * e->ch);
+  {                                                     /* refs[0] now holds the picture just coded, refs[k] the one k pictures before it */
+    orc_pic *t = e->refs[e->nref - 1];
+    for (int k = e->nref - 1; k > 0; k--) e->refs[k] = e->refs[k - 1];
+    e->refs[0] = e->cur; e->cur = t;
+  }
+  if (e->cfg.me_source) {                               /* the next picture's search looks at this input picture (and its references at the ones before) */
+    pixel *t = e->prev_src[e->nref - 1];
+    if (!t) t = (pixel *)malloc((size_t)e->cw * e->ch);
+    for (int k = e->nref - 1; k > 0; k--) e->prev_src[k] = e->prev_src[k - 1];
+    e->prev_src[0] = t;
+    memcpy(t, e->src[0], (size_t)e->cw * e->ch);
   }
   *au = e->au.buf;
   return e->au.len;
@@ -1254,6 +1300,26 @@ int orc_enc_set_option(orc_encoder *e, const char *name, int value)
     return 1;
   }
   if (!strcmp(name, "me-source")) { e->cfg.me_source = value != 0; return 1; }      /* the integer search on the previous input picture (build_refpad) */
+  if (!strcmp(name, "lp-refs")) {                      /* (before the first picture: the ring, the SPS's sets, the PPS's default count) */
+    if (value < 0 || value > ORC_MAX_LP_REFS || e->frame_idx > 0) return 0;
+    const int n = value > 1 ? value : 1;
+    for (int i = 1 + e->nref; i < 1 + n; i++) if (orc_pic_alloc(&e->pics[i], e->cw, e->ch)) return 0;
+    for (int i = 1 + n; i < 1 + e->nref; i++) orc_pic_free(&e->pics[i]);
+    e->cfg.lp_refs = value; e->nref = n;
+    e->cur = &e->pics[0];
+    for (int k = 0; k < n; k++) e->refs[k] = &e->pics[1 + k];
+    orc_sps *s = &e->sps;
+    s->max_dec_pic_buffering = n + 1;                    /* sps / vps_max_dec_pic_buffering_minus1 = n */
+    s->num_st_rps = n;                                   /* set i: the pictures -1 .. -(i + 1), all used by the current picture */
+    for (int i = 0; i < n; i++) {
+      memset(&s->st_rps[i], 0, sizeof(s->st_rps[i]));
+      s->st_rps[i].num_negative = i + 1;
+      for (int j = 0; j <= i; j++) { s->st_rps[i].delta_poc_s0[j] = -(j + 1); s->st_rps[i].used_s0[j] = 1; }
+    }
+    e->pps.num_ref_idx_l0_default = n;
+    return 1;
+  }
+  if (!strcmp(name, "tmvp")) { if (value < 0 || value > 1 || e->frame_idx > 0) return 0; e->cfg.tmvp = value; e->sps.temporal_mvp_enabled = value; return 1; }
   if (!strcmp(name, "rdoq")) { e->cfg.rdoq = value != 0; return 1; }
   if (!strcmp(name, "signhide")) { e->cfg.signhide = value != 0; e->pps.sign_data_hiding = e->cfg.signhide; return 1; }
   return 0;
@@ -1265,15 +1331,18 @@ void orc_enc_get_debug(orc_encoder *e, orc_enc_debug *d)
   d->coded_w = e->cw; d->coded_h = e->ch; d->is_intra = e->is_intra; d->poc = e->poc;
   d->cu_log2 = e->cu_log2; d->cu_intra = e->cu_intra; d->cu_flags = e->cu_flags; d->cu_merge_idx = e->cu_merge_idx;
   d->cu_mvp_idx = e->cu_mvp_idx; d->cu_intra_mode = e->cu_intra_mode; d->cu_cbf = e->cu_cbf; d->cu_mv = e->cu_mv;
-  for (int i = 0; i < 3; i++) { d->coef[i] = e->coef[i]; d->predeblock[i] = e->predeblock[i]; d->recon[i] = e->ref->plane[i]; }
+  for (int i = 0; i < 3; i++) { d->coef[i] = e->coef[i]; d->predeblock[i] = e->predeblock[i]; d->recon[i] = e->refs[0]->plane[i]; }
   d->bs_v = e->bs_v; d->bs_h = e->bs_h; d->bins = e->bins;
 }
+
+const uint8_t *orc_enc_debug_cu_ref(orc_encoder *e) { return e->cu_ref; }
+const int16_t *orc_enc_debug_cu_mvd(orc_encoder *e) { return e->cu_mvd; }
 
 void orc_enc_get_recon(orc_encoder *e, pixel *y, pixel *u, pixel *v)
 {
   pixel *out[3] = { y, u, v };
   for (int c = 0; c < 3; c++) {
     int w = c ? e->cfg.width / 2 : e->cfg.width, h = c ? e->cfg.height / 2 : e->cfg.height;
-    for (int yy = 0; yy < h; yy++) memcpy(out[c] + (size_t)yy * w, e->ref->plane[c] + (size_t)yy * e->ref->stride[c], (size_t)w);
+    for (int yy = 0; yy < h; yy++) memcpy(out[c] + (size_t)yy * w, e->refs[0]->plane[c] + (size_t)yy * e->refs[0]->stride[c], (size_t)w);
   }
 }

@@ -9,8 +9,9 @@
  *
  * Tool set (mirrors Kvazaar preset=ultrafast as far as SURVEY.md Appendix A records it):
  *   CTU 64, CUs 32/16 (inter, 2Nx2N) and 32/16/8 (intra, 2Nx2N), TU = CU (chroma half),
- *   integer-sample full-search motion estimation over +-range, 1 reference (previous picture),
- *   merge/skip with 5 candidates, AMVP, no TMVP, plain dead-zone quantiser, deblocking on,
+ *   integer-sample full-search motion estimation over +-range, 1 reference (previous picture) or with "lp-refs" n = 2..4 the
+ *   n previous pictures ("uvgx multi-reference v1"), merge/skip with 5 candidates, AMVP, TMVP off
+ *   or with "tmvp" 1 the previous picture as the collocated one, plain dead-zone quantiser, deblocking on,
  *   SAO off, sign hiding off, transform skip off, WPP on, one slice per picture,
  *   IDR every `period` pictures with VPS/SPS/PPS, constant QP or picture-level rate control (bitrate > 0).
  * Test infrastructure. */
@@ -75,6 +76,10 @@ typedef struct {
   int lossless;               /* kvazaar lossless (uvgComm's check box, kvazaarfilter.cpp:244): every coding unit with cu_transquant_bypass_flag -- the residual IS the
                                * level array, the reconstruction is the source picture; the decisions (modes, vectors, splits) are the lossy encoder's; no deblocking, no
                                * SAO (they would leave these samples alone anyway, 8.7.2.5.7 / 8.7.3), no RDOQ, no sign hiding, no rate control */
+  int lp_refs;                /* "lp-refs" (option by name): 0 / 1 one reference; n = 2..4: P picture t refers to the m = min(n, pictures since the IDR picture)
+                               * pictures t-1 .. t-m, reference k = picture t-1-k, all in list 0 (me_block32, inter_recon_cu, inter_decide_signalling, write_picture) */
+  int tmvp;                   /* "tmvp" (option by name): sps_temporal_mvp_enabled_flag; the collocated picture is reference 0, the previous picture, and the picture
+                               * right after an IDR picture says slice_temporal_mvp_enabled_flag = 0 */
 } orc_enc_config;
 
 typedef struct {
@@ -93,7 +98,8 @@ typedef struct {
 } orc_enc_debug;
 
 void orc_enc_default_config(orc_enc_config *c);
-/* options added after the packed open calls ran out of bits: by name, before the first picture.  "hash" 0/1/2, "rdoq" 0/1, "signhide" 0/1, "intra-in-p" 0/1.  Returns 1 when known. */
+/* options added after the packed open calls ran out of bits: by name, before the first picture.  "hash" 0/1/2, "rdoq" 0/1, "signhide" 0/1, "intra-in-p" 0/1,
+ * "lp-refs" 0..4, "tmvp" 0/1.  Returns 1 when known (0 also for a value out of range). */
 int orc_enc_set_option(orc_encoder *e, const char *name, int value);
 orc_encoder *orc_enc_open(const orc_enc_config *c);
 void orc_enc_close(orc_encoder *e);
@@ -104,6 +110,11 @@ void orc_enc_close(orc_encoder *e);
 void orc_enc_set_roi(orc_encoder *e, int w, int h, const int8_t *map);
 size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixel *v, const uint8_t **au);
 void orc_enc_get_debug(orc_encoder *e, orc_enc_debug *dbg);
+/* per 8x8 block arrays beside orc_enc_debug (whose size callers that were built against it allocate, so it does not grow), stride coded_w/8:
+ * ref_idx_l0 the search chose (lp-refs; 0 with one reference; intra units keep the search's value), and [b8][2] the coded motion vector
+ * difference of an AMVP-coded CU (0 where merged) */
+const uint8_t *orc_enc_debug_cu_ref(orc_encoder *e);
+const int16_t *orc_enc_debug_cu_mvd(orc_encoder *e);
 /* copy cropped reconstruction (width x height I420, packed) */
 void orc_enc_get_recon(orc_encoder *e, pixel *y, pixel *u, pixel *v);
 

@@ -25,6 +25,9 @@ def lib():
         L.orc_api_enc_encode.argtypes = [C.c_void_p] * 5 + [C.c_long]
         L.orc_enc_close.argtypes = [C.c_void_p]
         L.orc_enc_get_debug.argtypes = [C.c_void_p, C.c_void_p]
+        for f in (L.orc_enc_debug_cu_ref, L.orc_enc_debug_cu_mvd):
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p]
         L.orc_enc_get_recon.argtypes = [C.c_void_p] * 4
         L.orc_dec_open.restype = C.c_void_p
         L.orc_dec_close.argtypes = [C.c_void_p]
@@ -83,7 +86,7 @@ class OracleEncoder:
         self.buf = np.empty(w * h * 3 + (1 << 20), dtype=np.uint8)
 
     def set_option(self, name, value):
-        """options by name (oracle/hevc_enc.h orc_enc_set_option): "hash" 0 none / 1 checksum / 2 md5, ..."""
+        """options by name (oracle/hevc_enc.h orc_enc_set_option): "hash" 0 none / 1 checksum / 2 md5, ..., "lp-refs" 0..4, "tmvp" 0 / 1"""
         lib().orc_enc_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         if not lib().orc_enc_set_option(self.p, name.encode(), int(value)):
             raise ValueError("oracle encoder: unknown option %s" % name)
@@ -111,6 +114,9 @@ class OracleEncoder:
         for k in ("cu_log2", "cu_intra", "cu_flags", "cu_merge_idx", "cu_mvp_idx", "cu_intra_mode", "cu_cbf"):
             out[k] = _arr(getattr(d, k), b8, np.uint8)
         out["cu_mv"] = _arr(d.cu_mv, b8 + (2,), np.int16)
+        # (arrays of their own beside the struct: its layout stays what older bindings allocate)
+        out["cu_ref"] = _arr(lib().orc_enc_debug_cu_ref(self.p), b8, np.uint8)
+        out["cu_mvd"] = _arr(lib().orc_enc_debug_cu_mvd(self.p), b8 + (2,), np.int16)
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             out["coef%d" % c] = _arr(d.coef[c], shp, np.int16)

@@ -1,8 +1,9 @@
 """GPU: "uvgx multi-reference v1" (kvazaar.h lp-refs) -- P pictures that refer to up to four previous pictures.
 
-The checker's encoder has one reference, so the feature is held to three things: with lp-refs 0 / 1 the encoder is the one-reference encoder byte
-for byte; the integer search equals the numpy restatement tests/lp_refs_model.py (itself pinned to the checker by tests/test_lp_refs_host.py); and
-every picture's reconstruction equals what the checker's decoder and the library's HIP decoder make of the stream (closed loop)."""
+Here the feature is held to three things: with lp-refs 0 / 1 the encoder is the one-reference encoder byte for byte; the integer search equals
+the numpy restatement tests/lp_refs_model.py (itself pinned to the checker by tests/test_lp_refs_host.py); and every picture's reconstruction
+equals what the checker's decoder and the library's HIP decoder make of the stream (closed loop).  The checker's encoder states lp-refs itself,
+and tests/test_gpu_lp_refs_oracle.py holds the HIP encoder to it bit for bit."""
 import numpy as np
 import pytest
 

@@ -5,7 +5,8 @@ difference to a predictor, and nothing after k_inter_signal reads the signalling
 is the reconstruction with tmvp=0, picture for picture, whatever else is switched on.  What breaks the equality is a bitrate: the picture-level rate
 control follows the access units' sizes, which tmvp changes (the in-picture steps of rc-algorithm follow the levels' cost, which it does not change).
 Those cases are held to the closed loop only: every reconstruction equals what the checker's decoder (md5 SEI verified), the HIP decoder (synchronous
-and frame-threaded) and, for the small cases, tests/pyhevc.py make of the stream."""
+and frame-threaded) and, for the small cases, tests/pyhevc.py make of the stream.  (The checker's encoder states tmvp itself: tests/test_gpu_lp_refs_oracle.py holds the HIP
+encoder to it bit for bit, the bitrate cases included.)"""
 import numpy as np
 import pytest
 

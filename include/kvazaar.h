@@ -117,7 +117,7 @@ typedef struct kvz_config {
   int32_t fast_residual_cost_limit;
   int32_t pu_depth_inter_min, pu_depth_inter_max, pu_depth_intra_min, pu_depth_intra_max;
   /* kvazzup_amd extensions (not in Kvazaar) */
-  int32_t me_range;           /* "me-range": exhaustive search radius in integer samples, 1..32 */
+  int32_t me_range;           /* "me-range": exhaustive search radius in integer samples, 1..32, of the window around the zero vector (and, with "me-coarse", of the second window around the coarse stage's centre: that option is what reaches farther) */
   int32_t gpu_device;         /* "gpu": HIP device ordinal */
   int32_t recon_output;       /* "recon-output": 0 = encoder_encode leaves *pic_out NULL (no download) */
   int32_t intra_satd;         /* "intra-satd": 1 (default) = the intra mode search compares 8x8 Hadamard sums (SATD) like Kvazaar's rough search, 0 = SAD */
@@ -129,6 +129,7 @@ typedef struct kvz_config {
   int32_t intra_chain;        /* "intra-chain" (default 1): the blocks of a CTU whose below-left / above-right reference samples lie in ANOTHER CTU (its left-edge blocks, its above-right corner block) choose among the intra modes that do not read those samples: the CTU wavefront of the reconstruction chain (k_intra_recon, and k_dec_intra on the receiving side) advances in shorter lags; 0 = all 35 modes everywhere */
   int32_t me_source;          /* "me-source" 0 / 1 ("uvgx search pipelining v1"): the integer motion search of a P picture looks at the previous INPUT picture instead of the reference picture's reconstruction, so it depends on nothing the previous picture's reconstruction loop produces and runs beside it on the GPU (fractional refinement, motion compensation and everything behind them use the reconstruction as ever).  On at the presets superfast .. fast, whose subme >= 2 refinement against the reconstruction makes up for it (oracle, 640x384 / 720p: -0.6 .. +0.2 % bits, -0.01 .. -0.02 dB); off at ultrafast (no refinement there: +1.1 .. 1.4 % bits, -0.17 dB) and from medium on; ignored in band mode */
   int32_t lp_refs;            /* "lp-refs" 0..4 (extension, "uvgx multi-reference v1"): with n >= 2 a P picture refers to the min(n, pictures since the last IDR picture) pictures before it, all in list 0 -- what gop=lp-gXdYtZ asks Kvazaar for (uvgComm passes gop=lp-g4d3t1; "lp-refs=3" as a custom parameter gets that depth here).  Each 32x32 / 16x16 block searches every reference and codes ref_idx_l0.  0 / 1 (default): one reference, the encoder of before byte for byte ("ref" keeps its meaning and accepts 1 only; "gop" has no effect).  Not in band mode (encoder_open fails) */
+  int32_t me_coarse;          /* "me-coarse" 0 / 64 / 128 / 256 (extension, "uvgx coarse-to-fine search v1"): reach in full samples of a coarse search on quarter-resolution INPUT pictures that gives every 32x32 block and reference a centre; the integer search then looks at its +-me-range window around zero AND, when the centre lies outside it, at a second one around the centre -- vectors of up to me-coarse + me-range samples (scrolling, window drags, pans).  0 (default, also at every preset): the window around zero alone, the encoder of before byte for byte.  Not in band mode (encoder_open fails) */
 } kvz_config;
 
 /* Picture.  y/u/v are planar 8-bit with stride == width (chroma width/2), as uvgComm assumes

@@ -122,6 +122,9 @@ class Encoder:
         # ref_idx_l0 per 8x8 block: an array of its own only with lp-refs >= 2, else every block refers to reference 0
         d["cu_ref"] = np.zeros(b8, dtype=np.uint8)
         self.lib.kvzx_encoder_debug_copy(self.enc, b"cu_ref", d["cu_ref"].ctypes.data, d["cu_ref"].nbytes)
+        # me-coarse: the centres the coarse stage gave the picture's 32x32 blocks, (x, y) in full samples per reference -- a key of its own only with the option on
+        if int(self.cfg.contents.me_coarse):
+            d["me_coarse"] = self.debug("me_coarse", np.int16, (4, ch // 32, cw // 32, 2))
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             d["coef%d" % c] = self.debug("coef%d" % c, np.int16, shp)

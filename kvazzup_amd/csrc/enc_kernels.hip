@@ -52,13 +52,16 @@ namespace kvzx {
 // MR (lp-refs, f.nref references): the window of every reference in turn, and the minimum over (reference, candidate) pairs of the 64-bit key
 // cost << 16 | ref << 13 | candidate -- ties to the lower reference, then the lower candidate; cost includes ref_bins(ref).
 // One reference: the 32-bit key cost << 13 | candidate (the same order).
-template <bool MR>
+// CO (me-coarse): per reference the zero window and, where k_me_coarse's centre lies outside it (me_second_window), a second window
+// around that centre through the same LDS buffer; vectors are centre + displacement, rate and admissibility those of the whole vector; the 64-bit key
+// me_fine_key(): cost << 17 | ref << 14 | window << 13 | candidate.
+template <bool MR, bool CO = false>
 __global__ __launch_bounds__(256) void k_me(EncFrame f)
 {
-  using Key = typename std::conditional<MR, unsigned long long, uint32_t>::type;
-  constexpr int KS = MR ? 16 : 13;                                     // cost field's shift
+  using Key = typename std::conditional<MR || CO, unsigned long long, uint32_t>::type;
+  constexpr int KS = CO ? 17 : (MR ? 16 : 13);                         // cost field's shift
   constexpr Key KMAX = ~(Key)0;
-  __shared__ __attribute__((aligned(16))) uint8_t win[(32 + 2 * ME_MAXR + 1) * ME_WPITCH + 16];
+  __shared__ __attribute__((aligned(16))) uint8_t wbuf[(32 + 2 * ME_MAXR + 1) * ME_WPITCH + 16];
   __shared__ __attribute__((aligned(16))) uint32_t cur[32 * 8];
   __shared__ Key red[5];
   const int tid = threadIdx.x, nthreads = blockDim.x;
@@ -96,12 +99,21 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
   Key best[5] = {KMAX, KMAX, KMAX, KMAX, KMAX};
   const int nr = MR ? f.nref : 1;
 #pragma unroll 1
-  for (int rf = 0; rf < nr; rf++) {                                    // (MR: one reference after the other through the same LDS window)
+  for (int it = 0; it < (CO ? 2 * nr : nr); it++) {                    // (MR: one reference after the other through the same LDS window; CO: each reference's two windows)
+  const int rf = CO ? it >> 1 : it, win = CO ? it & 1 : 0;
+  int ox = 0, oy = 0;                                                  // the window's centre (CO, second window: k_me_coarse's)
+  if constexpr (CO) {
+    if (win) {
+      const int16_t *c = f.mc_centres + 2 * ((size_t)rf * (f.cw >> 5) * (f.ch >> 5) + (size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
+      ox = c[0]; oy = c[1];
+      if (!me_second_window(ox, oy, R)) continue;                      // (the same for every thread of the workgroup)
+    }
+  }
   const uint8_t *refp = MR ? f.me_refs[rf] : ref;
   __syncthreads();                                                     // (red[] is about to be re-initialised; MR: the previous reference's window is done with)
   for (int i = tid; i < (WW + 1) * (ME_WPITCH / 4); i += nthreads) {   // four window samples per thread; columns >= WW and row WW are padding
     const int wy = i / (ME_WPITCH / 4), wx = (i - wy * (ME_WPITCH / 4)) * 4;
-    const int gy = clip3(0, f.ch - 1, y0 - R + wy), gx = x0 - R + wx;
+    const int gy = clip3(0, f.ch - 1, y0 + oy - R + wy), gx = x0 + ox - R + wx;
     const uint8_t *row = refp + (size_t)gy * f.cw;
     uint32_t v;
     if (gx >= 0 && gx + 7 < f.cw) {
@@ -111,9 +123,9 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
       v = 0;
       for (int k = 0; k < 4; k++) v |= (uint32_t)row[clip3(0, f.cw - 1, gx + k)] << (8 * k);
     }
-    *(uint32_t *)&win[wy * ME_WPITCH + wx] = v;
+    *(uint32_t *)&wbuf[wy * ME_WPITCH + wx] = v;
   }
-  if (rf == 0 && tid < 5) red[tid] = KMAX;
+  if (it == 0 && tid < 5) red[tid] = KMAX;
   __syncthreads();
   const uint32_t rbins = MR ? (uint32_t)ref_bins(rf, nr) : 0u;
   // tile constraint (statement: me_block32() in oracle/hevc_enc.c): the displaced 32x32 block, plus 4 rows each side for
@@ -131,7 +143,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
   for (int item = tid; item < NQ * NG; item += nthreads) {
     const int g = item / NQ, q = item - g * NQ, dy0 = 2 * g;
     uint64_t acc[2][4];                                          // [candidate of the pair][quarter]: four u16 sums, one per candidate of the quad
-    const uint8_t *wbase = win + dy0 * ME_WPITCH + 4 * q;
+    const uint8_t *wbase = wbuf + dy0 * ME_WPITCH + 4 * q;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
       uint64_t al = 0, ar = 0, bl = 0, br = 0;                   // left / right quarter of this half, candidates A and B
@@ -164,17 +176,17 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     for (int e = 0; e < 2; e++) {
       const int dyi = dy0 + e;
       if (dyi >= W) continue;
-      { const int dy = dyi - R, m = (dy & 1) ? 4 : 0; if ((ty0 > 0 && y0 + dy - m < ty0) || (ty1 < f.ch && y0 + dy + 32 + m > ty1)) continue; }
-      if (f.mv_frame) { const int dy = dyi - R, my = (f.mv_frame == 2 && (dy & 1)) ? 4 : 0; if (y0 + dy - my < 0 || y0 + dy + 32 + my > f.ch) continue; }
-      const int ry = mvd_bits((dyi - R) * 4);
+      { const int dy = oy + dyi - R, m = (dy & 1) ? 4 : 0; if ((ty0 > 0 && y0 + dy - m < ty0) || (ty1 < f.ch && y0 + dy + 32 + m > ty1)) continue; }
+      if (f.mv_frame) { const int dy = oy + dyi - R, my = (f.mv_frame == 2 && (dy & 1)) ? 4 : 0; if (y0 + dy - my < 0 || y0 + dy + 32 + my > f.ch) continue; }
+      const int ry = mvd_bits((oy + dyi - R) * 4);
 #pragma unroll
       for (int k4 = 0; k4 < 4; k4++) {
         const int dxi = 4 * q + k4;
         if (dxi >= W) continue;
-        { const int dx = dxi - R, m = (dx & 1) ? 4 : 0; if ((tx0 > 0 && x0 + dx - m < tx0) || (tx1 < f.cw && x0 + dx + 32 + m > tx1)) continue; }
-        if (f.mv_frame) { const int dx = dxi - R, mx = (f.mv_frame == 2 && (dx & 1)) ? 4 : 0; if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > f.cw) continue; }
-        const Key cand = (Key)(dyi * W + dxi) | ((Key)rf << 13);
-        const uint32_t rate = (lam * (uint32_t)(mvd_bits((dxi - R) * 4) + ry + rbins)) >> 4;
+        { const int dx = ox + dxi - R, m = (dx & 1) ? 4 : 0; if ((tx0 > 0 && x0 + dx - m < tx0) || (tx1 < f.cw && x0 + dx + 32 + m > tx1)) continue; }
+        if (f.mv_frame) { const int dx = ox + dxi - R, mx = (f.mv_frame == 2 && (dx & 1)) ? 4 : 0; if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > f.cw) continue; }
+        const Key cand = CO ? (Key)me_fine_key(0u, rf, win, dyi * W + dxi) : ((Key)(dyi * W + dxi) | ((Key)rf << 13));
+        const uint32_t rate = (lam * (uint32_t)(mvd_bits((ox + dxi - R) * 4) + ry + rbins)) >> 4;
         uint32_t sq[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) sq[k] = (uint32_t)(acc[e][k] >> (16 * k4)) & 0xffffu;
@@ -188,7 +200,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
 #pragma unroll
   for (int k = 0; k < 5; k++) {
     Key v = best[k];
-    if constexpr (MR) { for (int o = 32; o > 0; o >>= 1) v = min(v, (Key)__shfl_xor((unsigned long long)v, o)); }
+    if constexpr (MR || CO) { for (int o = 32; o > 0; o >>= 1) v = min(v, (Key)__shfl_xor((unsigned long long)v, o)); }
     else { for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o)); }
     if ((tid & 63) == 0) atomicMin(&red[k], v);
   }
@@ -204,9 +216,17 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     f.cu_log2[i] = split ? 4 : 5;
     f.cu_intra[i] = 0;
     f.cu_mvp_idx[i] = 1;                                 // mark for k_subpel: searched
-    if (MR) f.cu_ref[i] = (uint8_t)(((split ? red[k] : red[4]) >> 13) & 7);
-    f.cu_mv[i * 2] = (int16_t)(((int)(ci % W) - R) * 4);
-    f.cu_mv[i * 2 + 1] = (int16_t)(((int)(ci / W) - R) * 4);
+    const int rsel = CO ? (int)(((split ? red[k] : red[4]) >> 14) & 7) : (MR ? (int)(((split ? red[k] : red[4]) >> 13) & 7) : 0);
+    if (MR) f.cu_ref[i] = (uint8_t)rsel;
+    int cx = 0, cy = 0;                                  // (CO: a candidate of the second window counts from the chosen reference's centre)
+    if constexpr (CO) {
+      if (((split ? red[k] : red[4]) >> 13) & 1) {
+        const int16_t *c = f.mc_centres + 2 * ((size_t)rsel * (f.cw >> 5) * (f.ch >> 5) + (size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
+        cx = c[0]; cy = c[1];
+      }
+    }
+    f.cu_mv[i * 2] = (int16_t)((cx + (int)(ci % W) - R) * 4);
+    f.cu_mv[i * 2 + 1] = (int16_t)((cy + (int)(ci / W) - R) * 4);
     // intra-in-P: the inter cost of the block's 16x16 quarters -- what the search found for a quarter, or a quarter of the 32x32 block's cost
     if (f.intra_p && tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = split ? (uint32_t)(red[tid] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2;
     if (f.intra_p && tid == 0) {
@@ -215,6 +235,100 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
       for (int k = 0; k < 4; k++) any |= (split ? (uint32_t)(red[k] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2) > (uint32_t)INTRA_P_GATE * lam;
       if (any) f.me_cand[1 + atomicAdd(&f.me_cand[0], 1u)] = (uint32_t)((y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
     }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// "uvgx coarse-to-fine search v1" (me-coarse): the quarter picture and the coarse stage
+// ---------------------------------------------------------------------------------------------
+// Quarter picture of the padded luma plane: q(x, y) = (sum of the 4x4 samples at (4x, 4y) + 8) >> 4.  A thread reads four rows of 16 bytes and writes
+// four quarter samples as one word; cw is a multiple of 64, so every access is aligned.
+__global__ __launch_bounds__(256) void k_luma_quarter(const uint8_t *src, uint8_t *q, int cw, int ch)
+{
+  const int gx = blockIdx.x * 64 + threadIdx.x, gy = blockIdx.y * 4 + threadIdx.y;        // word gx of quarter row gy
+  if (gx * 16 >= cw || gy * 4 >= ch) return;
+  kv_u32x4 v[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) v[k] = *reinterpret_cast<const kv_u32x4 *>(src + (size_t)(gy * 4 + k) * cw + gx * 16);
+  uint32_t out = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    uint32_t sum = 8;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const uint32_t w = j == 0 ? v[k].x : (j == 1 ? v[k].y : (j == 2 ? v[k].z : v[k].w)); sum = __builtin_amdgcn_sad_u8(w, 0u, sum); }
+    out |= (sum >> 4) << (8 * j);
+  }
+  *reinterpret_cast<uint32_t *>(q + (size_t)gy * (cw >> 2) + gx * 4) = out;
+}
+
+// Coarse stage: one workgroup per (32x32 block, reference).  The block is 8x8 samples of the quarter picture; its window of the reference's quarter
+// picture, (8 + 2 rq)^2 samples clamped to the picture's edge, sits in LDS.  A work item is a QUAD of horizontally adjacent candidates:
+// v_qsad_pk_u16_u8 gives the four SADs of 4 samples of a row, two of them a row (an 8x8 SAD is at most 16 320: the u16 accumulators hold it).
+// Minimum of me_coarse_key() -- cost << 16 | raster index of the candidate -- over the admissible candidates; the centre goes to mc_centres.
+#define MEC_MAXRQ 64
+#define MEC_PITCH (2 * MEC_MAXRQ + 12)        // bytes per window row: 8 + 2 rq samples, + 4 so the last quad's third word stays inside
+__global__ __launch_bounds__(256) void k_me_coarse(EncFrame f)
+{
+  __shared__ __attribute__((aligned(16))) uint8_t wbuf[(8 + 2 * MEC_MAXRQ) * MEC_PITCH];
+  __shared__ unsigned long long red;
+  const int tid = threadIdx.x, nthreads = blockDim.x;
+  const int bx = blockIdx.x, by = blockIdx.y, rf = blockIdx.z;
+  const int rq = f.mc_rq, wq = 2 * rq + 1, wcols = 8 + 2 * rq, pitch = wcols + 4;
+  const int qw = f.cw >> 2, qh = f.ch >> 2, x0 = bx * 32, y0 = by * 32;
+  const uint8_t *refq = f.mc_qrefs[rf];
+  if (tid == 0) red = ~0ull;
+  // the window: word wx of row wy is quarter-picture samples (8 bx - rq + 4 wx ..) of row 8 by - rq + wy; rq and the picture's width are multiples of 4,
+  // so a word lies inside the picture or outside it as a whole
+  for (int i = tid; i < wcols * (pitch >> 2); i += nthreads) {
+    const int wy = i / (pitch >> 2), wx = i - wy * (pitch >> 2);
+    const int gy = clip3(0, qh - 1, by * 8 - rq + wy), gx = bx * 8 - rq + wx * 4;
+    const uint8_t *row = refq + (size_t)gy * qw;
+    uint32_t v;
+    if (gx >= 0 && gx + 3 < qw) v = *reinterpret_cast<const uint32_t *>(row + gx);
+    else v = (uint32_t)row[gx < 0 ? 0 : qw - 1] * 0x01010101u;
+    *reinterpret_cast<uint32_t *>(&wbuf[wy * pitch + wx * 4]) = v;
+  }
+  uint32_t cur[16];                                              // the block: 8 rows of two words
+#pragma unroll
+  for (int r = 0; r < 8; r++) {
+    const uint32_t *c = reinterpret_cast<const uint32_t *>(f.mc_q + (size_t)(by * 8 + r) * qw + bx * 8);
+    cur[2 * r] = c[0]; cur[2 * r + 1] = c[1];
+  }
+  int ty0, ty1, tx0, tx1;
+  me_tile_span(f.ch >> 6, f.tile_rows, y0 >> 6, true, &ty0, &ty1);
+  me_tile_span(f.cw >> 6, f.tile_cols, x0 >> 6, false, &tx0, &tx1);
+  __syncthreads();
+  const uint32_t lam = (uint32_t)f.lambda_q4;
+  const int NQ = (wq + 3) >> 2;
+  unsigned long long best = ~0ull;
+  for (int item = tid; item < NQ * wq; item += nthreads) {
+    const int dyi = item / NQ, q = item - dyi * NQ;
+    if (!me_axis_ok(4 * (dyi - rq), y0, ty0, ty1, f.ch, f.mv_frame)) continue;
+    const uint8_t *wbase = wbuf + dyi * pitch + 4 * q;
+    uint64_t acc = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+      const uint32_t *wp = reinterpret_cast<const uint32_t *>(wbase + r * pitch);
+      const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
+      acc = __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)d1 << 32) | d0, cur[2 * r], acc);
+      acc = __builtin_amdgcn_qsad_pk_u16_u8(((uint64_t)d2 << 32) | d1, cur[2 * r + 1], acc);
+    }
+#pragma unroll
+    for (int k4 = 0; k4 < 4; k4++) {
+      const int dxi = 4 * q + k4;
+      if (dxi >= wq || !me_axis_ok(4 * (dxi - rq), x0, tx0, tx1, f.cw, f.mv_frame)) continue;
+      const unsigned long long key = me_coarse_key((uint32_t)(acc >> (16 * k4)) & 0xffffu, dxi, dyi, rq, lam);
+      best = key < best ? key : best;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { const unsigned long long v = __shfl_xor(best, o); best = v < best ? v : best; }
+  if ((tid & 63) == 0) atomicMin(&red, best);
+  __syncthreads();
+  if (tid == 0) {
+    int cx, cy;
+    me_coarse_centre(red, rq, &cx, &cy);
+    int16_t *c = f.mc_centres + 2 * ((size_t)rf * (f.cw >> 5) * (f.ch >> 5) + (size_t)by * (f.cw >> 5) + bx);
+    c[0] = (int16_t)cx; c[1] = (int16_t)cy;
   }
 }
 
@@ -2475,11 +2589,23 @@ void launch_pad_input(const uint8_t *in, int w, int h, uint8_t *dy, uint8_t *du,
   dim3 g((cw / 16 + 63) / 64, ch * 2 / 16);
   hipLaunchKernelGGL(k_pad_input, g, dim3(64, 4), 0, st, in, w, h, dy, du, dv, cw, ch);
 }
+void launch_luma_quarter(const uint8_t *src, uint8_t *q, int cw, int ch, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_luma_quarter, dim3((cw / 16 + 63) / 64, (ch / 4 + 3) / 4), dim3(64, 4), 0, st, src, q, cw, ch);
+}
+void launch_me_coarse(const EncFrame &f, hipStream_t st)
+{
+  hipLaunchKernelGGL(k_me_coarse, dim3(f.cw / 32, f.ch / 32, f.nref > 1 ? f.nref : 1), dim3(256), 0, st, f);
+}
 void launch_me(const EncFrame &f, hipStream_t st)
 {
   const int W = 2 * f.range + 1, items = ((W + 3) / 4) * ((W + 1) / 2);          // quads x pairs; R = 16: 153 items -> 192 threads
   const int threads = items >= 256 ? 256 : ((items + 63) / 64) * 64;
-  if (f.cu_ref) hipLaunchKernelGGL(k_me<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // lp-refs
+  if (f.mc_rq) {                                                                                                  // me-coarse: the form with the second window
+    if (f.cu_ref) hipLaunchKernelGGL((k_me<true, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
+    else hipLaunchKernelGGL((k_me<false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
+  }
+  else if (f.cu_ref) hipLaunchKernelGGL(k_me<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // lp-refs
   else hipLaunchKernelGGL(k_me<false>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
 }
 void launch_inter_recon(const EncFrame &f, hipStream_t st)

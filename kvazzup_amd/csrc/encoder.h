@@ -58,6 +58,7 @@ struct EncoderConfig {
   int entropy_gpu = 0;        // arithmetic coder: 1 = on the GPU (k_cabac_rows, cabac_kernels.hip), 0 = host thread pool (entropy_host.h); band mode always uses the host pool
   int lp_refs = 1;            // "lp-refs" (extension, "uvgx multi-reference v1"): references per P picture, 1..4 -- picture t refers to pictures
                               // t - 1 .. t - min(lp_refs, pictures since the IDR picture), all in list 0; 1 = one reference (the encoder of before); not in band mode
+  int me_coarse = 0;          // "me-coarse" (extension, "uvgx coarse-to-fine search v1"): 0 / 64 / 128 / 256 -- reach in full samples of the coarse search on quarter-resolution input pictures whose centres give k_me a second window; 0 = off (nothing allocated, nothing launched); not in band mode
   int tmvp = 0;               // kvazaar "tmvp" (DESIGN.md section 9b): temporal motion vector prediction -- merge / AMVP candidates from the previous picture's motion
                               // (collocated_ref_idx 0); changes the signalling only, never the motion chosen; not in band mode
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
@@ -116,7 +117,7 @@ class Encoder {
   void set_recon_sink(uint8_t *y, uint8_t *u, uint8_t *v) { sink_[0] = y; sink_[1] = u; sink_[2] = v; }
   // debug: copy an internal device array of the last coded picture to the host
   //   "cu_log2","cu_intra","cu_flags","cu_merge_idx","cu_mvp_idx","cu_intra_mode","cu_cbf" (b8 bytes),
-  //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16)
+  //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
   int coded_width() const { return cw_; }
   int coded_height() const { return ch_; }
@@ -177,6 +178,7 @@ class Encoder {
   uint8_t *cu_bytes_[kSets] = {};          // 7 byte arrays back to back
   int16_t *cu_mv_[kSets] = {}, *cu_mvd_[kSets] = {};
   uint8_t *cu_ref_[kSets] = {};            // lp-refs >= 2: ref_idx_l0 per 8x8 block (EncFrame::cu_ref)
+  uint8_t *mc_q_[kSets] = {}; int16_t *mc_centres_[kSets] = {};      // me-coarse: the quarter picture of the set's input picture and the centres of the set's picture [reference][32x32 block] (EncFrame::mc_*)
   ColMv *col_[kSets] = {};                 // tmvp: the collocated record of the set's picture (EncFrame::col_out), which the next picture reads (col_prev)
   int set_ = 0, out_set_ = 0;
   char prio_[3] = {'h', 'n', 'n'};                      // priority levels of the main, tokenizer and input streams (stream_pool.h keys)

@@ -57,6 +57,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.lp_refs < 1 || cfg.lp_refs > KVZ_MAX_LP_REFS) { if (error) *error = "lp-refs out of range (0 .. 4)"; return false; }
   if (cfg.lp_refs > 1 && cfg.band_rows > 0) { if (error) *error = "lp-refs >= 2 is not available in band mode (the halo exchange carries one reference picture's rows)"; return false; }
   if (cfg.tmvp && cfg.band_rows > 0) { if (error) *error = "tmvp is not available in band mode"; return false; }
+  if (cfg.me_coarse != 0 && cfg.me_coarse != 64 && cfg.me_coarse != 128 && cfg.me_coarse != 256) { if (error) *error = "me-coarse must be 0, 64, 128 or 256"; return false; }
+  if (cfg.me_coarse && cfg.band_rows > 0) { if (error) *error = "me-coarse is not available in band mode (the halo exchange carries a few rows)"; return false; }
 
   const char *prio = getenv("KVAZZUP_AMD_PRIO"); if (!prio || strlen(prio) < 4) prio = "hnnn";   // main, tokenizer, input, decoder: the chain the next picture waits for is the urgent one (+6 % at 1080p; any explicit priority also gives the stream a hardware queue of its own)
 
@@ -115,6 +117,10 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     HIP_OK(hipMalloc(&cu_mvd_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mvd_[k], 0, nb8 * 2 * sizeof(int16_t)));
     if (cfg.lp_refs > 1) { HIP_OK(hipMalloc(&cu_ref_[k], nb8)); HIP_OK(hipMemset(cu_ref_[k], 0, nb8)); }
     if (cfg.tmvp) { HIP_OK(hipMalloc(&col_[k], nb8 / 4 * sizeof(ColMv))); HIP_OK(hipMemset(col_[k], 0, nb8 / 4 * sizeof(ColMv))); }
+    if (cfg.me_coarse) {
+      HIP_OK(hipMalloc(&mc_q_[k], npx / 16)); HIP_OK(hipMemset(mc_q_[k], 0, npx / 16));
+      HIP_OK(hipMalloc(&mc_centres_[k], (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t))); HIP_OK(hipMemset(mc_centres_[k], 0, (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t)));
+    }
     HIP_OK(hipEventCreateWithFlags(&ev_tok_done_[k], kDeviceEvent));
   }
   if (cfg.qp_in_cu) {
@@ -313,7 +319,7 @@ Encoder::~Encoder()
   for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kMaxDepth + 2 + KVZ_MAX_LP_REFS; b++) hipFree(rec_[b][c]); }
   hipFree(vaq_act_); hipFree(vaq_sum_); hipFree(rc_state_);
   for (int k = 0; k < kSets; k++) { hipFree(ctu_qt_[k]); hipFree(ctu_qy_[k]); hipFree(ctu_delta_[k]); hipFree(ctu_first_[k]); if (h_ctu_qt_[k]) hipHostFree(h_ctu_qt_[k]); hipFree(ctu_roi_[k]); }
-  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
+  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (mc_q_[k]) hipFree(mc_q_[k]); if (mc_centres_[k]) hipFree(mc_centres_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
   for (int c = 0; c < 3; c++) { hipFree(work_[c]); hipFree(work_idr_[c]); }
   hipFree(sync_idr_); hipFree(edge_col_idr_); hipFree(edge_row_); hipFree(edge_row_idr_);
   for (int k = 0; k < kSets; k++) hipFree(sao_[k]);
@@ -621,6 +627,13 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   }
   // tmvp: the previous picture -- set k - 1 -- filed its record on the tokenizer's stream, where this picture's k_inter_signal reads it; right after the IDR
   // picture (which files none) the slice says slice_temporal_mvp_enabled_flag = 0 (hevc_headers.h slice_tmvp) and nothing is read
+  // me-coarse: the quarter picture of this set's input and of the sets that hold input pictures t - 1 - r (written on the input stream, where the coarse stage
+  // reads them), and the set's centres
+  if (mc_q_[k]) {
+    f.mc_rq = cfg_.me_coarse / 4; f.mc_q = mc_q_[k]; f.mc_centres = mc_centres_[k];
+    const int nr = f.cu_ref ? f.nref : 1;
+    for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - 1 - (r < nr ? r : 0)) % kSets];
+  }
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
   if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
   f.tok_dense = sl.d_tok_dense; f.tok_count_out = sl.d_tok_count; f.tok_off_out = sl.d_tok_off; f.err_out = sl.d_err; f.ent_cursors = sl.g_cursors;
@@ -657,6 +670,8 @@ bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i42
   if (src_busy_[set_]) { HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_src_free_[set_], 0)); src_busy_[set_] = false; }   // the last picture that used this set (t - kSets) has been reconstructed
   timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[set_][0], src_[set_][1], src_[set_][2], cw_, ch_, stream_in_); });
   if (in_ring >= 0) { HIP_CHECK(hipEventRecord(ev_pad_[in_ring], stream_in_)); pad_pending_[in_ring] = true; }
+  // me-coarse: every picture's quarter picture (an intra picture's is searched by the P picture behind it)
+  if (f.mc_rq) launch_luma_quarter(src_[set_][0], f.mc_q, cw_, ch_, stream_in_);      // (no kernel id of its own: the profile's keys are the default encoder's)
   // The tokenizer of the set's previous picture must be done with the set's CU arrays before this picture writes them: the INPUT stream waits for it (the
   // event is long past when it gets there), so that the main stream's one wait for in_done_ says both -- a wait of its own in front of every picture's chain
   // cost the chain a barrier packet, a few microseconds with nothing running.
@@ -665,6 +680,9 @@ bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i42
     // The intra decisions need the source picture only: they run on the input stream, beside what is left of picture t - 1 on the main stream.
     timed(K_INTRA_ANALYSE, stream_in_, [&] { launch_intra_analyse(f, stream_in_); });
   }
+  // me-coarse: the coarse stage needs input pictures only, so it runs here whatever me-source says -- beside the chains of the pictures in front, and behind the
+  // wait above (the centres are the set's own: its previous picture's k_me has long read them); in_done_ covers it for a k_me on the main stream
+  if (f.mc_rq && !p.intra) launch_me_coarse(f, stream_in_);
   if (p.ahead) {
     // "uvgx search pipelining v1": the search needs the two input pictures only, the pricing of its expensive quarters as intra blocks the search and the source --
     // both run HERE, on the input stream, beside what the main stream still has of the pictures in front (k_me 31-34 us and k_intra_analyse<P> 19-24 us at
@@ -1082,6 +1100,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
   if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }
+  if (w == "me_coarse") { src = mc_centres_[out_set_]; have = mc_centres_[out_set_] ? (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t) : 0; }
   if (w == "col") { src = col_[out_set_]; have = col_[out_set_] ? nb8 / 4 * sizeof(ColMv) : 0; }
   if (w == "trace" && trace_) { src = trace_; have = sizeof(unsigned long long) * (rows_ * (cw_ / 64) * 72); }
   for (int c = 0; c < 3; c++) {

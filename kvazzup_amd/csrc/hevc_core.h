@@ -138,6 +138,13 @@ struct EncFrame {
   // picture's, which the temporal candidates read (NULL: slice_temporal_mvp_enabled_flag 0 -- the previous picture is the IDR picture)
   ColMv *col_out;
   const ColMv *col_prev;
+  // "me-coarse" (mc_rq 0: off, and nothing below is read): mc_rq = reach of the coarse stage in quarter-picture samples (me-coarse / 4);
+  // mc_q = the quarter picture of this picture's input (cw / 4 x ch / 4, written by k_luma_quarter), mc_qrefs[k] = that of input picture t - 1 - k;
+  // mc_centres = [reference][32x32 block, raster] the centres (x, y) in full samples, written by k_me_coarse, read by k_me<.., true>
+  int mc_rq;
+  uint8_t *mc_q;
+  const uint8_t *mc_qrefs[KVZ_MAX_LP_REFS];
+  int16_t *mc_centres;
 };
 
 // the reference planes of ref_idx k (one reference: ref[])
@@ -897,6 +904,51 @@ KVZ_HD int mvd_bits(int q)
   while (x >= (1 << k)) { x -= 1 << k; k++; len++; }
   return 2 + len + 1 + k + 1;
 }
+
+// ---------------------------------------------------------------------------------------------
+// "uvgx coarse-to-fine search v1" (kvazaar.h me-coarse; statement of record: tests/me_coarse_model.py).  The arithmetic the
+// kernels k_luma_quarter, k_me_coarse and k_me<.., true> share with the host build tests/hostcoarse.
+// ---------------------------------------------------------------------------------------------
+// one sample of the quarter picture: the rounded mean of the 4x4 luma samples at p (rows `pitch` apart) -- k_luma_quarter forms the same sum with v_sad_u8 against zero, four samples a
+// thread; tests/test_gpu_me_coarse.py holds its output to this through the centres
+KVZ_HD int me_quarter_sample(const uint8_t *p, int pitch)
+{
+  int s = 8;
+  for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) s += p[y * pitch + x];
+  return s >> 4;
+}
+// one axis of the search's admissibility rule: the 32-sample block at p0 displaced by v full samples (plus 4 samples each side for the chroma half-sample
+// taps when v is odd) stays inside its tile [lo, hi) -- except across the picture's own edges [0, size) -- and, with mv-constraint, inside the picture
+// (margin only with frametilemargin, mv_frame 2)
+KVZ_HD bool me_axis_ok(int v, int p0, int lo, int hi, int size, int mv_frame)
+{
+  const int m = (v & 1) ? 4 : 0;
+  if ((lo > 0 && p0 + v - m < lo) || (hi < size && p0 + v + 32 + m > hi)) return false;
+  if (mv_frame) { const int mm = (mv_frame == 2 && (v & 1)) ? 4 : 0; if (p0 + v - mm < 0 || p0 + v + 32 + mm > size) return false; }
+  return true;
+}
+// [lo, hi) in samples of the tile row / column holding CTU index c of n, with `parts` uniform tiles
+KVZ_HD void me_tile_span(int n, int parts, int c, bool rows, int *lo, int *hi)
+{
+  *lo = 0; *hi = n * 64;
+  if (parts <= 1) return;
+  if (rows) { const int t = tile_row_of(n, parts, c); *lo = tile_row_first(n, parts, t) * 64; *hi = tile_row_first(n, parts, t + 1) * 64; }
+  else { const int t = tile_col_of(n, parts, c); *lo = tile_col_first(n, parts, t) * 64; *hi = tile_col_first(n, parts, t + 1) * 64; }
+}
+// coarse stage: candidate (dxi, dyi) of the (2 rq + 1)^2 grid, displacement (dxi - rq, dyi - rq) quarter-picture samples, with the SAD of the 8x8 blocks.
+// key = cost << 16 | raster index: the minimum is the lowest cost and, among equals, the first candidate in raster order of (dy, dx)
+// (mvd_bits without its loop -- 1 for 0, else 2 floor(log2 |q|) + 3: the coarse stage prices 16 641 candidates a block at the widest reach)
+KVZ_HD int me_mvd_bits_closed(int q) { const int a = iabs(q); return a == 0 ? 1 : 2 * (31 - kv_clz32((uint32_t)a)) + 3; }
+KVZ_HD uint32_t me_coarse_cost(uint32_t sad8, int dxq, int dyq, uint32_t lam) { return 16u * sad8 + ((lam * (uint32_t)(me_mvd_bits_closed(16 * dxq) + me_mvd_bits_closed(16 * dyq))) >> 4); }
+KVZ_HD unsigned long long me_coarse_key(uint32_t sad8, int dxi, int dyi, int rq, uint32_t lam)
+{
+  return ((unsigned long long)me_coarse_cost(sad8, dxi - rq, dyi - rq, lam) << 16) | (unsigned long long)(dyi * (2 * rq + 1) + dxi);
+}
+KVZ_HD void me_coarse_centre(unsigned long long key, int rq, int *cx, int *cy) { const int i = (int)(key & 0xffffu), wq = 2 * rq + 1; *cx = 4 * (i % wq - rq); *cy = 4 * (i / wq - rq); }
+// fine stage: a centre gets a window of its own iff it lies outside the zero window less the coarse grid's width
+KVZ_HD bool me_second_window(int cx, int cy, int range) { return iabs(cx) > range - 4 || iabs(cy) > range - 4; }
+// ... and its candidates are ordered by cost, then reference, then zero window before centred window, then index inside the window (cand < 8192, ref < 8)
+KVZ_HD unsigned long long me_fine_key(uint32_t cost, int ref, int win, int cand) { return ((unsigned long long)cost << 17) | ((unsigned long long)ref << 14) | ((unsigned long long)win << 13) | (unsigned long long)cand; }
 
 struct NbMv { bool ok; int mx, my, ref; };
 // where the derivations below read a CU's record from: the frame's arrays (host tests, band encoder) or a tile of them staged in LDS (k_inter_signal)

@@ -107,8 +107,8 @@ typedef struct kvz_config {
   int32_t target_bitrate;     /* "bitrate" in bits per second: 0 = constant QP; > 0 = this library's rate control (picture level; with rc_algorithm lambda / oba also between groups of CTU rows, decided on the device) */
   enum kvz_rc_algorithm rc_algorithm;
   int32_t max_merge;
-  int32_t gop_len, gop_lowdelay;      /* "gop": lp-g<len>d<depth>t<layers> accepted; one reference is used */
-  int32_t gop_lp_ref_depth, gop_lp_temporal_layers;
+  int32_t gop_len, gop_lowdelay;      /* "gop": lp-g<len>d<depth>t<layers> (and "0") accepted and recorded; without effect unless "lp-gop" is 1 (below) */
+  int32_t gop_lp_ref_depth, gop_lp_temporal_layers;   /* d = the number of QP layers (not a reference count: that is "lp-refs"), t = temporal sub-layers (only 1 is implemented) */
   int32_t set_qp_in_cu;
   int32_t vaq;
   enum kvz_scalinglist scaling_list;
@@ -128,8 +128,9 @@ typedef struct kvz_config {
   int32_t gpu_entropy;        /* "gpu-entropy": 1 = the arithmetic coder runs on the GPU too (k_cabac_rows: no host coder threads, 2-4 ms more latency per picture), 0 (default) = host thread pool sized by "threads" */
   int32_t intra_chain;        /* "intra-chain" (default 1): the blocks of a CTU whose below-left / above-right reference samples lie in ANOTHER CTU (its left-edge blocks, its above-right corner block) choose among the intra modes that do not read those samples: the CTU wavefront of the reconstruction chain (k_intra_recon, and k_dec_intra on the receiving side) advances in shorter lags; 0 = all 35 modes everywhere */
   int32_t me_source;          /* "me-source" 0 / 1 ("uvgx search pipelining v1"): the integer motion search of a P picture looks at the previous INPUT picture instead of the reference picture's reconstruction, so it depends on nothing the previous picture's reconstruction loop produces and runs beside it on the GPU (fractional refinement, motion compensation and everything behind them use the reconstruction as ever).  On at the presets superfast .. fast, whose subme >= 2 refinement against the reconstruction makes up for it (oracle, 640x384 / 720p: -0.6 .. +0.2 % bits, -0.01 .. -0.02 dB); off at ultrafast (no refinement there: +1.1 .. 1.4 % bits, -0.17 dB) and from medium on; ignored in band mode */
-  int32_t lp_refs;            /* "lp-refs" 0..4 (extension, "uvgx multi-reference v1"): with n >= 2 a P picture refers to the min(n, pictures since the last IDR picture) pictures before it, all in list 0 -- what gop=lp-gXdYtZ asks Kvazaar for (uvgComm passes gop=lp-g4d3t1; "lp-refs=3" as a custom parameter gets that depth here).  Each 32x32 / 16x16 block searches every reference and codes ref_idx_l0.  0 / 1 (default): one reference, the encoder of before byte for byte ("ref" keeps its meaning and accepts 1 only; "gop" has no effect).  Not in band mode (encoder_open fails) */
+  int32_t lp_refs;            /* "lp-refs" 0..4 (extension, "uvgx multi-reference v1"): with n >= 2 a P picture refers to the min(n, pictures since the last IDR picture) pictures before it, all in list 0 (with "lp-gop" the same count, chosen as that option says).  The gop string says nothing about this count -- its d is the number of QP layers -- so uvgComm users who want three references pass "lp-refs=3" as a custom parameter.  Each 32x32 / 16x16 block searches every reference and codes ref_idx_l0.  0 / 1 (default): one reference, the encoder of before byte for byte ("ref" keeps its meaning and accepts 1 only; "gop" takes effect under "lp-gop" alone).  Not in band mode (encoder_open fails) */
   int32_t me_coarse;          /* "me-coarse" 0 / 64 / 128 / 256 (extension, "uvgx coarse-to-fine search v1"): reach in full samples of a coarse search on quarter-resolution INPUT pictures that gives every 32x32 block and reference a centre; the integer search then looks at its +-me-range window around zero AND, when the centre lies outside it, at a second one around the centre -- vectors of up to me-coarse + me-range samples (scrolling, window drags, pans).  0 (default, also at every preset): the window around zero alone, the encoder of before byte for byte.  Not in band mode (encoder_open fails) */
+  int32_t lp_gop;             /* "lp-gop" 0 / 1 (extension, "uvgx low-delay GOP v1"; statement of record: tests/lp_gop_model.py): 1 = gop=lp-g<g>d<d>t1 takes effect -- every g-th picture after an IDR picture is a key picture coded at QP + 1, the pictures between lie on the layers QP + 2 .. QP + d (g4d3: +3, +2, +3, +1), and a P picture refers to the previous picture, the most recent key picture (at most 7 pictures back) and then the pictures before the previous one, "lp-refs" pictures in all; each picture's reference picture set travels in its slice headers, the parameter sets are those of lp-refs.  0 (default, also at every preset), or no gop string / gop=0: the streams of before byte for byte.  encoder_open fails with it in band mode, with t > 1 and with d > 6 */
 } kvz_config;
 
 /* Picture.  y/u/v are planar 8-bit with stride == width (chroma width/2), as uvgComm assumes

@@ -89,7 +89,8 @@ class Encoder:
             rec = np.concatenate([np.frombuffer((C.c_char * n).from_address(ptr), dtype=np.uint8).copy()
                                   for ptr, n in ((r.y, ny), (r.u, ny // 4), (r.v, ny // 4))])
             self.api.picture_free(recon)
-        self.info = {"poc": info.poc, "qp": info.qp, "nal_unit_type": info.nal_unit_type, "slice_type": info.slice_type}
+        self.info = {"poc": info.poc, "qp": info.qp, "nal_unit_type": info.nal_unit_type, "slice_type": info.slice_type,
+                     "ref_list": [int(info.ref_list[0][k]) for k in range(int(info.ref_list_len[0]))]}
         return au, rec
 
     # -- extension entry points
@@ -125,6 +126,10 @@ class Encoder:
         # me-coarse: the centres the coarse stage gave the picture's 32x32 blocks, (x, y) in full samples per reference -- a key of its own only with the option on
         if int(self.cfg.contents.me_coarse):
             d["me_coarse"] = self.debug("me_coarse", np.int16, (4, ch // 32, cw // 32, 2))
+        # lp-gop: what the encoder planned for the picture -- its QP layer, QP and references (POC distances in list 0 order) -- a key of its own only with the option on
+        if int(self.cfg.contents.lp_gop):
+            g = self.debug("lp_gop", np.int32, (8,))
+            d["lp_gop"] = {"active": int(g[0]), "layer": int(g[1]), "qp": int(g[2]), "dists": [int(v) for v in g[4:4 + int(g[3])]]}
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             d["coef%d" % c] = self.debug("coef%d" % c, np.int16, shp)

@@ -853,7 +853,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
 // picture), and the thread at each 16x16 origin files this picture's (f.col_out).  Both on the tokenizer's stream in picture order, which orders the write
 // of picture t - 1 before the read of picture t, and the read of t before the write of t + kSets - 1 into the same set's record.  A separate
 // instantiation: without tmvp the launch runs the code of before.
-template <bool TMVP>
+// GOP ("lp-gop"): the references' POC distances come from the picture's table (f.ref_dist) instead of ref_idx + 1 -- AMVP's spatial scaling,
+// the temporal candidates and the record filed.  The table forms are instantiations of their own: the launches without the option run the code of before.
+template <bool TMVP, bool GOP = false>
 __global__ __launch_bounds__(1024) void k_inter_signal(EncFrame f)
 {
   const int w8 = f.cw >> 3, h8 = band_rows(f) * 8;
@@ -867,7 +869,8 @@ __global__ __launch_bounds__(1024) void k_inter_signal(EncFrame f)
     const int n = 1 << cl;
     CuSignal r;
     // (inlined on purpose: left to itself the compiler makes the longer TMVP derivation a call, with a 1 KB stack frame in scratch memory per thread)
-    if constexpr (TMVP) { FrameMvView v{f}; [[clang::always_inline]] r = decide_signalling_values(v, f.cw, f.chp, x & ~(n - 1), y & ~(n - 1), cl, f.cu_ref && f.nref > 1 ? f.nref : 1, f.col_prev); }
+    if constexpr (GOP) { FrameMvView v{f}; [[clang::always_inline]] r = decide_signalling_values(v, f.cw, f.chp, x & ~(n - 1), y & ~(n - 1), cl, f.cu_ref && f.nref > 1 ? f.nref : 1, TMVP ? f.col_prev : nullptr, TabDist{f.ref_dist}); }
+    else if constexpr (TMVP) { FrameMvView v{f}; [[clang::always_inline]] r = decide_signalling_values(v, f.cw, f.chp, x & ~(n - 1), y & ~(n - 1), cl, f.cu_ref && f.nref > 1 ? f.nref : 1, f.col_prev); }
     else r = decide_signalling_values(f, x & ~(n - 1), y & ~(n - 1), cl);
     flags = r.flags;
     f.cu_flags[g] = (uint8_t)r.flags; f.cu_merge_idx[g] = (uint8_t)r.midx; f.cu_mvp_idx[g] = (uint8_t)r.mvp;
@@ -875,7 +878,7 @@ __global__ __launch_bounds__(1024) void k_inter_signal(EncFrame f)
   }
   if constexpr (TMVP) {
     if (valid && !((x | y) & 15)) {
-      ColMv c; c.mx = intra ? 0 : f.cu_mv[g * 2]; c.my = intra ? 0 : f.cu_mv[g * 2 + 1]; c.dist = intra ? 0 : (int16_t)(cu_ref_at(f, g) + 1); c.pad = 0;
+      ColMv c; c.mx = intra ? 0 : f.cu_mv[g * 2]; c.my = intra ? 0 : f.cu_mv[g * 2 + 1]; c.dist = intra ? 0 : (int16_t)(GOP ? TabDist{f.ref_dist}(cu_ref_at(f, g)) : cu_ref_at(f, g) + 1); c.pad = 0;
       f.col_out[(y >> 4) * (f.cw >> 4) + (x >> 4)] = c;
     }
   }
@@ -2629,7 +2632,9 @@ void launch_inter_recon(const EncFrame &f, hipStream_t st)
 void launch_inter_signal(const EncFrame &f, hipStream_t st)
 {
   const int n = (f.cw / 8) * (band_rows(f) * 8);
-  if (f.col_out) hipLaunchKernelGGL(k_inter_signal<true>, dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
+  if (f.ref_dist && f.col_out) hipLaunchKernelGGL((k_inter_signal<true, true>), dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
+  else if (f.ref_dist) hipLaunchKernelGGL((k_inter_signal<false, true>), dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
+  else if (f.col_out) hipLaunchKernelGGL(k_inter_signal<true>, dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
   else hipLaunchKernelGGL(k_inter_signal<false>, dim3((n + 1023) / 1024), dim3(1024), 0, st, f);
 }
 void launch_intra_analyse(const EncFrame &f, hipStream_t st)

@@ -57,8 +57,13 @@ struct EncoderConfig {
   int hash = 0;               // kvazaar "hash": 1 checksum, 2 md5 -- a decoded picture hash SEI (D.2.19) behind every picture's slices, from the reconstruction downloaded for it
   int entropy_gpu = 0;        // arithmetic coder: 1 = on the GPU (k_cabac_rows, cabac_kernels.hip), 0 = host thread pool (entropy_host.h); band mode always uses the host pool
   int lp_refs = 1;            // "lp-refs" (extension, "uvgx multi-reference v1"): references per P picture, 1..4 -- picture t refers to pictures
-                              // t - 1 .. t - min(lp_refs, pictures since the IDR picture), all in list 0; 1 = one reference (the encoder of before); not in band mode
+                              // t - 1 .. t - min(lp_refs, pictures since the IDR picture), all in list 0 (with lp_gop: the same count, chosen as lp_gop says); 1 = one reference (the encoder of before); not in band mode
   int me_coarse = 0;          // "me-coarse" (extension, "uvgx coarse-to-fine search v1"): 0 / 64 / 128 / 256 -- reach in full samples of the coarse search on quarter-resolution input pictures whose centres give k_me a second window; 0 = off (nothing allocated, nothing launched); not in band mode
+  int lp_gop = 0;             // "lp-gop" (extension, "uvgx low-delay GOP v1"; statement of record: tests/lp_gop_model.py): 1 = the low-delay structure of
+                              // gop=lp-g<gop_g>d<gop_d>t1 -- every gop_g-th picture after the IDR picture a key picture, P pictures at QP + layer (1 .. gop_d), and references
+                              // that are the previous picture, the most recent key picture within kMaxRefDist pictures, then the pictures before (lp_refs in all); without effect
+                              // while gop_g == 0 (no gop string, or gop=0); not in band mode, not with gop_t > 1 or gop_d > 6
+  int gop_g = 0, gop_d = 1, gop_t = 1;   // the numbers of the gop string (kvz_config.gop_len, gop_lp_ref_depth, gop_lp_temporal_layers)
   int tmvp = 0;               // kvazaar "tmvp" (DESIGN.md section 9b): temporal motion vector prediction -- merge / AMVP candidates from the previous picture's motion
                               // (collocated_ref_idx 0); changes the signalling only, never the motion chosen; not in band mode
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
@@ -70,6 +75,7 @@ struct EncodedPicture {
   bool valid = false;         // false: nothing was output by this call (pipeline filling, owf >= 1)
   std::vector<uint8_t> au;
   int poc = 0, qp = 0; bool is_intra = false;
+  int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop, a P picture: its QP layer and its references' POC distances in list 0 order (nref 0: the option is off)
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
 };
@@ -117,6 +123,7 @@ class Encoder {
   void set_recon_sink(uint8_t *y, uint8_t *u, uint8_t *v) { sink_[0] = y; sink_[1] = u; sink_[2] = v; }
   // debug: copy an internal device array of the last coded picture to the host
   //   "cu_log2","cu_intra","cu_flags","cu_merge_idx","cu_mvp_idx","cu_intra_mode","cu_cbf" (b8 bytes),
+  //   "lp_gop" (host values, 8 int32: option active, layer, QP, number of references, their four POC distances),
   //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
   int coded_width() const { return cw_; }
@@ -136,7 +143,11 @@ class Encoder {
   bool collect(EncodedPicture *out);
   struct Slot;
   // submit() in stages: plan (sets set_, POC, rate control), the picture's frame, then the input stage, its chain and the hand-off, in this order
-  struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; };   // side: the chain on stream_idr_; ahead: me-source search on the input stream; ms: the chain's stream
+  // side: the chain on stream_idr_; ahead: me-source search on the input stream; ms: the chain's stream; qp: the picture's QP (rate control's, plus the layer with
+  // lp-gop); nref / dist: its references in list 0 order, dist[k] pictures back (k + 1 without lp-gop); layer: lp-gop's QP layer of a P picture, else 0
+  struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; int qp = 0, layer = 0, nref = 1; int8_t dist[KVZ_MAX_LP_REFS] = {1, 2, 3, 4}; };
+  bool gop_on() const { return cfg_.lp_gop && cfg_.gop_g >= 1; }
+  bool sl_gop_timeline(const Plan &p) const { return gop_on() && !p.intra && Timeline::get().path; }
   Plan plan(int set);
   EncFrame picture_frame(const Plan &p, const Slot &sl, uint32_t chain_gen) const;
   bool input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i420, int in_ring);
@@ -165,9 +176,11 @@ class Encoder {
   // the input stage of picture t waited for the reconstruction of t - 2, and the calling thread with it: the main stream ran dry between pictures)
   static constexpr int kSets = 8;
   uint8_t *src_[kSets][3] = {};         // padded source planes
-  // reconstruction ring: the picture being coded, its reference(s) (lp-refs), and (owf >= 2) the one still waiting to be output
+  // reconstruction ring: the picture being coded, its reference(s) (lp-refs; lp-gop: every picture a later one may still refer to), and (owf >= 2) the one still waiting to be output
   static constexpr int kMaxDepth = 16;    // pictures in flight behind the one being submitted (owf), at most
-  uint8_t *rec_[kMaxDepth + 2 + KVZ_MAX_LP_REFS][3] = {};
+  static constexpr int kMaxRefDist = kSets - 1;   // lp-gop: the oldest picture a P picture refers to -- its input picture, quarter picture and collocated record are still in a working set
+  static constexpr int kRecRing = kMaxDepth + 2 + kMaxRefDist;
+  uint8_t *rec_[kRecRing][3] = {};
   bool spin_wait_ = false;      // KVAZZUP_AMD_SPIN: poll the GPU instead of napping between queries
   int rc_delay_ = 3;            // rate control: pictures between a picture and the access unit size booked before it (3 .. 7)
   int nrec_ = 3;                // reconstruction ring: the picture being written, its reference, and the ones whose output is still owed (owf)
@@ -181,6 +194,7 @@ class Encoder {
   uint8_t *mc_q_[kSets] = {}; int16_t *mc_centres_[kSets] = {};      // me-coarse: the quarter picture of the set's input picture and the centres of the set's picture [reference][32x32 block] (EncFrame::mc_*)
   ColMv *col_[kSets] = {};                 // tmvp: the collocated record of the set's picture (EncFrame::col_out), which the next picture reads (col_prev)
   int set_ = 0, out_set_ = 0;
+  int32_t out_gop_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug_copy("lp_gop") of the picture last output
   char prio_[3] = {'h', 'n', 'n'};                      // priority levels of the main, tokenizer and input streams (stream_pool.h keys)
   std::vector<int8_t> roi_; int roi_w_ = 0, roi_h_ = 0;           // as set by the caller (set_roi)
   std::vector<int8_t> roi_sub_; int roi_sub_w_ = 0, roi_sub_h_ = 0;   // the map of the picture being submitted (it travels with the picture to the submitter thread)
@@ -234,6 +248,7 @@ class Encoder {
     hipEvent_t done = nullptr, rec_done = nullptr;       // tokens / substreams delivered (stream_tok_ / ent_stream) / reconstruction final (stream_)
     hipEvent_t sink_done = nullptr; bool has_sink = false; // set_recon_sink: the reconstruction's copy into the caller's picture (stream_rec_)
     int poc = 0, rec_idx = 0, set = 0, qp = 0; bool intra = false, write_ps = false; long pic_idx = 0;
+    int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop (nref 0: off): what the slice header's reference picture set and debug_copy("lp_gop") say
     std::vector<EvPair> ev; size_t ev_used = 0;
     EncodedPicture result; bool ready = false, ok = true;   // owf >= 2: filled by the background thread
     EncFrame f_tok{}; bool prof = false, tok_failed = false;                    // tok_deferred_: what the tokenizer's launches need, kept until the launcher thread makes them

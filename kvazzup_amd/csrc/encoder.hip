@@ -57,6 +57,11 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.lp_refs < 1 || cfg.lp_refs > KVZ_MAX_LP_REFS) { if (error) *error = "lp-refs out of range (0 .. 4)"; return false; }
   if (cfg.lp_refs > 1 && cfg.band_rows > 0) { if (error) *error = "lp-refs >= 2 is not available in band mode (the halo exchange carries one reference picture's rows)"; return false; }
   if (cfg.tmvp && cfg.band_rows > 0) { if (error) *error = "tmvp is not available in band mode"; return false; }
+  if (cfg.lp_gop && cfg.gop_g >= 1) {                      // "lp-gop" with a gop=lp-g<g>d<d>t<t> string; without the string the option has nothing to say
+    if (cfg.band_rows > 0) { if (error) *error = "lp-gop is not available in band mode (the halo exchange carries one reference picture's rows)"; return false; }
+    if (cfg.gop_t > 1) { if (error) *error = "lp-gop: temporal sub-layers (gop=lp-g..d..t2 and more) are not implemented, only t1"; return false; }
+    if (cfg.gop_d < 1 || cfg.gop_d > 6) { if (error) *error = "lp-gop: the gop string's d (QP layers) must be 1 .. 6"; return false; }
+  }
   if (cfg.me_coarse != 0 && cfg.me_coarse != 64 && cfg.me_coarse != 128 && cfg.me_coarse != 256) { if (error) *error = "me-coarse must be 0, 64, 128 or 256"; return false; }
   if (cfg.me_coarse && cfg.band_rows > 0) { if (error) *error = "me-coarse is not available in band mode (the halo exchange carries a few rows)"; return false; }
 
@@ -100,7 +105,9 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   // the picture being written, the lp_refs pictures before it, and the depth_ pictures in flight in front of it -- none of whose references may be
   // overwritten (the oldest, t - depth_, reads t - depth_ - lp_refs); + 1 (at least): an intra picture is written ahead of its turn, beside the P pictures
   // in front of it, which still read theirs
-  nrec_ = depth_ + 1 + cfg.lp_refs < 2 + cfg.lp_refs ? 2 + cfg.lp_refs : depth_ + 1 + cfg.lp_refs;
+  // (lp-gop with several references: a key picture stays a reference for up to kMaxRefDist pictures)
+  const int keep = cfg.lp_gop && cfg.gop_g > 1 && cfg.lp_refs > 1 ? kMaxRefDist : cfg.lp_refs;
+  nrec_ = depth_ + 1 + keep < 2 + keep ? 2 + keep : depth_ + 1 + keep;
   prio_[0] = prio[0]; prio_[1] = prio[1]; prio_[2] = prio[2];
   HIP_OK(stream_acquire(&stream_, cfg.device, 'M', prio_[0]));
   const size_t npx = (size_t)cw_ * ch_, nb8 = npx / 64, in_bytes = (size_t)cfg.width * cfg.height * 3 / 2;
@@ -316,7 +323,7 @@ Encoder::~Encoder()
   if (in_done_) hipEventDestroy(in_done_);
   for (int k = 0; k < kInRing; k++) { hipFree(d_in_[k]); if (h_in_[k]) hipHostFree(h_in_[k]); if (ev_h2d_[k]) hipEventDestroy(ev_h2d_[k]); if (ev_pad_[k]) hipEventDestroy(ev_pad_[k]); }
   stream_release(stream_rec_, cfg_.device, 'R', 'n');
-  for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kMaxDepth + 2 + KVZ_MAX_LP_REFS; b++) hipFree(rec_[b][c]); }
+  for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kRecRing; b++) hipFree(rec_[b][c]); }
   hipFree(vaq_act_); hipFree(vaq_sum_); hipFree(rc_state_);
   for (int k = 0; k < kSets; k++) { hipFree(ctu_qt_[k]); hipFree(ctu_qy_[k]); hipFree(ctu_delta_[k]); hipFree(ctu_first_[k]); if (h_ctu_qt_[k]) hipHostFree(h_ctu_qt_[k]); hipFree(ctu_roi_[k]); }
   for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (mc_q_[k]) hipFree(mc_q_[k]); if (mc_centres_[k]) hipFree(mc_centres_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
@@ -553,12 +560,12 @@ bool Encoder::picture_begin(const EncFrame &f, hipStream_t qt_stream, EncFrame *
   // P pictures behind it, which no P picture has pending while an intra picture starts on these arrays, and the CU cbf bits)
   void *za = zero ? (void *)f.sync : nullptr, *zb = zero ? (void *)f.cu_cbf : nullptr;
   const size_t na = zero ? sizeof(uint32_t) * (((size_t)rows_ * (cw_ / 64) * 3 + 2 + 3) & ~(size_t)3) : 0, nb = zero ? (size_t)f.b8w * f.b8h : 0;
-  if (qt_stream == stream_) launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, qt, roi_dev_, n, qp_cur_, cfg_.vaq > 0 ? 1 : 0, stream_, za, na, zb, nb);
+  if (qt_stream == stream_) launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, qt, roi_dev_, n, f.qp, cfg_.vaq > 0 ? 1 : 0, stream_, za, na, zb, nb);
   else {
     // an intra picture on its side stream: the rate control state is updated in PICTURE ORDER on the main stream (between the P pictures' row groups, which
     // run there), the picture's own per-CTU targets on its own stream
-    launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, nullptr, nullptr, 0, qp_cur_, 0, stream_);
-    launch_picture_begin(nullptr, 0, 0, 0, qt, roi_dev_, n, qp_cur_, 0, qt_stream, za, na, zb, nb);
+    launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, nullptr, nullptr, 0, f.qp, 0, stream_);
+    launch_picture_begin(nullptr, 0, 0, 0, qt, roi_dev_, n, f.qp, 0, qt_stream, za, na, zb, nb);
   }
   if (cfg_.qp_in_cu && cfg_.vaq > 0) launch_vaq(f, cfg_.vaq, vaq_act_, vaq_sum_, stream_);          // (reads f.qp, f.src and f.ctu_qt; the source is padded: stream_ waits for in_done_)
   return true;
@@ -577,7 +584,8 @@ void Encoder::rate_control()
   qp_cur_ = clip3(10, 51, qp_cur_ + step);
 }
 
-// What is decided for a picture before anything is queued: its working set, intra picture or not (POC), its QP (rate control), where its chain runs
+// What is decided for a picture before anything is queued: its working set, intra picture or not (POC), its QP (rate control; lp-gop: + the layer), its
+// references, where its chain runs
 Encoder::Plan Encoder::plan(int set)
 {
   Plan p;
@@ -586,6 +594,23 @@ Encoder::Plan Encoder::plan(int set)
   p.intra = (frame_idx_ == 0) || (period > 0 && (frame_idx_ % period) == 0);
   if (p.intra) poc_ = 0; else poc_++;
   rate_control();
+  // the references: the min(lp-refs, pictures since the IDR picture) pictures before this one ...
+  p.qp = qp_cur_;
+  p.nref = p.intra || poc_ < 1 ? 1 : (poc_ < cfg_.lp_refs ? poc_ : cfg_.lp_refs);
+  if (gop_on() && !p.intra) {
+    // ... or "uvgx low-delay GOP v1" (statement of record: tests/lp_gop_model.py): the QP layer -- the controller's own state is not told about the offset --, and
+    // the previous picture, the most recent key picture within reach, then the pictures before the previous one; list 0 holds them by increasing distance
+    const int g = cfg_.gop_g, d = cfg_.gop_d, pos = ((poc_ - 1) % g) + 1;
+    int layer = 1;
+    while (layer < d && pos % (layer == 1 ? g : 1 << (d - layer)) != 0) layer++;
+    p.layer = layer; p.qp = clip3(0, 51, qp_cur_ + layer);
+    int n = 0; int8_t set[KVZ_MAX_LP_REFS];
+    set[n++] = 1;
+    if (p.nref >= 2) { const int key = ((poc_ - 2) / g) * g; if (poc_ - key <= kMaxRefDist) set[n++] = (int8_t)(poc_ - key); }
+    for (int back = 2; n < p.nref; back++) { bool have = false; for (int k = 0; k < n; k++) have |= set[k] == back; if (!have) set[n++] = (int8_t)back; }
+    for (int k = 0; k < n; k++) { int j = k; const int8_t v = set[k]; for (; j > 0 && set[j - 1] > v; j--) set[j] = set[j - 1]; set[j] = v; }
+    for (int k = 0; k < KVZ_MAX_LP_REFS; k++) p.dist[k] = k < n ? set[k] : 1;
+  }
   p.ahead = me_ahead_ && !p.intra;
   // the stream this picture's chain runs on: an intra picture's own (encoder.h stream_idr_), else the main stream -- behind the last intra picture's chain
   p.side = p.intra && (idr_side_ || (all_intra_alt_ && (frame_idx_ & 1)));
@@ -608,31 +633,32 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   f.cu_ref = cu_ref_[k];                              // NULL with one reference
   f.sao = sao_[k];                                    // NULL without SAO
   f.ctu_qt = ctu_qt_[k]; f.ctu_qy = ctu_qy_[k]; f.ctu_delta = ctu_delta_[k]; f.ctu_first = ctu_first_[k];     // all NULL without qp_in_cu
-  f.qp = qp_cur_; f.qpc = kChromaQp[qp_cur_]; f.lambda_q4 = kLambdaQ4[qp_cur_];
+  f.qp = p.qp; f.qpc = kChromaQp[p.qp]; f.lambda_q4 = kLambdaQ4[p.qp];
   f.is_intra = p.intra; f.poc = poc_;
   for (int c = 0; c < 3; c++) { f.rec[c] = cfg_.sao ? work_[c] : rec_[cur_idx_][c]; f.sao_out[c] = rec_[cur_idx_][c]; f.ref[c] = rec_[ref_idx_][c]; }
   // me-source: the search looks at the previous input picture (still in its working set: the set is not padded into again before kSets - 1 more pictures have
   // gone through the input stream, behind this picture's k_me), and what the search and the intra pricing behind it write is the set's own
   f.me_ref = p.ahead ? src_[prev_set_][0] : f.ref[0];
-  // lp-refs: reference r is the picture r + 1 before this one -- ring slot cur_idx_ - 1 - r -- as far as pictures since the IDR picture go (poc_); the search
-  // looks at its reconstruction or (me-source) at its input picture, which is still in the working set it was padded into (set_ - 1 - r: a set is padded
+  // lp-refs: reference r is the picture p.dist[r] before this one (the plan: r + 1, or lp-gop's table) -- ring slot cur_idx_ - p.dist[r]; the search
+  // looks at its reconstruction or (me-source) at its input picture, which is still in the working set it was padded into (set_ - p.dist[r]: a set is padded
   // into again kSets pictures later, behind this picture's search on the input stream)
   if (f.cu_ref) {
-    f.nref = p.intra ? 1 : (poc_ < cfg_.lp_refs ? poc_ : cfg_.lp_refs);
+    f.nref = p.nref;
     for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
-      const int back = r < f.nref ? r : 0, slot = (cur_idx_ + nrec_ - 1 - back) % nrec_;
+      const int back = r < f.nref ? p.dist[r] : 1, slot = (cur_idx_ + nrec_ - back) % nrec_;
       for (int c = 0; c < 3; c++) f.refs[r][c] = rec_[slot][c];
-      f.me_refs[r] = p.ahead ? src_[(k + kSets - 1 - back) % kSets][0] : f.refs[r][0];
+      f.me_refs[r] = p.ahead ? src_[(k + kSets - back) % kSets][0] : f.refs[r][0];
     }
   }
+  if (gop_on() && !p.intra) f.ref_dist = (uint32_t)(uint8_t)p.dist[0] | (uint32_t)(uint8_t)p.dist[1] << 8 | (uint32_t)(uint8_t)p.dist[2] << 16 | (uint32_t)(uint8_t)p.dist[3] << 24;
   // tmvp: the previous picture -- set k - 1 -- filed its record on the tokenizer's stream, where this picture's k_inter_signal reads it; right after the IDR
   // picture (which files none) the slice says slice_temporal_mvp_enabled_flag = 0 (hevc_headers.h slice_tmvp) and nothing is read
-  // me-coarse: the quarter picture of this set's input and of the sets that hold input pictures t - 1 - r (written on the input stream, where the coarse stage
+  // me-coarse: the quarter picture of this set's input and of the sets that hold input pictures t - p.dist[r] (written on the input stream, where the coarse stage
   // reads them), and the set's centres
   if (mc_q_[k]) {
     f.mc_rq = cfg_.me_coarse / 4; f.mc_q = mc_q_[k]; f.mc_centres = mc_centres_[k];
     const int nr = f.cu_ref ? f.nref : 1;
-    for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - 1 - (r < nr ? r : 0)) % kSets];
+    for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - (r < nr ? p.dist[r] : 1)) % kSets];
   }
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
   if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
@@ -753,7 +779,7 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
     a.tok = sl.g_tok; a.count = sl.g_count; a.off = sl.g_off; a.stage = sl.g_stage; a.stage_cap = (uint32_t)stage_cap_; a.out = sl.d_out; a.out_cap = (uint32_t)out_cap_;
     a.cursors = sl.g_cursors; a.sub_off = sl.d_sub; a.sub_len = sl.d_sub + rows_; a.sub_bins = sl.d_sub + 2 * rows_;
     a.ctx_save = sl.g_ctx_save; a.ctx_ready = sl.g_ctx_ready; a.gen = ++sl.gen; a.err = err_;
-    a.wc = cw_ / 64; a.hc = rows_; a.wpp = cfg_.wpp; a.tile_rows = cfg_.tile_rows; a.init_type = p.intra ? 0 : 1; a.qp = qp_cur_; a.first_sub = 0;
+    a.wc = cw_ / 64; a.hc = rows_; a.wpp = cfg_.wpp; a.tile_rows = cfg_.tile_rows; a.init_type = p.intra ? 0 : 1; a.qp = f.qp; a.first_sub = 0;
     timed(K_CABAC_ROWS, sl.ent_stream, [&] { launch_cabac_rows(a, nsub, sl.ent_stream); });
     HIP_CHECK(hipEventRecord(sl.done, sl.ent_stream));
   } else if (!tok_deferred_) HIP_CHECK(hipEventRecord(sl.done, stream_tok_));      // (tok_deferred_: launch_tokenizer records it)
@@ -775,7 +801,9 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
     sl.has_sink = true;
   }
   sink_sub_[0] = sink_sub_[1] = sink_sub_[2] = nullptr;
-  sl.pic_idx = submitted_; sl.poc = poc_; sl.intra = p.intra; sl.rec_idx = cur_idx_; sl.qp = qp_cur_; sl.write_ps = false;
+  sl.pic_idx = submitted_; sl.poc = poc_; sl.intra = p.intra; sl.rec_idx = cur_idx_; sl.qp = f.qp; sl.write_ps = false;
+  if (sl_gop_timeline(p)) { char w[12]; snprintf(w, sizeof(w), "g%dq%02dd%d%d%d%d", p.layer, f.qp, p.nref > 0 ? p.dist[0] : 0, p.nref > 1 ? p.dist[1] : 0, p.nref > 2 ? p.dist[2] : 0, p.nref > 3 ? p.dist[3] : 0); tl(w, submitted_); }      // KVAZZUP_AMD_TIMELINE, lp-gop: a P picture's layer, QP and reference distances as a record "g<layer>q<QP>d<four distances, 0 = none>"
+  sl.layer = p.layer; sl.nref = gop_on() && !p.intra ? p.nref : 0; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) sl.dist[r] = r < sl.nref ? p.dist[r] : 0;
   if (p.intra) {
     sl.write_ps = (intra_count_ == 0) || (cfg_.vps_period > 0 && (intra_count_ % cfg_.vps_period) == 0);
     intra_count_++;
@@ -842,6 +870,7 @@ bool Encoder::collect(EncodedPicture *out)
     std::swap(*out, sl.result);
   } else ok = finish_slot(sl, out);
   out_idx_ = sl.rec_idx; out_set_ = sl.set;
+  out_gop_[0] = gop_on(); out_gop_[1] = out->layer; out_gop_[2] = out->qp; out_gop_[3] = out->nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out_gop_[4 + r] = out->dist[r];
   rc_bytes_[(collected_ - 1) & 7] = (uint32_t)out->au.size();   // (collected_ - 1 = index of this picture)
   return ok;
 }
@@ -911,8 +940,10 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
   { std::lock_guard<std::mutex> l(stat_m_); t_arith_ += ar; }
   // ---- access unit assembly (host): parameter sets with IDR pictures, then the slice NAL
   out->valid = true; out->poc = sl.poc; out->qp = sl.qp; out->is_intra = sl.intra; out->bins = bins;
+  out->layer = sl.layer; out->nref = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out->dist[r] = sl.dist[r];
+  PicRefs pr; pr.n = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
   bool assembled;
-  { Tick tk; assembled = assemble_access_unit(out->au, sp_, sl.intra, sl.poc, sl.write_ps, rows_out, nsub, sl.qp - cfg_.qp); const double a = tk.ms(); std::lock_guard<std::mutex> l(stat_m_); t_asm_ += a; }
+  { Tick tk; assembled = assemble_access_unit(out->au, sp_, sl.intra, sl.poc, sl.write_ps, rows_out, nsub, sl.qp - cfg_.qp, sl.nref ? &pr : nullptr); const double a = tk.ms(); std::lock_guard<std::mutex> l(stat_m_); t_asm_ += a; }
   if (!assembled) { fprintf(stderr, "kvazzup_amd: %d substreams do not fit the tile grid\n", nsub); out->valid = false; return false; }
   out->recon_delivered = false;
   if (sl.has_sink) {                                       // the reconstruction's copy into the caller's picture: queued at submission, long done by now
@@ -1097,6 +1128,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   std::string w(what);
   static const char *names[7] = {"cu_log2", "cu_intra", "cu_flags", "cu_merge_idx", "cu_mvp_idx", "cu_intra_mode", "cu_cbf"};
   for (int i = 0; i < 7; i++) if (w == names[i]) { src = cu_bytes_[out_set_] + i * nb8; have = nb8; }
+  if (w == "lp_gop") { if (bytes > sizeof(out_gop_)) return false; memcpy(dst, out_gop_, bytes); return true; }      // (host values: no copy from the device)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
   if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }

@@ -64,7 +64,7 @@ struct RcState {
   alignas(128) unsigned long long acc[8 * KVZ_RC_ACC_STRIDE];
 };
 // "tmvp" (DESIGN.md section 9b): the collocated record of a P picture, one entry per 16x16 block in raster order (pitch cw / 16) -- the motion of the block's
-// top-left 8x8 unit, the storage 8.5.3.2.8 reads ((x >> 4) << 4, (y >> 4) << 4).  dist: POC distance of the reference the vector points into (ref_idx + 1);
+// top-left 8x8 unit, the storage 8.5.3.2.8 reads ((x >> 4) << 4, (y >> 4) << 4).  dist: POC distance of the reference the vector points into (ref_idx + 1; lp-gop: the picture's table);
 // 0: an intra unit, no vector.
 struct ColMv { int16_t mx, my, dist, pad; };
 struct EncFrame {
@@ -129,8 +129,12 @@ struct EncFrame {
   RcState *rc; long long rc_target; int rc_nb, rc_slot;      // rc_target: bits for the picture; rc_slot: where the picture's level cost is filed (picture index & 7)
   unsigned long long *trace;    // KVAZZUP_AMD_INTRA_TRACE: per (CTU, plane) 8 words {start, first block, end, time in border waits, blocks, stores, publishes, number of blocks} of k_intra_recon, 100 MHz ticks; else NULL
   // "lp-refs" (extension, "uvgx multi-reference v1"): the picture's active references in list 0 -- reference k is the picture k + 1
-  // before this one (POC distance k + 1).  A zeroed frame means one reference: nref 0 / 1, cu_ref NULL, and ref[] / me_ref are what the kernels read.
+  // before this one (POC distance k + 1; with lp-gop the picture ref_dist says, below).  A zeroed frame means one reference: nref 0 / 1, cu_ref NULL, and ref[] / me_ref are what the kernels read.
   int nref;
+  // "lp-gop" (DESIGN.md section 9d): the POC distance of reference k in byte k (reference 0 is always the previous picture: 1); 0: no table, reference k
+  // lies k + 1 pictures back.  Read by the table forms of the signalling derivation only (TabDist, k_inter_signal<.., true>).  (In the four bytes that padded
+  // nref: the frame keeps its size and every other field its place in the kernels' argument block)
+  uint32_t ref_dist;
   uint8_t *cu_ref;              // [b8] ref_idx_l0 of the CU (NULL: every CU refers to reference 0)
   const uint8_t *refs[KVZ_MAX_LP_REFS][3];   // reconstruction planes of reference k (refs[0] = ref)
   const uint8_t *me_refs[KVZ_MAX_LP_REFS];   // the luma plane k_me searches for reference k (me_refs[0] = me_ref; me-source: input picture t - 1 - k)
@@ -951,6 +955,10 @@ KVZ_HD bool me_second_window(int cx, int cy, int range) { return iabs(cx) > rang
 KVZ_HD unsigned long long me_fine_key(uint32_t cost, int ref, int win, int cand) { return ((unsigned long long)cost << 17) | ((unsigned long long)ref << 14) | ((unsigned long long)win << 13) | (unsigned long long)cand; }
 
 struct NbMv { bool ok; int mx, my, ref; };
+// POC distance of ref_idx k, as the derivations below scale vectors with it: k + 1 (lp-refs: reference k is the picture k + 1 before this one), or the
+// picture's table (lp-gop, EncFrame::ref_dist: one byte per reference)
+struct SeqDist { KVZ_HD int operator()(int k) const { return k + 1; } };
+struct TabDist { uint32_t tab; KVZ_HD int operator()(int k) const { return (int)((tab >> (8 * k)) & 0xffu); } };
 // where the derivations below read a CU's record from: the frame's arrays (host tests, band encoder) or a tile of them staged in LDS (k_inter_signal)
 struct MvRec { int intra, mx, my, cbf, ref; };
 struct FrameMvView {
@@ -1022,32 +1030,35 @@ KVZ_HD ColMv col_block(const ColMv *col, int cw, int ch, int x0, int y0, int n)
   if (c.dist == 0) c = col[((y0 + (n >> 1)) >> 4) * w16 + ((x0 + (n >> 1)) >> 4)];
   return c;
 }
-// ... and the temporal candidate it gives for ref_idx `ref`: the vector scaled from the collocated block's POC distance to this reference's (ref + 1)
-KVZ_HD NbMv temporal_cand(const ColMv &c, int ref)
+// ... and the temporal candidate it gives for ref_idx `ref`: the vector scaled from the collocated block's POC distance to this reference's (dist(ref):
+// ref + 1 without a table)
+template <class D = SeqDist>
+KVZ_HD NbMv temporal_cand(const ColMv &c, int ref, D dist = D())
 {
   NbMv r; r.ok = c.dist != 0; r.ref = ref;
-  r.mx = r.ok ? mv_scale(c.mx, c.dist, ref + 1) : 0; r.my = r.ok ? mv_scale(c.my, c.dist, ref + 1) : 0;
+  r.mx = r.ok ? mv_scale(c.mx, c.dist, dist(ref)) : 0; r.my = r.ok ? mv_scale(c.my, c.dist, dist(ref)) : 0;
   return r;
 }
 // the two AMVP candidates for ref_idx `ref` (8.5.3.2.6-8.5.3.2.7): A from A0 / A1 referring to the same picture, else (scaled) from the first of
 // them that is available; B from B0 / B1 / B2 referring to the same picture, and when neither A0 nor A1 is available (isScaledFlag 0) A takes that
 // B and B becomes the first available of B0 / B1 / B2, scaled.  tcol: the temporal candidate for `ref` (temporal_cand), taken when A and B do not give two
 // different vectors (8.5.3.2.6); NULL: none
-KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0, const NbMv *tcol = nullptr)
+template <class D = SeqDist>
+KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0, const NbMv *tcol = nullptr, D dist = D())
 {
   const NbMv *An[2] = {&q.A0, &q.A1}, *Bn[3] = {&q.B0, &q.B1, &q.B2};
   bool haveA = false, haveB = false;
   int ax = 0, ay = 0, bx = 0, by = 0;
   for (int k = 0; k < 2 && !haveA; k++) if (An[k]->ok && An[k]->ref == ref) { haveA = true; ax = An[k]->mx; ay = An[k]->my; }
   for (int k = 0; k < 2 && !haveA; k++)
-    if (An[k]->ok) { haveA = true; ax = mv_scale(An[k]->mx, An[k]->ref + 1, ref + 1); ay = mv_scale(An[k]->my, An[k]->ref + 1, ref + 1); }
+    if (An[k]->ok) { haveA = true; ax = mv_scale(An[k]->mx, dist(An[k]->ref), dist(ref)); ay = mv_scale(An[k]->my, dist(An[k]->ref), dist(ref)); }
   const bool scaled = q.A0.ok || q.A1.ok;                  // isScaledFlagLX
   for (int k = 0; k < 3 && !haveB; k++) if (Bn[k]->ok && Bn[k]->ref == ref) { haveB = true; bx = Bn[k]->mx; by = Bn[k]->my; }
   if (!scaled && haveB) { haveA = true; ax = bx; ay = by; }          // isScaledFlag == 0: A takes B's vector ...
   if (!scaled) {                                                       // ... and B is derived again, from any reference
     haveB = false;
     for (int k = 0; k < 3 && !haveB; k++)
-      if (Bn[k]->ok) { haveB = true; bx = mv_scale(Bn[k]->mx, Bn[k]->ref + 1, ref + 1); by = mv_scale(Bn[k]->my, Bn[k]->ref + 1, ref + 1); }
+      if (Bn[k]->ok) { haveB = true; bx = mv_scale(Bn[k]->mx, dist(Bn[k]->ref), dist(ref)); by = mv_scale(Bn[k]->my, dist(Bn[k]->ref), dist(ref)); }
   }
   int np = 0;
   if (haveA) { px[np] = ax; py[np] = ay; np++; }
@@ -1058,17 +1069,18 @@ KVZ_HD void amvp_cand_list(const FiveNb &q, int px[2], int py[2], int ref = 0, c
 KVZ_HD void amvp_cand_list(const EncFrame &f, int x0, int y0, int n, int px[2], int py[2]) { FrameMvView v{f}; amvp_cand_list(five_neighbours(v, f.cw, f.chp, x0, y0, n), px, py, 0); }
 
 // the signalling of the inter CU at (x0, y0): merge (+ skip) with the first candidate that equals its (vector, reference), else AMVP for its
-// reference with the cheaper predictor.  nref: the slice's active references; col: the collocated record (tmvp; NULL: no temporal candidates).
+// reference with the cheaper predictor.  nref: the slice's active references; col: the collocated record (tmvp; NULL: no temporal candidates); dist: the
+// references' POC distances (lp-gop: the picture's table)
 struct CuSignal { int flags, midx, mvp, mvdx, mvdy; };
-template <class V>
-KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, int y0, int log2, int nref = 1, const ColMv *col = nullptr)
+template <class V, class D = SeqDist>
+KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, int y0, int log2, int nref = 1, const ColMv *col = nullptr, D dist = D())
 {
   const int n = 1 << log2;
   const MvRec own = v.at(x0, y0);
   const int mvx = own.mx, mvy = own.my, ref = own.ref;
   const FiveNb q = five_neighbours(v, cw, chp, x0, y0, n);      // (once for both derivations: ten availability tests and record fetches were most of k_inter_signal's code)
   const ColMv cb = col_block(col, cw, chp & 0xfffff, x0, y0, n);  // (one collocated block for both: merge scales it to ref_idx 0, AMVP to the CU's own)
-  const NbMv t0 = temporal_cand(cb, 0);
+  const NbMv t0 = temporal_cand(cb, 0, dist);
   int cmx[5], cmy[5], cref[5];
   merge_cand_list(q, cmx, cmy, cref, nref, col ? &t0 : nullptr);
   CuSignal r; r.flags = 0; r.midx = 0; r.mvp = 0; r.mvdx = 0; r.mvdy = 0;
@@ -1076,8 +1088,8 @@ KVZ_HD CuSignal decide_signalling_values(const V &v, int cw, int chp, int x0, in
   if (r.flags && own.cbf == 0) r.flags |= CU_SKIP;
   if (!r.flags) {
     int px[2], py[2];
-    const NbMv tr = temporal_cand(cb, ref);
-    amvp_cand_list(q, px, py, ref, col ? &tr : nullptr);
+    const NbMv tr = temporal_cand(cb, ref, dist);
+    amvp_cand_list(q, px, py, ref, col ? &tr : nullptr, dist);
     int b0 = mvd_bits(mvx - px[0]) + mvd_bits(mvy - py[0]);
     int b1 = mvd_bits(mvx - px[1]) + mvd_bits(mvy - py[1]);
     r.mvp = b1 < b0;

@@ -40,6 +40,11 @@ struct StreamParams {
   int tmvp = 0;             // sps_temporal_mvp_enabled_flag; the slices: slice_temporal_mvp_enabled_flag (slice_tmvp), collocated_ref_idx 0
 };
 
+// "lp-gop" (DESIGN.md section 9d): the references of one P picture -- n of them, dist[k] pictures back, by increasing distance (dist[0] = 1).  A slice header
+// given one writes the picture's reference picture set itself (short_term_ref_pic_set_sps_flag 0), all entries used by the current picture, and n active
+// references; the parameter sets are the ones of lp-refs
+struct PicRefs { int n; int8_t dist[4]; };
+
 // pictures the DPB holds beside the current one: sps/vps_max_dec_pic_buffering_minus1
 inline int dpb_minus1(const StreamParams &s) { return s.lp_refs > 1 ? s.lp_refs : 1; }
 // active references of a P picture `poc` pictures after its IDR picture
@@ -145,7 +150,7 @@ inline size_t escaped_size(const uint8_t *p, size_t n)
 // slice segment header (7.3.6.1).  address < 0: the picture's first segment; else slice_segment_address of a further one, `dependent`
 // = a dependent slice segment (nothing but the address and the entry points)
 inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, int poc, const std::vector<uint32_t> &entry_sizes, int slice_qp_delta = 0,
-                               int address = -1, bool dependent = false)
+                               int address = -1, bool dependent = false, const PicRefs *refs = nullptr)
 {
   w.bit(address < 0);
   if (idr) w.bit(0);
@@ -158,10 +163,15 @@ inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, in
   }
   if (!dependent) {
     w.ue(idr ? 2 : 1);
-    const int nact = active_refs(s, poc);
+    const int nact = refs && !idr ? refs->n : active_refs(s, poc);
     if (!idr) {
-      w.put((uint32_t)poc & 255, 8); w.bit(1);
-      if (s.lp_refs > 1) { int bits = 0; while ((1 << bits) < s.lp_refs) bits++; w.put((uint32_t)nact - 1, bits); }     // short_term_ref_pic_set_idx
+      w.put((uint32_t)poc & 255, 8);
+      if (refs) {                                                  // st_ref_pic_set(num_short_term_ref_pic_sets) (7.3.7): the SPS carries sets, so the prediction flag is present
+        w.bit(0); w.bit(0);                                        // short_term_ref_pic_set_sps_flag, inter_ref_pic_set_prediction_flag
+        w.ue((uint32_t)refs->n); w.ue(0);                          // num_negative_pics, num_positive_pics
+        for (int k = 0; k < refs->n; k++) { w.ue((uint32_t)(refs->dist[k] - (k ? refs->dist[k - 1] : 0) - 1)); w.bit(1); }      // delta_poc_s0_minus1, used_by_curr_pic_s0_flag
+      } else w.bit(1);
+      if (!refs && s.lp_refs > 1) { int bits = 0; while ((1 << bits) < s.lp_refs) bits++; w.put((uint32_t)nact - 1, bits); }     // short_term_ref_pic_set_idx
       if (s.tmvp) w.bit(slice_tmvp(s, idr, poc));                  // slice_temporal_mvp_enabled_flag
     }
     if (s.sao) { w.bit(1); w.bit(1); }                             // slice_sao_luma_flag, slice_sao_chroma_flag
@@ -210,7 +220,7 @@ inline void append_nal(std::vector<uint8_t> &out, int nal_type, const uint8_t *r
 // One access unit: [VPS SPS PPS] + slice NAL whose data are the `nsub` substreams (CTU rows with
 // WPP, otherwise one) rows[r].  false (and an empty access unit): the substream count does not fit the tiling.
 inline bool assemble_access_unit(std::vector<uint8_t> &au, const StreamParams &sp, bool idr, int poc, bool write_ps,
-                                 const std::vector<std::vector<uint8_t>> &rows, int nsub, int slice_qp_delta = 0)
+                                 const std::vector<std::vector<uint8_t>> &rows, int nsub, int slice_qp_delta = 0, const PicRefs *refs = nullptr)
 {
   au.clear();
   if (write_ps) {
@@ -237,7 +247,7 @@ inline bool assemble_access_unit(std::vector<uint8_t> &au, const StreamParams &s
     std::vector<uint32_t> entry;
     for (int r = 0; r + 1 < n; r++) entry.push_back((uint32_t)escaped_size(rows[(size_t)(s0 + r)].data(), rows[(size_t)(s0 + r)].size()));
     BitWriter sh;
-    write_slice_header(sh, sp, idr, poc, entry, slice_qp_delta, addr, sp.slices == 1 && s0 > 0);
+    write_slice_header(sh, sp, idr, poc, entry, slice_qp_delta, addr, sp.slices == 1 && s0 > 0, refs);
     for (int r = 0; r < n; r++) sh.bytes(rows[(size_t)(s0 + r)].data(), rows[(size_t)(s0 + r)].size());
     append_nal(au, idr ? 19 : 1, sh.data().data(), sh.data().size());
     s0 += n;

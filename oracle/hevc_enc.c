@@ -19,6 +19,7 @@
 #define SPLIT_BITS 8          /* rate charged for splitting a CU one level, in bins */
 #define ME_PAD 64             /* padding of the reference copy used by the motion search */
 #define ORC_MAX_LP_REFS 4     /* lp-refs: references per P picture at most */
+#define ORC_MAX_REF_DIST 7    /* lp-gop: the oldest picture a P picture refers to lies this many pictures back */
 
 const uint16_t orc_lambda_q4[52] = {
   3, 3, 4, 4, 5, 5, 6, 7, 8, 9, 10, 11, 12, 14, 15, 17, 19, 22, 24, 27, 30, 34, 38, 43, 48, 54,
@@ -30,19 +31,28 @@ struct orc_encoder {
   uint8_t sfac[4][6][1024];            /* scaling-list default: the default lists' scaling factors per size and matrix */
   int cw, ch, b8w, b8h;
   int frame_idx, poc, intra_count;
-  int qp;                              /* QP of the picture being coded (== cfg.qp without rate control) */
+  int qp;                              /* QP of the picture being coded (== cfg.qp without rate control and lp-gop) */
+  int rc_qp;                           /* Q: the constant QP, or rate control v1's current QP (its state: lp-gop's layer offset is never written back into it) */
+  int lp_gop, gop_g, gop_d;            /* "lp-gop" with "lp-gop-g" / "lp-gop-d": "uvgx low-delay GOP v1"  */
+  int me_coarse;                       /* "me-coarse" 0 / 64 / 128 / 256: "uvgx coarse-to-fine search v1"  */
+  int layer;                           /* lp-gop: QP layer of the picture being coded (0: an IDR picture, or the option off) */
+  int dist[ORC_MAX_LP_REFS];           /* reference k of the picture being coded lies dist[k] pictures back (k + 1 without lp-gop) */
   int64_t rc_debt; uint32_t rc_bytes[8];  /* rate control: bits spent above target so far; sizes of the last access units */
   /* rate control v2 (rc_bands): bits per unit of level cost (Q8, smoothed), whether it has been measured yet, the level cost of the
    * last eight pictures and whether they were P pictures coded in groups */
   uint32_t rc_ratio_q8; int rc_ratio_valid; uint32_t rc_cost[8]; uint8_t rc_cost_valid[8];
   orc_vps vps; orc_sps sps; orc_pps pps;
-  /* the picture being coded and its references: refs[k] = the picture coded k + 1 pictures before (lp-refs: nref = n of them, else 1); the
-   * pictures rotate through pics[] (orc_enc_encode's end) */
-  orc_pic pics[1 + ORC_MAX_LP_REFS]; orc_pic *cur, *refs[ORC_MAX_LP_REFS];
-  int nref;                            /* max(lp_refs, 1): references kept */
+  /* the picture being coded and its references: refs[k] = the picture coded dist[k] pictures before (k + 1 without lp-gop; lp-refs: nref = n
+   * of them, else 1); the pictures rotate through pics[] (orc_enc_encode's end) */
+  orc_pic pics[1 + ORC_MAX_REF_DIST]; orc_pic *cur, *refs[ORC_MAX_LP_REFS];
+  orc_pic *hist[ORC_MAX_REF_DIST];     /* hist[j]: the picture coded j + 1 pictures before; refs[k] = hist[dist[k] - 1] */
+  int nkeep;                           /* pictures kept behind the current one: nref, or ORC_MAX_REF_DIST when lp-gop can reach a key picture (g > 1, nref > 1) */
+  int nref;                            /* max(lp_refs, 1): references a P picture has at most */
   int nact;                            /* m: active references of the picture being coded (P: min(nref, pictures since the IDR picture)) */
   pixel *src[3];
-  pixel *prev_src[ORC_MAX_LP_REFS];    /* cfg.me_source: the luma planes of the previous input pictures, [k] = picture t-1-k (padded to the coded size), NULL until needed */
+  pixel *prev_src[ORC_MAX_REF_DIST];   /* cfg.me_source: the luma planes of the previous input pictures, [j] = picture t-1-j (padded to the coded size), NULL until needed */
+  pixel *qcur, *qprev[ORC_MAX_REF_DIST];   /* me-coarse: quarter picture of the input picture being coded and of the input pictures t-1-j */
+  int16_t *centres;                    /* me-coarse: [reference][32x32 block, raster][x, y] the coarse stage's centres, full samples */
   int16_t *coef[3];
   pixel *predeblock[3];
   pixel *refpad[ORC_MAX_LP_REFS]; int refpad_stride;   /* the plane the integer search looks at, per reference (build_refpad) */
@@ -102,13 +112,13 @@ orc_encoder *orc_enc_open(const orc_enc_config *c)
   if (e->cfg.bitrate <= 0) e->cfg.rc_bands = 0;
   if ((e->cfg.slices == 1 && !e->cfg.wpp) || (e->cfg.slices == 2 && e->cfg.tile_rows * e->cfg.tile_cols < 2) || (e->cfg.slices == 1 && e->cfg.tile_cols > 1) || e->cfg.slices < 0 || e->cfg.slices > 2) e->cfg.slices = 0;
   if (e->cfg.rc_bands > 0) e->cfg.qp_in_cu = 1;
-  e->qp = c->qp;
+  e->qp = e->rc_qp = c->qp;
   e->cw = (c->width + 63) & ~63; e->ch = (c->height + 63) & ~63;
   if (e->cw < 128) e->cw = 128;                 /* WPP context hand-over needs two CTUs per row */
   e->b8w = e->cw / 8; e->b8h = e->ch / 8;
   size_t nb8 = (size_t)e->b8w * e->b8h, npx = (size_t)e->cw * e->ch;
   for (int i = 0; i < 2; i++) if (orc_pic_alloc(&e->pics[i], e->cw, e->ch)) return NULL;
-  e->cur = &e->pics[0]; e->refs[0] = &e->pics[1]; e->nref = 1;
+  e->cur = &e->pics[0]; e->hist[0] = e->refs[0] = &e->pics[1]; e->nref = e->nkeep = 1;
   for (int i = 0; i < 3; i++) {
     size_t n = i ? npx / 4 : npx;
     e->src[i] = (pixel *)malloc(n); e->coef[i] = (int16_t *)calloc(n, sizeof(int16_t)); e->predeblock[i] = (pixel *)malloc(n);
@@ -174,9 +184,11 @@ orc_encoder *orc_enc_open(const orc_enc_config *c)
 void orc_enc_close(orc_encoder *e)
 {
   if (!e) return;
-  for (int i = 0; i < 1 + e->nref; i++) orc_pic_free(&e->pics[i]);
+  for (int i = 0; i < 1 + e->nkeep; i++) orc_pic_free(&e->pics[i]);
   for (int i = 0; i < 3; i++) { free(e->src[i]); free(e->coef[i]); free(e->predeblock[i]); }
-  for (int k = 0; k < ORC_MAX_LP_REFS; k++) { free(e->refpad[k]); free(e->prev_src[k]); }
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) free(e->refpad[k]);
+  for (int k = 0; k < ORC_MAX_REF_DIST; k++) { free(e->prev_src[k]); free(e->qprev[k]); }
+  free(e->qcur); free(e->centres);
   free(e->cu_ref); free(e->sao); for (int i = 0; i < 3; i++) free(e->sao_in[i]);
   free(e->cu_log2); free(e->cu_intra); free(e->cu_flags); free(e->cu_merge_idx); free(e->cu_mvp_idx);
   free(e->cu_intra_mode); free(e->cu_cbf); free(e->cu_mv); free(e->cu_mvd); free(e->bs_v); free(e->bs_h);
@@ -413,8 +425,9 @@ static void encode_intra_picture(orc_encoder *e)
 static void build_refpad(orc_encoder *e, int k)
 {
   int st = e->refpad_stride;
-  const pixel *plane = e->cfg.me_source && e->prev_src[k] ? e->prev_src[k] : e->refs[k]->plane[0];      /* reference k: picture t-1-k */
-  const int pstride = e->cfg.me_source && e->prev_src[k] ? e->cw : e->refs[k]->stride[0];
+  const pixel *in = e->prev_src[e->dist[k] - 1];                                     /* reference k: picture t - dist[k] (t-1-k without lp-gop) */
+  const pixel *plane = e->cfg.me_source && in ? in : e->refs[k]->plane[0];
+  const int pstride = e->cfg.me_source && in ? e->cw : e->refs[k]->stride[0];
   if (!e->refpad[k]) e->refpad[k] = (pixel *)malloc((size_t)st * (e->ch + 2 * ME_PAD));
   for (int y = -ME_PAD; y < e->ch + ME_PAD; y++) {
     const pixel *srow = plane + (size_t)orc_clip3(0, e->ch - 1, y) * pstride;
@@ -427,6 +440,18 @@ static inline uint32_t sad16(const pixel *a, int as, const pixel *b, int bs)
 {
   uint32_t s = 0;
   for (int y = 0; y < 16; y++) for (int x = 0; x < 16; x++) s += (uint32_t)orc_abs(a[y * as + x] - b[y * bs + x]);
+  return s;
+}
+
+/* me-coarse, second window: the displaced block may lie anywhere, so every sample position is clamped to the picture (what the padded copy holds inside its
+ * ME_PAD margin) */
+static uint32_t sad16_clamped(const orc_encoder *e, const pixel *a, const pixel *refpad, int x, int y)
+{
+  uint32_t s = 0;
+  for (int j = 0; j < 16; j++) {
+    const pixel *row = refpad + (size_t)(orc_clip3(0, e->ch - 1, y + j) + ME_PAD) * e->refpad_stride + ME_PAD;
+    for (int i = 0; i < 16; i++) s += (uint32_t)orc_abs(a[j * e->cw + i] - row[orc_clip3(0, e->cw - 1, x + i)]);
+  }
   return s;
 }
 
@@ -485,9 +510,80 @@ static void subme_refine(orc_encoder *e, int x0, int y0, int n, int ty0, int ty1
   for (int y = y0; y < y0 + n; y += 8) for (int x = x0; x < x0 + n; x += 8) { e->cu_mv[b8i(e, x, y) * 2] = (int16_t)cx; e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)cy; }
 }
 
+/* ---- "uvgx coarse-to-fine search v1" (option me-coarse; the same statement in numpy: tests/me_coarse_model.py).
+ * Quarter picture of a padded input luma plane: q(x, y) = (sum of the 4x4 samples at (4x, 4y) + 8) >> 4. */
+static void quarter_picture(const orc_encoder *e, const pixel *src, pixel *q)
+{
+  const int qw = e->cw / 4, qh = e->ch / 4;
+  for (int y = 0; y < qh; y++) for (int x = 0; x < qw; x++) {
+    uint32_t sum = 8;
+    for (int j = 0; j < 4; j++) for (int i = 0; i < 4; i++) sum += src[(size_t)(4 * y + j) * e->cw + 4 * x + i];
+    q[(size_t)y * qw + x] = (pixel)(sum >> 4);
+  }
+}
+/* the fine search's rule for one axis: may the 32-sample block at p0 be displaced by v full samples (tile [lo, hi), picture [0, size))?  An odd
+ * displacement needs 4 samples more on either side (the chroma half-sample taps); the picture's own edges count only with mv-constraint. */
+static int me_axis_allowed(int v, int p0, int lo, int hi, int size, int mv_frame)
+{
+  const int m = (v & 1) ? 4 : 0;
+  if ((lo > 0 && p0 + v - m < lo) || (hi < size && p0 + v + 32 + m > hi)) return 0;
+  if (mv_frame) {
+    const int mm = (mv_frame == 2 && (v & 1)) ? 4 : 0;
+    if (p0 + v - mm < 0 || p0 + v + 32 + mm > size) return 0;
+  }
+  return 1;
+}
+static void block_tile(const orc_encoder *e, int x0, int y0, int *tx0, int *tx1, int *ty0, int *ty1)
+{
+  *ty0 = 0; *ty1 = e->ch; *tx0 = 0; *tx1 = e->cw;
+  for (int i = 0; i < e->cfg.tile_rows; i++) if ((y0 >> 6) >= e->tile_row_bd[i] && (y0 >> 6) < e->tile_row_bd[i + 1]) { *ty0 = e->tile_row_bd[i] * 64; *ty1 = e->tile_row_bd[i + 1] * 64; }
+  for (int j = 0; j < e->cfg.tile_cols; j++) if ((x0 >> 6) >= e->tile_col_bd[j] && (x0 >> 6) < e->tile_col_bd[j + 1]) { *tx0 = e->tile_col_bd[j] * 64; *tx1 = e->tile_col_bd[j + 1] * 64; }
+}
+/* Coarse stage: per 32x32 block and active reference k, the block's 8x8 samples of the quarter picture of the INPUT picture against the quarter picture of INPUT
+ * picture t - dist[k] (whatever me-source says), candidates (dxq, dyq) in [-Rq, Rq]^2, samples outside the quarter picture clamped to its edge; a candidate
+ * is admissible when the block displaced by (4 dxq, 4 dyq) passes the fine search's rules; cost = 16 SAD + ((lambda (mvd_bits(16 dxq) + mvd_bits(16 dyq))) >> 4);
+ * the first minimum in raster order of (dyq, dxq) is the centre (4 dxq, 4 dyq). */
+static void coarse_stage(orc_encoder *e)
+{
+  const int rq = e->me_coarse / 4, qw = e->cw / 4, qh = e->ch / 4, nbx = e->cw / 32, nby = e->ch / 32;
+  const uint32_t lam = orc_lambda_q4[e->qp];
+  if (!e->qcur) e->qcur = (pixel *)malloc((size_t)qw * qh);
+  if (!e->centres) e->centres = (int16_t *)calloc((size_t)ORC_MAX_LP_REFS * nbx * nby * 2, sizeof(int16_t));
+  memset(e->centres, 0, sizeof(int16_t) * (size_t)ORC_MAX_LP_REFS * nbx * nby * 2);
+  quarter_picture(e, e->src[0], e->qcur);
+  int *bits = (int *)malloc(sizeof(int) * (size_t)(2 * rq + 1));
+  for (int d = -rq; d <= rq; d++) bits[d + rq] = orc_mvd_bits(16 * d);
+  for (int k = 0; k < e->nact; k++) {
+    const pixel *rp = e->qprev[e->dist[k] - 1];
+    for (int by = 0; by < nby; by++) for (int bx = 0; bx < nbx; bx++) {
+      int tx0, tx1, ty0, ty1;
+      block_tile(e, bx * 32, by * 32, &tx0, &tx1, &ty0, &ty1);
+      uint64_t best = UINT64_MAX; int cx = 0, cy = 0;
+      for (int dy = -rq; dy <= rq; dy++) {
+        if (!me_axis_allowed(4 * dy, by * 32, ty0, ty1, e->ch, e->cfg.mv_frame)) continue;
+        for (int dx = -rq; dx <= rq; dx++) {
+          if (!me_axis_allowed(4 * dx, bx * 32, tx0, tx1, e->cw, e->cfg.mv_frame)) continue;
+          uint32_t sad = 0;
+          for (int y = 0; y < 8; y++) {
+            const pixel *c = e->qcur + (size_t)(by * 8 + y) * qw + bx * 8, *r = rp + (size_t)orc_clip3(0, qh - 1, by * 8 + y + dy) * qw;
+            for (int x = 0; x < 8; x++) sad += (uint32_t)orc_abs(c[x] - r[orc_clip3(0, qw - 1, bx * 8 + x + dx)]);
+          }
+          const uint64_t cost = 16u * (uint64_t)sad + ((lam * (uint32_t)(bits[dx + rq] + bits[dy + rq])) >> 4);
+          if (cost < best) { best = cost; cx = 4 * dx; cy = 4 * dy; }
+        }
+      }
+      int16_t *c = e->centres + 2 * ((size_t)k * nbx * nby + (size_t)by * nbx + bx);
+      c[0] = (int16_t)cx; c[1] = (int16_t)cy;
+    }
+  }
+  free(bits);
+}
+
 /* Full search for one 32x32 block over the m active references (reference k: refpad[k]), each with candidates in raster order (dy outer,
  * dx inner), cost = SAD + (lambda * (bits(mv as mvd from zero) + ref_bins(k, m))) >> 4, key = cost << 16 | k << 13 | candidate index:
- * lower cost, then lower reference, then lower candidate (with one reference the order of cost << 13 | candidate). */
+ * lower cost, then lower reference, then lower candidate (with one reference the order of cost << 13 | candidate).
+ * me-coarse: reference k has a second window of the same size around its centre c_k iff |c_k.x| > R - 4 or |c_k.y| > R - 4; rate and admissibility are those
+ * of the WHOLE vector; key = cost << 17 | k << 14 | window << 13 | candidate index inside the window: the zero window before the centred one. */
 static void me_block32(orc_encoder *e, int x0, int y0)
 {
   int R = e->cfg.search_range, st = e->refpad_stride, m = e->nact;
@@ -511,12 +607,17 @@ static void me_block32(orc_encoder *e, int x0, int y0)
   for (int i = 0; i < e->cfg.tile_rows; i++) if ((y0 >> 6) >= e->tile_row_bd[i] && (y0 >> 6) < e->tile_row_bd[i + 1]) { ty0 = e->tile_row_bd[i] * 64; ty1 = e->tile_row_bd[i + 1] * 64; }
   int tx0 = 0, tx1 = e->cw;                                      /* ... and the same in x with tile columns */
   for (int j = 0; j < e->cfg.tile_cols; j++) if ((x0 >> 6) >= e->tile_col_bd[j] && (x0 >> 6) < e->tile_col_bd[j + 1]) { tx0 = e->tile_col_bd[j] * 64; tx1 = e->tile_col_bd[j + 1] * 64; }
-  for (int rk = 0; rk < m; rk++) {
+  const int16_t *centres = e->me_coarse ? e->centres + 2 * ((size_t)(y0 >> 5) * (e->cw >> 5) + (x0 >> 5)) : NULL;
+  const size_t cstep = 2 * (size_t)(e->cw >> 5) * (e->ch >> 5);
+  for (int rk = 0; rk < m; rk++) for (int win = 0; win < (centres ? 2 : 1); win++) {
     const pixel *refpad = e->refpad[rk];
     const uint32_t rb = (uint32_t)ref_bins(rk, m);
+    const int ox = win ? centres[rk * cstep] : 0, oy = win ? centres[rk * cstep + 1] : 0;
+    if (win && !(orc_abs(ox) > R - 4 || orc_abs(oy) > R - 4)) continue;
     int idx = 0;
-  for (int dy = -R; dy <= R; dy++)
-    for (int dx = -R; dx <= R; dx++, idx++) {
+  for (int wy = -R; wy <= R; wy++)
+    for (int wx = -R; wx <= R; wx++, idx++) {
+      const int dx = ox + wx, dy = oy + wy;
       int myt = (dy & 1) ? 4 : 0, mxt = (dx & 1) ? 4 : 0;
       if ((ty0 > 0 && y0 + dy - myt < ty0) || (ty1 < e->ch && y0 + dy + 32 + myt > ty1)) continue;
       if ((tx0 > 0 && x0 + dx - mxt < tx0) || (tx1 < e->cw && x0 + dx + 32 + mxt > tx1)) continue;
@@ -525,37 +626,42 @@ static void me_block32(orc_encoder *e, int x0, int y0)
         if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > e->cw || y0 + dy - my < 0 || y0 + dy + 32 + my > e->ch) continue;
       }
       uint32_t rate = (lam * (uint32_t)(orc_mvd_bits(dx * 4) + orc_mvd_bits(dy * 4) + rb)) >> 4;
-      const uint64_t cand = ((uint64_t)rk << 13) | (uint64_t)idx;
+      const uint64_t cand = ((uint64_t)rk << 14) | ((uint64_t)win << 13) | (uint64_t)idx;
       uint32_t s32 = 0;
       for (int k = 0; k < 4; k++) {
         int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16;
-        uint32_t s = sad16(e->src[0] + by * e->cw + bx, e->cw, refpad + (size_t)(by + dy + ME_PAD) * st + bx + dx + ME_PAD, st);
+        uint32_t s = win ? sad16_clamped(e, e->src[0] + by * e->cw + bx, refpad, bx + dx, by + dy)
+                         : sad16(e->src[0] + by * e->cw + bx, e->cw, refpad + (size_t)(by + dy + ME_PAD) * st + bx + dx + ME_PAD, st);
         s32 += s;
-        uint64_t key = ((uint64_t)(s + rate) << 16) | cand;
+        uint64_t key = ((uint64_t)(s + rate) << 17) | cand;
         if (key < best16[k]) best16[k] = key;
       }
-      uint64_t key = ((uint64_t)(s32 + rate) << 16) | cand;
+      uint64_t key = ((uint64_t)(s32 + rate) << 17) | cand;
       if (key < best32) best32 = key;
     }
   }
   uint32_t pen = (lam * SPLIT_BITS) >> 4;
   uint32_t csplit = pen;
-  for (int k = 0; k < 4; k++) csplit += (uint32_t)(best16[k] >> 16);
-  const uint32_t c32 = (uint32_t)(best32 >> 16);
+  for (int k = 0; k < 4; k++) csplit += (uint32_t)(best16[k] >> 17);
+  const uint32_t c32 = (uint32_t)(best32 >> 17);
   int W = 2 * R + 1;
   if (csplit < c32) {
     for (int k = 0; k < 4; k++) {
       int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16, ci = (int)(best16[k] & 0x1fff);
-      set_cu(e, e->cu_log2, bx, by, 16, 4); set_cu(e, e->cu_ref, bx, by, 16, (int)((best16[k] >> 13) & 7));      /* quarters keep their own reference */
+      const int rsel = (int)((best16[k] >> 14) & 7), second = (int)((best16[k] >> 13) & 1);
+      const int ox = second ? centres[rsel * cstep] : 0, oy = second ? centres[rsel * cstep + 1] : 0;
+      set_cu(e, e->cu_log2, bx, by, 16, 4); set_cu(e, e->cu_ref, bx, by, 16, rsel);      /* quarters keep their own reference */
       for (int y = by; y < by + 16; y += 8) for (int x = bx; x < bx + 16; x += 8) {
-        e->cu_mv[b8i(e, x, y) * 2] = (int16_t)(((ci % W) - R) * 4); e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)(((ci / W) - R) * 4);
+        e->cu_mv[b8i(e, x, y) * 2] = (int16_t)((ox + (ci % W) - R) * 4); e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)((oy + (ci / W) - R) * 4);
       }
     }
   } else {
     int ci = (int)(best32 & 0x1fff);
-    set_cu(e, e->cu_log2, x0, y0, 32, 5); set_cu(e, e->cu_ref, x0, y0, 32, (int)((best32 >> 13) & 7));
+    const int rsel = (int)((best32 >> 14) & 7), second = (int)((best32 >> 13) & 1);
+    const int ox = second ? centres[rsel * cstep] : 0, oy = second ? centres[rsel * cstep + 1] : 0;
+    set_cu(e, e->cu_log2, x0, y0, 32, 5); set_cu(e, e->cu_ref, x0, y0, 32, rsel);
     for (int y = y0; y < y0 + 32; y += 8) for (int x = x0; x < x0 + 32; x += 8) {
-      e->cu_mv[b8i(e, x, y) * 2] = (int16_t)(((ci % W) - R) * 4); e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)(((ci / W) - R) * 4);
+      e->cu_mv[b8i(e, x, y) * 2] = (int16_t)((ox + (ci % W) - R) * 4); e->cu_mv[b8i(e, x, y) * 2 + 1] = (int16_t)((oy + (ci / W) - R) * 4);
     }
   }
   set_cu(e, e->cu_intra, x0, y0, 32, 0);
@@ -566,7 +672,7 @@ static void me_block32(orc_encoder *e, int x0, int y0)
      * units (the inter ones keep their vectors; an intra quarter is one 16x16 or four 8x8 intra units). */
     uint32_t ic[4]; int any = 0, cand[4];
     for (int k = 0; k < 4; k++) {
-      ic[k] = csplit < c32 ? (uint32_t)(best16[k] >> 16) : (c32 + 2) >> 2;      /* (the chosen costs: reference bins included) */
+      ic[k] = csplit < c32 ? (uint32_t)(best16[k] >> 17) : (c32 + 2) >> 2;      /* (the chosen costs: reference bins included) */
       cand[k] = ic[k] > INTRA_P_GATE * lam; any |= cand[k];
     }
     if (any) {
@@ -644,6 +750,9 @@ static void inter_recon_cu(orc_encoder *e, int x0, int y0, int log2)
   set_cu(e, e->cu_intra, x0, y0, n, 0);
 }
 
+/* lp-gop takes effect with the switch and a g (the gop string's numbers) */
+static int gop_on(const orc_encoder *e) { return e->lp_gop && e->gop_g >= 1; }
+
 /* tmvp: slice_temporal_mvp_enabled_flag of the picture being coded -- 1 on every P picture but the one right after an IDR picture, whose
  * collocated picture (the previous one) is intra and gives no candidate */
 static int slice_tmvp(const orc_encoder *e) { return e->cfg.tmvp && !e->is_intra && e->poc != 1; }
@@ -655,7 +764,7 @@ static void inter_decide_signalling(orc_encoder *e, int x0, int y0, int log2)
   orc_mvpred_ctx mc; memset(&mc, 0, sizeof(mc)); mc.collocated_from_l0 = 1;
   mc.pic = p; mc.av = e->av; mc.log2_par_mrg_level = 2; mc.max_num_merge_cand = 5; mc.num_ref_idx = e->nact;
   mc.cur_poc = e->poc;
-  for (int k = 0; k < e->nact; k++) mc.ref_poc[k] = e->poc - 1 - k;          /* reference k: POC distance k + 1 */
+  for (int k = 0; k < e->nact; k++) mc.ref_poc[k] = e->poc - e->dist[k];     /* reference k: POC distance k + 1, or lp-gop's (the scaling of 8.5.3.2.7 / 8.5.3.2.8 takes these) */
   if (slice_tmvp(e)) mc.col = e->refs[0];                                       /* collocated_ref_idx 0: the previous picture */
   const int rk = e->cu_ref[bi];
   int16_t mvx = e->cu_mv[bi * 2], mvy = e->cu_mv[bi * 2 + 1];
@@ -723,6 +832,7 @@ static void intra_recon_tree(orc_encoder *e, int x0, int y0, int log2);
 static void encode_inter_picture(orc_encoder *e)
 {
   for (int k = 0; k < e->nact; k++) build_refpad(e, k);
+  if (e->me_coarse) coarse_stage(e);
   e->intra_p_ready = 0;
   for (int y = 0; y < e->ch; y += 32) for (int x = 0; x < e->cw; x += 32) me_block32(e, x, y);
   /* Reconstruction, in rc_bands groups of CTU rows when rate control v2 is on: after each group the level cost so far is priced
@@ -1083,6 +1193,11 @@ static void write_picture(orc_encoder *e, int write_ps)
   sh.poc_lsb = e->poc & 255; sh.short_term_ref_pic_set_sps_flag = 1;
   sh.num_ref_idx_l0 = e->is_intra ? 1 : e->nact; sh.num_ref_idx_l1 = 1; sh.max_num_merge_cand = 5; sh.collocated_from_l0 = 1;
   sh.short_term_rps_idx = e->is_intra ? 0 : e->nact - 1;          /* set m - 1: the m previous pictures; num_ref_idx_active_override when m < n */
+  if (gop_on(e) && !e->is_intra) {                                  /* lp-gop: the header carries the picture's set itself -- no prediction from the SPS's sets, m negative pictures by increasing distance, all used */
+    sh.short_term_ref_pic_set_sps_flag = 0; sh.short_term_rps_idx = 0;
+    sh.st_rps.num_negative = e->nact;
+    for (int k = 0; k < e->nact; k++) { sh.st_rps.delta_poc_s0[k] = -e->dist[k]; sh.st_rps.used_s0[k] = 1; }
+  }
   sh.slice_temporal_mvp_enabled = slice_tmvp(e); sh.collocated_ref_idx = 0;
   sh.slice_deblocking_disabled = !e->cfg.deblock;
   sh.loop_filter_across_slices = 1;
@@ -1123,7 +1238,24 @@ static void rate_control(orc_encoder *e)
   int step = 0;
   if (e->rc_debt > 4 * T && trend > 0) step = e->rc_debt > 16 * T ? 2 : 1;
   if (e->rc_debt < -4 * T && trend < 0) step = e->rc_debt < -16 * T ? -2 : -1;
-  e->qp = orc_clip3(10, 51, e->qp + step);
+  e->rc_qp = orc_clip3(10, 51, e->rc_qp + step);
+}
+
+/* "uvgx low-delay GOP v1" (the same statement in python: tests/lp_gop_model.py) for P picture t = POC: its QP layer -- pos = ((t - 1) % g) + 1,
+ * mod[0] = g, mod[i] = 1 << (d - 1 - i), the first layer l in 1 .. d - 1 with pos % mod[l - 1] == 0, else d -- and its references: t - 1; with m >= 2 the most
+ * recent key picture (a multiple of g) <= t - 2 when it lies within ORC_MAX_REF_DIST; then t - 2, t - 3, ... until there are m; by increasing distance. */
+static void gop_plan(orc_encoder *e)
+{
+  const int t = e->poc, g = e->gop_g, d = e->gop_d, m = e->nact, pos = ((t - 1) % g) + 1;
+  int layer = 1;
+  while (layer < d && pos % (layer == 1 ? g : 1 << (d - layer)) != 0) layer++;
+  e->layer = layer;
+  int n = 0, set[ORC_MAX_LP_REFS];
+  set[n++] = 1;
+  if (m >= 2) { const int key = ((t - 2) / g) * g; if (t - key <= ORC_MAX_REF_DIST) set[n++] = t - key; }
+  for (int back = 2; n < m; back++) { int have = 0; for (int k = 0; k < n; k++) have |= set[k] == back; if (!have) set[n++] = back; }
+  for (int k = 1; k < n; k++) { const int v = set[k]; int j = k; for (; j > 0 && set[j - 1] > v; j--) set[j] = set[j - 1]; set[j] = v; }
+  for (int k = 0; k < n; k++) e->dist[k] = set[k];
 }
 
 void orc_enc_set_roi(orc_encoder *e, int w, int h, const int8_t *map)
@@ -1209,12 +1341,16 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
   if (e->is_intra) e->poc = 0; else e->poc++;
   e->nact = e->is_intra ? 0 : (e->poc < e->nref ? e->poc : e->nref);
   rate_control(e);
+  e->qp = e->rc_qp; e->layer = 0;
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) e->dist[k] = k + 1;
+  if (gop_on(e) && !e->is_intra) { gop_plan(e); e->qp = orc_clip3(0, 51, e->rc_qp + e->layer); }      /* (IDR pictures keep Q; the controller's state never sees the offset) */
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) e->refs[k] = e->hist[e->dist[k] <= e->nkeep ? e->dist[k] - 1 : 0];
   rc_picture_start(e);
   load_input(e, y, u, v);
   roi_targets(e);
   orc_pic_reset_side(e->cur);
   e->cur->poc = e->poc;
-  for (int i = 0; i < 16; i++) e->cur->ref_poc_list[i] = e->poc - 1 - (i < e->nref ? i : 0);      /* reference k = picture t-1-k (bS compares these, TMVP scales by them) */
+  for (int i = 0; i < 16; i++) e->cur->ref_poc_list[i] = e->poc - (i < e->nref ? e->dist[i] : 1);      /* reference k = picture t - dist[k] (bS compares these, TMVP scales by them) */
   for (int c = 0; c < 3; c++) memset(e->coef[c], 0, sizeof(int16_t) * (size_t)(c ? e->cw * e->ch / 4 : e->cw * e->ch));
   if (e->is_intra) encode_intra_picture(e); else encode_inter_picture(e);
   roi_resolve(e);
@@ -1262,20 +1398,40 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
   }
   e->rc_bytes[e->frame_idx & 7] = (uint32_t)e->au.len;
   e->frame_idx++;
-  {                                                     /* refs[0] now holds the picture just coded, refs[k] the one k pictures before it */
-    orc_pic *t = e->refs[e->nref - 1];
-    for (int k = e->nref - 1; k > 0; k--) e->refs[k] = e->refs[k - 1];
-    e->refs[0] = e->cur; e->cur = t;
+  {                                                     /* hist[0] now holds the picture just coded, hist[j] the one j pictures before it */
+    orc_pic *t = e->hist[e->nkeep - 1];
+    for (int k = e->nkeep - 1; k > 0; k--) e->hist[k] = e->hist[k - 1];
+    e->hist[0] = e->cur; e->cur = t;
   }
   if (e->cfg.me_source) {                               /* the next picture's search looks at this input picture (and its references at the ones before) */
-    pixel *t = e->prev_src[e->nref - 1];
+    pixel *t = e->prev_src[e->nkeep - 1];
     if (!t) t = (pixel *)malloc((size_t)e->cw * e->ch);
-    for (int k = e->nref - 1; k > 0; k--) e->prev_src[k] = e->prev_src[k - 1];
+    for (int k = e->nkeep - 1; k > 0; k--) e->prev_src[k] = e->prev_src[k - 1];
     e->prev_src[0] = t;
     memcpy(t, e->src[0], (size_t)e->cw * e->ch);
   }
+  if (e->me_coarse) {                                   /* ... and its coarse stage at this input picture's quarter picture (an IDR picture's too) */
+    pixel *t = e->qprev[e->nkeep - 1];
+    if (!t) t = (pixel *)malloc((size_t)e->cw * e->ch / 16);
+    for (int k = e->nkeep - 1; k > 0; k--) e->qprev[k] = e->qprev[k - 1];
+    e->qprev[0] = t;
+    quarter_picture(e, e->src[0], t);
+  }
   *au = e->au.buf;
   return e->au.len;
+}
+
+/* the pictures kept behind the current one: lp-refs of them, or -- lp-gop reaching for a key picture (g > 1, more than one reference) -- ORC_MAX_REF_DIST */
+static int ring_resize(orc_encoder *e)
+{
+  const int keep = gop_on(e) && e->gop_g > 1 && e->nref > 1 ? ORC_MAX_REF_DIST : e->nref;
+  for (int i = 1 + e->nkeep; i < 1 + keep; i++) if (orc_pic_alloc(&e->pics[i], e->cw, e->ch)) return 0;
+  for (int i = 1 + keep; i < 1 + e->nkeep; i++) orc_pic_free(&e->pics[i]);
+  e->nkeep = keep;
+  e->cur = &e->pics[0];
+  for (int k = 0; k < keep; k++) e->hist[k] = &e->pics[1 + k];
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) e->refs[k] = e->hist[k < keep ? k : 0];
+  return 1;
 }
 
 int orc_enc_set_option(orc_encoder *e, const char *name, int value)
@@ -1303,11 +1459,8 @@ int orc_enc_set_option(orc_encoder *e, const char *name, int value)
   if (!strcmp(name, "lp-refs")) {                      /* (before the first picture: the ring, the SPS's sets, the PPS's default count) */
     if (value < 0 || value > ORC_MAX_LP_REFS || e->frame_idx > 0) return 0;
     const int n = value > 1 ? value : 1;
-    for (int i = 1 + e->nref; i < 1 + n; i++) if (orc_pic_alloc(&e->pics[i], e->cw, e->ch)) return 0;
-    for (int i = 1 + n; i < 1 + e->nref; i++) orc_pic_free(&e->pics[i]);
     e->cfg.lp_refs = value; e->nref = n;
-    e->cur = &e->pics[0];
-    for (int k = 0; k < n; k++) e->refs[k] = &e->pics[1 + k];
+    if (!ring_resize(e)) return 0;
     orc_sps *s = &e->sps;
     s->max_dec_pic_buffering = n + 1;                    /* sps / vps_max_dec_pic_buffering_minus1 = n */
     s->num_st_rps = n;                                   /* set i: the pictures -1 .. -(i + 1), all used by the current picture */
@@ -1319,6 +1472,14 @@ int orc_enc_set_option(orc_encoder *e, const char *name, int value)
     e->pps.num_ref_idx_l0_default = n;
     return 1;
   }
+  /* lp-gop: the gop string's g and d first ("lp-gop-g" >= 0, 0 = no string; "lp-gop-d" 1 .. 6: more layers are refused, as the library does), then the switch */
+  if (!strcmp(name, "lp-gop-g")) { if (value < 0 || e->frame_idx > 0) return 0; e->gop_g = value; return ring_resize(e); }
+  if (!strcmp(name, "lp-gop-d")) { if (value < 1 || value > 6 || e->frame_idx > 0) return 0; e->gop_d = value; return 1; }
+  if (!strcmp(name, "lp-gop")) {
+    if (value < 0 || value > 1 || e->frame_idx > 0 || (value && e->gop_g >= 1 && (e->gop_d < 1 || e->gop_d > 6))) return 0;
+    e->lp_gop = value; return ring_resize(e);
+  }
+  if (!strcmp(name, "me-coarse")) { if ((value != 0 && value != 64 && value != 128 && value != 256) || e->frame_idx > 0) return 0; e->me_coarse = value; return 1; }
   if (!strcmp(name, "tmvp")) { if (value < 0 || value > 1 || e->frame_idx > 0) return 0; e->cfg.tmvp = value; e->sps.temporal_mvp_enabled = value; return 1; }
   if (!strcmp(name, "rdoq")) { e->cfg.rdoq = value != 0; return 1; }
   if (!strcmp(name, "signhide")) { e->cfg.signhide = value != 0; e->pps.sign_data_hiding = e->cfg.signhide; return 1; }
@@ -1331,18 +1492,24 @@ void orc_enc_get_debug(orc_encoder *e, orc_enc_debug *d)
   d->coded_w = e->cw; d->coded_h = e->ch; d->is_intra = e->is_intra; d->poc = e->poc;
   d->cu_log2 = e->cu_log2; d->cu_intra = e->cu_intra; d->cu_flags = e->cu_flags; d->cu_merge_idx = e->cu_merge_idx;
   d->cu_mvp_idx = e->cu_mvp_idx; d->cu_intra_mode = e->cu_intra_mode; d->cu_cbf = e->cu_cbf; d->cu_mv = e->cu_mv;
-  for (int i = 0; i < 3; i++) { d->coef[i] = e->coef[i]; d->predeblock[i] = e->predeblock[i]; d->recon[i] = e->refs[0]->plane[i]; }
+  for (int i = 0; i < 3; i++) { d->coef[i] = e->coef[i]; d->predeblock[i] = e->predeblock[i]; d->recon[i] = e->hist[0]->plane[i]; }
   d->bs_v = e->bs_v; d->bs_h = e->bs_h; d->bins = e->bins;
 }
 
 const uint8_t *orc_enc_debug_cu_ref(orc_encoder *e) { return e->cu_ref; }
 const int16_t *orc_enc_debug_cu_mvd(orc_encoder *e) { return e->cu_mvd; }
+void orc_enc_debug_gop(orc_encoder *e, int out[8])
+{
+  out[0] = gop_on(e); out[1] = e->layer; out[2] = e->qp; out[3] = e->is_intra ? 0 : e->nact;
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) out[4 + k] = !e->is_intra && k < e->nact ? e->dist[k] : 0;
+}
+const int16_t *orc_enc_debug_centres(orc_encoder *e) { return e->me_coarse && !e->is_intra ? e->centres : NULL; }
 
 void orc_enc_get_recon(orc_encoder *e, pixel *y, pixel *u, pixel *v)
 {
   pixel *out[3] = { y, u, v };
   for (int c = 0; c < 3; c++) {
     int w = c ? e->cfg.width / 2 : e->cfg.width, h = c ? e->cfg.height / 2 : e->cfg.height;
-    for (int yy = 0; yy < h; yy++) memcpy(out[c] + (size_t)yy * w, e->refs[0]->plane[c] + (size_t)yy * e->refs[0]->stride[c], (size_t)w);
+    for (int yy = 0; yy < h; yy++) memcpy(out[c] + (size_t)yy * w, e->hist[0]->plane[c] + (size_t)yy * e->hist[0]->stride[c], (size_t)w);
   }
 }

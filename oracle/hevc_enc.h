@@ -11,7 +11,9 @@
  *   CTU 64, CUs 32/16 (inter, 2Nx2N) and 32/16/8 (intra, 2Nx2N), TU = CU (chroma half),
  *   integer-sample full-search motion estimation over +-range, 1 reference (previous picture) or with "lp-refs" n = 2..4 the
  *   n previous pictures ("uvgx multi-reference v1"), merge/skip with 5 candidates, AMVP, TMVP off
- *   or with "tmvp" 1 the previous picture as the collocated one, plain dead-zone quantiser, deblocking on,
+ *   or with "tmvp" 1 the previous picture as the collocated one, with "me-coarse" 64 / 128 / 256 a coarse stage on quarter
+ *   pictures and a second search window around its centre ("uvgx coarse-to-fine search v1", section 9c), with "lp-gop" QP layers and key-picture
+ *   references ("uvgx low-delay GOP v1", section 9d), plain dead-zone quantiser, deblocking on,
  *   SAO off, sign hiding off, transform skip off, WPP on, one slice per picture,
  *   IDR every `period` pictures with VPS/SPS/PPS, constant QP or picture-level rate control (bitrate > 0).
  * Test infrastructure. */
@@ -99,7 +101,9 @@ typedef struct {
 
 void orc_enc_default_config(orc_enc_config *c);
 /* options added after the packed open calls ran out of bits: by name, before the first picture.  "hash" 0/1/2, "rdoq" 0/1, "signhide" 0/1, "intra-in-p" 0/1,
- * "lp-refs" 0..4, "tmvp" 0/1.  Returns 1 when known (0 also for a value out of range). */
+ * "lp-refs" 0..4, "tmvp" 0/1, "me-coarse" 0/64/128/256, "lp-gop-g" >= 0 and "lp-gop-d" 1..6 (the numbers of gop=lp-g<g>d<d>t1; g 0 = no string) followed by
+ * "lp-gop" 0/1 (without a g the switch has nothing to say).  "lp-refs", "tmvp", "me-coarse" and the three of lp-gop are refused after the first picture.
+ * Returns 1 when known (0 also for a value out of range). */
 int orc_enc_set_option(orc_encoder *e, const char *name, int value);
 orc_encoder *orc_enc_open(const orc_enc_config *c);
 void orc_enc_close(orc_encoder *e);
@@ -115,6 +119,11 @@ void orc_enc_get_debug(orc_encoder *e, orc_enc_debug *dbg);
  * difference of an AMVP-coded CU (0 where merged) */
 const uint8_t *orc_enc_debug_cu_ref(orc_encoder *e);
 const int16_t *orc_enc_debug_cu_mvd(orc_encoder *e);
+/* per picture, beside orc_enc_debug likewise.  lp-gop: out = { option in effect, QP layer (0: IDR picture or off), the picture's QP, active references m,
+ * the POC distances of references 0 .. 3 (0 beyond m) }.  me-coarse: the coarse stage's centres of the P picture just coded, [4 references][32x32 block,
+ * raster][x, y] in full samples (references >= m hold zeros); NULL for an intra picture or without the option */
+void orc_enc_debug_gop(orc_encoder *e, int out[8]);
+const int16_t *orc_enc_debug_centres(orc_encoder *e);
 /* copy cropped reconstruction (width x height I420, packed) */
 void orc_enc_get_recon(orc_encoder *e, pixel *y, pixel *u, pixel *v);
 

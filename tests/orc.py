@@ -28,6 +28,9 @@ def lib():
         for f in (L.orc_enc_debug_cu_ref, L.orc_enc_debug_cu_mvd):
             f.restype = C.c_void_p
             f.argtypes = [C.c_void_p]
+        L.orc_enc_debug_centres.restype = C.c_void_p
+        L.orc_enc_debug_centres.argtypes = [C.c_void_p]
+        L.orc_enc_debug_gop.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_enc_get_recon.argtypes = [C.c_void_p] * 4
         L.orc_dec_open.restype = C.c_void_p
         L.orc_dec_close.argtypes = [C.c_void_p]
@@ -86,10 +89,17 @@ class OracleEncoder:
         self.buf = np.empty(w * h * 3 + (1 << 20), dtype=np.uint8)
 
     def set_option(self, name, value):
-        """options by name (oracle/hevc_enc.h orc_enc_set_option): "hash" 0 none / 1 checksum / 2 md5, ..., "lp-refs" 0..4, "tmvp" 0 / 1"""
+        """options by name (oracle/hevc_enc.h orc_enc_set_option): "hash" 0 none / 1 checksum / 2 md5, ..., "lp-refs" 0..4, "tmvp" 0 / 1, "me-coarse" 0 / 64 / 128 / 256,
+        "lp-gop-g", "lp-gop-d" and then "lp-gop" 0 / 1 (set_lp_gop)"""
         lib().orc_enc_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         if not lib().orc_enc_set_option(self.p, name.encode(), int(value)):
             raise ValueError("oracle encoder: unknown option %s" % name)
+
+    def set_lp_gop(self, g, d, on=1):
+        """gop=lp-g<g>d<d>t1 with lp-gop=<on>"""
+        self.set_option("lp-gop-g", g)
+        self.set_option("lp-gop-d", d)
+        self.set_option("lp-gop", on)
 
     def set_roi(self, rw, rh, deltas):
         """delta-QP map (kvz_picture.roi): rw x rh int8 cells over the picture; rw = 0 removes it"""
@@ -117,6 +127,12 @@ class OracleEncoder:
         # (arrays of their own beside the struct: its layout stays what older bindings allocate)
         out["cu_ref"] = _arr(lib().orc_enc_debug_cu_ref(self.p), b8, np.uint8)
         out["cu_mvd"] = _arr(lib().orc_enc_debug_cu_mvd(self.p), b8 + (2,), np.int16)
+        g = (C.c_int * 8)()
+        lib().orc_enc_debug_gop(self.p, g)
+        out["lp_gop"] = {"active": g[0], "layer": g[1], "qp": g[2], "dists": [int(v) for v in g[4:4 + g[3]]]}
+        cen = lib().orc_enc_debug_centres(self.p)
+        if cen:
+            out["me_coarse"] = _arr(cen, (4, ch // 32, cw // 32, 2), np.int16)
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             out["coef%d" % c] = _arr(d.coef[c], shp, np.int16)

@@ -2,7 +2,8 @@
 
 The feature is held to four things: every stream's structure, read from the stream alone, is the one tests/lp_gop_model.py states; the integer search equals
 tests/lp_refs_model.search() handed the model's reference planes and the picture's QP; every reconstruction equals what the checker's decoder, the library's
-HIP decoder and (a subset) tests/pyhevc.py make of the stream; and the gop string without the switch, or the switch without the string, changes nothing."""
+HIP decoder and (a subset) tests/pyhevc.py make of the stream; and the gop string without the switch, or the switch without the string, changes nothing.  The checker's encoder states
+the option itself (oracle/hevc_enc.c "lp-gop"); tests/test_gpu_coarse_gop_oracle.py holds the HIP encoder to it bit for bit."""
 import numpy as np
 import pytest
 

@@ -28,6 +28,10 @@ def _checker(w, h, c):
         oe.set_option("rc-delay", owf + 1)            # the controller books picture t - (pictures in flight + 1), as encoder.hip does
     oe.set_option("lp-refs", c["n"])
     oe.set_option("tmvp", c.get("tmvp", 0))
+    if c.get("coarse"):                               # "me-coarse"  and "lp-gop" with the gop string's g, d (section 9d): tests/test_gpu_coarse_gop_oracle.py
+        oe.set_option("me-coarse", c["coarse"])
+    if c.get("gop"):
+        oe.set_lp_gop(*c["gop"])
     for name, key in (("intra-in-p", "intra_in_p"), ("rdoq", "rdoq"), ("signhide", "signhide"), ("me-source", "me_source"), ("hash", "hash"),
                       ("scaling-list", "scaling_list"), ("lossless", "lossless")):     # (lossless last: it switches tools off)
         if c.get(key):
@@ -48,6 +52,7 @@ def _hip(w, h, c):
         ("lp-refs", c["n"]), ("tmvp", c.get("tmvp", 0)))
     o += ((("vaq", c["vaq"]),) if c.get("vaq") else ()) + ((("bitrate", br),) if br else ()) + ((("rc-algorithm", "lambda"),) if c.get("rc_lambda") else ())
     o += ((("scaling-list", "default"),) if c.get("scaling_list") else ()) + ((("lossless", 1),) if c.get("lossless") else ())
+    o += ((("me-coarse", c["coarse"]),) if c.get("coarse") else ()) + ((("gop", "lp-g%dd%dt1" % tuple(c["gop"])), ("lp-gop", 1)) if c.get("gop") else ())
     fields = dict(({"target_bitrate": br} if br else {}), **({"hash": c["hash"]} if c.get("hash") else {}))
     ge = Encoder(w, h, options=o, fields=fields or None)
     assert not ge.rejected, ge.rejected
@@ -58,6 +63,17 @@ def _first_stage(do, dg):
     """the first stage at which the checker's picture (do) and the HIP encoder's (dg) differ, in the order the encoder decides them"""
     inter = (do["cu_intra"] == 0)
     intra = ~inter
+    m = do.get("m")                                     # active references of the picture (run_case)
+    if "me_coarse" in do and "me_coarse" in dg:         # the coarse stage's centres of the active references (the library's array keeps what an earlier picture left beyond them)
+        a, b = np.asarray(do["me_coarse"])[:m], np.asarray(dg["me_coarse"])[:m]
+        bad = np.argwhere((a != b).any(axis=-1))
+        if len(bad):
+            i = tuple(bad[0])
+            return "first stage that differs: me_coarse (centres) at %d blocks, first (reference, block row, column) %s: checker %s, HIP %s" % (len(bad), list(i), a[i], b[i])
+    if "lp_gop" in do and "lp_gop" in dg:
+        for k in ("layer", "qp", "dists"):              # the layer and the QP, then the reference distances
+            if do["lp_gop"][k] != dg["lp_gop"][k]:
+                return "first stage that differs: lp_gop %s: checker %s, HIP %s" % (k, do["lp_gop"][k], dg["lp_gop"][k])
     order = [("cu_log2", None), ("cu_intra", None), ("cu_intra_mode", intra), ("cu_ref", inter), ("cu_mv", inter), ("cu_flags", inter),
              ("cu_merge_idx", inter), ("cu_mvp_idx", inter), ("cu_mvd", inter), ("cu_cbf", None), ("coef0", None), ("coef1", None), ("coef2", None),
              ("predeblock0", None), ("predeblock1", None), ("predeblock2", None), ("bs_v", None), ("bs_h", None), ("rec0", None), ("rec1", None), ("rec2", None)]
@@ -88,10 +104,17 @@ def _frames(c):
     if c.get("clip") == "pan":
         from test_gpu_tmvp import _pan
         return _pan(w, h, nf)
+    if c.get("pan"):                                   # a global pan of (vx, vy) samples a picture (tests/pan_content.py)
+        import pan_content
+        return pan_content.clip(w, h, nf, *c["pan"])
+    if c.get("clip") == "blink":                       # a background that is covered for four pictures and shown again (tests/occluder_content.py)
+        import occluder_content
+        return occluder_content.blink_clip(w, h, nf, kind=c.get("kind", 0))
     return [orc.synth_frame(c.get("kind", 0), c.get("seed", SEED), w, h, t) for t in range(nf)]
 
 
-def run_case(c):
+def run_case(c, check=None):
+    """check(want): conditions on the checker's pictures [(access unit, debug arrays)] alone -- that the case exercises its subject -- before the HIP encoder runs"""
     from kvazzup_amd.codec import Decoder
     w, h, owf = c["w"], c["h"], c.get("owf", 0)
     frames = _frames(c)
@@ -105,8 +128,11 @@ def run_case(c):
         au = oe.encode(f)
         d = oe.debug()
         d["recon"] = oe.recon()
+        d["m"] = 0 if d["is_intra"] else min(max(c["n"], 1), d["poc"])
         want.append((au, d))
     oe.close()
+    if check:
+        check(want)
     ge = _hip(w, h, c)
     gd = Decoder()
     try:
@@ -123,7 +149,7 @@ def run_case(c):
             if au is None:
                 continue
             au_o, d = want[t]
-            what = "picture %d (%s, m = %d)" % (t, "I" if d["is_intra"] else "P", 0 if d["is_intra"] else min(max(c["n"], 1), d["poc"]))
+            what = "picture %d (%s, m = %d)" % (t, "I" if d["is_intra"] else "P", d["m"])
             if au != au_o or not np.array_equal(rec, d["recon"]):
                 pytest.fail("%s: access unit %d vs %d bytes (checker / HIP), equal=%s, reconstruction equal=%s; %s" % (
                     what, len(au_o), len(au), au == au_o, np.array_equal(rec, d["recon"]), _first_stage(d, _hip_debug(ge))))

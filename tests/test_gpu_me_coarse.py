@@ -1,7 +1,7 @@
 """GPU: "uvgx coarse-to-fine search v1" (kvazaar.h me-coarse) -- a coarse search on quarter-resolution input pictures gives every 32x32
 block and reference a centre, and k_me searches a second window around it.
 
-T1: absent and with me-coarse=0 the encoder writes what the checker writes (the checker does not know the option: it stands for the encoder of before).
+T1: absent and with me-coarse=0 the encoder writes what the checker writes (the checker opened without the option: it stands for the encoder of before; with the option it states the feature itself, tests/test_gpu_coarse_gop_oracle.py).
 T2: cu_log2 / cu_mv / cu_ref and the centres equal the numpy statement tests/me_coarse_model.py, every P picture.
 T3: closed loop -- every reconstruction is what the checker's decoder and the HIP decoder make of the stream -- over the tool set, with vectors that leave the picture.
 T4: what it buys on the pan clip; T5: through the filter chain; T6: band mode refuses it."""

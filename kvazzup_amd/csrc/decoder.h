@@ -1,6 +1,10 @@
 // kvazzup_amd/csrc/decoder.h -- host engine of the HIP decoder behind libOpenHevc*
 // (/root/reference/src/media/processing/openhevcfilter.cpp:36-56,145-146,195-199).
 //
+// Three translation units share this class: dec_syntax.{h,hip} turns header bits into plain structs (parameter sets, slice header parts; knows no Decoder),
+// dec_parse.hip is the slice-data parser (parse_job / parse_substream), decoder.hip is everything between them -- NAL dispatch, picture assembly, reference
+// management, the job ring, buffers, launches, output.
+//
 // Division of labour: the host parses NAL units and runs CABAC decoding (bit-serial, one substream per CTU row or tile),
 // which yields per-4x4 records (motion, edges, QpY), the transform blocks in decoding order and their non-zero levels
 // (dec_frame.h); those go to the GPU in one copy and the GPU does everything that touches samples: motion compensation,
@@ -34,6 +38,7 @@
 #include <thread>
 #include <vector>
 #include "hevc_core.h"
+#include "dec_syntax.h"
 #include "host_pool.h"
 #include "dec_frame.h"
 #include "dec_kernels.h"
@@ -42,44 +47,8 @@
 namespace kvzx {
 
 // DK_HOST_PARSE is not a kernel: wall time of the host CABAC parsing stage
+enum { PM_INTER = 0, PM_INTRA = 1, PM_SKIP = 2, PM_NONE = 255 };      // PicJob::pred_mode
 enum DecKernelId { DK_INTER = 0, DK_INTRA, DK_DEBLOCK, DK_HOST_PARSE, DK_SAO, DK_INTRA_P, DK_COUNT };      // (DK_INTRA_P: the intra blocks of a picture that also has inter blocks)
-
-// short-term reference picture set (7.4.8): negative deltas first (closest first), then positive ones
-struct StRps { int n_neg = 0, n_pos = 0; int dpoc[16]; uint8_t used[16]; };
-
-struct DecSps {
-  bool valid = false;
-  int width = 0, height = 0;          // coded size
-  int crop_r = 0, crop_b = 0, crop_l = 0, crop_t = 0;   // luma samples
-  int log2_max_poc_lsb = 8;
-  int num_st_rps = 0; StRps st_rps[65];
-  uint32_t fps_num = 0, fps_den = 0;
-  int num_reorder = 0;                // sps_max_num_reorder_pics of the highest sub-layer: pictures that may precede a picture in decoding order and follow it in output order
-  int strong_intra = 0, sao = 0, tmvp = 0, amp = 0, th_depth_inter = 0, th_depth_intra = 0;
-  int ctb_log2 = 6;                   // CtbLog2SizeY: 6 (every Kvazaar stream), 5 or 4 (round 6: other encoders' streams); transform blocks 4 .. min(32, CTB)
-  int min_cb_log2 = 3;                // MinCbLog2SizeY: 3 (every Kvazaar stream), 4 or 5
-  int num_lt_sps = -1; uint16_t lt_lsb_sps[32] = {}; uint8_t lt_used_sps[32] = {};      // long_term_ref_pics_present_flag (-1: not set): the SPS's candidates
-  int pcm_depth[2] = {0, 0}, pcm_min_log2 = 0, pcm_max_log2 = 0, pcm_no_filter = 0;      // pcm_enabled_flag: PcmBitDepthY / C (0: no PCM), Log2MinIpcmCbSizeY .. Log2MaxIpcmCbSizeY, pcm_loop_filter_disabled_flag
-  // scaling_list_enabled_flag: the scaling factors (dec_frame.h KVZ_SCALING_BYTES) of the SPS's lists -- the default ones (Tables 7-5 / 7-6) without
-  // sps_scaling_list_data; NULL: flat.  What uvgComm's "scaling list" checkbox switches on in a peer's Kvazaar (kvazaarfilter.cpp:235-242).
-  std::shared_ptr<const std::vector<uint8_t>> scaling;
-};
-struct DecPps {
-  bool valid = false;
-  int sps_id = 0;
-  int sign_hiding = 0, cabac_init_present = 0, num_ref_idx_default = 1, num_ref_idx1_default = 1, init_qp = 26, tskip = 0;
-  int dependent_slices = 0;
-  int cu_qp_delta = 0, qp_delta_depth = 0, cb_qp_offset = 0, cr_qp_offset = 0, slice_chroma_offsets = 0;
-  int weighted_pred = 0, weighted_bipred = 0, lists_mod = 0;
-  int output_flag_present = 0, extra_header_bits = 0, header_extension = 0;
-  int wpp = 0, tile_rows = 1, row_bd[34];   // tile row i covers CTB rows [row_bd[i], row_bd[i + 1]); filled at slice time when uniform
-  int tile_cols = 1, col_bd[34];            // tile column j covers CTB columns [col_bd[j], col_bd[j + 1])
-  int uniform_tiles = 1, row_height[33], col_width[33];
-  int deblock_control = 0, deblock_override = 0, deblock_disabled = 0, beta_offset_div2 = 0, tc_offset_div2 = 0, loop_filter_across_slices = 1, across_tiles = 1, cip = 0;
-  int par_mrg_level = 2;
-  int tq_bypass = 0;                                   // transquant_bypass_enabled_flag (a peer's Kvazaar with `lossless`, kvazaarfilter.cpp:244)
-  std::shared_ptr<const std::vector<uint8_t>> scaling; // pps_scaling_list_data: these factors instead of the SPS's
-};
 
 struct DecodedPicture {
   int width = 0, height = 0;          // cropped
@@ -168,7 +137,7 @@ class Decoder {
   void flush() {}
   int pending() const { return (int)(job_head_ - job_tail_) + (gpu_job_ ? 1 : 0) + (int)gpu_q_.size(); }
 
-  // ---- per-picture state shared with the slice-data parser (decoder.hip)
+  // ---- per-picture state shared with the slice-data parser (dec_parse.hip)
   // one per substream.  Two cache lines each: the rows of a picture are parsed side by side, every one appending to ITS vectors all the time -- the
   // vectors' headers of neighbouring rows do not share a cache line.  (What limits the row-parallel parse is WPP itself: a unit can start when its left neighbour
   // and the unit above-right are done, and a picture takes as long as the heaviest path through that graph.  The benchmark's moving objects are a few very heavy
@@ -176,17 +145,6 @@ class Decoder {
   // at best with any number of threads, tools/measure/wpp_critical_path.py, profiles/r06_wpp_critical_path.txt; seventeen rows end 55 us apart, owf0_timeline.py.)
   struct alignas(128) SubOut { std::vector<uint32_t> levels; std::vector<DecTu> tus; int rc = 0; };
   struct alignas(64) Progress { std::atomic<int> v{0}; char pad[60]; };   // one cache line per row: no false sharing between pollers
-  struct SliceHdr {
-    bool is_intra = false, is_b = false; int poc = 0;
-    bool no_output = false;                                              // pic_output_flag = 0: decoded and kept as a reference, never handed out
-    int num_ref_idx1 = 0, mvd_l1_zero = 0, collocated_from_l0 = 1;      // B slices: num_ref_idx_l1_active, mvd_l1_zero_flag, collocated_from_l0_flag
-    int tmvp = 0, collocated_ref_idx = 0, sao_luma = 0, sao_chroma = 0, num_ref_idx = 1, cabac_init_flag = 0, max_merge = 5;
-    int slice_qp = 26, cb_qp_offset = 0, cr_qp_offset = 0;      // offsets: PPS + slice
-    int deblock_disabled = 0, beta_offset_div2 = 0, tc_offset_div2 = 0;
-    uint8_t list_mod[2] = {0, 0}, list_entry[2][16] = {};      // ref_pic_lists_modification() (7.3.6.2): entries of the temporary lists (8.3.4)
-    bool weighted = false; uint8_t wt_log2[2] = {0, 0}; DecWt wt[32] = {};
-    uint32_t wt_explicit = 0;                                        // bit list * 16 + index: the entry's weights or offsets differ from the defaults (with the defaults the explicit formulas ARE the default ones)      // pred_weight_table() (7.3.6.3) as derived by 7.4.7.3: entry list * 16 + index
-  };
   // everything one picture needs between its slice header and its reconstruction
   struct PicJob {
     std::vector<uint8_t> rbsp; size_t data_off = 0, data_len = 0;
@@ -270,6 +228,7 @@ class Decoder {
   bool ensure_buffers(int w, int h, int ctb_log2);
   void free_buffers();
   int decode_slice(const uint8_t *rbsp, size_t len, int nal_type, int64_t pts);
+  size_t unescape(const uint8_t *data, size_t len); int decode_parameter_set(int nal_type, BitReader &r);
   int hash_sei(const uint8_t *rbsp, size_t len);
   int verify_hash(const PicJob &job, const std::vector<uint8_t> &want);
   bool check_hash_ = false; int hash_checked_ = 0, hash_mismatch_ = 0;
@@ -278,15 +237,22 @@ class Decoder {
   int close_open_picture();
   int close_free_picture(PicJob &job);
   void take_back_job(PicJob &job);
-  // the slice segments of the picture being assembled, as they arrived (one tile): kept beside the row bookkeeping of Kvazaar's forms, which is dropped the moment a
-  // segment turns up that those forms do not have (asm_free_) -- the picture is then put together from this list when the access unit ends
+  // ---- a picture arriving in several slice segment NAL units: its job is filled segment by segment and submitted with the last one.  Everything that is known
+  // about the picture being assembled lives in ONE value, reset by assignment when a picture is opened (open_job).
+  // FreeSeg: the slice segments as they arrived (one tile), kept beside the row bookkeeping of Kvazaar's forms, which is dropped the moment a segment turns up
+  // that those forms do not have (OpenPicture::free) -- the picture is then put together from this list when the access unit ends.
+  // LfSlice: in-loop filtering across slice and tile boundaries -- the picture's independent slices (first coding tree block, slice_loop_filter_across_
+  // slices_enabled_flag) in every form a picture's slices come in; note_lf_restrictions turns them (and the PPS's tile flag) into PicJob::lf_restricted / the map
+  // the parser's last step writes for the kernels (DecFrame::ctu_nb)
   struct FreeSeg { int address; bool dependent; int slice_qp; std::vector<size_t> subs; };
-  std::vector<FreeSeg> asm_segs_; bool asm_free_ = false, free_stream_ = false; bool asm_cur_dependent_ = false; int asm_cur_qp_ = 26;
-  // in-loop filtering across slice and tile boundaries: the independent slices of the picture being assembled -- first coding tree block, slice_loop_filter_across_
-  // slices_enabled_flag -- in every form a picture's slices come in; build_lf_map turns them (and the PPS's tile flag) into PicJob::lf_restricted / the map the
-  // parser's last step writes for the kernels (DecFrame::ctu_nb)
   struct LfSlice { int address; bool across; };
-  std::vector<LfSlice> asm_lf_;
+  struct OpenPicture {
+    bool active = false, guessed_one_row = false, free = false, irap = false;
+    int subs = 0, rows = 0, pps_id = 0, nal_type = 0;      // progress in substreams (tile columns) / CTB rows; what a further segment must match
+    bool cur_dependent = false; int cur_qp = 26;           // the segment at hand: dependent?  SliceQpY of its slice
+    std::vector<FreeSeg> segs; std::vector<LfSlice> lf;
+  } asm_;
+  bool free_stream_ = false;                               // per STREAM: its pictures come in free slices (append_segment)
   void note_lf_restrictions(PicJob &job);
   int finish_oldest();
   void drop_pending();
@@ -317,11 +283,16 @@ class Decoder {
   std::shared_ptr<const DecSps> sps_[16]; DecPps pps_[64]; uint32_t vps_fps_num_ = 0, vps_fps_den_ = 0;
   int w_ = 0, h_ = 0, pw_ = 0, ph_ = 0; int ctbl_ = 6;      // ctbl_: CtbLog2SizeY of the active sequence (the padded size stays a multiple of 64: the kernels that tile the picture do so in 64x64 / 32x32 pieces whatever the CTB)
   std::vector<PicJob> jobs_; int frame_threads_ = 1; long job_head_ = 0, job_tail_ = 0;
-  // a picture arriving in several slice segment NAL units: its job is filled segment by segment and submitted with the last one
-  bool asm_active_ = false, asm_guessed_one_row_ = false; int asm_subs_ = 0, asm_rows_ = 0, asm_pps_id_ = 0, asm_nal_type_ = 0; bool asm_irap_ = false;
   int submit_job(PicJob &job, int nal_type, bool irap);
-  int append_segment_tiles(PicJob &job, size_t bitpos, const uint8_t *rbsp, size_t len, const DecPps &p, const DecPps &pp, int wc, int hc, int address);
-  int append_segment(PicJob &job, size_t bitpos, const uint8_t *rbsp, size_t len, const DecPps &p, const DecPps &pp, int wc, int hc, int address, int64_t pts);
+  int submit_closed(PicJob &job, int rc);                  // close_open_picture: submit, keep the error for last_error, stash a picture that came out
+  // decode_slice's steps (decoder.hip), in the order of 7.3.6.1 / 8.1.3 / 8.3.2; SliceCtx: what they hand on to each other
+  struct SliceCtx;
+  bool slice_front(SliceCtx &c, int &rc);
+  void sequence_state(const SliceCtx &c);
+  int apply_rps_and_build_lists(SliceCtx &c);
+  PicJob &open_job(const SliceCtx &c, const DecPps &pp, int slot);
+  int append_segment_tiles(PicJob &job, const SliceCtx &c, int address);
+  int append_segment(PicJob &job, const SliceCtx &c, const DecPps &pp, int address);
   std::deque<OwnedPic> ready_q_; OwnedPic cur_owned_;       // pictures completed ahead of their turn (resolution change), the one last handed out
   // Output order (C.5.2): a stream whose SPS allows reordering (sps_max_num_reorder_pics > 0: B pictures in groups, Kvazaar gop=8) has its pictures
   // copied out as they are completed and handed on by POC -- the smallest of those waiting once more than the SPS's count wait, all of a coded

@@ -36,7 +36,7 @@ struct SaoParams {
 };
 
 
-// Scaling factors m[x][y] of 8.6.4.2 for the active scaling lists (7.4.5; host: decoder.hip build_scaling), one byte per coefficient, raster inside the block
+// Scaling factors m[x][y] of 8.6.4.2 for the active scaling lists (7.4.5; host: dec_syntax.hip build_scaling), one byte per coefficient, raster inside the block
 // (index = the level word's position field): [6][16] 4x4 | [6][64] 8x8 | [6][256] 16x16 | [2][1024] 32x32; matrix = 3 * inter + plane (32x32: inter)
 #define KVZ_SCALING_BYTES 4064
 KVZ_HD int scaling_offset(int log2n, int plane, int inter)

@@ -1,7 +1,7 @@
 // kvazzup_amd/csrc/host_pool.h -- a small persistent pool of host threads that hands out the
 // tasks of one job in increasing index order (task r may wait for task r-1, which is therefore
 // always already running: the CTU-row wavefront of WPP, H.265 9.3.2.2).  Used by the host halves
-// of entropy coding (entropy_host.h) and entropy decoding (decoder.hip).
+// of entropy coding (entropy_host.h) and entropy decoding (dec_parse.hip).
 #pragma once
 #include <atomic>
 #include <emmintrin.h>

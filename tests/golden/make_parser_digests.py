@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tests/golden/make_parser_digests.py -- digests of what the PRODUCT's slice-data parser (csrc/decoder.hip, host half of the decoder) produces for the
+"""tests/golden/make_parser_digests.py -- digests of what the PRODUCT's slice-data parser (csrc/dec_parse.hip behind dec_syntax.hip / decoder.hip, host half of the decoder) produces for the
 committed golden streams and for streams the checker's encoder writes here: per stream {pictures, transform blocks, level words, FNV-1a digest of every
 picture's records / tables / blocks / levels}.  Written with a library whose parser had just passed the whole GPU suite against the checker's decoder
 (round 5: the parser before its registers moved into locals); tests/test_parser_probe.py (CPU) then pins every later parser to the same output.

@@ -1,8 +1,10 @@
 """The decoder's host half alone (include/kvazzup_amd.h kvzx_decoder_set_parse_only): helper shared by tests/test_parser_probe.py and
 tests/golden/make_parser_digests.py.  No device is touched; nothing is decoded."""
 import ctypes as C
+import hashlib
 import json
 import os
+import random
 
 import orc
 
@@ -77,3 +79,68 @@ def all_cases():
     yield from golden_cases()
     for n, *_ in ENCODED:
         yield n, encoded_case(n)
+
+
+# ---- hostile input: tools/fuzz_parser.py's mutations, and what the parser ANSWERS to them (tests/test_parser_hostile_trace.py)
+def mutate(rng, nals):
+    out = [bytearray(n) for n in nals]
+    for _ in range(rng.choice((1, 1, 1, 2, 3, 6))):
+        kind = rng.random()
+        i = rng.randrange(len(out))
+        n = out[i]
+        hdr = 6                                                    # start code + NAL header
+        if kind < 0.35 and len(n) > hdr:                           # bit flips, anywhere behind the NAL header (the first bytes twice as often)
+            for _ in range(rng.choice((1, 1, 2, 4, 16))):
+                p = rng.randrange(hdr, len(n)) if rng.random() < 0.5 else rng.randrange(hdr, min(len(n), hdr + 24))
+                n[p] ^= 1 << rng.randrange(8)
+        elif kind < 0.5 and len(n) > hdr + 1:                      # a run overwritten
+            p = rng.randrange(hdr, len(n)); k = min(len(n) - p, rng.choice((1, 2, 4, 8, 64)))
+            n[p:p + k] = bytes(rng.randrange(256) for _ in range(k)) if rng.random() < 0.7 else bytes([rng.choice((0, 0xff))]) * k
+        elif kind < 0.65 and len(n) > hdr + 1:                     # truncation
+            del n[rng.randrange(hdr, len(n)):]
+        elif kind < 0.72:                                          # insertion
+            p = rng.randrange(hdr, len(n) + 1); n[p:p] = bytes(rng.randrange(256) for _ in range(rng.choice((1, 2, 3, 8))))
+        elif kind < 0.8 and len(out) > 1:                          # a NAL unit dropped
+            del out[i]
+        elif kind < 0.87:                                          # ... duplicated
+            out.insert(i, bytearray(n))
+        elif kind < 0.94 and len(out) > 1:                         # ... swapped with another
+            j = rng.randrange(len(out)); out[i], out[j] = out[j], out[i]
+        elif kind < 0.97:                                          # the NAL header itself (type, layer, temporal id)
+            if len(n) > 5:
+                n[4 + rng.randrange(2)] = rng.randrange(256)
+        elif len(n) > hdr + 2:                                     # a run of zero BITS spliced into the head (parameter sets, slice headers): an Exp-Golomb field of any size, wherever it lands
+            head = min(len(n), hdr + 40)
+            bits = "".join("{:08b}".format(b) for b in n[hdr:head])
+            at = rng.randrange(len(bits))
+            bits = bits[:at] + "0" * rng.choice((8, 16, 24, 30, 31, 32, 33, 48)) + "1" + bits[at:]
+            bits += "0" * (-len(bits) % 8)
+            n[hdr:head] = bytes(int(bits[i:i + 8], 2) for i in range(0, len(bits), 8))
+    return [bytes(n) for n in out if len(n) > 4]
+
+
+def hostile_trace(trials, threads=1, first_seed=1):
+    """trials first_seed .. first_seed + trials - 1 as tools/fuzz_parser.py draws them (case, its thread choice -- drawn and dropped: `threads` holds --, mutation):
+    SHA-256 of the mutated inputs; SHA-256 of every call's (libOpenHevcDecode return value, kvzx_decoder_last_error) and the trial's first four probe statistics;
+    the count of calls that returned an error code.  The trace depends on the parse thread count (pictures of a broken stream fail at different rows): compare like with like."""
+    cases = list(all_cases())
+    lib = _lib()
+    h_in, h_out, errors = hashlib.sha256(), hashlib.sha256(), 0
+    for seed in range(first_seed, first_seed + trials):
+        rng = random.Random(seed)
+        name, nals = cases[rng.randrange(len(cases))]
+        rng.choice(["1", "4"])
+        mut = mutate(rng, nals)
+        h_in.update(repr((seed, name, mut)).encode())
+        d = lib.libOpenHevcInit(1, 2)
+        assert lib.kvzx_decoder_set_parse_only(d, threads) == 1 and lib.libOpenHevcStartDecoder(d) == 0
+        calls = []
+        for k, n in enumerate(mut):
+            rc = lib.libOpenHevcDecode(d, n, len(n), k)
+            calls.append((rc, lib.kvzx_decoder_last_error(d)))
+            errors += rc < 0
+        out = (C.c_uint64 * 5)()
+        lib.kvzx_decoder_parse_probe_stats(d, out, None)
+        lib.libOpenHevcClose(d)
+        h_out.update(repr((seed, calls, list(out)[:4])).encode())
+    return {"trials": trials, "threads": threads, "inputs_sha256": h_in.hexdigest(), "trace_sha256": h_out.hexdigest(), "error_calls": int(errors)}

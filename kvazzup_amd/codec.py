@@ -130,6 +130,9 @@ class Encoder:
         if int(self.cfg.contents.lp_gop):
             g = self.debug("lp_gop", np.int32, (8,))
             d["lp_gop"] = {"active": int(g[0]), "layer": int(g[1]), "qp": int(g[2]), "dists": [int(v) for v in g[4:4 + int(g[3])]]}
+        # weightp: the luma weights the picture's slice headers carry, per reference in list 0 order -- a key of its own only with the option on
+        if int(self.cfg.contents.weightp):
+            d["wp"] = self.debug("wp", np.int32, (4, 3))
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             d["coef%d" % c] = self.debug("coef%d" % c, np.int16, shp)

@@ -23,6 +23,23 @@ void launch_tok_compact(const EncFrame &f, hipStream_t st); // k_tok_compact: co
 // rate control v2 (rc_kernels.hip; the groups of CTU rows themselves: k_inter_recon's RC form, EncFrame::rc)
 void launch_picture_begin(RcState *rc, uint32_t bits3, int slot3, int have3, int8_t *ctu_qt, const int8_t *roi, int nctu, int qp, int vaq, hipStream_t st,
                           void *zero_a = nullptr, size_t bytes_a = 0, void *zero_b = nullptr, size_t bytes_b = 0);      // head of a picture's chain: rate control state (rc != NULL) and the per-CTU target QPs (ctu_qt != NULL) in one launch
+// "weightp" (wp_kernels.hip)
+struct WpArgs {
+  const unsigned long long *partial; int nblk;        // k_wp_stats' partial sums {S1, S2} of the picture, wp_stat_blocks(height) pairs
+  long long n;                                       // width * height
+  int64_t *stat;                                     // the picture's {m, v} (wp_moments), kept with its working set
+  const int64_t *stat_ref[KVZ_MAX_LP_REFS];          // ... and those of its references' input pictures
+  const uint8_t *in_ref[KVZ_MAX_LP_REFS];            // the references' padded input luma planes
+  int nref;                                          // 0: an intra picture -- the moments only
+  int32_t *cand; unsigned long long *acc;            // scratch: [reference][candidate, w, o] and the check's [reference][plain, weighted]
+  int32_t *rec, *rec_host;                           // the record [reference][flag, w, o]: device memory / the slot's host-mapped copy
+};
+struct WpPlaneArgs { const int32_t *rec; const uint8_t *from[KVZ_MAX_LP_REFS]; uint8_t *to[KVZ_MAX_LP_REFS]; };
+int wp_stat_blocks(int height);
+void launch_wp_stats(const uint8_t *src, int cw, int width, int height, unsigned long long *partial, hipStream_t st);
+void launch_wp_decide(const WpArgs &a, int phase, hipStream_t st);      // phase 0: moments, candidates; phase 1: the record
+void launch_wp_check(const WpArgs &a, const uint8_t *cur, int cw, int width, int height, hipStream_t st);
+void launch_wp_plane(const WpPlaneArgs &a, int nref, int cw, int ch, hipStream_t st);      // the references' search planes
 // k_cabac_rows (cabac_kernels.hip): the arithmetic coder proper on the GPU, one wave per substream
 struct CabacRowsArgs {
   const uint16_t *tok; const int32_t *count; const uint32_t *off;   // dense tokens (device): CTU i has count[i] tokens at tok + off[i]

@@ -623,14 +623,17 @@ __device__ __forceinline__ void rc_group_done(const EncFrame &f, InterLds &s, in
 // dispatched in the order of their linear index (rows top to bottom here: no XCD permutation), so every workgroup of a group is resident or done when one of
 // the next group starts to wait -- the wait cannot starve what it waits for (the intra chains' argument).
 // LL: `lossless` (cu_transquant_bypass): the residual itself goes to the level planes, sample by sample, and the reconstruction is the source
-template <bool DEC, bool FRAC, bool ADJ = false, bool RC = false, bool LL = false>
+// WP (encoder, weightp): luma of every quarter is predicted from its reference with that reference's (w, o) of the picture's record (f.wp) --
+// wp_pred14 on the 14-bit intermediate, wp_sample at integer vectors; chroma as ever.  Forms of their own, at the register budget of the fractional forms --
+// a wave less where the form of before already spills (rdoq / signhide: 4; rate control v2 with fractional vectors: 6), so that no weighted form uses scratch.
+template <bool DEC, bool FRAC, bool ADJ = false, bool RC = false, bool LL = false, bool WP = false>
 // waves per SIMD the fractional / rate-control forms are held to: 7 (72 registers, one spilled in the rate-control form) -- their 22 KB of LDS allow seven workgroups
 // per compute unit, 78 registers only six; default mode 5 450-5 530 -> 5 580-5 660 frames/s, the launch 51.3 -> 49.3 us (profiles/r06_recon_waves_ab.txt).  The forms
 // with the level-adjustment pass (ADJ: rdoq / signhide) keep 5: they spill at anything tighter.
 #ifndef KVZ_RECON_WAVES
 #define KVZ_RECON_WAVES 7
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || ADJ || RC) ? (ADJ ? 5 : KVZ_RECON_WAVES) : 8))) void k_inter_recon(EncFrame f)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || ADJ || RC || WP) ? (ADJ ? (WP ? 4 : 5) : ((WP && RC && FRAC) ? KVZ_RECON_WAVES - 1 : KVZ_RECON_WAVES)) : 8))) void k_inter_recon(EncFrame f)
 {
   __shared__ InterLds s;
   InterFracLds *fr = nullptr;
@@ -707,6 +710,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
     const int y = tid >> 3, x = (tid & 7) * 4, k = (y >> 4) * 2 + (x >> 4);
     const int l2 = split ? 4 : 5, n = 1 << l2, tu = split ? k : 0;
     uint32_t p4 = 0;
+    int wp_w = 64, wp_o = 0;
+    if constexpr (WP) { const int32_t *rec = f.wp + 3 * s.rf[k]; wp_w = rec[1]; wp_o = rec[2]; }
     if (anyfrac) {                             // (block-uniform) separable 8-tap interpolation through LDS
       const int mvx = s.mv[k][0], mvy = s.mv[k][1], xf = mvx & 3, yf = mvy & 3;
       const int *tp = &fr->ltmp[k][(y & 15) * 16 + (x & 15)];
@@ -718,9 +723,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FRAC || AD
           for (int j = 0; j < 8; j++) a += (int)kLumaFilter[yf][j] * tp[j * 16 + i];
           v = xf ? (a >> 6) : a;
         } else v = xf ? tp[3 * 16 + i] : tp[3 * 16 + i] * 64;
-        p4 |= (uint32_t)clip8((v + 32) >> 6) << (8 * i);
+        p4 |= (uint32_t)(WP ? wp_pred14(v, wp_w, wp_o) : clip8((v + 32) >> 6)) << (8 * i);
       }
-    } else p4 = mc_luma4(ref_plane(f, s.rf[k], 0), f.cw, f.ch, x0 + x, y0 + y, s.mv[k][0], s.mv[k][1]);
+    } else {
+      p4 = mc_luma4(ref_plane(f, s.rf[k], 0), f.cw, f.ch, x0 + x, y0 + y, s.mv[k][0], s.mv[k][1]);
+      if constexpr (WP) {                      // (the encoder's vectors are whole here: without subme always, with it when no quarter has a fraction)
+        uint32_t q4 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++) q4 |= (uint32_t)wp_sample((int)((p4 >> (8 * i)) & 255u), wp_w, wp_o) << (8 * i);
+        p4 = q4;
+      }
+    }
     const size_t g = (size_t)(y0 + y) * f.cw + x0 + x;
     if (!coded) *(uint32_t *)&f.rec[0][g] = p4;
     *(uint32_t *)&s.px[y * 32 + x] = p4;
@@ -2614,7 +2627,19 @@ void launch_me(const EncFrame &f, hipStream_t st)
 void launch_inter_recon(const EncFrame &f, hipStream_t st)
 {
   const dim3 grid(f.cw / 32, band_rows(f) * 2);
-  if (f.rc) {                                  // rate control v2: the groups of CTU rows inside the one launch
+  if (f.wp) {                                  // weightp: the weighted forms (never with lossless: the encoder refuses the pair)
+    const int k = (f.rc ? 4 : 0) | ((f.rdoq || f.signhide) ? 2 : 0) | (f.subme > 0 ? 1 : 0);
+    switch (k) {
+      case 7: hipLaunchKernelGGL((k_inter_recon<false, true, true, true, false, true>), grid, dim3(256), 0, st, f); break;
+      case 6: hipLaunchKernelGGL((k_inter_recon<false, false, true, true, false, true>), grid, dim3(256), 0, st, f); break;
+      case 5: hipLaunchKernelGGL((k_inter_recon<false, true, false, true, false, true>), grid, dim3(256), 0, st, f); break;
+      case 4: hipLaunchKernelGGL((k_inter_recon<false, false, false, true, false, true>), grid, dim3(256), 0, st, f); break;
+      case 3: hipLaunchKernelGGL((k_inter_recon<false, true, true, false, false, true>), grid, dim3(256), 0, st, f); break;
+      case 2: hipLaunchKernelGGL((k_inter_recon<false, false, true, false, false, true>), grid, dim3(256), 0, st, f); break;
+      case 1: hipLaunchKernelGGL((k_inter_recon<false, true, false, false, false, true>), grid, dim3(256), 0, st, f); break;
+      default: hipLaunchKernelGGL((k_inter_recon<false, false, false, false, false, true>), grid, dim3(256), 0, st, f); break;
+    }
+  } else if (f.rc) {                                  // rate control v2: the groups of CTU rows inside the one launch
     const int k = ((f.rdoq || f.signhide) ? 2 : 0) | (f.subme > 0 ? 1 : 0);
     if (k == 3) hipLaunchKernelGGL((k_inter_recon<false, true, true, true>), grid, dim3(256), 0, st, f);
     else if (k == 2) hipLaunchKernelGGL((k_inter_recon<false, false, true, true>), grid, dim3(256), 0, st, f);

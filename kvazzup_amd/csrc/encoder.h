@@ -66,6 +66,10 @@ struct EncoderConfig {
   int gop_g = 0, gop_d = 1, gop_t = 1;   // the numbers of the gop string (kvz_config.gop_len, gop_lp_ref_depth, gop_lp_temporal_layers)
   int tmvp = 0;               // kvazaar "tmvp" (DESIGN.md section 9b): temporal motion vector prediction -- merge / AMVP candidates from the previous picture's motion
                               // (collocated_ref_idx 0); changes the signalling only, never the motion chosen; not in band mode
+  int weightp = 0;            // "weightp" (extension, "uvgx weighted prediction v1"; restated in tests/wp_model.py): 1 = explicit weighted prediction of luma --
+                              // per P picture and reference a weight and an offset from the two INPUT pictures' luma statistics, kept when a check on every fourth sample says
+                              // they pay; the integer search reads weighted copies of its reference planes, k_subpel and k_inter_recon predict with the weights, the slice
+                              // headers carry pred_weight_table(); 0 = off (nothing allocated, nothing launched); not in band mode, not with lossless
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -76,6 +80,7 @@ struct EncodedPicture {
   std::vector<uint8_t> au;
   int poc = 0, qp = 0; bool is_intra = false;
   int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop, a P picture: its QP layer and its references' POC distances in list 0 order (nref 0: the option is off)
+  int32_t wp[3 * KVZ_MAX_LP_REFS] = {0, 64, 0, 0, 64, 0, 0, 64, 0, 0, 64, 0};   // weightp: the picture's record [reference][flag, w, o]
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
 };
@@ -124,6 +129,7 @@ class Encoder {
   // debug: copy an internal device array of the last coded picture to the host
   //   "cu_log2","cu_intra","cu_flags","cu_merge_idx","cu_mvp_idx","cu_intra_mode","cu_cbf" (b8 bytes),
   //   "lp_gop" (host values, 8 int32: option active, layer, QP, number of references, their four POC distances),
+  //   "wp" (weightp; host values, 12 int32: [reference][flag, w, o] as the picture's slice headers say them -- an intra picture: 0, 64, 0 throughout),
   //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
   int coded_width() const { return cw_; }
@@ -195,6 +201,13 @@ class Encoder {
   ColMv *col_[kSets] = {};                 // tmvp: the collocated record of the set's picture (EncFrame::col_out), which the next picture reads (col_prev)
   int set_ = 0, out_set_ = 0;
   int32_t out_gop_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug_copy("lp_gop") of the picture last output
+  // weightp (wp_kernels.hip): per working set the input picture's partial sums, its moments {m, v} and the picture's record; one set of scratch (candidates, the
+  // check's sums) and of search planes -- their writers and readers follow one another on one stream (the input stream; the planes without me-source: the main stream)
+  unsigned long long *wp_partial_[kSets] = {}; int64_t *wp_stat_[kSets] = {}; int32_t *wp_rec_[kSets] = {};
+  int32_t *wp_cand_ = nullptr; unsigned long long *wp_acc_ = nullptr; uint8_t *wp_plane_[KVZ_MAX_LP_REFS] = {};
+  int32_t out_wp_[3 * KVZ_MAX_LP_REFS] = {0, 64, 0, 0, 64, 0, 0, 64, 0, 0, 64, 0};   // debug_copy("wp") of the picture last output
+  bool wp_stage(const EncFrame &f, const Plan &p, const Slot &sl);   // input stream: statistics of the picture; a P picture: candidates, check, record
+  EncFrame wp_search_frame(const EncFrame &f, const Plan &p, hipStream_t st);   // the search planes of f's references built on `st`; returns f with me_ref / me_refs pointing at them
   char prio_[3] = {'h', 'n', 'n'};                      // priority levels of the main, tokenizer and input streams (stream_pool.h keys)
   std::vector<int8_t> roi_; int roi_w_ = 0, roi_h_ = 0;           // as set by the caller (set_roi)
   std::vector<int8_t> roi_sub_; int roi_sub_w_ = 0, roi_sub_h_ = 0;   // the map of the picture being submitted (it travels with the picture to the submitter thread)
@@ -239,6 +252,7 @@ class Encoder {
     uint16_t *h_tok_dense = nullptr, *d_tok_dense = nullptr; int32_t *h_tok_count = nullptr, *d_tok_count = nullptr;   // host-mapped pinned
     uint32_t *h_tok_off = nullptr, *d_tok_off = nullptr;
     uint32_t *h_err = nullptr, *d_err = nullptr;
+    int32_t *h_wp = nullptr, *d_wp = nullptr;            // weightp: the picture's record as k_wp_decide left it (host-mapped: the slice headers are written from it)
     // GPU arithmetic coder (cfg.entropy_gpu): dense tokens stay in device memory (d_tok_dense .. d_tok_off point there), the coder runs on the slot's own
     // stream -- a substream is a ~0.1-1 ms serial chain, so several pictures' coders must be able to run side by side
     uint16_t *g_tok = nullptr; int32_t *g_count = nullptr; uint32_t *g_off = nullptr;

@@ -64,6 +64,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   }
   if (cfg.me_coarse != 0 && cfg.me_coarse != 64 && cfg.me_coarse != 128 && cfg.me_coarse != 256) { if (error) *error = "me-coarse must be 0, 64, 128 or 256"; return false; }
   if (cfg.me_coarse && cfg.band_rows > 0) { if (error) *error = "me-coarse is not available in band mode (the halo exchange carries a few rows)"; return false; }
+  if (cfg.weightp && cfg.band_rows > 0) { if (error) *error = "weightp is not available in band mode (a band's encoder sees a part of the picture, the weights are the whole picture's)"; return false; }
+  if (cfg.weightp && cfg.lossless) { if (error) *error = "weightp is not available with lossless"; return false; }
 
   const char *prio = getenv("KVAZZUP_AMD_PRIO"); if (!prio || strlen(prio) < 4) prio = "hnnn";   // main, tokenizer, input, decoder: the chain the next picture waits for is the urgent one (+6 % at 1080p; any explicit priority also gives the stream a hardware queue of its own)
 
@@ -128,7 +130,16 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
       HIP_OK(hipMalloc(&mc_q_[k], npx / 16)); HIP_OK(hipMemset(mc_q_[k], 0, npx / 16));
       HIP_OK(hipMalloc(&mc_centres_[k], (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t))); HIP_OK(hipMemset(mc_centres_[k], 0, (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t)));
     }
+    if (cfg.weightp) {
+      HIP_OK(hipMalloc(&wp_partial_[k], (size_t)wp_stat_blocks(cfg.height) * 2 * sizeof(unsigned long long)));
+      HIP_OK(hipMalloc(&wp_stat_[k], 2 * sizeof(int64_t))); HIP_OK(hipMemset(wp_stat_[k], 0, 2 * sizeof(int64_t)));
+      HIP_OK(hipMalloc(&wp_rec_[k], 3 * KVZ_MAX_LP_REFS * sizeof(int32_t))); HIP_OK(hipMemset(wp_rec_[k], 0, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t)));
+    }
     HIP_OK(hipEventCreateWithFlags(&ev_tok_done_[k], kDeviceEvent));
+  }
+  if (cfg.weightp) {
+    HIP_OK(hipMalloc(&wp_cand_, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t))); HIP_OK(hipMalloc(&wp_acc_, 2 * KVZ_MAX_LP_REFS * sizeof(unsigned long long)));
+    for (int r = 0; r < cfg.lp_refs; r++) HIP_OK(hipMalloc(&wp_plane_[r], npx));
   }
   if (cfg.qp_in_cu) {
     const size_t nctu = (size_t)(cw_ / 64) * rows_;
@@ -215,6 +226,11 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     }
     HIP_OK(hipHostMalloc(&sl.h_err, sizeof(uint32_t), hipHostMallocMapped)); *sl.h_err = 0;
     HIP_OK(hipHostGetDevicePointer(&dp, sl.h_err, 0)); sl.d_err = (uint32_t *)dp;
+    if (cfg.weightp) {
+      HIP_OK(hipHostMalloc(&sl.h_wp, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t), hipHostMallocMapped));
+      for (int r = 0; r < KVZ_MAX_LP_REFS; r++) { sl.h_wp[3 * r] = 0; sl.h_wp[3 * r + 1] = 64; sl.h_wp[3 * r + 2] = 0; }
+      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_wp, 0)); sl.d_wp = (int32_t *)dp;
+    }
     HIP_OK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&sl.rec_done, hipEventDisableTiming));
   }
@@ -276,6 +292,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   sp_.cw = cw_; sp_.ch = ch_; sp_.width = cfg.width; sp_.height = cfg.height; sp_.qp = cfg.qp; sp_.wpp = cfg.wpp; sp_.tile_rows = cfg.tile_rows; sp_.tile_cols = cfg.tile_cols; sp_.qp_in_cu = cfg.qp_in_cu; sp_.sao = cfg.sao; sp_.slices = cfg.slices; sp_.signhide = cfg.signhide; sp_.scaling_list = cfg.scaling_list; sp_.tq_bypass = cfg.lossless;
   sp_.lp_refs = cfg.lp_refs > 1 ? cfg.lp_refs : 0;
   sp_.tmvp = cfg.tmvp;
+  sp_.weightp = cfg.weightp;
   sp_.deblock = cfg.deblock; sp_.fps_num = cfg.fps_num; sp_.fps_den = cfg.fps_den;
   HIP_OK(hipStreamSynchronize(stream_));
   HIP_OK(hipDeviceSynchronize());
@@ -311,6 +328,7 @@ Encoder::~Encoder()
     if (sl.h_tok_dense) hipHostFree(sl.h_tok_dense);
     if (sl.h_tok_count) hipHostFree(sl.h_tok_count);
     if (sl.h_err) hipHostFree(sl.h_err);
+    if (sl.h_wp) hipHostFree(sl.h_wp);
     if (sl.h_tok_off) hipHostFree(sl.h_tok_off);
     stream_release(sl.ent_stream, cfg_.device, 'E', 'l');
     if (sl.tok_ev) hipEventDestroy(sl.tok_ev);
@@ -327,6 +345,8 @@ Encoder::~Encoder()
   hipFree(vaq_act_); hipFree(vaq_sum_); hipFree(rc_state_);
   for (int k = 0; k < kSets; k++) { hipFree(ctu_qt_[k]); hipFree(ctu_qy_[k]); hipFree(ctu_delta_[k]); hipFree(ctu_first_[k]); if (h_ctu_qt_[k]) hipHostFree(h_ctu_qt_[k]); hipFree(ctu_roi_[k]); }
   for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (mc_q_[k]) hipFree(mc_q_[k]); if (mc_centres_[k]) hipFree(mc_centres_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
+  for (int k = 0; k < kSets; k++) { hipFree(wp_partial_[k]); hipFree(wp_stat_[k]); hipFree(wp_rec_[k]); }
+  hipFree(wp_cand_); hipFree(wp_acc_); for (int r = 0; r < KVZ_MAX_LP_REFS; r++) hipFree(wp_plane_[r]);
   for (int c = 0; c < 3; c++) { hipFree(work_[c]); hipFree(work_idr_[c]); }
   hipFree(sync_idr_); hipFree(edge_col_idr_); hipFree(edge_row_); hipFree(edge_row_idr_);
   for (int k = 0; k < kSets; k++) hipFree(sao_[k]);
@@ -660,6 +680,7 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
     const int nr = f.cu_ref ? f.nref : 1;
     for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - (r < nr ? p.dist[r] : 1)) % kSets];
   }
+  if (wp_rec_[k] && !p.intra) f.wp = wp_rec_[k];       // weightp: the record k_wp_decide writes on the input stream, in front of everything that reads it
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
   if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
   f.tok_dense = sl.d_tok_dense; f.tok_count_out = sl.d_tok_count; f.tok_off_out = sl.d_tok_off; f.err_out = sl.d_err; f.ent_cursors = sl.g_cursors;
@@ -698,6 +719,9 @@ bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i42
   if (in_ring >= 0) { HIP_CHECK(hipEventRecord(ev_pad_[in_ring], stream_in_)); pad_pending_[in_ring] = true; }
   // me-coarse: every picture's quarter picture (an intra picture's is searched by the P picture behind it)
   if (f.mc_rq) launch_luma_quarter(src_[set_][0], f.mc_q, cw_, ch_, stream_in_);      // (no kernel id of its own: the profile's keys are the default encoder's)
+  // weightp: every picture's luma statistics (an intra picture's are its successors' reference's), and a P picture's weights -- from input pictures alone,
+  // whatever me-source says, like the coarse stage below
+  if (cfg_.weightp && !wp_stage(f, p, *cur_slot_)) return false;
   // The tokenizer of the set's previous picture must be done with the set's CU arrays before this picture writes them: the INPUT stream waits for it (the
   // event is long past when it gets there), so that the main stream's one wait for in_done_ says both -- a wait of its own in front of every picture's chain
   // cost the chain a barrier packet, a few microseconds with nothing running.
@@ -713,7 +737,8 @@ bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i42
     // "uvgx search pipelining v1": the search needs the two input pictures only, the pricing of its expensive quarters as intra blocks the search and the source --
     // both run HERE, on the input stream, beside what the main stream still has of the pictures in front (k_me 31-34 us and k_intra_analyse<P> 19-24 us at
     // 1080p leave the chain the next picture waits for; the head of the chain, when there is one, is a launch of its own on the main stream)
-    timed(K_ME, stream_in_, [&] { launch_me(f, stream_in_); });
+    const EncFrame fs = f.wp ? wp_search_frame(f, p, stream_in_) : f;      // weightp: the search reads the references' weighted planes
+    timed(K_ME, stream_in_, [&] { launch_me(fs, stream_in_); });
     if (cfg_.intra_in_p) timed(K_INTRA_ANALYSE_P, stream_in_, [&] { launch_intra_analyse(f, stream_in_); });
   }
   if (!stage_roi(stream_in_)) return false;
@@ -732,7 +757,7 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
   if (p.intra) {
     timed(K_INTRA_RECON, ms, [&] { launch_intra_recon(f, ms); });
   } else {
-    if (!p.ahead) timed(K_ME, stream_, [&] { launch_me(fm, stream_); });
+    if (!p.ahead) { const EncFrame fs = f.wp ? wp_search_frame(fm, p, stream_) : fm; timed(K_ME, stream_, [&] { launch_me(fs, stream_); }); }      // (weightp: the planes are made of reconstructions here, so on this stream)
     // intra-in-P: quarters whose inter cost is high are priced as intra blocks and may become intra units (the launch leaves at once where none is)
     if (cfg_.intra_in_p && !p.ahead) timed(K_INTRA_ANALYSE_P, stream_, [&] { launch_intra_analyse(f, stream_); });
     if (cfg_.subme > 0) timed(K_SUBPEL, stream_, [&] { launch_subpel(p.ahead ? fm : f, stream_); });
@@ -759,6 +784,40 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
   HIP_CHECK(hipEventRecord(ev_src_free_[set_], ms)); src_busy_[set_] = true;
   if (p.side) { HIP_CHECK(hipEventRecord(ev_idr_done_, ms)); idr_pending_ = true; }
   return true;
+}
+
+// weightp, the input stream: the picture's statistics; a P picture: candidate weights against every reference's input picture (the set it was padded into, as
+// me-source's planes), the check, and the record -- into the set's device copy and the slot's host-mapped one.  Nothing waits for the host.
+bool Encoder::wp_stage(const EncFrame &f, const Plan &p, const Slot &sl)
+{
+  const int k = set_;
+  launch_wp_stats(src_[k][0], cw_, cfg_.width, cfg_.height, wp_partial_[k], stream_in_);
+  WpArgs a{};
+  a.partial = wp_partial_[k]; a.nblk = wp_stat_blocks(cfg_.height); a.n = (long long)cfg_.width * cfg_.height; a.stat = wp_stat_[k];
+  a.nref = p.intra ? 0 : (f.cu_ref ? f.nref : 1);
+  for (int r = 0; r < a.nref; r++) { const int ks = (k + kSets - p.dist[r]) % kSets; a.stat_ref[r] = wp_stat_[ks]; a.in_ref[r] = src_[ks][0]; }
+  a.cand = wp_cand_; a.acc = wp_acc_; a.rec = wp_rec_[k]; a.rec_host = sl.d_wp;
+  launch_wp_decide(a, 0, stream_in_);
+  if (p.intra) return true;
+  launch_wp_check(a, src_[k][0], cw_, cfg_.width, cfg_.height, stream_in_);
+  launch_wp_decide(a, 1, stream_in_);
+  return true;
+}
+
+// weightp: the planes the integer search reads -- the plane it would have read of every reference (f.me_ref / f.me_refs: reconstruction or, me-source, input
+// picture) through wp_sample with the reference's (w, o), a copy where the reference is not weighted
+EncFrame Encoder::wp_search_frame(const EncFrame &f, const Plan &p, hipStream_t st)
+{
+  (void)p;
+  EncFrame fs = f;
+  const int nref = f.cu_ref ? f.nref : 1;
+  WpPlaneArgs a{};
+  a.rec = f.wp;
+  for (int r = 0; r < nref; r++) { a.from[r] = f.cu_ref ? f.me_refs[r] : f.me_ref; a.to[r] = wp_plane_[r]; }
+  launch_wp_plane(a, nref, cw_, ch_, st);
+  fs.me_ref = wp_plane_[0];
+  if (f.cu_ref) for (int r = 0; r < KVZ_MAX_LP_REFS; r++) fs.me_refs[r] = wp_plane_[r < nref ? r : 0];
+  return fs;
 }
 
 // the picture handed on: tokenizer, GPU arithmetic coder, copy of the reconstruction into the caller's picture, the slot to the workers
@@ -871,6 +930,7 @@ bool Encoder::collect(EncodedPicture *out)
   } else ok = finish_slot(sl, out);
   out_idx_ = sl.rec_idx; out_set_ = sl.set;
   out_gop_[0] = gop_on(); out_gop_[1] = out->layer; out_gop_[2] = out->qp; out_gop_[3] = out->nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out_gop_[4 + r] = out->dist[r];
+  memcpy(out_wp_, out->wp, sizeof(out_wp_));
   rc_bytes_[(collected_ - 1) & 7] = (uint32_t)out->au.size();   // (collected_ - 1 = index of this picture)
   return ok;
 }
@@ -942,8 +1002,14 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
   out->valid = true; out->poc = sl.poc; out->qp = sl.qp; out->is_intra = sl.intra; out->bins = bins;
   out->layer = sl.layer; out->nref = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out->dist[r] = sl.dist[r];
   PicRefs pr; pr.n = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
+  PicWeights pw{};                                         // weightp: the record k_wp_decide left in the slot (final long before the tokens are)
+  for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
+    const bool on = cfg_.weightp && !sl.intra && sl.h_wp[3 * r] != 0;
+    pw.flag[r] = on ? 1 : 0; pw.w[r] = (int16_t)(on ? sl.h_wp[3 * r + 1] : 64); pw.o[r] = (int16_t)(on ? sl.h_wp[3 * r + 2] : 0);
+    out->wp[3 * r] = pw.flag[r]; out->wp[3 * r + 1] = pw.w[r]; out->wp[3 * r + 2] = pw.o[r];
+  }
   bool assembled;
-  { Tick tk; assembled = assemble_access_unit(out->au, sp_, sl.intra, sl.poc, sl.write_ps, rows_out, nsub, sl.qp - cfg_.qp, sl.nref ? &pr : nullptr); const double a = tk.ms(); std::lock_guard<std::mutex> l(stat_m_); t_asm_ += a; }
+  { Tick tk; assembled = assemble_access_unit(out->au, sp_, sl.intra, sl.poc, sl.write_ps, rows_out, nsub, sl.qp - cfg_.qp, sl.nref ? &pr : nullptr, cfg_.weightp ? &pw : nullptr); const double a = tk.ms(); std::lock_guard<std::mutex> l(stat_m_); t_asm_ += a; }
   if (!assembled) { fprintf(stderr, "kvazzup_amd: %d substreams do not fit the tile grid\n", nsub); out->valid = false; return false; }
   out->recon_delivered = false;
   if (sl.has_sink) {                                       // the reconstruction's copy into the caller's picture: queued at submission, long done by now
@@ -1129,6 +1195,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   static const char *names[7] = {"cu_log2", "cu_intra", "cu_flags", "cu_merge_idx", "cu_mvp_idx", "cu_intra_mode", "cu_cbf"};
   for (int i = 0; i < 7; i++) if (w == names[i]) { src = cu_bytes_[out_set_] + i * nb8; have = nb8; }
   if (w == "lp_gop") { if (bytes > sizeof(out_gop_)) return false; memcpy(dst, out_gop_, bytes); return true; }      // (host values: no copy from the device)
+  if (w == "wp") { if (!cfg_.weightp || bytes > sizeof(out_wp_)) return false; memcpy(dst, out_wp_, bytes); return true; }      // (host values, as the slice headers said them)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
   if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }

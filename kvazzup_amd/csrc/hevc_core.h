@@ -149,7 +149,46 @@ struct EncFrame {
   uint8_t *mc_q;
   const uint8_t *mc_qrefs[KVZ_MAX_LP_REFS];
   int16_t *mc_centres;
+  // "weightp" (NULL: off, and a P picture's kernels run the forms of before): the picture's record [reference][flag, w, o] in device memory,
+  // written by k_wp_decide on the input stream.  k_subpel and k_inter_recon predict luma from reference k as wp_pred14(.., w, o); me_ref / me_refs then point at
+  // the references' search planes (k_wp_plane), which k_me reads as it reads any reference
+  const int32_t *wp;
 };
+
+// ---------------------------------------------------------------------------------------------
+// "uvgx weighted prediction v1" (weightp; restated in tests/wp_model.py).  All integer.
+// ---------------------------------------------------------------------------------------------
+// floor(sqrt(v))
+KVZ_HD uint32_t wp_isqrt(uint64_t v)
+{
+  uint64_t r = 0, bit = (uint64_t)1 << 62;
+  while (bit > v) bit >>= 2;
+  while (bit) { if (v >= r + bit) { v -= r + bit; r = (r >> 1) + bit; } else r >>= 1; bit >>= 2; }
+  return (uint32_t)r;
+}
+// mean and variance of n samples with sum s1 and sum of squares s2, in units of 1 / 256 and 1 / 65536 (n <= 2^28 samples of 8 bits: everything stays below 2^53).
+// The rounding of m can take 256 q - m^2 a little below zero on a nearly flat picture: the variance is then 0
+KVZ_HD void wp_moments(uint64_t s1, uint64_t s2, uint64_t n, int64_t *m, int64_t *v)
+{
+  const int64_t mm = (int64_t)((256 * s1 + n / 2) / n), q = (int64_t)((256 * s2 + n / 2) / n), vv = 256 * q - mm * mm;
+  *m = mm; *v = vv < 0 ? 0 : vv;
+}
+// candidate weight and offset of a picture (m_c, v_c) against a reference (m_r, v_r); returns whether the pair is worth the check
+KVZ_HD bool wp_candidate(int64_t m_c, int64_t v_c, int64_t m_r, int64_t v_r, int *w, int *o)
+{
+  int ww = 64;
+  if (v_c != 0 && v_r != 0) ww = clip3(16, 127, (int)((wp_isqrt((uint64_t)(16384 * v_c) / (uint64_t)v_r) + 1) >> 1));
+  const int64_t t = (64 * m_c - ww * m_r + 8192) >> 14;
+  const int oo = t < -128 ? -128 : (t > 127 ? 127 : (int)t);
+  *w = ww; *o = oo;
+  return iabs(ww - 64) >= 2 || oo != 0;
+}
+// the check's verdict from the two sums over the samples at (4i, 4j)
+KVZ_HD bool wp_accept(bool candidate, uint64_t plain, uint64_t wt) { return candidate && 16 * wt < 15 * plain; }
+// a full sample of a weighted reference (the search plane; = wp_pred14(64 s, w, o))
+KVZ_HD int wp_sample(int s, int w, int o) { return clip8(((s * w + 32) >> 6) + o); }
+// 8.5.3.3.4.3 with luma_log2_weight_denom 6 on the 14-bit intermediate sample
+KVZ_HD int wp_pred14(int p, int w, int o) { return clip8(((p * w + 2048) >> 12) + o); }
 
 // the reference planes of ref_idx k (one reference: ref[])
 KVZ_HD const uint8_t *ref_plane(const EncFrame &f, int k, int c) { return f.cu_ref ? f.refs[k][c] : f.ref[c]; }

@@ -38,12 +38,15 @@ struct StreamParams {
   int slices = 0;           // kvazaar slices: 1 = "wpp", a dependent slice segment per CTU row (dependent_slice_segments_enabled_flag); 2 = "tiles", a slice per tile
   int lp_refs = 0;          // "lp-refs" n >= 2: n short-term RPS sets (set i: pictures -1 .. -(i + 1)), n references by default, DPB of n + 1 pictures; 0 / 1: one reference
   int tmvp = 0;             // sps_temporal_mvp_enabled_flag; the slices: slice_temporal_mvp_enabled_flag (slice_tmvp), collocated_ref_idx 0
+  int weightp = 0;          // "weightp" (DESIGN.md section 9e): PPS weighted_pred_flag; every independent P slice segment header carries pred_weight_table() (PicWeights)
 };
 
 // "lp-gop" (DESIGN.md section 9d): the references of one P picture -- n of them, dist[k] pictures back, by increasing distance (dist[0] = 1).  A slice header
 // given one writes the picture's reference picture set itself (short_term_ref_pic_set_sps_flag 0), all entries used by the current picture, and n active
 // references; the parameter sets are the ones of lp-refs
 struct PicRefs { int n; int8_t dist[4]; };
+// "weightp": the luma weights of one P picture's references, list 0 order -- flag[k] 0: reference k is predicted from as ever (w 64, o 0)
+struct PicWeights { int8_t flag[4]; int16_t w[4], o[4]; };
 
 // pictures the DPB holds beside the current one: sps/vps_max_dec_pic_buffering_minus1
 inline int dpb_minus1(const StreamParams &s) { return s.lp_refs > 1 ? s.lp_refs : 1; }
@@ -119,7 +122,7 @@ inline void write_pps(BitWriter &w, const StreamParams &s)
   w.bit(0); w.bit(0); w.bit(s.qp_in_cu != 0);                    // constrained intra, transform skip, cu_qp_delta
   if (s.qp_in_cu) w.ue(0);                                       // diff_cu_qp_delta_depth
   w.se(0); w.se(0); w.bit(0);
-  w.bit(0); w.bit(0); w.bit(s.tq_bypass != 0);                  // weighted_pred, weighted_bipred, transquant_bypass_enabled
+  w.bit(s.weightp != 0); w.bit(0); w.bit(s.tq_bypass != 0);     // weighted_pred, weighted_bipred, transquant_bypass_enabled
   w.bit(s.tile_rows > 1 || s.tile_cols > 1); w.bit(s.wpp);       // tiles, entropy_coding_sync
   if (s.tile_rows > 1 || s.tile_cols > 1) { w.ue((uint32_t)s.tile_cols - 1); w.ue((uint32_t)s.tile_rows - 1); w.bit(1); w.bit(1); }   // columns - 1, rows - 1, uniform spacing, loop filter across tiles
   w.bit(1);                                                      // loop filter across slices
@@ -150,7 +153,7 @@ inline size_t escaped_size(const uint8_t *p, size_t n)
 // slice segment header (7.3.6.1).  address < 0: the picture's first segment; else slice_segment_address of a further one, `dependent`
 // = a dependent slice segment (nothing but the address and the entry points)
 inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, int poc, const std::vector<uint32_t> &entry_sizes, int slice_qp_delta = 0,
-                               int address = -1, bool dependent = false, const PicRefs *refs = nullptr)
+                               int address = -1, bool dependent = false, const PicRefs *refs = nullptr, const PicWeights *wt = nullptr)
 {
   w.bit(address < 0);
   if (idr) w.bit(0);
@@ -179,6 +182,12 @@ inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, in
       const int ndef = dpb_minus1(s);
       w.bit(nact != ndef); if (nact != ndef) w.ue((uint32_t)nact - 1);   // num_ref_idx_active_override_flag (fewer pictures since the IDR picture than lp-refs)
       if (slice_tmvp(s, idr, poc) && nact > 1) w.ue(0);             // collocated_ref_idx: the previous picture (P slice: collocated_from_l0_flag inferred 1)
+      if (s.weightp) {                                             // pred_weight_table() (7.3.6.3): denominators 6, chroma never weighted
+        w.ue(6); w.se(0);                                          // luma_log2_weight_denom, delta_chroma_log2_weight_denom
+        for (int k = 0; k < nact; k++) w.bit(wt && wt->flag[k]);   // luma_weight_l0_flag
+        for (int k = 0; k < nact; k++) w.bit(0);                   // chroma_weight_l0_flag
+        for (int k = 0; k < nact; k++) if (wt && wt->flag[k]) { w.se(wt->w[k] - 64); w.se(wt->o[k]); }      // delta_luma_weight_l0, luma_offset_l0
+      }
       w.ue(0);                                                     // five_minus_max_num_merge_cand
     }
     w.se(slice_qp_delta);                                          // against the PPS init_qp (= the configured QP)
@@ -220,7 +229,8 @@ inline void append_nal(std::vector<uint8_t> &out, int nal_type, const uint8_t *r
 // One access unit: [VPS SPS PPS] + slice NAL whose data are the `nsub` substreams (CTU rows with
 // WPP, otherwise one) rows[r].  false (and an empty access unit): the substream count does not fit the tiling.
 inline bool assemble_access_unit(std::vector<uint8_t> &au, const StreamParams &sp, bool idr, int poc, bool write_ps,
-                                 const std::vector<std::vector<uint8_t>> &rows, int nsub, int slice_qp_delta = 0, const PicRefs *refs = nullptr)
+                                 const std::vector<std::vector<uint8_t>> &rows, int nsub, int slice_qp_delta = 0, const PicRefs *refs = nullptr,
+                                 const PicWeights *wt = nullptr)
 {
   au.clear();
   if (write_ps) {
@@ -247,7 +257,7 @@ inline bool assemble_access_unit(std::vector<uint8_t> &au, const StreamParams &s
     std::vector<uint32_t> entry;
     for (int r = 0; r + 1 < n; r++) entry.push_back((uint32_t)escaped_size(rows[(size_t)(s0 + r)].data(), rows[(size_t)(s0 + r)].size()));
     BitWriter sh;
-    write_slice_header(sh, sp, idr, poc, entry, slice_qp_delta, addr, sp.slices == 1 && s0 > 0, refs);
+    write_slice_header(sh, sp, idr, poc, entry, slice_qp_delta, addr, sp.slices == 1 && s0 > 0, refs, wt);
     for (int r = 0; r < n; r++) sh.bytes(rows[(size_t)(s0 + r)].data(), rows[(size_t)(s0 + r)].size());
     append_nal(au, idr ? 19 : 1, sh.data().data(), sh.data().size());
     s0 += n;

@@ -112,7 +112,9 @@ __device__ __forceinline__ void hplane(const uint8_t *win, int16_t *hp, int mvx,
   }
 }
 // SATD between the quadrant's source samples (s4: this lane's four) and its prediction from plane hp with vertical component mvy
-__device__ __forceinline__ uint32_t price(const int16_t *hp, uint32_t s4, int mvy, int iy, int lane, const Filters &F, kv_f16x4 hm)
+// WP (weightp): the prediction is the reference's weighted one, wp_pred14 of the 14-bit intermediate with the (w, o) in wo = w | o << 16
+template <bool WP>
+__device__ __forceinline__ uint32_t price(const int16_t *hp, uint32_t s4, int mvy, int iy, int lane, const Filters &F, kv_f16x4 hm, int wo = 0)
 {
   const int yf = mvy & 3, oy = (mvy >> 2) - iy + 1, g = lane >> 4, c = lane & 15;
   const uint32_t flo = pick(F, yf, 0), fhi = pick(F, yf, 1);
@@ -125,7 +127,7 @@ __device__ __forceinline__ uint32_t price(const int16_t *hp, uint32_t s4, int mv
   }
   int d[4];
 #pragma unroll
-  for (int r = 0; r < 4; r++) d[r] = (int)((s4 >> (8 * r)) & 255u) - clip8(((v[r] >> 6) + 32) >> 6);
+  for (int r = 0; r < 4; r++) d[r] = (int)((s4 >> (8 * r)) & 255u) - (WP ? wp_pred14(v[r] >> 6, wo & 0xffff, wo >> 16) : clip8(((v[r] >> 6) + 32) >> 6));
   return tile_satd(d, hm);
 }
 
@@ -153,6 +155,9 @@ __device__ __forceinline__ bool allowed(const EncFrame &f, int x0, int y0, int n
 // two, part 1 the third).  Within a wave the four candidates are priced in one unrolled block, so that their dependent chains
 // (LDS reads, multiply-adds, conversions, the two matrix products) interleave: a wave alone on its SIMD has nothing else to
 // cover latencies with.
+// WP (weightp): the candidates are priced on the weighted prediction from the quadrant's reference; a form of its own, so that the
+// launches without the option run the code of before.
+template <bool WP>
 __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
 {
   __shared__ SubpelLds s;
@@ -173,6 +178,8 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
   const int bq = b8idx(f, X, Y);
   const int mvx0 = f.cu_mv[bq * 2], mvy0 = f.cu_mv[bq * 2 + 1], ix = mvx0 >> 2, iy = mvy0 >> 2;    // integer vector (multiples of 4)
   const uint8_t *rp = ref_plane(f, cu_ref_at(f, bq), 0);   // lp-refs: the reference the search chose (the refinement never changes it)
+  int wo = 0;
+  if constexpr (WP) { const int32_t *rec = f.wp + 3 * cu_ref_at(f, bq); wo = (int)(((uint32_t)rec[1] & 0xffffu) | ((uint32_t)rec[2] << 16)); }
   const int ux = split ? X : x0, uy = split ? Y : y0, un = split ? 16 : 32;                          // the coding unit the quadrant belongs to
   int ty0 = 0, ty1 = f.ch;
   if (f.tile_rows > 1) {
@@ -226,18 +233,18 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
     if (ncand) {
       if (part == 0) {
         uint32_t v[5];
-        v[0] = step == 0 ? price(s.hp[w][1], s4, cy, iy, lane, F, hm) : 0u;
-        v[1] = price(s.hp[w][0], s4, cy, iy, lane, F, hm);                       // (-1, 0)
-        v[2] = price(s.hp[w][2], s4, cy, iy, lane, F, hm);                       // (+1, 0)
-        v[3] = price(s.hp[w][1], s4, cy - scale, iy, lane, F, hm);               // (0, -1)
-        v[4] = price(s.hp[w][1], s4, cy + scale, iy, lane, F, hm);               // (0, +1)
+        v[0] = step == 0 ? price<WP>(s.hp[w][1], s4, cy, iy, lane, F, hm, wo) : 0u;
+        v[1] = price<WP>(s.hp[w][0], s4, cy, iy, lane, F, hm, wo);                       // (-1, 0)
+        v[2] = price<WP>(s.hp[w][2], s4, cy, iy, lane, F, hm, wo);                       // (+1, 0)
+        v[3] = price<WP>(s.hp[w][1], s4, cy - scale, iy, lane, F, hm, wo);               // (0, -1)
+        v[4] = price<WP>(s.hp[w][1], s4, cy + scale, iy, lane, F, hm, wo);               // (0, +1)
         if (lane < 5 && (lane || step == 0)) s.satd[w][lane] = lane == 0 ? v[0] : (lane == 1 ? v[1] : (lane == 2 ? v[2] : (lane == 3 ? v[3] : v[4])));
       } else if (ncand == 8) {
         uint32_t v[4];
-        v[0] = price(s.hp[w][0], s4, cy - scale, iy, lane, F, hm);               // (-1, -1)
-        v[1] = price(s.hp[w][2], s4, cy - scale, iy, lane, F, hm);               // (+1, -1)
-        v[2] = price(s.hp[w][0], s4, cy + scale, iy, lane, F, hm);               // (-1, +1)
-        v[3] = price(s.hp[w][2], s4, cy + scale, iy, lane, F, hm);               // (+1, +1)
+        v[0] = price<WP>(s.hp[w][0], s4, cy - scale, iy, lane, F, hm, wo);               // (-1, -1)
+        v[1] = price<WP>(s.hp[w][2], s4, cy - scale, iy, lane, F, hm, wo);               // (+1, -1)
+        v[2] = price<WP>(s.hp[w][0], s4, cy + scale, iy, lane, F, hm, wo);               // (-1, +1)
+        v[3] = price<WP>(s.hp[w][2], s4, cy + scale, iy, lane, F, hm, wo);               // (+1, +1)
         if (lane < 4) s.satd[w][5 + lane] = lane == 0 ? v[0] : (lane == 1 ? v[1] : (lane == 2 ? v[2] : v[3]));
       }
     }
@@ -269,6 +276,10 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
   }
 }
 
-void launch_subpel(const EncFrame &f, hipStream_t st) { hipLaunchKernelGGL(k_subpel, dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f); }
+void launch_subpel(const EncFrame &f, hipStream_t st)
+{
+  if (f.wp) hipLaunchKernelGGL(k_subpel<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
+  else hipLaunchKernelGGL(k_subpel<false>, dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
+}
 
 }  // namespace kvzx

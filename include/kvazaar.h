@@ -132,6 +132,7 @@ typedef struct kvz_config {
   int32_t me_coarse;          /* "me-coarse" 0 / 64 / 128 / 256 (extension, "uvgx coarse-to-fine search v1"): reach in full samples of a coarse search on quarter-resolution INPUT pictures that gives every 32x32 block and reference a centre; the integer search then looks at its +-me-range window around zero AND, when the centre lies outside it, at a second one around the centre -- vectors of up to me-coarse + me-range samples (scrolling, window drags, pans).  0 (default, also at every preset): the window around zero alone, the encoder of before byte for byte.  Not in band mode (encoder_open fails) */
   int32_t lp_gop;             /* "lp-gop" 0 / 1 (extension, "uvgx low-delay GOP v1"; statement of record: tests/lp_gop_model.py): 1 = gop=lp-g<g>d<d>t1 takes effect -- every g-th picture after an IDR picture is a key picture coded at QP + 1, the pictures between lie on the layers QP + 2 .. QP + d (g4d3: +3, +2, +3, +1), and a P picture refers to the previous picture, the most recent key picture (at most 7 pictures back) and then the pictures before the previous one, "lp-refs" pictures in all; each picture's reference picture set travels in its slice headers, the parameter sets are those of lp-refs.  0 (default, also at every preset), or no gop string / gop=0: the streams of before byte for byte.  encoder_open fails with it in band mode, with t > 1 and with d > 6 */
   int32_t weightp;            /* "weightp" 0 / 1 (extension, "uvgx weighted prediction v1"; restated in tests/wp_model.py): 1 = explicit weighted prediction of luma (PPS weighted_pred_flag, pred_weight_table() in every independent P slice segment header, denominator 6, chroma never weighted).  Per P picture and reference a weight and an offset are derived from the luma mean and variance of the two INPUT pictures and kept when a check on every fourth sample of every fourth row says they pay (16 * weighted SAD < 15 * plain SAD); the integer search then reads weighted copies of its reference planes, and the fractional refinement and the reconstruction predict luma with the weights -- brightness steps, fades, auto-exposure.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it in band mode and with lossless */
+  int32_t intra_refresh;      /* "intra-refresh" 0 / 2..255 (extension, "uvgx intra refresh v1"; restated in tests/ir_model.py): N = the number of P pictures a refresh cycle may take.  A band of intra units (the step ceil(B / N) block columns of 32 samples, B = coded width / 32, plus 16 columns of overlap) walks across the P pictures, one step a picture, cycle after cycle from the first P picture behind an IDR picture; the 32x32 blocks the band has passed keep their vectors out of what it has not.  A decoder that concealed a lost picture has the encoder's pictures again, exactly, once a cycle that began after the loss is complete -- no IDR picture needed, so uvgComm users pass it beside "period=0" or a long period.  The first picture of a cycle carries a recovery point SEI (recovery_poc_cnt = cycle length - 1, exact_match_flag 1).  With "intra-in-p=0" the band's units are the only intra units.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it beside lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless and intra-chain=0 */
 } kvz_config;
 
 /* Picture.  y/u/v are planar 8-bit with stride == width (chroma width/2), as uvgComm assumes

@@ -133,6 +133,9 @@ class Encoder:
         # weightp: the luma weights the picture's slice headers carry, per reference in list 0 order -- a key of its own only with the option on
         if int(self.cfg.contents.weightp):
             d["wp"] = self.debug("wp", np.int32, (4, 3))
+        # intra-refresh: position in the cycle, the band's first and end column, the cycle's length -- a key of its own only with the option on
+        if int(self.cfg.contents.intra_refresh):
+            d["ir"] = [int(v) for v in self.debug("ir", np.int32, (4,))]
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             d["coef%d" % c] = self.debug("coef%d" % c, np.int16, shp)

@@ -55,7 +55,11 @@ namespace kvzx {
 // CO (me-coarse): per reference the zero window and, where k_me_coarse's centre lies outside it (me_second_window), a second window
 // around that centre through the same LDS buffer; vectors are centre + displacement, rate and admissibility those of the whole vector; the 64-bit key
 // me_fine_key(): cost << 17 | ref << 14 | window << 13 | candidate.
-template <bool MR, bool CO = false>
+// IR (intra-refresh; one reference, no coarse stage: the encoder refuses the others): a block all of whose quarters lie in the picture's
+// band is not searched -- its quarters go to k_intra_analyse<true, true> with the cost 0xffffffff, which passes the gate and beats every intra price; the block
+// whose left quarters alone are forced is searched as ever (never left early) and joins the list as well; a clean block (left of the band, position >= 1)
+// drops the candidates beyond ir_mvx_max.  A form of its own: the launches without the option run the code of before.
+template <bool MR, bool CO = false, bool IR = false>
 __global__ __launch_bounds__(256) void k_me(EncFrame f)
 {
   using Key = typename std::conditional<MR || CO, unsigned long long, uint32_t>::type;
@@ -74,6 +78,21 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
   // the block itself, and (me-early-termination) its SAD against the co-located block of the reference: a block that differs
   // from it by no more than quantisation noise is coded unsplit with the zero vector, without a search
   if (tid == 0) red[0] = 0;
+  int ir_forced = 0, ir_dx = 0x7fffffff;                               // IR: the block's forced quarters; a clean block's largest horizontal displacement in full samples
+  if constexpr (IR) {
+    ir_forced = ir_forced_quarters(x0, f.ir_s, f.ir_e);
+    if (ir_clean_block(x0, f.ir_s, f.ir_j)) ir_dx = ir_mvx_max(x0, f.ir_s) >> 2;
+    if (ir_forced == 15) {                                             // (the same for every thread, in front of the first barrier)
+      if (tid < 16) {
+        const int i = b8idx(f, x0 + (tid & 3) * 8, y0 + (tid >> 2) * 8);
+        f.cu_log2[i] = 5; f.cu_intra[i] = 0; f.cu_mv[i * 2] = 0; f.cu_mv[i * 2 + 1] = 0;
+        f.cu_mvp_idx[i] = 0;                             // mark for k_subpel: not searched
+      }
+      if (tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = 0xffffffffu;
+      if (tid == 0) f.me_cand[1 + atomicAdd(&f.me_cand[0], 1u)] = (uint32_t)((y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
+      return;
+    }
+  }
   __syncthreads();
   {
     uint32_t s0 = 0;
@@ -86,7 +105,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     if (f.me_early) { s0 = wave_sum_u32(s0); if ((tid & 63) == 0) atomicAdd(&red[0], (Key)s0); }
   }
   __syncthreads();
-  if (f.me_early && red[0] <= 64u * lam) {
+  if (f.me_early && !(IR && ir_forced) && red[0] <= 64u * lam) {
     if (tid < 16) {
       const int i = b8idx(f, x0 + (tid & 3) * 8, y0 + (tid >> 2) * 8);
       f.cu_log2[i] = 5; f.cu_intra[i] = 0; f.cu_mv[i * 2] = 0; f.cu_mv[i * 2 + 1] = 0;
@@ -185,6 +204,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
         if (dxi >= W) continue;
         { const int dx = ox + dxi - R, m = (dx & 1) ? 4 : 0; if ((tx0 > 0 && x0 + dx - m < tx0) || (tx1 < f.cw && x0 + dx + 32 + m > tx1)) continue; }
         if (f.mv_frame) { const int dx = ox + dxi - R, mx = (f.mv_frame == 2 && (dx & 1)) ? 4 : 0; if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > f.cw) continue; }
+        if constexpr (IR) { if (ox + dxi - R > ir_dx) continue; }     // a clean block stays out of what the reference has not cleaned
         const Key cand = CO ? (Key)me_fine_key(0u, rf, win, dyi * W + dxi) : ((Key)(dyi * W + dxi) | ((Key)rf << 13));
         const uint32_t rate = (lam * (uint32_t)(mvd_bits((ox + dxi - R) * 4) + ry + rbins)) >> 4;
         uint32_t sq[4];
@@ -228,12 +248,22 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     f.cu_mv[i * 2] = (int16_t)((cx + (int)(ci % W) - R) * 4);
     f.cu_mv[i * 2 + 1] = (int16_t)((cy + (int)(ci / W) - R) * 4);
     // intra-in-P: the inter cost of the block's 16x16 quarters -- what the search found for a quarter, or a quarter of the 32x32 block's cost
+    if constexpr (IR) {                                  // a forced quarter: past the gate whatever the search found; ir_free 0 (intra-in-p 0): no other quarter is priced
+      if (tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] =
+        ((ir_forced >> tid) & 1) ? 0xffffffffu : (!f.ir_free ? 0u : (split ? (uint32_t)(red[tid] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2));
+      if (tid == 0) {
+        bool any = ir_forced != 0;
+        if (f.ir_free) for (int k = 0; k < 4; k++) any |= (split ? (uint32_t)(red[k] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2) > (uint32_t)INTRA_P_GATE * lam;
+        if (any) f.me_cand[1 + atomicAdd(&f.me_cand[0], 1u)] = (uint32_t)((y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
+      }
+    } else {
     if (f.intra_p && tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = split ? (uint32_t)(red[tid] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2;
     if (f.intra_p && tid == 0) {
       // ... and the block joins the list k_intra_analyse<P> works through when a quarter is above the gate (f.me_cand: count, then block indices)
       bool any = false;
       for (int k = 0; k < 4; k++) any |= (split ? (uint32_t)(red[k] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2) > (uint32_t)INTRA_P_GATE * lam;
       if (any) f.me_cand[1 + atomicAdd(&f.me_cand[0], 1u)] = (uint32_t)((y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
+    }
     }
   }
 }
@@ -1125,7 +1155,10 @@ __device__ __forceinline__ void analyse_tile_satd(AnalyseLds &s, int wave, int t
 // PP = false: intra pictures.  PP = true ("uvgx intra-in-P v1"): launched behind k_me in a P picture; a region none of whose quarters'
 // inter cost is above the gate leaves at once (nearly all of them), the others are analysed like an intra picture's and the quarters
 // that come out cheaper as intra blocks are turned into intra units.
-template <bool PP>
+// IR (intra-refresh; with PP): the quarters k_me<.., true> sent with the cost 0xffffffff are the band's -- they pass the gate and the price
+// comparison as they stand -- and a forced unit on the band's last unit column keeps to the modes that read no above-right samples (ir_last_column), beside
+// the rules of intra-chain.  A form of its own: the launches without the option run the code of before.
+template <bool PP, bool IR = false>
 __global__ __launch_bounds__(PP ? 1024 : 256) void k_intra_analyse(EncFrame f)
 {
   // (PP: few regions get past the gate, so what counts is how long ONE of them takes, not how many fit on the chip: sixteen waves share its items)
@@ -1240,6 +1273,11 @@ __global__ __launch_bounds__(PP ? 1024 : 256) void k_intra_analyse(EncFrame f)
       const int xb = X0 + (bib % nbb) * nb_, yb = Y0 + (bib / nbb) * nb_;
       if ((yb & 63) == 0 && ((xb + nb_) & 63) == 0 && avail64(f.cw, f.chp, xb, yb, xb + nb_, yb - 1)) excl |= intra_uses_above_right(l2b, 0);      // the CTU's above-right corner block
       if ((xb & 63) == 0 && avail64(f.cw, f.chp, xb, yb, xb - 1, yb + nb_)) excl |= intra_uses_below_left(l2b, 0);                                  // a block on the CTU's left edge
+    }
+    if constexpr (IR) {
+      const int l2b = tid < 16 ? 3 : 4, nb_ = 1 << l2b, bib = tid < 16 ? tid : tid - 16, nbb = 32 >> l2b;
+      const int xb = X0 + (bib % nbb) * nb_, yb = Y0 + (bib / nbb) * nb_;
+      if (ir_last_column(xb, nb_, f.ir_e, f.cw) && avail64(f.cw, f.chp, xb, yb, xb + nb_, yb - 1)) excl |= intra_uses_above_right(l2b, 0);      // beyond the band the reference picture is not clean yet
     }
     for (int m = 0; m < 35; m++) if (!((excl >> m) & 1) && s.cost[tid][m] < bc) { bc = s.cost[tid][m]; bm = m; }
     s.bestc[tid] = bc; s.bestm[tid] = bm;
@@ -2403,7 +2441,11 @@ __device__ __forceinline__ void sao_stats_column(SaoLds &s, int c, const uint8_t
     }
 }
 
-template <bool DEC>
+// IR (encoder, intra-refresh): the coding tree blocks that hold luma column ir_e - 5 leave luma SAO off.  Deblocking the band's end against what
+// lies beyond it changes three columns left of it, and through the horizontal edges' decisions (taken per four columns) a fourth; an edge class of SAO would
+// carry that one column further.  With luma SAO off there the columns < ir_e - 4 of a picture are what a decoder that lost a picture makes of them as well.  A
+// form of its own: the launches without the option run the code of before.
+template <bool DEC, bool IR = false>
 __global__ __launch_bounds__(KVZ_SAO_THREADS) void k_sao(EncFrame f)
 {
   __shared__ SaoLds s;
@@ -2492,6 +2534,7 @@ __global__ __launch_bounds__(KVZ_SAO_THREADS) void k_sao(EncFrame f)
         const long long cost = 256LL * s.cand_dist[0][t - 1] + l2 * (2 + s.cand_bins[0][t - 1] + (t <= 4 ? 2 : 0));
         if (cost < best) { best = cost; pick[0] = t; }
       }
+      if constexpr (IR) { if (f.ir_e < f.cw && cx == ((f.ir_e - 5) >> 6)) pick[0] = 0; }
       best = l2;
       for (int t = 1; t <= 5; t++) {
         const long long cost = 256LL * ((long long)s.cand_dist[1][t - 1] + s.cand_dist[2][t - 1]) + l2 * (2 + s.cand_bins[1][t - 1] + s.cand_bins[2][t - 1] + (t <= 4 ? 2 : 0));
@@ -2622,6 +2665,7 @@ void launch_me(const EncFrame &f, hipStream_t st)
     else hipLaunchKernelGGL((k_me<false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
   }
   else if (f.cu_ref) hipLaunchKernelGGL(k_me<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // lp-refs
+  else if (f.ir_e) hipLaunchKernelGGL((k_me<false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // intra-refresh (one reference, no coarse stage)
   else hipLaunchKernelGGL(k_me<false>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
 }
 void launch_inter_recon(const EncFrame &f, hipStream_t st)
@@ -2673,6 +2717,7 @@ void launch_intra_analyse(const EncFrame &f, hipStream_t st)
   static const int per_cu = getenv("KVAZZUP_AMD_ANALYSE_PER_CU") ? atoi(getenv("KVAZZUP_AMD_ANALYSE_PER_CU")) : 4;
   const size_t pad = per_cu > 1 && per_cu < 8 && !f.analyse_alone ? (size_t)(160 * 1024 / (per_cu + 1) + 1024 - 9264) & ~(size_t)255 : 0;
   if (f.is_intra) hipLaunchKernelGGL(k_intra_analyse<false>, dim3(f.cw / 32, band_rows(f) * 2), dim3(256), pad, st, f);
+  else if (f.ir_e) hipLaunchKernelGGL((k_intra_analyse<true, true>), dim3(512), dim3(1024), 0, st, f);      // intra-refresh: the band's quarters are on the list whatever they cost
   else hipLaunchKernelGGL(k_intra_analyse<true>, dim3(512), dim3(1024), 0, st, f);       // intra-in-P, behind k_me: 512 workgroups (two per compute unit) share the candidate list, a quarter of a listed block at a time
 }
 void launch_intra_recon(const EncFrame &f, hipStream_t st)
@@ -2727,7 +2772,11 @@ void launch_vaq(const EncFrame &f, int vaq, int *act, int *sum, hipStream_t st)
   hipLaunchKernelGGL(k_vaq_stats, dim3(nctu), dim3(256), 0, st, f, act, sum);
   hipLaunchKernelGGL(k_vaq_apply, dim3((nctu + 255) / 256), dim3(256), 0, st, f, vaq, (const int *)act, (const int *)sum, nctu);
 }
-void launch_sao(const EncFrame &f, hipStream_t st) { hipLaunchKernelGGL(k_sao<false>, dim3((f.cw / 64) * (f.ch / 64)), dim3(KVZ_SAO_THREADS), 0, st, f); }
+void launch_sao(const EncFrame &f, hipStream_t st)
+{
+  if (f.ir_e) hipLaunchKernelGGL((k_sao<false, true>), dim3((f.cw / 64) * (f.ch / 64)), dim3(KVZ_SAO_THREADS), 0, st, f);      // intra-refresh: no luma SAO at the band's end
+  else hipLaunchKernelGGL(k_sao<false>, dim3((f.cw / 64) * (f.ch / 64)), dim3(KVZ_SAO_THREADS), 0, st, f);
+}
 void launch_tokenize(const EncFrame &f, hipStream_t st)
 {
   // One wave per unit and colour component keeps the longest wave short: the kernel lasts as long as its slowest wave.  (One wave per unit that takes

@@ -70,6 +70,10 @@ struct EncoderConfig {
                               // per P picture and reference a weight and an offset from the two INPUT pictures' luma statistics, kept when a check on every fourth sample says
                               // they pay; the integer search reads weighted copies of its reference planes, k_subpel and k_inter_recon predict with the weights, the slice
                               // headers carry pred_weight_table(); 0 = off (nothing allocated, nothing launched); not in band mode, not with lossless
+  int intra_refresh = 0;      // "intra-refresh" N (extension, "uvgx intra refresh v1"; restated in tests/ir_model.py): 0 = off; 2 .. 255 = a band of intra
+                              // units walks across every P picture, one step a picture and at most N pictures a pass, and the blocks it has passed keep their vectors out of
+                              // what it has not -- after one pass a decoder that lost a picture has the encoder's pictures again, without an IDR picture.  The first picture
+                              // of a cycle carries a recovery point SEI.  Not with lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless or intra-chain=0
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -81,6 +85,7 @@ struct EncodedPicture {
   int poc = 0, qp = 0; bool is_intra = false;
   int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop, a P picture: its QP layer and its references' POC distances in list 0 order (nref 0: the option is off)
   int32_t wp[3 * KVZ_MAX_LP_REFS] = {0, 64, 0, 0, 64, 0, 0, 64, 0, 0, 64, 0};   // weightp: the picture's record [reference][flag, w, o]
+  int32_t ir[4] = {-1, 0, 0, 0};  // intra-refresh: position j in the cycle (-1: an IDR picture, or the option is off), the band [s_j, e_j), the cycle's length n
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
 };
@@ -130,6 +135,7 @@ class Encoder {
   //   "cu_log2","cu_intra","cu_flags","cu_merge_idx","cu_mvp_idx","cu_intra_mode","cu_cbf" (b8 bytes),
   //   "lp_gop" (host values, 8 int32: option active, layer, QP, number of references, their four POC distances),
   //   "wp" (weightp; host values, 12 int32: [reference][flag, w, o] as the picture's slice headers say them -- an intra picture: 0, 64, 0 throughout),
+  //   "ir" (intra-refresh; host values, 4 int32: position j in the cycle, the band's s_j and e_j, the cycle's length n -- an IDR picture: -1, 0, 0, n),
   //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
   int coded_width() const { return cw_; }
@@ -151,7 +157,8 @@ class Encoder {
   // submit() in stages: plan (sets set_, POC, rate control), the picture's frame, then the input stage, its chain and the hand-off, in this order
   // side: the chain on stream_idr_; ahead: me-source search on the input stream; ms: the chain's stream; qp: the picture's QP (rate control's, plus the layer with
   // lp-gop); nref / dist: its references in list 0 order, dist[k] pictures back (k + 1 without lp-gop); layer: lp-gop's QP layer of a P picture, else 0
-  struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; int qp = 0, layer = 0, nref = 1; int8_t dist[KVZ_MAX_LP_REFS] = {1, 2, 3, 4}; };
+  struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; int qp = 0, layer = 0, nref = 1; int8_t dist[KVZ_MAX_LP_REFS] = {1, 2, 3, 4};
+                int ir_j = -1, ir_s = 0, ir_e = 0; };   // intra-refresh: the P picture's position in the cycle and its band (ir_e 0: none)
   bool gop_on() const { return cfg_.lp_gop && cfg_.gop_g >= 1; }
   bool sl_gop_timeline(const Plan &p) const { return gop_on() && !p.intra && Timeline::get().path; }
   Plan plan(int set);
@@ -201,6 +208,8 @@ class Encoder {
   ColMv *col_[kSets] = {};                 // tmvp: the collocated record of the set's picture (EncFrame::col_out), which the next picture reads (col_prev)
   int set_ = 0, out_set_ = 0;
   int32_t out_gop_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug_copy("lp_gop") of the picture last output
+  int32_t out_ir_[4] = {-1, 0, 0, 0};               // debug_copy("ir") of the picture last output
+  bool ir_free_ = true;                             // intra-refresh with intra-in-p=0: false -- the intra-in-P stages run for the band alone
   // weightp (wp_kernels.hip): per working set the input picture's partial sums, its moments {m, v} and the picture's record; one set of scratch (candidates, the
   // check's sums) and of search planes -- their writers and readers follow one another on one stream (the input stream; the planes without me-source: the main stream)
   unsigned long long *wp_partial_[kSets] = {}; int64_t *wp_stat_[kSets] = {}; int32_t *wp_rec_[kSets] = {};
@@ -262,6 +271,7 @@ class Encoder {
     hipEvent_t done = nullptr, rec_done = nullptr;       // tokens / substreams delivered (stream_tok_ / ent_stream) / reconstruction final (stream_)
     hipEvent_t sink_done = nullptr; bool has_sink = false; // set_recon_sink: the reconstruction's copy into the caller's picture (stream_rec_)
     int poc = 0, rec_idx = 0, set = 0, qp = 0; bool intra = false, write_ps = false; long pic_idx = 0;
+    int32_t ir[4] = {-1, 0, 0, 0};                         // intra-refresh: what debug_copy("ir") says of the picture; ir[0] == 0: its access unit starts with the recovery point SEI
     int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop (nref 0: off): what the slice header's reference picture set and debug_copy("lp_gop") say
     std::vector<EvPair> ev; size_t ev_used = 0;
     EncodedPicture result; bool ready = false, ok = true;   // owf >= 2: filled by the background thread

@@ -66,6 +66,22 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.me_coarse && cfg.band_rows > 0) { if (error) *error = "me-coarse is not available in band mode (the halo exchange carries a few rows)"; return false; }
   if (cfg.weightp && cfg.band_rows > 0) { if (error) *error = "weightp is not available in band mode (a band's encoder sees a part of the picture, the weights are the whole picture's)"; return false; }
   if (cfg.weightp && cfg.lossless) { if (error) *error = "weightp is not available with lossless"; return false; }
+  if (cfg.intra_refresh) {                                 // "uvgx intra refresh v1" ("not covered")
+    const char *why = nullptr;
+    if (cfg.intra_refresh < 2 || cfg.intra_refresh > 255) why = "intra-refresh must be 0 or 2 .. 255";
+    else if (cfg.lp_refs >= 2) why = "intra-refresh is not available with lp-refs >= 2 (a clean block may refer to the previous picture only)";
+    else if (cfg.lp_gop) why = "intra-refresh is not available with lp-gop";
+    else if (cfg.tmvp) why = "intra-refresh is not available with tmvp (a temporal candidate is read from a picture the decoder may have concealed)";
+    else if (cfg.me_coarse) why = "intra-refresh is not available with me-coarse";
+    else if (cfg.tile_rows != 1 || cfg.tile_cols != 1) why = "intra-refresh is not available with tiles";
+    else if (cfg.band_rows > 0) why = "intra-refresh is not available in band mode";
+    else if (cfg.lossless) why = "intra-refresh is not available with lossless";
+    else if (!cfg.intra_chain) why = "intra-refresh is not available with intra-chain=0";
+    if (why) { if (error) *error = why; return false; }
+    // intra-in-p = 0: the working sets and launches of intra-in-P are brought up for the band alone (16x16 units, as at level 1); outside it nothing is priced
+    ir_free_ = cfg.intra_in_p != 0;
+    if (!cfg.intra_in_p) cfg.intra_in_p = 1;
+  }
 
   const char *prio = getenv("KVAZZUP_AMD_PRIO"); if (!prio || strlen(prio) < 4) prio = "hnnn";   // main, tokenizer, input, decoder: the chain the next picture waits for is the urgent one (+6 % at 1080p; any explicit priority also gives the stream a hardware queue of its own)
 
@@ -631,6 +647,10 @@ Encoder::Plan Encoder::plan(int set)
     for (int k = 0; k < n; k++) { int j = k; const int8_t v = set[k]; for (; j > 0 && set[j - 1] > v; j--) set[j] = set[j - 1]; set[j] = v; }
     for (int k = 0; k < KVZ_MAX_LP_REFS; k++) p.dist[k] = k < n ? set[k] : 1;
   }
+  if (cfg_.intra_refresh && !p.intra) {                     // intra-refresh: a cycle begins behind the IDR picture and again behind each cycle's last picture
+    p.ir_j = ir_position(cw_, cfg_.intra_refresh, poc_);
+    p.ir_s = ir_band_start(cw_, cfg_.intra_refresh, p.ir_j); p.ir_e = ir_band_end(cw_, cfg_.intra_refresh, p.ir_j);
+  }
   p.ahead = me_ahead_ && !p.intra;
   // the stream this picture's chain runs on: an intra picture's own (encoder.h stream_idr_), else the main stream -- behind the last intra picture's chain
   p.side = p.intra && (idr_side_ || (all_intra_alt_ && (frame_idx_ & 1)));
@@ -680,6 +700,7 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
     const int nr = f.cu_ref ? f.nref : 1;
     for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - (r < nr ? p.dist[r] : 1)) % kSets];
   }
+  if (p.ir_e) { f.ir_j = p.ir_j; f.ir_s = p.ir_s; f.ir_e = p.ir_e; f.ir_free = ir_free_ ? 1 : 0; }      // intra-refresh: the picture's band
   if (wp_rec_[k] && !p.intra) f.wp = wp_rec_[k];       // weightp: the record k_wp_decide writes on the input stream, in front of everything that reads it
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
   if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
@@ -862,6 +883,7 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
   sink_sub_[0] = sink_sub_[1] = sink_sub_[2] = nullptr;
   sl.pic_idx = submitted_; sl.poc = poc_; sl.intra = p.intra; sl.rec_idx = cur_idx_; sl.qp = f.qp; sl.write_ps = false;
   if (sl_gop_timeline(p)) { char w[12]; snprintf(w, sizeof(w), "g%dq%02dd%d%d%d%d", p.layer, f.qp, p.nref > 0 ? p.dist[0] : 0, p.nref > 1 ? p.dist[1] : 0, p.nref > 2 ? p.dist[2] : 0, p.nref > 3 ? p.dist[3] : 0); tl(w, submitted_); }      // KVAZZUP_AMD_TIMELINE, lp-gop: a P picture's layer, QP and reference distances as a record "g<layer>q<QP>d<four distances, 0 = none>"
+  sl.ir[0] = p.ir_j; sl.ir[1] = p.ir_s; sl.ir[2] = p.ir_e; sl.ir[3] = cfg_.intra_refresh ? ir_cycle(cw_, cfg_.intra_refresh) : 0;
   sl.layer = p.layer; sl.nref = gop_on() && !p.intra ? p.nref : 0; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) sl.dist[r] = r < sl.nref ? p.dist[r] : 0;
   if (p.intra) {
     sl.write_ps = (intra_count_ == 0) || (cfg_.vps_period > 0 && (intra_count_ % cfg_.vps_period) == 0);
@@ -931,6 +953,7 @@ bool Encoder::collect(EncodedPicture *out)
   out_idx_ = sl.rec_idx; out_set_ = sl.set;
   out_gop_[0] = gop_on(); out_gop_[1] = out->layer; out_gop_[2] = out->qp; out_gop_[3] = out->nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out_gop_[4 + r] = out->dist[r];
   memcpy(out_wp_, out->wp, sizeof(out_wp_));
+  memcpy(out_ir_, out->ir, sizeof(out_ir_));
   rc_bytes_[(collected_ - 1) & 7] = (uint32_t)out->au.size();   // (collected_ - 1 = index of this picture)
   return ok;
 }
@@ -1002,6 +1025,8 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
   out->valid = true; out->poc = sl.poc; out->qp = sl.qp; out->is_intra = sl.intra; out->bins = bins;
   out->layer = sl.layer; out->nref = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out->dist[r] = sl.dist[r];
   PicRefs pr; pr.n = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
+  memcpy(out->ir, sl.ir, sizeof(out->ir));
+  const int recovery = cfg_.intra_refresh && !sl.intra && sl.ir[0] == 0 ? sl.ir[3] - 1 : -1;      // intra-refresh: a cycle's first picture says when the pass is complete
   PicWeights pw{};                                         // weightp: the record k_wp_decide left in the slot (final long before the tokens are)
   for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
     const bool on = cfg_.weightp && !sl.intra && sl.h_wp[3 * r] != 0;
@@ -1009,7 +1034,7 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
     out->wp[3 * r] = pw.flag[r]; out->wp[3 * r + 1] = pw.w[r]; out->wp[3 * r + 2] = pw.o[r];
   }
   bool assembled;
-  { Tick tk; assembled = assemble_access_unit(out->au, sp_, sl.intra, sl.poc, sl.write_ps, rows_out, nsub, sl.qp - cfg_.qp, sl.nref ? &pr : nullptr, cfg_.weightp ? &pw : nullptr); const double a = tk.ms(); std::lock_guard<std::mutex> l(stat_m_); t_asm_ += a; }
+  { Tick tk; assembled = assemble_access_unit(out->au, sp_, sl.intra, sl.poc, sl.write_ps, rows_out, nsub, sl.qp - cfg_.qp, sl.nref ? &pr : nullptr, cfg_.weightp ? &pw : nullptr, recovery); const double a = tk.ms(); std::lock_guard<std::mutex> l(stat_m_); t_asm_ += a; }
   if (!assembled) { fprintf(stderr, "kvazzup_amd: %d substreams do not fit the tile grid\n", nsub); out->valid = false; return false; }
   out->recon_delivered = false;
   if (sl.has_sink) {                                       // the reconstruction's copy into the caller's picture: queued at submission, long done by now
@@ -1195,6 +1220,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   static const char *names[7] = {"cu_log2", "cu_intra", "cu_flags", "cu_merge_idx", "cu_mvp_idx", "cu_intra_mode", "cu_cbf"};
   for (int i = 0; i < 7; i++) if (w == names[i]) { src = cu_bytes_[out_set_] + i * nb8; have = nb8; }
   if (w == "lp_gop") { if (bytes > sizeof(out_gop_)) return false; memcpy(dst, out_gop_, bytes); return true; }      // (host values: no copy from the device)
+  if (w == "ir") { if (!cfg_.intra_refresh || bytes > sizeof(out_ir_)) return false; memcpy(dst, out_ir_, bytes); return true; }      // (host values)
   if (w == "wp") { if (!cfg_.weightp || bytes > sizeof(out_wp_)) return false; memcpy(dst, out_wp_, bytes); return true; }      // (host values, as the slice headers said them)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }

@@ -153,7 +153,31 @@ struct EncFrame {
   // written by k_wp_decide on the input stream.  k_subpel and k_inter_recon predict luma from reference k as wp_pred14(.., w, o); me_ref / me_refs then point at
   // the references' search planes (k_wp_plane), which k_me reads as it reads any reference
   const int32_t *wp;
+  // "intra-refresh" (ir_e 0: off, and a P picture's kernels run the forms of before): the picture's band is the luma columns [ir_s, ir_e),
+  // ir_j its position in the cycle.  Every 16x16 quarter inside the band is coded as intra units (k_me<.., true>, k_intra_analyse<true, true>), and at ir_j >= 1
+  // the 32x32 blocks left of the band keep their vectors out of it (ir_mvx_max; k_me, k_subpel<.., true>).  ir_free 0: intra-in-p is 0 -- outside the band no
+  // quarter is priced as an intra block (intra_p is then 1 for the kernels' sake: the forced units are 16x16)
+  int ir_s, ir_e, ir_j, ir_free;
 };
+
+// ---------------------------------------------------------------------------------------------
+// "uvgx intra refresh v1" (intra-refresh=N; restated in tests/ir_model.py).  All integer.  cw = coded width (a multiple of 64),
+// B = cw / 32 block columns, N = 2 .. 255 P pictures a cycle may take.
+// ---------------------------------------------------------------------------------------------
+KVZ_HD int ir_step(int cw, int N) { const int B = cw / 32; return (B + N - 1) / N; }                                   // m: block columns a picture advances
+KVZ_HD int ir_cycle(int cw, int N) { const int B = cw / 32, m = ir_step(cw, N); return (B + m - 1) / m; }              // n <= N: pictures of a cycle
+KVZ_HD int ir_band_start(int cw, int N, int j) { return 32 * ir_step(cw, N) * j; }                                     // s_j
+KVZ_HD int ir_band_end(int cw, int N, int j) { const int e = ir_band_start(cw, N, j) + 32 * ir_step(cw, N) + 16; return e < cw ? e : cw; }      // e_j: the step and 16 columns of overlap
+// position in the cycle of the P picture `poc` pictures behind its IDR picture (poc >= 1): cycles follow one another without a gap
+KVZ_HD int ir_position(int cw, int N, int poc) { return (poc - 1) % ir_cycle(cw, N); }
+// the 16x16 quarters (bit k: quarter k, raster of 2 x 2) of the 32x32 block at x0 that lie in the band [s, e): 0, 5 (the left ones: e = x0 + 16) or 15
+KVZ_HD int ir_forced_quarters(int x0, int s, int e) { return (x0 >= s && x0 + 16 <= e ? 5 : 0) | (x0 + 16 >= s && x0 + 32 <= e ? 10 : 0); }
+// a clean block: coded in this cycle's earlier pictures, left of the band
+KVZ_HD bool ir_clean_block(int x0, int s, int j) { return j >= 1 && x0 + 32 <= s; }
+// ... keeps every vector of the block and of its quarters to 4 (x0 + 32) + mvx <= 4 s (mvx in quarter samples; never below zero: the zero vector is admissible)
+KVZ_HD int ir_mvx_max(int x0, int s) { return 4 * (s - x0 - 32); }
+// a forced unit of size nb at xb on the band's last unit column (beyond it lies what the reference picture has not cleaned): no mode that reads above-right samples
+KVZ_HD bool ir_last_column(int xb, int nb, int e, int cw) { return xb + nb == e && e < cw; }
 
 // ---------------------------------------------------------------------------------------------
 // "uvgx weighted prediction v1" (weightp; restated in tests/wp_model.py).  All integer.

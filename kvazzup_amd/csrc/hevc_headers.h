@@ -226,11 +226,23 @@ inline void append_nal(std::vector<uint8_t> &out, int nal_type, const uint8_t *r
   }
 }
 
-// One access unit: [VPS SPS PPS] + slice NAL whose data are the `nsub` substreams (CTU rows with
+// Recovery point SEI message (D.2.8, payload type 6) as a prefix SEI NAL unit's RBSP: recovery_poc_cnt, exact_match_flag 1, broken_link_flag 0 ("intra-refresh",
+// the first picture of a cycle; cnt = pictures until the pass is complete)
+inline void write_recovery_point_sei(BitWriter &w, int recovery_poc_cnt)
+{
+  BitWriter p;
+  p.se(recovery_poc_cnt); p.bit(1); p.bit(0);
+  if (!p.aligned()) p.trailing();                                // payload_bit_equal_to_one, payload_bit_equal_to_zero
+  w.put(6, 8); w.put((uint32_t)p.data().size(), 8);
+  w.bytes(p.data().data(), p.data().size());
+  w.trailing();
+}
+
+// One access unit: [VPS SPS PPS] + [recovery point SEI, recovery_poc_cnt >= 0] + slice NAL whose data are the `nsub` substreams (CTU rows with
 // WPP, otherwise one) rows[r].  false (and an empty access unit): the substream count does not fit the tiling.
 inline bool assemble_access_unit(std::vector<uint8_t> &au, const StreamParams &sp, bool idr, int poc, bool write_ps,
                                  const std::vector<std::vector<uint8_t>> &rows, int nsub, int slice_qp_delta = 0, const PicRefs *refs = nullptr,
-                                 const PicWeights *wt = nullptr)
+                                 const PicWeights *wt = nullptr, int recovery_poc_cnt = -1)
 {
   au.clear();
   if (write_ps) {
@@ -239,6 +251,7 @@ inline bool assemble_access_unit(std::vector<uint8_t> &au, const StreamParams &s
     write_sps(b, sp); append_nal(au, 33, b.data().data(), b.data().size());
     write_pps(c, sp); append_nal(au, 34, c.data().data(), c.data().size());
   }
+  if (recovery_poc_cnt >= 0) { BitWriter r; write_recovery_point_sei(r, recovery_poc_cnt); append_nal(au, 39, r.data().data(), r.data().size()); }      // PREFIX_SEI_NUT
   // slice segments, one NAL unit each: the whole picture; or (slices 1, WPP) a dependent slice segment per CTU row; or (slices 2) an
   // independent slice per tile -- the tile's CTU rows with WPP, else its one substream
   const int hc = sp.ch / 64, wc = sp.cw / 64;

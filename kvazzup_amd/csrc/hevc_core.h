@@ -974,7 +974,7 @@ KVZ_HD int mvd_bits(int q)
 
 // ---------------------------------------------------------------------------------------------
 // "uvgx coarse-to-fine search v1" (kvazaar.h me-coarse; statement of record: tests/me_coarse_model.py).  The arithmetic the
-// kernels k_luma_quarter, k_me_coarse and k_me<.., true> share with the host build tests/hostcoarse.
+// kernels k_luma_quarter, k_me_coarse and k_me<.., true> share with the host build tests/hostcheck/statements.cpp.
 // ---------------------------------------------------------------------------------------------
 // one sample of the quarter picture: the rounded mean of the 4x4 luma samples at p (rows `pitch` apart) -- k_luma_quarter forms the same sum with v_sad_u8 against zero, four samples a
 // thread; tests/test_gpu_me_coarse.py holds its output to this through the centres

@@ -1,31 +1,9 @@
-"""ctypes bindings of tests/hostcoder (host build of the product's arithmetic coder, entropy_host.h).  Test infrastructure."""
+"""ctypes bindings of tests/hostcheck/coder.cpp (host build of the product's arithmetic coder, entropy_host.h).  Test infrastructure."""
 import ctypes as C
-import os
-import subprocess
 import numpy as np
+from hc import lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CTX_COUNT = 154
-_LIB = None
-
-
-def lib():
-    global _LIB
-    if _LIB is None:
-        d = os.path.join(ROOT, "tests", "hostcoder")
-        import fcntl
-        with open(os.path.join(d, ".build.lock"), "w") as lk:      # (pytest -n: several workers reach this at once)
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhostcoder.so"))
-        P = C.c_void_p
-        L.hcr_play.argtypes = [C.c_int, P, P, P, C.c_int, P, P, C.c_int, P, P]
-        L.hcr_code_picture.argtypes = [C.c_int, C.c_int, P, P, P] + [C.c_int] * 7 + [P, C.c_int, P, C.c_int, P]
-        L.hcr_code_band.argtypes = [C.c_int, C.c_int, P, P, P] + [C.c_int] * 8 + [P, C.c_int, P, C.c_int, P]
-        L.hcr_bench.restype = C.c_double
-        L.hcr_bench.argtypes = [P, C.c_long, C.c_int, C.c_int, C.c_int]
-        _LIB = L
-    return _LIB
 
 
 def play(lanes, subs, ctx0):
@@ -46,7 +24,7 @@ def play(lanes, subs, ctx0):
 
 
 def _rows(n, out, cap, ln, bins):
-    assert n >= 0
+    assert n >= 0, "the coder filed more substreams, or longer ones, than the buffers hold (%d)" % n
     return [bytes(out[k * cap:k * cap + ln[k]]) for k in range(n)], bins.value
 
 

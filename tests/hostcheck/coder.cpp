@@ -1,4 +1,4 @@
-// tests/hostcoder/hostcoder.cpp -- host build of the product's arithmetic coder (kvazzup_amd/csrc/entropy_host.h) for the CPU
+// tests/hostcheck/coder.cpp -- host build of the product's arithmetic coder (kvazzup_amd/csrc/entropy_host.h) for the CPU
 // tests of the interleaved coder (tests/test_host_coder_rows.py) and its microbenchmark (tools/arith_bench.py).  Test infrastructure.
 #include <chrono>
 #include "../../kvazzup_amd/csrc/entropy_host.h"

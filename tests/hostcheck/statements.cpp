@@ -1,7 +1,7 @@
-// tests/hostcoarse/hostcoarse.cpp -- host build of the arithmetic the kernels of "uvgx coarse-to-fine search v1" (me-coarse) share
-// through hevc_core.h: the quarter sample, the coarse stage's cost, key and centre, the admissibility rule, the second-window rule and the fine stage's
-// candidate order.  The loops around them are plain C++ here (the kernels' are lanes and LDS windows); tests/test_me_coarse_model.py holds the result to
-// the numpy statement tests/me_coarse_model.py.  Test infrastructure.
+// tests/hostcheck/statements.cpp -- host build of the statement functions the kernels share through hevc_core.h, for the CPU tests that hold them to the numpy
+// restatements: me-coarse's arithmetic (me_*: the quarter sample, the coarse stage's cost, key and centre, the admissibility rule, the second-window rule and
+// the fine stage's candidate order; the loops around them are plain C++ here, the kernels' are lanes and LDS windows; tests/me_coarse_model.py), weightp's
+// (wp_*; tests/wp_model.py) and intra-refresh's (ir_*; tests/ir_model.py).  Test infrastructure.
 #include <cstring>
 #include "../../kvazzup_amd/csrc/hevc_core.h"
 
@@ -90,5 +90,48 @@ void hc_fine(const uint8_t *src, const uint8_t *const *refs, const int16_t *cent
       }
     }
 }
+
+void hw_moments(uint64_t s1, uint64_t s2, uint64_t n, int64_t *mv) { wp_moments(s1, s2, n, &mv[0], &mv[1]); }
+uint32_t hw_isqrt(uint64_t v) { return wp_isqrt(v); }
+// out = {w, o, candidate}
+void hw_candidate(int64_t mc, int64_t vc, int64_t mr, int64_t vr, int32_t *out) { int w, o; out[2] = wp_candidate(mc, vc, mr, vr, &w, &o) ? 1 : 0; out[0] = w; out[1] = o; }
+int hw_accept(int cand, uint64_t plain, uint64_t wt) { return wp_accept(cand != 0, plain, wt) ? 1 : 0; }
+int hw_sample(int s, int w, int o) { return wp_sample(s, w, o); }
+int hw_pred14(int p, int w, int o) { return wp_pred14(p, w, o); }
+
+// the whole decision of picture `cur` against input picture `ref` (planes of `pitch` bytes a row, width x height visible) as the kernels compose it: sums, moments,
+// candidate, check, verdict.  out = {flag, w, o}
+void hw_decide(const uint8_t *cur, const uint8_t *ref, int width, int height, int pitch, int32_t *out)
+{
+  uint64_t s[2][2] = {{0, 0}, {0, 0}};
+  const uint8_t *pl[2] = {cur, ref};
+  for (int k = 0; k < 2; k++)
+    for (int y = 0; y < height; y++) for (int x = 0; x < width; x++) { const uint64_t v = pl[k][(size_t)y * pitch + x]; s[k][0] += v; s[k][1] += v * v; }
+  int64_t m[2], v[2];
+  for (int k = 0; k < 2; k++) wp_moments(s[k][0], s[k][1], (uint64_t)width * height, &m[k], &v[k]);
+  int w, o;
+  const bool cand = wp_candidate(m[0], v[0], m[1], v[1], &w, &o);
+  uint64_t plain = 0, wt = 0;
+  for (int y = 0; y < height; y += 4) for (int x = 0; x < width; x += 4) {
+    const int c = cur[(size_t)y * pitch + x], r = ref[(size_t)y * pitch + x];
+    plain += (uint64_t)iabs(c - r); wt += (uint64_t)iabs(c - wp_sample(r, w, o));
+  }
+  const bool on = wp_accept(cand, plain, wt);
+  out[0] = on ? 1 : 0; out[1] = on ? w : 64; out[2] = on ? o : 0;
+}
+
+int hi_step(int cw, int N) { return ir_step(cw, N); }
+int hi_cycle(int cw, int N) { return ir_cycle(cw, N); }
+// out = {s_j, e_j}
+void hi_band(int cw, int N, int j, int32_t *out) { out[0] = ir_band_start(cw, N, j); out[1] = ir_band_end(cw, N, j); }
+int hi_position(int cw, int N, int poc) { return ir_position(cw, N, poc); }
+int hi_forced_quarters(int x0, int s, int e) { return ir_forced_quarters(x0, s, e); }
+int hi_clean_block(int x0, int s, int j) { return ir_clean_block(x0, s, j) ? 1 : 0; }
+int hi_mvx_max(int x0, int s) { return ir_mvx_max(x0, s); }
+int hi_last_column(int xb, int nb, int e, int cw) { return ir_last_column(xb, nb, e, cw) ? 1 : 0; }
+// every schedule of a coded width in one call: out[2 (N - 2)] = m, out[2 (N - 2) + 1] = n for N = 2 .. 255
+void hi_schedules(int cw, int32_t *out) { for (int N = 2; N <= 255; N++) { out[2 * (N - 2)] = ir_step(cw, N); out[2 * (N - 2) + 1] = ir_cycle(cw, N); } }
+// the bands of one cycle: out[2 j] = s_j, out[2 j + 1] = e_j for j < ir_cycle(cw, N); returns the cycle's length
+int hi_bands(int cw, int N, int32_t *out) { const int n = ir_cycle(cw, N); for (int j = 0; j < n; j++) { out[2 * j] = ir_band_start(cw, N, j); out[2 * j + 1] = ir_band_end(cw, N, j); } return n; }
 
 }

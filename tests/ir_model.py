@@ -1,5 +1,5 @@
 """"uvgx intra refresh v1" (kvazaar.h intra-refresh) restated in Python: the schedule, the forced quarters, the vector bound, the mode
-rule and the recovery point SEI.  hevc_core.h's ir_* functions (host build: tests/hostir) and the HIP encoder are held to it.  All integer.
+rule and the recovery point SEI.  hevc_core.h's ir_* functions (host build: tests/hostcheck) and the HIP encoder are held to it.  All integer.
 
 cw = coded width (a multiple of 64), B = cw / 32 block columns, N = 2 .. 255 the number of P pictures a cycle may take.
   m = ceil(B / N)   block columns a picture advances

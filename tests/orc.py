@@ -273,3 +273,10 @@ class OracleGen:
 
     def __del__(self):
         self.close()
+
+
+def table(which, dtype, shape):
+    """the checker's copy of a normative table (oracle orc_api_tables)"""
+    out = np.zeros(shape, dtype=dtype)
+    lib().orc_api_tables(which, out.ctypes.data_as(C.c_void_p))
+    return out

@@ -3,7 +3,7 @@ prediction -- availability becomes any pattern along a block's two borders, and 
 per-wave blocks, a unit mask in the 32x32 form).  The synthesiser sets the flag (cip); the HIP decoder must reproduce the checker's decoder bit for bit."""
 import pytest
 
-from test_gpu_foreign import PLAIN, run_stream
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 """GPU parity for "me-coarse"  and "lp-gop" (section 9d): the HIP encoder against the CPU checker (oracle/hevc_enc.c), which states
 both features itself.  For every picture of every case: the access unit equals the checker's byte for byte, the reconstruction and the CABAC bin count
-equal the checker's, and the HIP decoder turns the access unit into exactly that reconstruction (run_case of tests/test_gpu_lp_refs_oracle.py).  On a mismatch
+equal the checker's, and the HIP decoder turns the access unit into exactly that reconstruction (run_case of tests/enckit.py).  On a mismatch
 the message names the first stage that differs: the coarse centres, the layer / QP, the reference distances, then the decisions, levels and samples.
 
 These cases hold to the checker what the models (tests/me_coarse_model.py, tests/lp_gop_model.py: the integer search at subme 0, the structure) and the closed
@@ -16,9 +16,8 @@ import pytest
 
 import lp_gop_model as M
 import lp_refs_model
-from test_gpu_lp_refs_oracle import _ROI, _id, run_case, sweep_case
-from test_gpu_lp_gop import ROWS as GOP_ROWS
-from test_gpu_me_coarse import CLOSED as COARSE_ROWS
+from cases import LP_GOP_ROWS as GOP_ROWS, ME_COARSE_CLOSED as COARSE_ROWS
+from enckit import ROI as _ROI, case_id as _id, run_case, sweep_case
 
 _NAMES = {"subme": "subme", "rdoq": "rdoq", "signhide": "signhide", "intra-in-p": "intra_in_p", "lp-refs": "n", "tmvp": "tmvp", "wpp": "wpp", "period": "period",
           "vaq": "vaq", "lossless": "lossless", "gpu-entropy": "gpu_entropy", "deblock": "deblock", "me-source": "me_source", "qp": "qp", "owf": "owf",
@@ -26,7 +25,7 @@ _NAMES = {"subme": "subme", "rdoq": "rdoq", "signhide": "signhide", "intra-in-p"
 
 
 def case_from_opts(opts, fields=None):
-    """a row's kvazaar options in the vocabulary of _checker / _hip (tests/test_gpu_lp_refs_oracle.py); an option without a mapping is an error, not a dropped row"""
+    """a row's kvazaar options in the vocabulary of checker() / hip() (tests/enckit.py); an option without a mapping is an error, not a dropped row"""
     c = {}
     for k, v in opts:
         if k in _NAMES:
@@ -44,7 +43,7 @@ def case_from_opts(opts, fields=None):
         elif k == "me-early-termination":
             c["me_early"] = int(v == "on")
         elif k == "set-qp-in-cu":
-            pass                                      # (_checker / _hip switch it on with the ROI map)
+            pass                                      # (checker() / hip() switch it on with the ROI map)
         else:
             raise KeyError("no checker mapping for option %s" % k)
     for k, v in (fields or {}).items():
@@ -182,7 +181,7 @@ def test_edge_content_matches_the_checker(gpu, cfg):
     run(cfg)
 
 
-# ---- a seeded sweep: sweep_case of tests/test_gpu_lp_refs_oracle.py plus me-coarse, lp-gop and the content drawn from the generator
+# ---- a seeded sweep: sweep_case of tests/enckit.py plus me-coarse, lp-gop and the content drawn from the generator
 def coarse_gop_sweep_case(seed):
     c = sweep_case(seed)
     rng = np.random.default_rng(7000 + seed)

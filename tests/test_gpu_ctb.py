@@ -3,7 +3,7 @@ whatever arrives; the SDP offers plain "H265").  The synthesiser (oracle/hevc_ge
 decoder -- which tests/test_python_decoder.py holds to the second, independently written decoder on the same kind of stream -- bit for bit."""
 import pytest
 
-from test_gpu_foreign import PLAIN, run_stream
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

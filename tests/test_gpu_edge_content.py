@@ -7,7 +7,7 @@ import pytest
 
 import edge_content as ec
 import orc
-from test_gpu_encoder import _diagnose
+from enckit import diagnose as _diagnose
 
 
 def _first_difference(a, b, w, h):

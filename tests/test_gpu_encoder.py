@@ -4,29 +4,9 @@ import numpy as np
 import pytest
 
 import orc
+from enckit import diagnose as _diagnose
 
 SEED = 0x5EED0000
-
-
-def _diagnose(dbg_o, dbg_g):
-    msgs = []
-    for k in ("cu_log2", "cu_intra", "cu_intra_mode", "cu_mv", "cu_cbf", "cu_flags"):
-        a, b = dbg_o[k], dbg_g[k]
-        if k == "cu_mv":
-            m = (dbg_o["cu_intra"] == 0)
-            a, b = a[m], b[m]
-        if k == "cu_intra_mode":
-            m = dbg_o["cu_intra"] == 1
-            a, b = a[m], b[m]
-        if not np.array_equal(a, b):
-            bad = np.argwhere(np.asarray(a != b))
-            msgs.append("%s differs at %d entries, first %s (oracle %s gpu %s)" % (k, len(bad), bad[0].tolist(), a[tuple(bad[0])] if a.ndim == bad.shape[1] else "?", b[tuple(bad[0])] if b.ndim == bad.shape[1] else "?"))
-    for c in range(3):
-        a, b = dbg_o["rec%d" % c], dbg_g["rec%d" % c]
-        if not np.array_equal(a, b):
-            bad = np.argwhere(a != b)
-            msgs.append("rec%d differs at %d samples, first (y,x)=%s" % (c, len(bad), bad[0].tolist()))
-    return "; ".join(msgs) if msgs else "no stage-level difference found (entropy coding / assembly?)"
 
 
 def run_clip(w, h, frames, qp, period, me_range, kind, wpp=1, deblock=1, via_picture=True, tile_rows=1, sao=0, mv_frame=0, vaq=0, gpu_entropy=0, subme=0, me_early=1, slices=0):

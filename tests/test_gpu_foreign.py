@@ -6,43 +6,7 @@ import numpy as np
 import pytest
 
 import orc
-
-
-def run_stream(w, h, pictures, threads=1, frame_threads=False, **cfg):
-    from kvazzup_amd.codec import Decoder
-    g = orc.OracleGen(w, h, **cfg)
-    od = orc.OracleDecoder()
-    gd = Decoder(threads=threads, frame_threads=frame_threads) if frame_threads else Decoder()
-    refs, got, pocs = [], [], []
-    try:
-        reorder = g.config.get("gop", 0) > 1              # (pictures come out in POC order, later than they go in)
-        for t in range(pictures):
-            au = g.picture()
-            r = od.decode_au(au, t)
-            assert reorder or len(r) == 1, (t, g.config)
-            refs += [f["i420"] for f in r]
-            pocs += [f["poc"] for f in r]
-            got += gd.decode_au(au, t)
-        refs += [f["i420"] for f in od.flush()]
-        if frame_threads or reorder or g.config.get("slices") == 3:      # (free slices: a picture is closed by what follows it in the stream)
-            got += gd.drain()
-        assert len(got) == pictures and len(refs) == pictures, (len(got), len(refs), g.config)
-        for t in range(pictures):
-            assert got[t]["width"] == w and got[t]["height"] == h
-            if not np.array_equal(got[t]["i420"], refs[t]):
-                d = np.flatnonzero(got[t]["i420"] != refs[t])
-                plane = "Y" if d[0] < w * h else "C"
-                pytest.fail("picture %d: %d samples differ, first at %d (%s, x=%d y=%d); config %r"
-                            % (t, len(d), d[0], plane, d[0] % w, d[0] // w, g.config))
-    finally:
-        gd.close()
-        od.close()
-        g.close()
-
-
-PLAIN = dict(num_refs=1, tmvp=0, amp=0, sao=0, strong_intra=1, sign_hiding=0, transform_skip=0, cabac_init=0, wpp=1, tile_rows=1, uniform_tiles=1,
-             th_depth_inter=0, th_depth_intra=0, qp_delta=0, chroma_qp_offsets=0, deblock_mode=0, par_mrg_level=2, intra_in_p=0, all_part_modes=0,
-             chroma_modes=0, nxn_intra=0, max_cu_log2=5, min_cu_log2=3, big_mvd=0)
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

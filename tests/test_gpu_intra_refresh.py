@@ -11,10 +11,10 @@ import functools
 import numpy as np
 import pytest
 
+import enckit
 import ir_model as M
 import orc
 import pyhevc
-from test_gpu_lp_refs import _closed_loop, _encode_all
 
 QP, RANGE = 32, 8
 # (width, height, N): m = 2, n = 5; m = 1, n = 10; coded 256 wide, visible narrower, n = 8; m = 5, n = 4
@@ -26,11 +26,8 @@ def _cw(w):
     return (w + 63) & ~63
 
 
-def _encoder(w, h, N, opts=(), fields=None):
-    from kvazzup_amd.codec import Encoder
-    ge = Encoder(w, h, options=(("qp", QP), ("me-range", RANGE), ("intra-refresh", N)) + tuple(opts), fields=fields)
-    assert not ge.rejected, ge.rejected
-    return ge
+def _opts(N):
+    return (("qp", QP), ("me-range", RANGE), ("intra-refresh", N))
 
 
 @functools.lru_cache(maxsize=None)
@@ -45,8 +42,8 @@ def _npics(w, N):
 @functools.lru_cache(maxsize=None)
 def _stream(w, h, N, opts=(), npics=0):
     """(access unit, reconstruction) of the clip's pictures under intra-refresh=N (0: without the option), owf 0"""
-    ge = _encoder(w, h, N, opts)
-    out = _encode_all(ge, _clip(w, h, npics or _npics(w, N)))
+    ge = enckit.encoder(w, h, _opts(N) + opts)
+    out = enckit.encode_all(ge, _clip(w, h, npics or _npics(w, N)))
     ge.close()
     return out
 
@@ -107,7 +104,7 @@ STRUCT = [(s, 1) for s in SIZES] + [(SIZES[0], 0), (SIZES[0], 2)]
 def test_every_picture_has_the_structure_the_statement_asks_for(gpu, size, ip):
     w, h, N = size
     cw = _cw(w)
-    ge = _encoder(w, h, N, (("intra-in-p", ip), ("subme", 2)))
+    ge = enckit.encoder(w, h, _opts(N) + (("intra-in-p", ip), ("subme", 2)))
     total = {}
     try:
         for t, fr in enumerate(_clip(w, h, _npics(w, N))):
@@ -171,7 +168,7 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
     if cfg.get("change"):
         import wp_model
         frames = wp_model.change(frames, w, h, cfg["change"])
-    ge = _encoder(w, h, N, opts, fields={"target_bitrate": br} if br else None)
+    ge = enckit.encoder(w, h, _opts(N) + opts, fields={"target_bitrate": br} if br else None)
     pairs, irs = [], []
     try:
         for t in range(len(frames) + owf + 1):
@@ -190,7 +187,7 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
         assert len(sei) == (1 if irs[t][0] == 0 else 0), t
         if sei:
             assert bytes(pyhevc.unescape(sei[0])[2:]) == M.recovery_point_sei(irs[t][3] - 1)
-    _closed_loop(w, h, pairs)
+    enckit.closed_loop(pairs)
 
 
 @pytest.mark.gpu
@@ -199,7 +196,7 @@ def test_closed_loop_smallest_case_also_matches_pyhevc(gpu):
     for extra in ((("subme", 2),), (("intra-in-p", 2), ("sao", "full"))):
         pairs = _stream(w, h, N, extra)
         assert len(pairs) == 2 * M.cycle(w, N) + 4
-        _closed_loop(w, h, pairs, pyhevc_too=True)
+        enckit.closed_loop(pairs, pyhevc_too=True)
 
 
 # ---- 3. recovery
@@ -221,11 +218,6 @@ def _decode_with_a_loss(aus, lost, which):
     finally:
         dec.close()
     return {f["pts"]: f["i420"] for f in got}
-
-
-def _planes(i420, w, h):
-    ny = w * h
-    return i420[:ny].reshape(h, w), i420[ny:ny + ny // 4].reshape(h // 2, w // 2), i420[ny + ny // 4:].reshape(h // 2, w // 2)
 
 
 @pytest.mark.gpu
@@ -250,7 +242,7 @@ def test_a_lost_picture_is_healed_by_the_next_cycle(gpu, size, where):
             j, s, e, _ = M.record(cw, N, t)
             whole = t > 2 * n or e == cw
             lim = w if whole else min(w, e - 4)
-            for c, (a, b) in enumerate(zip(_planes(got[t], w, h), _planes(pairs[t][1], w, h))):
+            for c, (a, b) in enumerate(zip(enckit.planes(got[t], w, h), enckit.planes(pairs[t][1], w, h))):
                 k = lim if c == 0 else lim // 2
                 assert np.array_equal(a[:, :k], b[:, :k]), "%s decoder, picture %d (position %d, band [%d, %d)), plane %d: %d samples differ left of column %d, first column %d" % (
                     which, t, j, s, e, c, int((a[:, :k] != b[:, :k]).sum()), k, int(np.flatnonzero((a[:, :k] != b[:, :k]).any(axis=0))[0]))

@@ -4,7 +4,7 @@ decides: 7.4.7.1).  Deblocking leaves the edges on a closed boundary alone, SAO 
 (lf_across); the HIP decoder must reproduce the checker's decoder bit for bit."""
 import pytest
 
-from test_gpu_foreign import PLAIN, run_stream
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

@@ -3,7 +3,7 @@ delta_poc_msb_present_flag, used by the current picture or only kept; the refere
 The synthesiser writes them (long_term); the HIP decoder -- whose kernels only ever see picture buffers -- must reproduce the checker's decoder bit for bit."""
 import pytest
 
-from test_gpu_foreign import PLAIN, run_stream
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

@@ -6,30 +6,8 @@ import numpy as np
 import pytest
 
 import orc
-from test_lost_pictures import lossy
-
-
-def run(cut, threads, must_conceal=True):
-    from kvazzup_amd.codec import Decoder
-    od = orc.OracleDecoder()
-    gd = Decoder(threads=threads, frame_threads=True) if threads > 1 else Decoder()
-    want, got = [], []
-    try:
-        for t, au in cut:
-            want += od.decode_au(au, t)
-            got += gd.decode_au(au, t)
-        want += od.flush()
-        got += gd.drain()
-        assert od.concealed() > 0 or not must_conceal
-    finally:
-        gd.close()
-        od.close()
-    assert [f["pts"] for f in got] == [f["pts"] for f in want], ([f["pts"] for f in got], [f["pts"] for f in want])
-    assert len(got) == len(cut) or not must_conceal
-    for a, b in zip(got, want):
-        if not np.array_equal(a["i420"], b["i420"]):
-            d = np.flatnonzero(a["i420"] != b["i420"])
-            pytest.fail("picture with time stamp %d: %d samples differ, first at %d" % (a["pts"], len(d), d[0]))
+from deckit import run
+from nalkit import lossy
 
 
 @pytest.mark.gpu

@@ -7,23 +7,17 @@ the option itself (oracle/hevc_enc.c "lp-gop"); tests/test_gpu_coarse_gop_oracle
 import numpy as np
 import pytest
 
+import enckit
 import lp_gop_model as M
 import lp_gop_stream
 import lp_refs_model
 import occluder_content
-import orc
 import pyhevc
-from test_gpu_lp_refs import CLOSED, SEARCH, SEED, _closed_loop, _encode_all, _frames
-
-GDN = ((4, 3, 1), (4, 3, 2), (4, 3, 3), (4, 3, 4), (8, 4, 3), (3, 2, 4), (1, 1, 2))
+from cases import GDN, LP_GOP_ROWS as ROWS, LP_REFS_SEARCH as SEARCH
 
 
-def _encoder(w, h, g, d, n, opts=(), fields=None, on=1):
-    from kvazzup_amd.codec import Encoder
-    o = (("lp-refs", n), ("gop", "lp-g%dd%dt1" % (g, d)), ("lp-gop", on)) + tuple(opts)
-    ge = Encoder(w, h, options=o, fields=fields)
-    assert not ge.rejected, ge.rejected
-    return ge
+def _gop(g, d, n, on=1):
+    return (("lp-refs", n), ("gop", "lp-g%dd%dt1" % (g, d)), ("lp-gop", on))
 
 
 # ---- 1. the structure, from the stream alone
@@ -33,11 +27,11 @@ def _encoder(w, h, g, d, n, opts=(), fields=None, on=1):
 def test_structure_from_the_stream(gpu, gdn, period):
     g, d, n = gdn
     w, h, qp, nf = 128, 64, 30, 2 * period + 3
-    ge = _encoder(w, h, g, d, n, (("period", period), ("qp", qp), ("me-range", 8)))
+    ge = enckit.encoder(w, h, _gop(g, d, n) + (("period", period), ("qp", qp), ("me-range", 8)))
     want = M.structure(period, nf, g, d, n, qp)
     sps = pps = None
     try:
-        for i, fr in enumerate(_frames(0, w, h, nf)):
+        for i, fr in enumerate(enckit.frames(0, w, h, nf)):
             au, _ = ge.encode(fr)
             nals = pyhevc.split_nals(au)
             if (nals[0][0] >> 1) & 63 == 32:
@@ -70,7 +64,7 @@ def test_integer_search_matches_the_model(gpu, cfg):
     tiles = cfg.get("tiles", "1x1"); tc, tr = [int(v) for v in tiles.split("x")]
     opts = (("qp", qp), ("me-range", R), ("subme", 0), ("me-early-termination", "on" if cfg["me_early"] else "off"), ("me-source", cfg.get("me_source", 0)),
             ("mv-constraint", ("none", "frame", "frametilemargin")[cfg.get("mv_frame", 0)])) + ((("tiles", tiles),) if tiles != "1x1" else ())
-    ge = _encoder(w, h, g, d, n, opts)
+    ge = enckit.encoder(w, h, _gop(g, d, n) + opts)
     # background that pictures 1 .. 4 cover and picture 5 shows again: only the key picture (POC 0, five pictures back) holds it
     frames = occluder_content.blink_clip(w, h, nf, kind=cfg["kind"])
     y0, y1, x0, x1 = occluder_content.region(w, h)
@@ -100,15 +94,6 @@ def test_integer_search_matches_the_model(gpu, cfg):
 
 
 # ---- 3. closed loop over the tool set
-EXTRA = [
-    dict(n=3, opts=(("tmvp", 1),)), dict(n=4, opts=(("tmvp", 1), ("subme", 2), ("sao", "full")), owf=3), dict(n=2, opts=(("tmvp", 1), ("slices", "wpp"))),
-    dict(n=3, opts=(("me-coarse", 128),), w=384, h=256), dict(n=3, opts=(("me-coarse", 128), ("me-source", 1), ("tmvp", 1)), w=384, h=256, owf=2),
-    dict(n=3, opts=(("me-source", 1),)), dict(n=4, opts=(("me-source", 1), ("tmvp", 1)), w=200, h=120),
-    dict(n=3, opts=(("tmvp", 1),), w=328, h=184, frames=12), dict(n=3, opts=(("qp", 50), ("tmvp", 1))),
-    dict(n=3, opts=(("tmvp", 1),), g=8, d=4, frames=14), dict(n=4, opts=(("tmvp", 1),), g=3, d=2, frames=10), dict(n=2, opts=(("tmvp", 1),), g=1, d=1),
-    dict(n=1, opts=(("tmvp", 1),)), dict(n=3, opts=(("tmvp", 1), ("period", 5)), owf=6, frames=14),
-]
-ROWS = CLOSED + EXTRA
 
 
 @pytest.mark.gpu
@@ -121,7 +106,7 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
     if br:
         opts += (("bitrate", br),)
     fields = dict(cfg.get("fields", {}), **({"target_bitrate": br} if br else {}))
-    ge = _encoder(w, h, cfg.get("g", 4), cfg.get("d", 3), cfg["n"], opts, fields=fields or None)
+    ge = enckit.encoder(w, h, _gop(cfg.get("g", 4), cfg.get("d", 3), cfg["n"]) + opts, fields=fields or None)
     if cfg.get("roi"):
         import ctypes as C
         deltas = (np.arange(12, dtype=np.int8) % 7 - 3).astype(np.int8)
@@ -129,20 +114,20 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
         for pic in ge.pics:
             pic.contents.roi.width, pic.contents.roi.height = 4, 3
             pic.contents.roi.roi_array = deltas.ctypes.data_as(C.POINTER(C.c_int8))
-    frames = _frames(cfg.get("kind", 0), w, h, cfg.get("frames", 10))
-    pairs = _encode_all(ge, frames, owf)
+    frames = enckit.frames(cfg.get("kind", 0), w, h, cfg.get("frames", 10))
+    pairs = enckit.encode_all(ge, frames, owf)
     ge.close()
-    _closed_loop(w, h, pairs, sei=cfg.get("sei", False))
+    enckit.closed_loop(pairs, sei=cfg.get("sei", False))
 
 
 @pytest.mark.gpu
 def test_closed_loop_smallest_case_also_matches_pyhevc(gpu):
     w, h = 128, 64
     for n, extra in ((3, ()), (2, (("tmvp", 1),))):
-        ge = _encoder(w, h, 4, 3, n, (("me-range", 8),) + extra)
-        pairs = _encode_all(ge, occluder_content.blink_clip(w, h, 7))
+        ge = enckit.encoder(w, h, _gop(4, 3, n) + (("me-range", 8),) + extra)
+        pairs = enckit.encode_all(ge, occluder_content.blink_clip(w, h, 7))
         ge.close()
-        _closed_loop(w, h, pairs, pyhevc_too=True)
+        enckit.closed_loop(pairs, pyhevc_too=True)
 
 
 @pytest.mark.gpu
@@ -150,8 +135,8 @@ def test_closed_loop_decodes_scaled_amvp(gpu):
     """a stream in which adjacent inter CUs hold references of different distance with a non-merged CU among them (counted from debug_all()): the decoders
     scale a neighbour's vector by the true POC distances (8.5.3.2.7) to read its vector differences"""
     w, h, g, d, n = 320, 192, 4, 3, 3
-    ge = _encoder(w, h, g, d, n, (("qp", 22), ("me-range", 12), ("me-early-termination", "off"), ("tmvp", 1)))
-    frames = _frames(2, w, h, 10)
+    ge = enckit.encoder(w, h, _gop(g, d, n) + (("qp", 22), ("me-range", 12), ("me-early-termination", "off"), ("tmvp", 1)))
+    frames = enckit.frames(2, w, h, 10)
     pairs, count = [], 0
     for t, fr in enumerate(frames):
         au, rec = ge.encode(fr)
@@ -165,16 +150,16 @@ def test_closed_loop_decodes_scaled_amvp(gpu):
             count += int((inter[a] & inter[b] & (dist[a] != dist[b]) & (amvp[a] | amvp[b])).sum())
     ge.close()
     assert count > 0, "no non-merged CU beside a CU with a reference of another distance"
-    _closed_loop(w, h, pairs, pyhevc_too=False)
+    enckit.closed_loop(pairs, pyhevc_too=False)
 
 
 @pytest.mark.gpu
 def test_closed_loop_1080p(gpu):
     w, h = 1920, 1080
-    ge = _encoder(w, h, 4, 3, 3, (("preset", "veryfast"), ("tmvp", 1)))
-    pairs = _encode_all(ge, _frames(0, w, h, 10))
+    ge = enckit.encoder(w, h, _gop(4, 3, 3) + (("preset", "veryfast"), ("tmvp", 1)))
+    pairs = enckit.encode_all(ge, enckit.frames(0, w, h, 10))
     ge.close()
-    _closed_loop(w, h, pairs)
+    enckit.closed_loop(pairs)
 
 
 # ---- 4. off is off
@@ -183,7 +168,7 @@ def test_closed_loop_1080p(gpu):
 def test_the_string_alone_and_the_switch_alone_change_nothing(gpu, opts):
     from kvazzup_amd.codec import Encoder
     w, h = 320, 192
-    frames = _frames(0, w, h, 9)
+    frames = enckit.frames(0, w, h, 9)
     owf = dict(opts).get("owf", 0)
 
     def run(extra, gop_default=True):
@@ -196,7 +181,7 @@ def test_the_string_alone_and_the_switch_alone_change_nothing(gpu, opts):
         finally:
             codec.DEFAULT_OPTIONS = keep
         assert not ge.rejected, ge.rejected
-        out = _encode_all(ge, frames, owf)
+        out = enckit.encode_all(ge, frames, owf)
         ge.close()
         return out
     want = run((), gop_default=False)

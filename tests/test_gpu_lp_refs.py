@@ -3,65 +3,15 @@
 Here the feature is held to three things: with lp-refs 0 / 1 the encoder is the one-reference encoder byte for byte; the integer search equals
 the numpy restatement tests/lp_refs_model.py (itself pinned to the checker by tests/test_lp_refs_host.py); and every picture's reconstruction
 equals what the checker's decoder and the library's HIP decoder make of the stream (closed loop).  The checker's encoder states lp-refs itself,
-and tests/test_gpu_lp_refs_oracle.py holds the HIP encoder to it bit for bit."""
+and tests/test_gpu_lp_refs_oracle.py (run_case of tests/enckit.py) holds the HIP encoder to it bit for bit."""
 import numpy as np
 import pytest
 
+import enckit
 import orc
 import lp_refs_model
-
-SEED = 0x5EED0000
-
-
-def _encoder(w, h, n, opts=(), fields=None):
-    from kvazzup_amd.codec import Encoder
-    o = ((("lp-refs", n),) if n is not None else ()) + tuple(opts)
-    ge = Encoder(w, h, options=o, fields=fields)
-    assert not ge.rejected, ge.rejected
-    return ge
-
-
-def _encode_all(ge, frames, owf=0):
-    """(access unit, reconstruction) of every picture, the pictures in flight flushed"""
-    out = []
-    for t in range(len(frames) + owf + 1):
-        au, rec = ge.encode(frames[t] if t < len(frames) else None)
-        if au:
-            out.append((au, rec))
-    assert len(out) == len(frames), len(out)
-    return out
-
-
-def _closed_loop(w, h, pairs, sei=False, pyhevc_too=False):
-    """every reconstruction == the checker's decoder's picture == the HIP decoder's picture; on a mismatch the first picture and which decoder"""
-    from kvazzup_amd.codec import Decoder
-    od, gd = orc.OracleDecoder(), Decoder()
-    try:
-        for t, (au, rec) in enumerate(pairs):
-            a = od.decode_au(au, t)
-            assert len(a) == 1, ("checker's decoder returned %d pictures" % len(a), t)
-            assert np.array_equal(a[0]["i420"], rec), "picture %d: the checker's decoder differs from the encoder's reconstruction (%d samples)" % (t, int((a[0]["i420"] != rec).sum()))
-            b = gd.decode_au(au, t)
-            assert len(b) == 1 and np.array_equal(b[0]["i420"], rec), "picture %d: the HIP decoder differs from the encoder's reconstruction" % t
-        if sei:
-            checked, bad = od.hash_stats()
-            assert checked == len(pairs) and bad == 0, (checked, bad)
-    finally:
-        od.close(); gd.close()
-    if pyhevc_too:
-        import pyhevc
-        from test_python_decoder import tabs
-        dec = pyhevc.Decoder(tabs())
-        for au, _ in pairs:
-            dec.decode(au)
-        pics = dec.flush()
-        assert len(pics) == len(pairs)
-        for t, p in enumerate(pics):
-            assert np.array_equal(p["i420"], pairs[t][1]), "picture %d: tests/pyhevc.py differs" % t
-
-
-def _frames(kind, w, h, n):
-    return [orc.synth_frame(kind, SEED, w, h, t) for t in range(n)]
+from cases import LP_REFS_CLOSED as CLOSED, LP_REFS_SEARCH as SEARCH
+from enckit import SEED
 
 
 # ---- 1. guard: lp-refs 0 and 1 are the one-reference encoder
@@ -69,27 +19,20 @@ def _frames(kind, w, h, n):
 @pytest.mark.parametrize("opts", [(), (("subme", 2), ("sao", "full"), ("intra-in-p", 1)), (("tiles", "2x2"), ("owf", 3), ("me-source", 1))])
 def test_lp_refs_0_and_1_are_the_one_reference_encoder(gpu, opts):
     w, h = 320, 192
-    frames = _frames(0, w, h, 5)
+    frames = enckit.frames(0, w, h, 5)
     owf = dict(opts).get("owf", 0)
-    base = _encoder(w, h, None, opts)
-    want = _encode_all(base, frames, owf)
+    base = enckit.encoder(w, h, opts)
+    want = enckit.encode_all(base, frames, owf)
     base.close()
     for n in (0, 1):
-        ge = _encoder(w, h, n, opts)
-        got = _encode_all(ge, frames, owf)
+        ge = enckit.encoder(w, h, (("lp-refs", n),) + opts)
+        got = enckit.encode_all(ge, frames, owf)
         ge.close()
         for t in range(len(frames)):
             assert got[t][0] == want[t][0] and np.array_equal(got[t][1], want[t][1]), (n, t)
 
 
 # ---- 2. the integer search against the numpy restatement
-SEARCH = [
-    dict(w=256, h=128, n=2, R=8, me_early=1, kind=0, frames=5),
-    dict(w=256, h=192, n=3, R=8, me_early=0, kind=0, frames=6, qp=27),
-    dict(w=192, h=128, n=4, R=6, me_early=0, kind=2, frames=6, qp=37),
-    dict(w=256, h=256, n=4, R=8, me_early=1, kind=0, frames=6, tiles="2x2", mv_frame=2),
-    dict(w=256, h=128, n=3, R=8, me_early=0, kind=0, frames=5, me_source=1),
-]
 
 
 @pytest.mark.gpu
@@ -99,8 +42,8 @@ def test_integer_search_matches_the_model(gpu, cfg):
     tiles = cfg.get("tiles", "1x1"); tc, tr = [int(v) for v in tiles.split("x")]
     opts = (("qp", qp), ("me-range", R), ("subme", 0), ("me-early-termination", "on" if cfg["me_early"] else "off"), ("me-source", cfg.get("me_source", 0)),
             ("mv-constraint", ("none", "frame", "frametilemargin")[cfg.get("mv_frame", 0)])) + ((("tiles", tiles),) if tiles != "1x1" else ())
-    ge = _encoder(w, h, n, opts)
-    frames = _frames(cfg["kind"], w, h, cfg["frames"])
+    ge = enckit.encoder(w, h, (("lp-refs", n),) + opts)
+    frames = enckit.frames(cfg["kind"], w, h, cfg["frames"])
     recs = []
     try:
         for t, fr in enumerate(frames):
@@ -123,25 +66,6 @@ def test_integer_search_matches_the_model(gpu, cfg):
 
 
 # ---- 3. closed loop over the tool set
-CLOSED = [
-    dict(n=2), dict(n=3), dict(n=4),
-    dict(n=3, opts=(("wpp", 0), ("tiles", "2x2"))),
-    dict(n=2, opts=(("slices", "wpp"),)),
-    dict(n=4, opts=(("tiles", "2x2"), ("slices", "tiles"), ("wpp", 0))),
-    dict(n=3, owf=1), dict(n=4, owf=3), dict(n=4, owf=6, opts=(("period", 5),)), dict(n=2, owf=6, opts=(("period", 1),)),
-    dict(n=3, opts=(("period", 5),)), dict(n=4, opts=(("period", 64),), frames=12),
-    dict(n=3, opts=(("subme", 2),)), dict(n=4, opts=(("subme", 4), ("sao", "full"))),
-    dict(n=3, opts=(("rdoq", 1), ("signhide", 1))),
-    dict(n=3, opts=(("intra-in-p", 1), ("subme", 2))), dict(n=4, opts=(("intra-in-p", 2),), kind=2),
-    dict(n=3, bitrate=400000), dict(n=3, bitrate=400000, opts=(("rc-algorithm", "lambda"), ("sao", "full"))),
-    dict(n=2, opts=(("set-qp-in-cu", 1),), roi=True), dict(n=3, opts=(("vaq", 6),)),
-    dict(n=3, opts=(("lossless", 1),)), dict(n=4, opts=(("scaling-list", "default"),)),
-    dict(n=3, opts=(("gpu-entropy", 1),)), dict(n=4, opts=(("gpu-entropy", 1), ("owf", 2))),
-    dict(n=3, fields={"hash": 2}, sei=True),                        # md5 SEI (the wrapper sets kvz_config.hash itself)
-    dict(n=4, opts=(("me-source", 1), ("subme", 2), ("intra-in-p", 1), ("sao", "full")), owf=3),
-    dict(n=2, opts=(("deblock", 0),)),
-    dict(n=4, kind=2, opts=(("qp", 22), ("me-early-termination", "off"))),
-]
 
 
 @pytest.mark.gpu
@@ -154,7 +78,7 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
     if br:
         opts += (("bitrate", br),)
     fields = dict(cfg.get("fields", {}), **({"target_bitrate": br} if br else {}))
-    ge = _encoder(w, h, cfg["n"], opts, fields=fields or None)
+    ge = enckit.encoder(w, h, (("lp-refs", cfg["n"]),) + opts, fields=fields or None)
     if cfg.get("roi"):
         import ctypes as C
         deltas = (np.arange(12, dtype=np.int8) % 7 - 3).astype(np.int8)
@@ -162,28 +86,28 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
         for pic in ge.pics:
             pic.contents.roi.width, pic.contents.roi.height = 4, 3
             pic.contents.roi.roi_array = deltas.ctypes.data_as(C.POINTER(C.c_int8))
-    frames = _frames(cfg.get("kind", 0), w, h, cfg.get("frames", 8))
-    pairs = _encode_all(ge, frames, owf)
+    frames = enckit.frames(cfg.get("kind", 0), w, h, cfg.get("frames", 8))
+    pairs = enckit.encode_all(ge, frames, owf)
     ge.close()
-    _closed_loop(w, h, pairs, sei=cfg.get("sei", False))
+    enckit.closed_loop(pairs, sei=cfg.get("sei", False))
 
 
 @pytest.mark.gpu
 def test_closed_loop_smallest_case_also_matches_pyhevc(gpu):
     w, h = 128, 64
-    ge = _encoder(w, h, 3, (("me-range", 8),))
-    pairs = _encode_all(ge, _frames(0, w, h, 5))
+    ge = enckit.encoder(w, h, (("lp-refs", 3), ("me-range", 8)))
+    pairs = enckit.encode_all(ge, enckit.frames(0, w, h, 5))
     ge.close()
-    _closed_loop(w, h, pairs, pyhevc_too=True)
+    enckit.closed_loop(pairs, pyhevc_too=True)
 
 
 @pytest.mark.gpu
 def test_closed_loop_1080p_three_references(gpu):
     w, h = 1920, 1080
-    ge = _encoder(w, h, 3, (("preset", "veryfast"),))
-    pairs = _encode_all(ge, _frames(0, w, h, 8))
+    ge = enckit.encoder(w, h, (("lp-refs", 3), ("preset", "veryfast")))
+    pairs = enckit.encode_all(ge, enckit.frames(0, w, h, 8))
     ge.close()
-    _closed_loop(w, h, pairs)
+    enckit.closed_loop(pairs)
 
 
 # ---- 4. the benefit: picture t repeats picture t - 2
@@ -199,7 +123,7 @@ def test_two_alternating_scenes_use_the_older_reference(gpu):
     frames = _alternating(w, h, nf)
     sizes = {}
     for n in (1, 2):
-        ge = _encoder(w, h, n, (("qp", 30),))
+        ge = enckit.encoder(w, h, (("lp-refs", n), ("qp", 30)))
         sz, refs = [], []
         for t, f in enumerate(frames):
             au, _ = ge.encode(f)
@@ -224,7 +148,7 @@ def test_filter_chain_with_three_references(gpu):
     pl = Pipeline(w, h, settings={"video/QP": 30, "video/Intra": 64}, custom=(("me-range", 12), ("lp-refs", 3)))
     od = orc.OracleDecoder()
     try:
-        clip = _frames(0, w, h, nf)
+        clip = enckit.frames(0, w, h, nf)
         for f in clip:
             pl.push(f)
         assert pl.wait(nf, 60000)

@@ -8,19 +8,12 @@ T4: what it buys on the pan clip; T5: through the filter chain; T6: band mode re
 import numpy as np
 import pytest
 
+import enckit
 import me_coarse_model
 import orc
 import pan_content
-from test_gpu_lp_refs import _closed_loop, _encode_all
-
-SEED = 0x5EED0000
-
-
-def _encoder(w, h, opts=(), fields=None):
-    from kvazzup_amd.codec import Encoder
-    ge = Encoder(w, h, options=tuple(opts), fields=fields)
-    assert not ge.rejected, ge.rejected
-    return ge
+from cases import ME_COARSE_CLOSED as CLOSED, ME_COARSE_SEARCH as SEARCH
+from enckit import SEED
 
 
 def _clip(name, w, h, n):
@@ -39,11 +32,10 @@ GUARD = [dict(n=1), dict(n=1, subme=2, sao=1, intra_in_p=1), dict(n=1, tiles=(2,
 @pytest.mark.parametrize("clip", ["moving", (36, -20)], ids=["moving", "pan"])
 @pytest.mark.parametrize("cfg", GUARD, ids=["plain", "subme2_sao_intra_in_p1", "tiles2x2_owf3_me_source1", "lp_refs3_tmvp1"])
 def test_off_is_the_encoder_of_before(gpu, cfg, clip):
-    import test_gpu_lp_refs_oracle as tlo
     w, h, nf = 320, 192, 5
     c = dict(dict(w=w, h=h, R=12), **cfg)
     frames = _clip(clip, w, h, nf)
-    oe = tlo._checker(w, h, c)
+    oe = enckit.checker(w, h, c)
     want = []
     for f in frames:
         au = oe.encode(f)
@@ -54,8 +46,8 @@ def test_off_is_the_encoder_of_before(gpu, cfg, clip):
             ("subme", c.get("subme", 0)), ("intra-in-p", c.get("intra_in_p", 0)), ("me-source", c.get("me_source", 0)), ("owf", c.get("owf", 0)),
             ("lp-refs", c["n"]), ("tmvp", c.get("tmvp", 0)))
     for extra in ((), (("me-coarse", 0),)):
-        ge = _encoder(w, h, base + extra)
-        got = _encode_all(ge, frames, c.get("owf", 0))
+        ge = enckit.encoder(w, h, base + extra)
+        got = enckit.encode_all(ge, frames, c.get("owf", 0))
         if extra:
             assert "me_coarse" not in ge.debug_all()
         ge.close()
@@ -65,21 +57,6 @@ def test_off_is_the_encoder_of_before(gpu, cfg, clip):
 
 
 # ---- T2 search = model
-SEARCH = [
-    dict(clip=(72, -40), reach=128),
-    dict(clip=(-100, 24), reach=128, me_source=1),
-    dict(clip=(9, 150), reach=256),
-    dict(clip=(200, 0), reach=256, R=8),
-    dict(clip=(-44, -52), reach=64, n=3, frames=5),
-    dict(clip=(72, -40), reach=128, n=3, me_source=1, frames=4),
-    dict(clip=(-60, 36), reach=64, tiles="2x2"),
-    dict(clip=(50, 70), reach=128, mv_frame=2, tiles="2x2"),
-    dict(clip=(-72, 40), reach=128, mv_frame=2),
-    dict(clip="moving", reach=128, me_early=1, frames=4),
-    dict(clip="moving", reach=64, me_early=0, kind=2, n=3, frames=4, R=8),
-    dict(clip=(72, -40), reach=128, me_early=0),
-    dict(clip=(40, 28), reach=64, w=1920, h=1080, frames=2),
-]
 
 
 def _sid(c):
@@ -100,7 +77,7 @@ def test_search_matches_the_model(gpu, cfg):
         frames = [orc.synth_frame(cfg.get("kind", 0), SEED, w, h, t) for t in range(nf)]
     else:
         frames = pan_content.clip(w, h, nf, *cfg["clip"])
-    ge = _encoder(w, h, opts)
+    ge = enckit.encoder(w, h, opts)
     srcs, recs = [], []
     longest = 0
     try:
@@ -131,22 +108,6 @@ def test_search_matches_the_model(gpu, cfg):
 
 
 # ---- T3 closed loop over the tool set
-CLOSED = [
-    dict(pan=(72, -40)), dict(pan=(-72, 40), opts=(("subme", 2),)), dict(pan=(40, 72), opts=(("subme", 4), ("sao", "full"))),
-    dict(pan=(-40, -72), opts=(("rdoq", 1), ("signhide", 1))),
-    dict(pan=(72, -40), opts=(("intra-in-p", 1), ("subme", 2))), dict(pan=(-100, 24), opts=(("intra-in-p", 2),)),
-    dict(pan=(72, 40), opts=(("lp-refs", 2),)), dict(pan=(-72, -40), opts=(("lp-refs", 3), ("tmvp", 1))), dict(pan=(20, -90), opts=(("lp-refs", 4), ("subme", 2), ("tmvp", 1))),
-    dict(pan=(72, -40), opts=(("tmvp", 1),)),
-    dict(pan=(-72, 40), opts=(("tiles", "2x2"), ("wpp", 0))), dict(pan=(72, 40), opts=(("tiles", "2x2"), ("slices", "tiles"), ("wpp", 0))), dict(pan=(-72, -40), opts=(("slices", "wpp"),)),
-    dict(pan=(72, -40), opts=(("wpp", 0),)),
-    dict(pan=(72, -40), owf=1), dict(pan=(-72, 40), owf=3), dict(pan=(40, -72), owf=6, opts=(("period", 5),), frames=12),
-    dict(pan=(72, -40), bitrate=400000), dict(pan=(-72, 40), bitrate=400000, opts=(("rc-algorithm", "lambda"), ("sao", "full"))),
-    dict(pan=(72, 40), opts=(("vaq", 6),)), dict(pan=(-72, -40), opts=(("lossless", 1),)), dict(pan=(72, -40), opts=(("scaling-list", "default"),)),
-    dict(pan=(-72, 40), opts=(("gpu-entropy", 1),)), dict(pan=(72, 40), fields={"hash": 2}, sei=True), dict(pan=(-72, -40), opts=(("deblock", 0),)),
-    dict(pan=(230, 0), reach=256), dict(pan=(-9, -150), reach=256, opts=(("subme", 2), ("lp-refs", 2))), dict(pan=(0, 260), reach=256, opts=(("me-source", 1), ("subme", 2))),
-    dict(pan=(-250, 120), reach=256, opts=(("sao", "full"), ("tmvp", 1))),
-    dict(pan=(60, -36), reach=64, opts=(("me-source", 1), ("subme", 2), ("intra-in-p", 1), ("sao", "full")), owf=3),
-]
 
 
 @pytest.mark.gpu
@@ -159,33 +120,28 @@ def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
     if br:
         opts += (("bitrate", br),)
     fields = dict(cfg.get("fields", {}), **({"target_bitrate": br} if br else {}))
-    ge = _encoder(w, h, opts, fields=fields or None)
+    ge = enckit.encoder(w, h, opts, fields=fields or None)
     frames = pan_content.clip(w, h, cfg.get("frames", 6), *cfg["pan"])
-    pairs = _encode_all(ge, frames, owf)
+    pairs = enckit.encode_all(ge, frames, owf)
     d = ge.debug_all()
     ge.close()
     if not br and "lossless" not in dict(cfg.get("opts", ())):
         assert int(np.abs(d["cu_mv"].astype(np.int32)).max()) > 4 * 32, "the case does not leave the old window"
-    _closed_loop(w, h, pairs, sei=cfg.get("sei", False))
+    enckit.closed_loop(pairs, sei=cfg.get("sei", False))
 
 
 @pytest.mark.gpu
 def test_closed_loop_small_case_also_matches_pyhevc(gpu):
     w, h = 256, 128
-    ge = _encoder(w, h, (("me-range", 8), ("me-coarse", 64), ("subme", 2)))
-    pairs = _encode_all(ge, pan_content.clip(w, h, 4, 44, -36))
+    ge = enckit.encoder(w, h, (("me-range", 8), ("me-coarse", 64), ("subme", 2)))
+    pairs = enckit.encode_all(ge, pan_content.clip(w, h, 4, 44, -36))
     d = ge.debug_all()
     ge.close()
     assert int(np.abs(d["cu_mv"].astype(np.int32)).max()) > 4 * 32
-    _closed_loop(w, h, pairs, pyhevc_too=True)
+    enckit.closed_loop(pairs, pyhevc_too=True)
 
 
 # ---- T4 what it buys
-def _psnr_y(a, b, n):
-    mse = np.mean((a[:n].astype(np.float64) - b[:n].astype(np.float64)) ** 2)
-    return 10 * np.log10(255.0 ** 2 / mse)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("subme", [0, 2])
 def test_pan_costs_fewer_bytes(gpu, subme):
@@ -193,10 +149,10 @@ def test_pan_costs_fewer_bytes(gpu, subme):
     frames = pan_content.clip(w, h, nf, 72, -40)
     res = {}
     for mc in (0, 128):
-        ge = _encoder(w, h, (("qp", 32), ("me-range", 16), ("subme", subme), ("me-coarse", mc)))
-        pairs = _encode_all(ge, frames)
+        ge = enckit.encoder(w, h, (("qp", 32), ("me-range", 16), ("subme", subme), ("me-coarse", mc)))
+        pairs = enckit.encode_all(ge, frames)
         ge.close()
-        res[mc] = (sum(len(au) for au, _ in pairs[1:]), np.mean([_psnr_y(rec, frames[t], w * h) for t, (_, rec) in enumerate(pairs) if t]))
+        res[mc] = (sum(len(au) for au, _ in pairs[1:]), np.mean([enckit.psnr_y(rec, frames[t], w * h) for t, (_, rec) in enumerate(pairs) if t]))
     print("me-coarse 0: %d bytes of P pictures, %.3f dB; 128: %d bytes, %.3f dB" % (res[0] + res[128]))
     assert res[128][0] < res[0][0], res
     assert res[128][1] >= res[0][1] - 0.1, res
@@ -208,8 +164,8 @@ def test_flat_clip_does_not_change(gpu):
     frames = _clip("flat", w, h, 5)
     out = []
     for mc in (0, 128):
-        ge = _encoder(w, h, (("qp", 32), ("me-coarse", mc)))
-        out.append(_encode_all(ge, frames))
+        ge = enckit.encoder(w, h, (("qp", 32), ("me-coarse", mc)))
+        out.append(enckit.encode_all(ge, frames))
         ge.close()
     for (a, ra), (b, rb) in zip(*out):
         assert a == b and np.array_equal(ra, rb)

@@ -6,13 +6,10 @@ import numpy as np
 import pytest
 
 import orc
-from test_gpu_encoder import _diagnose
-
-SEED = 0x5EED0000
+from enckit import SEED, diagnose as _diagnose, encoder
 
 
 def _pair(w, h, cfg, owf=0):
-    from kvazzup_amd.codec import Encoder
     tiles = cfg.get("tiles", "1x1"); tc, tr = [int(v) for v in tiles.split("x")]
     br = cfg.get("bitrate", 0)
     oe = orc.OracleEncoder(w, h, qp=cfg.get("qp", 32), period=cfg.get("period", 64), me_range=cfg.get("me_range", 16), subme=cfg.get("subme", 0), sao=cfg.get("sao", 0),
@@ -24,9 +21,7 @@ def _pair(w, h, cfg, owf=0):
             ("subme", cfg.get("subme", 0)), ("sao", "full" if cfg.get("sao") else "off"), ("owf", owf), ("me-early-termination", "on" if cfg.get("me_early", 1) else "off"),
             ("mv-constraint", ("none", "frame", "frametilemargin")[cfg.get("mv_frame", 0)]))
     opts += ((("tiles", tiles),) if tiles != "1x1" else ()) + ((("vaq", cfg["vaq"]),) if cfg.get("vaq") else ()) + ((("bitrate", br), ("rc-algorithm", "lambda")) if br else ())
-    ge = Encoder(w, h, options=opts, fields={"target_bitrate": br})
-    assert not ge.rejected, ge.rejected
-    return oe, ge
+    return oe, encoder(w, h, opts, fields={"target_bitrate": br})
 
 
 def _frame(cfg, w, h, t):

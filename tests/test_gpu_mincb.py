@@ -3,7 +3,7 @@ binarisation of the minimum size, an inter coding unit cut into four square pred
 prediction blocks.  The synthesiser writes them (min_cb_log2); the HIP decoder must reproduce the checker's decoder bit for bit."""
 import pytest
 
-from test_gpu_foreign import PLAIN, run_stream
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

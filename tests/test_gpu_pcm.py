@@ -3,7 +3,7 @@ and starts again behind them; pcm_loop_filter_disabled_flag) -- round 6.  The sy
 checker's decoder bit for bit."""
 import pytest
 
-from test_gpu_foreign import PLAIN, run_stream
+from deckit import PLAIN, run_stream
 
 
 @pytest.mark.gpu

@@ -7,32 +7,8 @@ import numpy as np
 import pytest
 
 import orc
-from test_gpu_foreign import PLAIN
-from test_random_access import EOS, rasl_of, rename, vcl_type
-
-
-def both(cut, pts, threads=1, frame_threads=False):
-    """the access units `cut` (time stamps `pts`) through the checker and the product: the pictures must agree, in order"""
-    from kvazzup_amd.codec import Decoder
-    od = orc.OracleDecoder()
-    gd = Decoder(threads=threads, frame_threads=frame_threads) if frame_threads else Decoder()
-    want, got = [], []
-    try:
-        for p, au in zip(pts, cut):
-            want += od.decode_au(au, p)
-            got += gd.decode_au(au, p)
-        want += od.flush()
-        got += gd.drain()
-        assert [f["pts"] for f in got] == [f["pts"] for f in want]
-        for a, b in zip(got, want):
-            assert (a["width"], a["height"]) == (b["width"], b["height"])
-            if not np.array_equal(a["i420"], b["i420"]):
-                d = np.flatnonzero(a["i420"] != b["i420"])
-                pytest.fail("picture with time stamp %d: %d samples differ, first at %d" % (a["pts"], len(d), d[0]))
-    finally:
-        gd.close()
-        od.close()
-    return [f["pts"] for f in want]
+from deckit import PLAIN, both
+from nalkit import EOS, rasl_of, rename, vcl_type
 
 
 def stream(w, h, n, seed, **kw):
@@ -135,7 +111,7 @@ def test_random_streams_with_random_access_points(gpu, seed):
 def test_no_output_of_prior_pics_flag(gpu, seed, threads):
     """C.5.2.2: IDR pictures (and a CRA picture called BLA) whose flag says that what still waits for its turn is not to be shown -- exactly the pictures the standard's
     process holds at that instant disappear, whatever the frame threads' timing"""
-    from test_random_access import discard_prior
+    from nalkit import discard_prior
     g = orc.OracleGen(416, 240, seed=seed, gop=(2, 4, 8)[seed % 3], open_gop=seed & 1, intra_period=7 + seed % 4, b_slices=50, num_refs=1 + seed % 4, tmvp=1,
                       hidden_pics=(0, 10)[seed % 2], slices=(0, 1, 3)[seed % 3])
     aus = [g.picture() for _ in range(32)]
@@ -154,7 +130,7 @@ def test_no_output_of_prior_pics_flag(gpu, seed, threads):
 def test_temporal_sub_layers(gpu, seed, threads):
     """TemporalId in the NAL unit headers, parameter sets with sub-layers, sub-layer non-reference pictures (what Kvazaar's gop=8 sends) -- the whole stream, and the
     stream a middlebox has thinned to its lower sub-layers"""
-    from test_random_access import layered, tid_of
+    from nalkit import layered, tid_of
     aus = layered(seed, n=28, w=416, h=240, slices=(0, 1, 3)[seed % 3], hidden_pics=(0, 10)[seed & 1])
     tids = [tid_of(a) for a in aus]
     both(aus, range(len(aus)), threads, threads > 1)
@@ -228,7 +204,7 @@ def test_the_highest_sub_layer_to_decode_can_be_set(gpu, seed, threads):
     """libOpenHevcSetTemporalLayer_id(h, k): the WHOLE stream goes in, the slice NAL units of the sub-layers above k are dropped inside -- the pictures are those of the
     stream thinned by hand.  (OpenHEVC's default is 7; uvgComm's filter passes 0, openhevcfilter.cpp:54 -- a peer's gop=8 stream plays at its base layer's rate there.)"""
     from kvazzup_amd.codec import Decoder
-    from test_random_access import layered, tid_of
+    from nalkit import layered, tid_of
     aus = layered(seed, n=28, w=416, h=240)
     tids = [tid_of(a) for a in aus]
     for keep in range(max(tids) + 1):

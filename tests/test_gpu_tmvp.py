@@ -10,78 +10,10 @@ encoder to it bit for bit, the bitrate cases included.)"""
 import numpy as np
 import pytest
 
+import enckit
+import hc
 import orc
-from test_tmvp_host import ht, col_record
-
-SEED = 0x5EED0000
-
-
-def _encoder(w, h, opts=(), fields=None):
-    from kvazzup_amd.codec import Encoder
-    ge = Encoder(w, h, options=tuple(opts), fields=fields)
-    assert not ge.rejected, ge.rejected
-    return ge
-
-
-def _encode_all(ge, frames, owf=0):
-    out = []
-    for t in range(len(frames) + owf + 1):
-        au, rec = ge.encode(frames[t] if t < len(frames) else None)
-        if au:
-            out.append((au, rec))
-    assert len(out) == len(frames), len(out)
-    return out
-
-
-def _frames(kind, w, h, n):
-    return [orc.synth_frame(kind, SEED, w, h, t) for t in range(n)]
-
-
-def _pan(w, h, n, dx=4, dy=2):
-    """a textured picture moving (dx, dy) samples per picture: every block's motion is its collocated block's"""
-    big = orc.synth_frame(0, SEED, 2 * w, 2 * h, 0)
-    Y = big[:4 * w * h].reshape(2 * h, 2 * w)
-    U = big[4 * w * h:5 * w * h].reshape(h, w)
-    V = big[5 * w * h:].reshape(h, w)
-    out = []
-    for t in range(n):
-        x0, y0 = w // 2 - dx * t, h // 2 - dy * t
-        out.append(np.concatenate([Y[y0:y0 + h, x0:x0 + w].ravel(), U[y0 // 2:y0 // 2 + h // 2, x0 // 2:x0 // 2 + w // 2].ravel(),
-                                   V[y0 // 2:y0 // 2 + h // 2, x0 // 2:x0 // 2 + w // 2].ravel()]).astype(np.uint8))
-    return out
-
-
-def _closed_loop(pairs, sei=False, pyhevc_too=False):
-    from kvazzup_amd.codec import Decoder
-    od, gd, gf = orc.OracleDecoder(), Decoder(), Decoder(threads=4, frame_threads=True)
-    try:
-        for t, (au, rec) in enumerate(pairs):
-            a = od.decode_au(au, t)
-            assert len(a) == 1 and np.array_equal(a[0]["i420"], rec), "picture %d: the checker's decoder differs from the encoder's reconstruction" % t
-            b = gd.decode_au(au, t)
-            assert len(b) == 1 and np.array_equal(b[0]["i420"], rec), "picture %d: the HIP decoder differs from the encoder's reconstruction" % t
-        if sei:
-            checked, bad = od.hash_stats()
-            assert checked == len(pairs) and bad == 0, (checked, bad)
-        got = []
-        for t, (au, _) in enumerate(pairs):
-            got += gf.decode_au(au, t)
-        got += gf.drain()
-        assert len(got) == len(pairs), len(got)
-        for t, p in enumerate(got):
-            assert np.array_equal(p["i420"], pairs[t][1]), "picture %d: the frame-threaded HIP decoder differs" % t
-    finally:
-        od.close(); gd.close(); gf.close()
-    if pyhevc_too:
-        import pyhevc
-        from test_python_decoder import tabs
-        dec = pyhevc.Decoder(tabs())
-        for au, _ in pairs:
-            dec.decode(au)
-        pics = dec.flush()
-        assert len(pics) == len(pairs)
-        for t, p in enumerate(pics):
-            assert np.array_equal(p["i420"], pairs[t][1]), "picture %d: tests/pyhevc.py differs" % t
+from hc import col_record
 
 
 # ---- 4 + 5. the same pictures as without tmvp, and the closed loop
@@ -111,17 +43,17 @@ def test_same_pictures_and_closed_loop(gpu, cfg):
     opts = (("owf", owf), ("me-range", 12)) + tuple(cfg.get("opts", ())) + ((("bitrate", br),) if br else ())
     fields = dict(({"target_bitrate": br} if br else {}), **({"hash": 2} if cfg.get("sei") else {}))
     n = cfg.get("frames", 9)
-    frames = _pan(w, h, n) if cfg.get("pan") else _frames(cfg.get("kind", 0), w, h, n)
+    frames = enckit.pan(w, h, n) if cfg.get("pan") else enckit.frames(cfg.get("kind", 0), w, h, n)
     runs = {}
     for tmvp in (0, 1):
-        ge = _encoder(w, h, opts + (("tmvp", tmvp),), fields=fields or None)
-        runs[tmvp] = _encode_all(ge, frames, owf)
+        ge = enckit.encoder(w, h, opts + (("tmvp", tmvp),), fields=fields or None)
+        runs[tmvp] = enckit.encode_all(ge, frames, owf)
         ge.close()
     if not br:
         for t in range(n):
             assert np.array_equal(runs[0][t][1], runs[1][t][1]), "picture %d: tmvp changed the reconstruction" % t
     assert any(a[0] != b[0] for a, b in zip(runs[0], runs[1])), "tmvp changed no access unit"
-    _closed_loop(runs[1], sei=cfg.get("sei", False), pyhevc_too=cfg.get("pyhevc", False))
+    enckit.closed_loop(runs[1], sei=cfg.get("sei", False), pyhevc_too=cfg.get("pyhevc", False), frame_threaded=True)
 
 
 # ---- 6. the decisions against the host derivation, the record against the picture's fields
@@ -137,9 +69,9 @@ def test_decisions_match_the_host_derivation(gpu, cfg):
     opts = dict(cfg.get("opts", ()))
     period = int(opts.get("period", 64))
     tc, tr = [int(v) for v in opts.get("tiles", "1x1").split("x")]
-    ge = _encoder(w, h, (("me-range", 12), ("lp-refs", lp), ("tmvp", 1)) + tuple(cfg.get("opts", ())))
+    ge = enckit.encoder(w, h, (("me-range", 12), ("lp-refs", lp), ("tmvp", 1)) + tuple(cfg.get("opts", ())))
     cw, ch = ge.coded_size()
-    frames = _frames(0, w, h, 9)
+    frames = enckit.frames(0, w, h, 9)
     prev_col = None
     temporal_used = 0
     try:
@@ -154,22 +86,18 @@ def test_decisions_match_the_host_derivation(gpu, cfg):
             col = ge.debug("col", np.int16, (ch // 16, cw // 16, 4))
             assert np.array_equal(col, col_record(d["cu_intra"], d["cu_mv"], d["cu_ref"])), "picture %d: the collocated record" % t
             nact = min(max(lp, 1), poc)
-            b8 = (ch // 8, cw // 8)
-            want = {k: np.zeros(b8, np.uint8) for k in ("flags", "midx", "mvp")}
-            wmvd = np.zeros(b8 + (2,), np.int16); out = np.zeros_like(col)
-            a = [np.ascontiguousarray(d[k]) for k in ("cu_log2", "cu_intra", "cu_mv", "cu_ref", "cu_cbf")]
+            a = [d[k] for k in ("cu_log2", "cu_intra", "cu_mv", "cu_ref", "cu_cbf")]
             use = prev_col if poc >= 2 else None
-            ht().ht_picture(cw, ch, tr, tc, nact, *[v.ctypes.data for v in a], use.ctypes.data if use is not None else None,
-                            want["flags"].ctypes.data, want["midx"].ctypes.data, want["mvp"].ctypes.data, wmvd.ctypes.data, out.ctypes.data)
+            want = {}
+            want["flags"], want["midx"], want["mvp"], wmvd, _ = hc.picture(cw, ch, tr, tc, nact, a, col=use)
             inter = d["cu_intra"] == 0
             for name, got, exp in (("cu_flags", d["cu_flags"], want["flags"]), ("cu_merge_idx", d["cu_merge_idx"], want["midx"]),
                                    ("cu_mvp_idx", d["cu_mvp_idx"], want["mvp"]), ("cu_mvd", mvd, wmvd)):
                 bad = np.argwhere(inter & (np.any(got != exp, axis=-1) if got.ndim == 3 else (got != exp)))
                 assert not len(bad), "picture %d: %s differs at %d units, first %s" % (t, name, len(bad), bad[0].tolist())
             if use is not None:
-                f0 = {k: np.zeros(b8, np.uint8) for k in ("flags", "midx", "mvp")}; m0 = np.zeros_like(wmvd)
-                ht().ht_picture(cw, ch, tr, tc, nact, *[v.ctypes.data for v in a], None, f0["flags"].ctypes.data, f0["midx"].ctypes.data, f0["mvp"].ctypes.data,
-                                m0.ctypes.data, out.ctypes.data)
+                f0 = {}
+                f0["flags"], f0["midx"], f0["mvp"], _, _ = hc.picture(cw, ch, tr, tc, nact, a)
                 temporal_used += int((inter & ((f0["flags"] != want["flags"]) | (f0["midx"] != want["midx"]) | (f0["mvp"] != want["mvp"]))).sum())
             prev_col = col
     finally:
@@ -181,9 +109,9 @@ def test_decisions_match_the_host_derivation(gpu, cfg):
 @pytest.mark.gpu
 def test_pan_uses_the_temporal_candidates(gpu):
     w, h = 320, 192
-    ge = _encoder(w, h, (("me-range", 12), ("tmvp", 1), ("qp", 30)))
+    ge = enckit.encoder(w, h, (("me-range", 12), ("tmvp", 1), ("qp", 30)))
     cw, ch = ge.coded_size()
-    frames = _pan(w, h, 6)
+    frames = enckit.pan(w, h, 6)
     prev_col, merged_t, amvp_t, inter_cus = None, 0, 0, 0
     try:
         for t, fr in enumerate(frames):
@@ -193,11 +121,8 @@ def test_pan_uses_the_temporal_candidates(gpu):
             d = ge.debug_all()
             col = ge.debug("col", np.int16, (ch // 16, cw // 16, 4))
             if t >= 2:
-                a = [np.ascontiguousarray(d[k]) for k in ("cu_log2", "cu_intra", "cu_mv", "cu_ref", "cu_cbf")]
-                b8 = (ch // 8, cw // 8)
-                f0, i0, p0 = np.zeros(b8, np.uint8), np.zeros(b8, np.uint8), np.zeros(b8, np.uint8)
-                m0, out = np.zeros(b8 + (2,), np.int16), np.zeros_like(col)
-                ht().ht_picture(cw, ch, 1, 1, 1, *[v.ctypes.data for v in a], None, f0.ctypes.data, i0.ctypes.data, p0.ctypes.data, m0.ctypes.data, out.ctypes.data)
+                a = [d[k] for k in ("cu_log2", "cu_intra", "cu_mv", "cu_ref", "cu_cbf")]
+                f0, i0, p0, _, _ = hc.picture(cw, ch, 1, 1, 1, a)
                 inter = d["cu_intra"] == 0
                 inter_cus += int(inter.sum())
                 # merged where the derivation without the temporal candidate could not merge, or merged elsewhere: the temporal candidate
@@ -213,14 +138,14 @@ def test_pan_uses_the_temporal_candidates(gpu):
 @pytest.mark.gpu
 def test_explicit_off_is_the_default(gpu):
     w, h = 320, 192
-    frames = _frames(0, w, h, 6)
+    frames = enckit.frames(0, w, h, 6)
     for opts in ((), (("lp-refs", 3), ("owf", 2), ("sao", "full"))):
         owf = int(dict(opts).get("owf", 0))
-        a = _encoder(w, h, opts)
-        ra = _encode_all(a, frames, owf)
+        a = enckit.encoder(w, h, opts)
+        ra = enckit.encode_all(a, frames, owf)
         a.close()
-        b = _encoder(w, h, opts + (("tmvp", 0),))
-        rb = _encode_all(b, frames, owf)
+        b = enckit.encoder(w, h, opts + (("tmvp", 0),))
+        rb = enckit.encode_all(b, frames, owf)
         b.close()
         assert [x[0] for x in ra] == [x[0] for x in rb]
 
@@ -241,7 +166,7 @@ def test_filter_chain_with_tmvp(gpu):
     pl = Pipeline(w, h, settings={"video/QP": 30, "video/Intra": 64}, custom=(("me-range", 12), ("tmvp", 1)))
     od = orc.OracleDecoder()
     try:
-        for f in _frames(0, w, h, nf):
+        for f in enckit.frames(0, w, h, nf):
             pl.push(f)
         assert pl.wait(nf, 60000)
         for t in range(nf):

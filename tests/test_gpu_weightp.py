@@ -7,39 +7,27 @@ table alone; on a clip that darkens the option saves bits.  The clips are the be
 import numpy as np
 import pytest
 
+import enckit
 import lp_gop_model
 import lp_refs_model
 import orc
 import wp_model as M
-from test_gpu_lp_refs import _closed_loop
 
 KINDS = ("none", "offset", "gain", "flash")
 # references per P picture, lp-gop (g, d) or None, me-source
 SETUPS = {"one": (1, None, 0), "three": (3, None, 0), "one-src": (1, None, 1), "gop-src": (3, (4, 3), 1)}
+ON = (("weightp", 1),)
 
 
-def _encoder(w, h, opts=(), fields=None, on=1):
-    from kvazzup_amd.codec import Encoder
-    ge = Encoder(w, h, options=(("weightp", on),) + tuple(opts), fields=fields)
-    assert not ge.rejected, ge.rejected
-    return ge
+def _record(ge):
+    """the delivered picture's (flag, w, o) per reference"""
+    return [tuple(int(v) for v in r) for r in ge.debug("wp", np.int32, (4, 3))]
 
 
 def _clip(kind, w, h, n):
     """the benchmark clip (synth kind 0, seed 1234) with the change `kind` on its luma"""
     frames = M.change([orc.synth_frame(0, 1234, w, h, t) for t in range(n)], w, h, kind)
     return frames, [f[:w * h].reshape(h, w) for f in frames]
-
-
-def _run(ge, frames, owf=0):
-    """(access unit, reconstruction, record) of every picture, the pictures in flight flushed"""
-    out = []
-    for t in range(len(frames) + owf + 1):
-        au, rec = ge.encode(frames[t] if t < len(frames) else None)
-        if au:
-            out.append((au, rec, [tuple(int(v) for v in r) for r in ge.debug("wp", np.int32, (4, 3))]))
-    assert len(out) == len(frames), len(out)
-    return out
 
 
 # ---- 1. the record and the integer search against the models
@@ -55,7 +43,7 @@ def test_record_and_search_match_the_models(gpu, size, kind, setup):
     if gop:
         opts += (("gop", "lp-g%dd%dt1" % gop), ("lp-gop", 1))
     frames, ys = _clip(kind, w, h, nf)
-    ge = _encoder(w, h, opts)
+    ge = enckit.encoder(w, h, ON + opts)
     recs, weighted0 = [], 0
     try:
         for t, fr in enumerate(frames):
@@ -105,25 +93,25 @@ CLOSED = [
 def test_closed_loop_decodes_to_the_reconstruction(gpu, cfg):
     w, h, owf, br = cfg.get("w", 320), cfg.get("h", 192), cfg.get("owf", 0), cfg.get("bitrate", 0)
     opts = (("owf", owf), ("me-range", 12)) + tuple(cfg.get("opts", ())) + ((("bitrate", br),) if br else ())
-    ge = _encoder(w, h, opts, fields={"target_bitrate": br} if br else None)
+    ge = enckit.encoder(w, h, ON + opts, fields={"target_bitrate": br} if br else None)
     frames, _ = _clip(cfg["kind"], w, h, 8)
-    out = _run(ge, frames, owf)
+    out = enckit.encode_all(ge, frames, owf, per_picture=_record)
     ge.close()
     weighted = sum(r[0][0] for _, _, r in out)
     assert (weighted == 0) if cfg["kind"] == "none" else (weighted >= 2), weighted      # (the streams exercise the weighted paths, the last one the plain path under the flag)
-    _closed_loop(w, h, [(au, rec) for au, rec, _ in out])
+    enckit.closed_loop([(au, rec) for au, rec, _ in out])
 
 
 @pytest.mark.gpu
 def test_closed_loop_smallest_case_also_matches_pyhevc(gpu):
     w, h = 128, 64
     for kind, extra in (("offset", (("lp-refs", 2),)), ("gain", (("subme", 2),))):
-        ge = _encoder(w, h, (("me-range", 8),) + extra)
+        ge = enckit.encoder(w, h, ON + (("me-range", 8),) + extra)
         frames, _ = _clip(kind, w, h, 5)
-        out = _run(ge, frames)
+        out = enckit.encode_all(ge, frames, per_picture=_record)
         ge.close()
         assert sum(r[0][0] for _, _, r in out) >= 2
-        _closed_loop(w, h, [(au, rec) for au, rec, _ in out], pyhevc_too=True)
+        enckit.closed_loop([(au, rec) for au, rec, _ in out], pyhevc_too=True)
 
 
 # ---- 3. an unchanged clip: the reconstructions of the encoder without the option, access units longer by the table alone
@@ -136,12 +124,8 @@ def test_unchanged_clip_costs_the_table_alone(gpu, opts):
     owf = dict(opts).get("owf", 0)
     runs = []
     for on in (0, 1):
-        ge = _encoder(w, h, (("me-range", 12),) + tuple(opts), on=on)
-        if on:
-            runs.append(_run(ge, frames, owf))
-        else:
-            from test_gpu_lp_refs import _encode_all
-            runs.append(_encode_all(ge, frames, owf))
+        ge = enckit.encoder(w, h, (("weightp", on), ("me-range", 12)) + tuple(opts))
+        runs.append(enckit.encode_all(ge, frames, owf, per_picture=_record if on else None))
         ge.close()
     for t in range(len(frames)):
         off_au, off_rec = runs[0][t]
@@ -161,7 +145,7 @@ def test_1080p_offset_clip_takes_fewer_bits(gpu):
     frames, _ = _clip("offset", w, h, 5)
     bits = []
     for on in (0, 1):
-        ge = _encoder(w, h, (("qp", 32), ("me-range", 16)), on=on)
+        ge = enckit.encoder(w, h, (("weightp", on), ("qp", 32), ("me-range", 16)))
         aus = [ge.encode(fr, want_recon=False)[0] for fr in frames]
         if on:
             assert int(ge.debug("wp", np.int32, (4, 3))[0][0]) == 1      # (the last picture's record)

@@ -23,8 +23,6 @@ def picture_tokens(w, h, t):
     dbg = oe.debug()
     f, hold = hc.make_frame(dbg, w, h, 32)
     L = hc.lib()
-    L.hc_picture_tokens.restype = C.c_long
-    L.hc_picture_tokens.argtypes = [C.c_void_p, C.c_void_p, C.c_long]
     tok = np.zeros(8 << 20, dtype=np.uint16)
     n = L.hc_picture_tokens(C.byref(f), tok.ctypes.data, len(tok))
     assert 0 < n < len(tok)

@@ -8,7 +8,7 @@ import pytest
 
 import hc
 import orc
-from test_oracle_kat import table
+from orc import table
 
 P = lambda a: a.ctypes.data_as(C.c_void_p)
 

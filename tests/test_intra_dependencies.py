@@ -49,8 +49,6 @@ def _masks(predict, n, cidx, trials=16):
 @pytest.mark.parametrize("which", ["checker", "product"])
 def test_masks_match_the_predictors(cidx, n, which):
     L = hc.lib()
-    L.hc_intra_uses.restype = C.c_uint64
-    L.hc_intra_uses.argtypes = [C.c_int, C.c_int, C.c_int]
     log2n = n.bit_length() - 1
     want = (L.hc_intra_uses(log2n, cidx, 0), L.hc_intra_uses(log2n, cidx, 1))
     got = _masks(_orc_predict if which == "checker" else _hc_predict, n, cidx)
@@ -65,8 +63,6 @@ def test_intra_chain_restriction_in_the_checker_encoder():
     below-left samples; off: all modes; both streams decode to the encoder's reconstruction, the restriction costs the intra picture a few per cent"""
     w, h = 320, 192
     L = hc.lib()
-    L.hc_intra_uses.restype = C.c_uint64
-    L.hc_intra_uses.argtypes = [C.c_int, C.c_int, C.c_int]
     sizes = {}
     for on in (1, 0):
         oe = orc.OracleEncoder(w, h, qp=30, period=1, me_range=8)

@@ -1,49 +1,20 @@
 """CPU side of "uvgx intra refresh v1" (kvazaar.h intra-refresh): the option's parsing; the statement functions of hevc_core.h (host build:
-tests/hostir) against the restatement tests/ir_model.py -- every coded width 64 .. 4096 under every N --; the access units: with the option off the bytes of
+tests/hostcheck) against the restatement tests/ir_model.py -- every coded width 64 .. 4096 under every N --; the access units: with the option off the bytes of
 before (tests/golden/tmvp_off_access_units.json), with it on one more NAL unit in a cycle's first picture, the recovery point SEI, which the decoder's host
 half (tests/parser_probe.py), the checker's decoder and tests/pyhevc.py pass over."""
-import ctypes as C
-import fcntl
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hc
 import ir_model as M
 import orc
 import pyhevc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-
-
-def hi():
-    global _LIB
-    if _LIB is None:
-        d = os.path.join(ROOT, "tests", "hostir")
-        with open(os.path.join(d, ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhostir.so"))
-        P = C.c_void_p
-        L.hi_band.argtypes = [C.c_int] * 3 + [P]
-        L.hi_schedules.argtypes = [C.c_int, P]
-        L.hi_bands.argtypes = [C.c_int, C.c_int, P]
-        L.hi_recovery_sei.argtypes = [C.c_int, P, C.c_int]
-        L.hi_access_unit.argtypes = [C.c_int] * 12 + [P, C.c_int, C.c_int, P, C.c_int]
-        _LIB = L
-    return _LIB
-
-
-def access_unit(w, h, poc, recovery=-1, lp=0, payload=b"", write_ps=1, sao=0, wpp=1, tr=1, tc=1, slices=0, weightp=0, qp_delta=0):
-    buf = np.zeros(1 << 20, np.uint8)
-    pl = np.frombuffer(bytes(payload) or b"\0", np.uint8)
-    n = hi().hi_access_unit(w, h, lp, sao, wpp, tr, tc, slices, weightp, poc, qp_delta, recovery, pl.ctypes.data, len(payload), write_ps, buf.ctypes.data, len(buf))
-    assert n > 0
-    return bytes(buf[:n])
 
 
 def nal_type(nal):
@@ -79,12 +50,12 @@ def test_every_schedule_matches_the_model_and_covers_the_picture():
     sched = np.zeros(2 * 254, np.int32)
     bands = np.zeros(2 * 256, np.int32)
     for cw in range(64, 4097, 64):
-        hi().hi_schedules(cw, sched.ctypes.data)
+        hc.lib().hi_schedules(cw, sched.ctypes.data)
         for N in range(2, 256):
             m, n = int(sched[2 * (N - 2)]), int(sched[2 * (N - 2) + 1])
             assert (m, n) == (M.step(cw, N), M.cycle(cw, N)), (cw, N)
             assert 1 <= n <= N and m >= 1, (cw, N, m, n)
-            assert hi().hi_bands(cw, N, bands.ctypes.data) == n
+            assert hc.lib().hi_bands(cw, N, bands.ctypes.data) == n
             got = [(int(bands[2 * j]), int(bands[2 * j + 1])) for j in range(n)]
             assert got == [M.band(cw, N, j) for j in range(n)], (cw, N)
             # the bands of a cycle cover [0, cw): they start at 0, end at cw, and each starts inside the one before
@@ -107,7 +78,7 @@ def test_positions_restart_behind_idr_pictures_and_cycles():
     for cw, N in ((320, 5), (320, 10), (256, 8), (640, 4), (1920, 30), (1920, 60), (3840, 255), (64, 2)):
         n = M.cycle(cw, N)
         for poc in range(1, 3 * n + 2):
-            assert hi().hi_position(cw, N, poc) == M.position(cw, N, poc) == (poc - 1) % n
+            assert hc.lib().hi_position(cw, N, poc) == M.position(cw, N, poc) == (poc - 1) % n
         assert M.record(cw, N, 0) == [-1, 0, 0, n] and M.record(cw, N, 1)[0] == 0 and M.record(cw, N, n + 1)[0] == 0 and M.record(cw, N, n)[2] == cw
 
 
@@ -118,17 +89,17 @@ def test_quarters_bound_and_last_column_match_the_model():
         for j in range(n):
             s, e = M.band(cw, N, j)
             for x0 in range(0, cw, 32):
-                q = hi().hi_forced_quarters(x0, s, e)
+                q = hc.lib().hi_forced_quarters(x0, s, e)
                 assert q == M.forced_quarters(x0, s, e) and q in (0, 5, 15), (cw, N, j, x0, q)
                 seen.add(q)
-                clean = bool(hi().hi_clean_block(x0, s, j))
+                clean = bool(hc.lib().hi_clean_block(x0, s, j))
                 assert clean == M.clean_block(x0, s, j)
                 if clean:
-                    assert q == 0 and hi().hi_mvx_max(x0, s) == M.mvx_max(x0, s) >= 0      # the zero vector is always admissible
+                    assert q == 0 and hc.lib().hi_mvx_max(x0, s) == M.mvx_max(x0, s) >= 0      # the zero vector is always admissible
                 assert not (q and clean)
                 for nb in (8, 16):
                     for xb in range(x0, x0 + 32, nb):
-                        assert bool(hi().hi_last_column(xb, nb, e, cw)) == M.last_column(xb, nb, e, cw)
+                        assert bool(hc.lib().hi_last_column(xb, nb, e, cw)) == M.last_column(xb, nb, e, cw)
             # the columns of the forced quarters are the band
             cols = sorted({x0 + 16 * (k & 1) for x0 in range(0, cw, 32) for k in range(4) if (M.forced_quarters(x0, s, e) >> k) & 1})
             assert cols == list(range(s, e, 16)), (cw, N, j)
@@ -137,10 +108,8 @@ def test_quarters_bound_and_last_column_match_the_model():
 
 # ---- 3. syntax
 def test_recovery_point_sei_is_the_models():
-    buf = np.zeros(64, np.uint8)
     for cnt in list(range(0, 255)) + [1000, 32767]:
-        n = hi().hi_recovery_sei(cnt, buf.ctypes.data, len(buf))
-        rbsp = bytes(buf[:n])
+        rbsp = hc.recovery_sei(cnt)
         assert rbsp == M.recovery_point_sei(cnt), cnt
         assert M.parse_recovery_point(rbsp) == (cnt, 1, 0), cnt
 
@@ -152,7 +121,7 @@ def test_access_units_with_the_option_off_are_the_parents_bytes():
     assert len(gold["cases"]) == 700
     for *args, digest in gold["cases"]:
         w, h, lp, sao, wpp, tr, tc, sl, poc = args
-        au = access_unit(w, h, poc, -1, lp=lp, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
+        au = hc.access_unit(w, h, poc, recovery=-1, lp=lp, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
         assert hashlib.sha256(au).hexdigest()[:16] == digest, args
 
 
@@ -162,9 +131,9 @@ def test_a_cycles_first_picture_gains_the_sei_and_nothing_else(cfg):
     n = M.cycle(320, N)
     for poc in range(0, 2 * n + 2):
         for ps in (0, 1):
-            off = pyhevc.split_nals(access_unit(w, h, poc, -1, write_ps=ps, **cfg))
+            off = pyhevc.split_nals(hc.access_unit(w, h, poc, recovery=-1, write_ps=ps, **cfg))
             first = poc >= 1 and M.position(320, N, poc) == 0
-            on = pyhevc.split_nals(access_unit(w, h, poc, n - 1 if first else -1, write_ps=ps, **cfg))
+            on = pyhevc.split_nals(hc.access_unit(w, h, poc, recovery=n - 1 if first else -1, write_ps=ps, **cfg))
             if not first:
                 assert on == off
                 continue
@@ -178,7 +147,7 @@ def test_the_three_parsers_pass_over_the_sei():
     """a stream of the checker's encoder with the recovery point SEI put in front of the slices of pictures 1 and 4: the decoder's host half parses the same
     pictures, the checker's decoder and tests/pyhevc.py decode the same pictures as without it"""
     import parser_probe
-    from test_python_decoder import tabs
+    from deckit import tabs
     w, h, nf = 128, 64, 6
     oe = orc.OracleEncoder(w, h, qp=32, period=64, me_range=8)
     aus, recs = [], []
@@ -186,8 +155,7 @@ def test_the_three_parsers_pass_over_the_sei():
         aus.append(oe.encode(orc.synth_frame(0, 1234, w, h, t)))
         recs.append(oe.recon())
     oe.close()
-    buf = np.zeros(64, np.uint8)
-    sei = b"\x00\x00\x00\x01" + bytes([39 << 1, 1]) + bytes(buf[:hi().hi_recovery_sei(2, buf.ctypes.data, 64)])
+    sei = b"\x00\x00\x00\x01" + bytes([39 << 1, 1]) + hc.recovery_sei(2)
     with_sei = []
     for t, au in enumerate(aus):
         nals = list(orc.split_nals(au))

@@ -7,23 +7,8 @@ import numpy as np
 import pytest
 
 import orc
-from test_random_access import python_pictures, vcl_type
-
-
-def lossy(seed, n=26, w=64, h=64, every=5, **extra):
-    """(access units with some lost, how many were lost): never the first picture, never an IDR or CRA picture"""
-    kw = dict(intra_period=12, num_refs=1 + seed % 4, tmvp=1)
-    if seed & 1:
-        kw.update(gop=(2, 4, 8)[seed % 3], b_slices=50)
-    else:
-        kw.update(long_term=(seed >> 1) & 1)
-    kw.update(extra)
-    g = orc.OracleGen(w, h, seed=seed, **kw)
-    aus = [g.picture() for _ in range(n)]
-    g.close()
-    types = [vcl_type(a) for a in aus]
-    lose = [i for i in range(1, n) if types[i] not in (19, 21) and i % every == 2]
-    return [(i, a) for i, a in enumerate(aus) if i not in lose], aus, lose
+from deckit import python_pictures
+from nalkit import lossy, vcl_type
 
 
 @pytest.mark.parametrize("seed", range(1, 13))

@@ -1,49 +1,22 @@
 """CPU side of "uvgx low-delay GOP v1" (kvazaar.h lp-gop): the option's parsing, the statement tests/lp_gop_model.py held to the
-tables and properties the design states, the slice segment headers with each picture's reference picture set read back (host build: tests/hostgop) --
+tables and properties the design states, the slice segment headers with each picture's reference picture set read back (host build: tests/hostcheck) --
 and, with the option off, byte equality of every header with the encoder of before (tests/golden/tmvp_off_access_units.json) --, and the merge / AMVP
 derivation of hevc_core.h with a table of POC distances against pyhevc's SliceDecoder on random motion fields whose references are the model's sets."""
-import ctypes as C
-import fcntl
 import hashlib
 import json
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import hc
 import lp_gop_model as M
 import lp_gop_stream
 import pyhevc
-import test_tmvp_host as T
+from cases import FORMS, GDN
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-GDN = ((4, 3, 1), (4, 3, 2), (4, 3, 3), (4, 3, 4), (8, 4, 3), (3, 2, 4), (1, 1, 2))
-
-
-def hg():
-    global _LIB
-    if _LIB is None:
-        d = os.path.join(ROOT, "tests", "hostgop")
-        with open(os.path.join(d, ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhostgop.so"))
-        P = C.c_void_p
-        L.hg_access_unit.argtypes = [C.c_int] * 12 + [P, P, C.c_int]
-        L.hg_cands.argtypes = [C.c_int] * 5 + [P] * 6 + [C.c_uint32] + [C.c_int] * 3 + [P] * 3
-        _LIB = L
-    return _LIB
-
-
-def access_unit(w, h, lp, tmvp, sao, wpp, tr, tc, slices, poc, qp_delta=0, dists=()):
-    buf = np.zeros(1 << 16, np.uint8)
-    d = np.array(list(dists) + [0] * (4 - len(dists)), np.int8)
-    n = hg().hg_access_unit(w, h, lp, tmvp, sao, wpp, tr, tc, slices, poc, qp_delta, len(dists), d.ctypes.data, buf.ctypes.data, len(buf))
-    assert n > 0
-    return bytes(buf[:n])
 
 
 # ---- 1. config_parse
@@ -104,7 +77,7 @@ def test_model_properties(g):
 
 # ---- 3. headers
 @pytest.mark.parametrize("gdn", GDN)
-@pytest.mark.parametrize("form", T.FORMS)
+@pytest.mark.parametrize("form", FORMS)
 def test_headers_carry_the_model(gdn, form):
     g, d, n = gdn
     wpp, tr, tc, sl = form
@@ -112,7 +85,7 @@ def test_headers_carry_the_model(gdn, form):
     for tmvp, sao in ((0, 0), (1, 1)):
         for pic in M.structure(period, 2 * period, g, d, n, 32):
             t = pic["poc"]
-            au = access_unit(256, 192, n, tmvp, sao, wpp, tr, tc, sl, t, pic["qp"] - 32, pic["dists"])
+            au = hc.access_unit(256, 192, t, lp=n, tmvp=tmvp, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl, qp_delta=pic["qp"] - 32, dists=pic["dists"])
             nals = pyhevc.split_nals(au)
             sps = pyhevc.parse_sps(pyhevc.unescape(nals[1]))
             pps = pyhevc.parse_pps(pyhevc.unescape(nals[2]))
@@ -132,8 +105,8 @@ def test_headers_carry_the_model(gdn, form):
                 assert f["nact"] == len(pic["refs"]) == min(max(n, 1), t)
                 assert f["tmvp"] == (1 if tmvp and t != 1 else 0)
     # the parameter sets are those of lp-refs alone
-    on = pyhevc.split_nals(access_unit(256, 192, n, 0, 0, wpp, tr, tc, sl, 0, 0, ()))
-    off = pyhevc.split_nals(T.access_unit(256, 192, n, 0, 0, wpp, tr, tc, sl, 0))
+    on = pyhevc.split_nals(hc.access_unit(256, 192, 0, lp=n, tmvp=0, sao=0, wpp=wpp, tr=tr, tc=tc, slices=sl, qp_delta=0, dists=()))
+    off = pyhevc.split_nals(hc.access_unit(256, 192, 0, lp=n, tmvp=0, sao=0, wpp=wpp, tr=tr, tc=tc, slices=sl))
     assert on[:3] == off[:3]
 
 
@@ -143,20 +116,20 @@ def test_headers_with_the_option_off_are_unchanged():
     assert len(gold["cases"]) == 700
     for *args, digest in gold["cases"]:
         w, h, lp, sao, wpp, tr, tc, sl, poc = args
-        au = access_unit(w, h, lp, 0, sao, wpp, tr, tc, sl, poc)
+        au = hc.access_unit(w, h, poc, lp=lp, tmvp=0, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
         assert hashlib.sha256(au).hexdigest()[:16] == digest, args
 
 
 # ---- 4. merge / AMVP with a distance table against pyhevc's derivation
 def _col_picture(poc, intra, mv, ref, dists):
-    p = T._col_picture(poc, intra, mv, ref)
+    p = hc.col_picture(poc, intra, mv, ref)
     up = lambda a: np.repeat(np.repeat(a, 2, 0), 2, 1)
     p.ref_poc[:, :, 0] = poc - np.asarray(dists, np.int32)[up(ref).astype(np.int32)]
     return p
 
 
 def _col_record(intra, mv, ref, dists):
-    rec = T.col_record(intra, mv, ref)
+    rec = hc.col_record(intra, mv, ref)
     rec[..., 2] = np.where(intra[::2, ::2] != 0, 0, np.asarray(dists, np.int16)[ref[::2, ::2].astype(np.int32)])
     return np.ascontiguousarray(rec)
 
@@ -171,14 +144,13 @@ def _run(seed, g, n, poc, seen, pairs):
     tr, tc = rng.choice(((1, 1), (2, 1), (1, 2), (2, 2)))
     dists, cdists = M.ref_dists(poc, g, n), M.ref_dists(poc - 1, g, n)
     nref, ncol = len(dists), len(cdists)
-    log2, intra, mv, ref, cbf = T.motion_field(rng, cw, ch, nref)
-    _, cintra, cmv, cref, _ = T.motion_field(rng, cw, ch, ncol, p_intra=0.2)
+    log2, intra, mv, ref, cbf = hc.motion_field(rng, cw, ch, nref)
+    _, cintra, cmv, cref, _ = hc.motion_field(rng, cw, ch, ncol, p_intra=0.2)
     same = np.array([[rng.random() < 0.5 for _ in range(cw // 8)] for _ in range(ch // 8)])
     cmv = np.where((same & (cintra == 0))[..., None], mv, cmv).astype(np.int16)
     col = _col_record(cintra, cmv, cref, cdists)
-    stub = T._Stub(cw, ch, tr, tc, nref, intra, mv, ref, _col_picture(poc - 1, cintra, cmv, cref, cdists), poc)
-    stub.refs = [[stub.refs[0][0]] + [T._Ref(poc - dists[k]) for k in range(1, nref)], []]
-    merge = np.zeros(15, np.int32); amvp = np.zeros(4, np.int32); sig = np.zeros(5, np.int32)
+    stub = hc.MotionStub(cw, ch, tr, tc, nref, intra, mv, ref, _col_picture(poc - 1, cintra, cmv, cref, cdists), poc)
+    stub.refs = [[stub.refs[0][0]] + [hc.Ref(poc - dists[k]) for k in range(1, nref)], []]
     a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
     for y in range(0, ch, 8):
         for x in range(0, cw, 8):
@@ -186,7 +158,7 @@ def _run(seed, g, n, poc, seen, pairs):
             if intra[y // 8, x // 8] or (x | y) & ((1 << l) - 1):
                 continue
             nn = 1 << l
-            hg().hg_cands(cw, ch, tr, tc, nref, *[v.ctypes.data for v in a], col.ctypes.data, _tab(dists), x, y, l, merge.ctypes.data, amvp.ctypes.data, sig.ctypes.data)
+            merge, amvp, sig = hc.cands(cw, ch, tr, tc, nref, a, x, y, l, col=col, tab=_tab(dists))
             want_m = [(c[0], c[1], c[2]) for c in stub.merge_candidates(x, y, nn, x, y, nn, nn, 0, 0)]
             assert [tuple(merge[3 * k:3 * k + 3]) for k in range(5)] == want_m, (seed, x, y)
             r = int(ref[y // 8, x // 8])
@@ -234,20 +206,18 @@ def test_merge_and_amvp_with_a_distance_table_match_pyhevc():
 
 
 def test_sequential_table_is_the_derivation_without_one():
-    """a table that says k + 1 gives what the entry points without a table give (tests/hosttmvp)"""
+    """a table that says k + 1 gives what the entry gives without a table"""
     rng = random.Random(11)
     cw, ch, nref = 256, 128, 3
-    log2, intra, mv, ref, cbf = T.motion_field(rng, cw, ch, nref)
-    _, cintra, cmv, cref, _ = T.motion_field(rng, cw, ch, nref)
-    col = T.col_record(cintra, cmv, cref)
+    log2, intra, mv, ref, cbf = hc.motion_field(rng, cw, ch, nref)
+    _, cintra, cmv, cref, _ = hc.motion_field(rng, cw, ch, nref)
+    col = hc.col_record(cintra, cmv, cref)
     a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
-    o1 = [np.zeros(15, np.int32), np.zeros(4, np.int32), np.zeros(5, np.int32)]
-    o2 = [np.zeros(15, np.int32), np.zeros(4, np.int32), np.zeros(5, np.int32)]
     for y in range(0, ch, 8):
         for x in range(0, cw, 8):
             l = int(log2[y // 8, x // 8])
             if intra[y // 8, x // 8] or (x | y) & ((1 << l) - 1):
                 continue
-            hg().hg_cands(cw, ch, 1, 1, nref, *[v.ctypes.data for v in a], col.ctypes.data, _tab([1, 2, 3]), x, y, l, *[o.ctypes.data for o in o1])
-            T.ht().ht_cands(cw, ch, 1, 1, nref, *[v.ctypes.data for v in a], col.ctypes.data, x, y, l, *[o.ctypes.data for o in o2])
+            o1 = hc.cands(cw, ch, 1, 1, nref, a, x, y, l, col=col, tab=_tab([1, 2, 3]))
+            o2 = hc.cands(cw, ch, 1, 1, nref, a, x, y, l, col=col)
             assert all(np.array_equal(p, q) for p, q in zip(o1, o2)), (x, y)

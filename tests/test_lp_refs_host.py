@@ -1,44 +1,17 @@
 """CPU side of "uvgx multi-reference v1" (kvazaar.h lp-refs): the option's parsing, the parameter sets and slice headers with n
-references read back by tests/pyhevc.py, the reference-aware merge / AMVP derivation of hevc_core.h (host build: tests/hostrefs) against pyhevc's, and the
+references read back by tests/pyhevc.py, the reference-aware merge / AMVP derivation of hevc_core.h (host build: tests/hostcheck) against pyhevc's, and the
 numpy restatement of the search (tests/lp_refs_model.py) pinned to the checker's single-reference encoder."""
-import ctypes as C
-import fcntl
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import hc
 import orc
 import pyhevc
 import lp_refs_model
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-
-
-def hr():
-    global _LIB
-    if _LIB is None:
-        d = os.path.join(ROOT, "tests", "hostrefs")
-        with open(os.path.join(d, ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhostrefs.so"))
-        P = C.c_void_p
-        L.hr_header.argtypes = [C.c_int] * 4 + [P, C.c_int]
-        L.hr_cands.argtypes = [C.c_int] * 5 + [P] * 5 + [C.c_int] * 3 + [P] * 3
-        L.hr_ref_idx_tokens.argtypes = [C.c_int, C.c_int, P, C.c_int]
-        _LIB = L
-    return _LIB
-
-
-def header(which, n, poc=0, sao=0):
-    buf = np.zeros(512, np.uint8)
-    k = hr().hr_header(which, n, poc, sao, buf.ctypes.data, len(buf))
-    assert k > 0
-    return bytes(buf[:k])
+from hc import header
 
 
 # ---- 1. config_parse
@@ -122,7 +95,7 @@ def test_ref_idx_binarisation():
     out = np.zeros(8, np.uint16)
     for n in range(2, 5):
         for r in range(n):
-            k = hr().hr_ref_idx_tokens(r, n, out.ctypes.data, 8)
+            k = hc.lib().hr_ref_idx_tokens(r, n, out.ctypes.data, 8)
             bins = [int(t) & 1 for t in out[:k]]
             assert bins == [1] * r + ([0] if r < n - 1 else []), (n, r, bins)
             ctx = [(int(t) >> 1) for t in out[:k] if not (int(t) & 0x8000)]
@@ -131,44 +104,6 @@ def test_ref_idx_binarisation():
 
 
 # ---- 3. merge / AMVP with reference indices against pyhevc's derivation
-class _Pic:
-    pass
-
-
-class _Ref:
-    def __init__(self, poc):
-        self.poc, self.is_lt = poc, False
-
-
-class _Stub:
-    """the state pyhevc.SliceDecoder's merge / AMVP derivations read, filled from one motion field"""
-    merge_candidates = pyhevc.SliceDecoder.merge_candidates
-    amvp_candidates = pyhevc.SliceDecoder.amvp_candidates
-    pb_avail = pyhevc.SliceDecoder.pb_avail
-    avail = pyhevc.SliceDecoder.avail
-    zaddr = pyhevc.SliceDecoder.zaddr
-    motion = pyhevc.SliceDecoder.motion
-    temporal = pyhevc.SliceDecoder.temporal
-    scale = staticmethod(pyhevc.SliceDecoder.scale)
-
-    def __init__(self, cw, ch, tr, tc, nref, intra, mv, ref, poc=10):
-        self.w, self.h, self.ctb_log2, self.ctb, self.wc = cw, ch, 6, 64, cw // 64
-        rows, cols = ch // 64, cw // 64
-        self.tile_of_row = [next(i for i in range(tr) if (i * rows) // tr <= y < ((i + 1) * rows) // tr) for y in range(rows)]
-        self.tile_of_col = [next(i for i in range(tc) if (i * cols) // tc <= x < ((i + 1) * cols) // tc) for x in range(cols)]
-        self.ctb_slice = [-1] * (rows * cols)
-        self.sps = {"min_cb": 3}
-        self.pps = {"par_mrg": 2}
-        self.cu_pred = intra.astype(np.int32)
-        self.pic = _Pic()
-        self.pic.mv = np.zeros((ch // 4, cw // 4, 2, 2), np.int32)
-        self.pic.mv[:, :, 0, :] = np.repeat(np.repeat(mv, 2, 0), 2, 1)
-        self.pic.ref_idx = np.full((ch // 4, cw // 4, 2), -1, np.int32)
-        self.pic.ref_idx[:, :, 0] = np.repeat(np.repeat(ref, 2, 0), 2, 1)
-        self.refs = [[_Ref(poc - 1 - k) for k in range(nref)], []]
-        self.sh = {"poc": poc, "max_merge": 5, "b": False, "nref": nref, "tmvp": False}
-
-
 def _motion_field(rng, cw, ch, nref):
     """a random quadtree of 32x32 / 16x16 / 8x8 units: some intra, vectors from a small set (so that neighbours often agree), random references"""
     b8h, b8w = ch // 8, cw // 8
@@ -196,8 +131,7 @@ def test_merge_and_amvp_match_pyhevc(seed):
     tr, tc = rng.choice(((1, 1), (2, 1), (1, 2), (2, 2)))
     nref = rng.choice((1, 2, 3, 4))
     log2, intra, mv, ref, cbf = _motion_field(rng, cw, ch, nref)
-    stub = _Stub(cw, ch, tr, tc, nref, intra, mv, ref)
-    merge = np.zeros(15, np.int32); amvp = np.zeros(4, np.int32); sig = np.zeros(5, np.int32)
+    stub = hc.MotionStub(cw, ch, tr, tc, nref, intra, mv, ref, None, 10)
     a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
     scaled = 0
     for y in range(0, ch, 8):
@@ -205,7 +139,7 @@ def test_merge_and_amvp_match_pyhevc(seed):
             l = int(log2[y // 8, x // 8])
             if intra[y // 8, x // 8] or (x | y) & ((1 << l) - 1):
                 continue
-            hr().hr_cands(cw, ch, tr, tc, nref, *[v.ctypes.data for v in a], x, y, l, merge.ctypes.data, amvp.ctypes.data, sig.ctypes.data)
+            merge, amvp, sig = hc.cands(cw, ch, tr, tc, nref, a, x, y, l)
             n = 1 << l
             want_m = [(c[0], c[1], c[2]) for c in stub.merge_candidates(x, y, n, x, y, n, n, 0, 0)]
             assert [tuple(merge[3 * k:3 * k + 3]) for k in range(5)] == want_m, (seed, x, y)

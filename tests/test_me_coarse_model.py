@@ -1,19 +1,15 @@
 """CPU: "uvgx coarse-to-fine search v1" (kvazaar.h me-coarse) -- the option, the numpy statement tests/me_coarse_model.py, and the
-device code's arithmetic built for the host (tests/hostcoarse) against that statement."""
+device code's arithmetic built for the host (tests/hostcheck) against that statement."""
 import ctypes as C
-import fcntl
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hc
 import lp_refs_model
 import me_coarse_model
 import pan_content
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 # ---- C1: the option
 @pytest.fixture(scope="module")
@@ -105,24 +101,6 @@ def test_reach_is_what_the_option_says():
 
 
 # ---- C4: the device code's arithmetic, built for the host, against the model
-_hc = {}
-
-
-def hostcoarse():
-    if "lib" not in _hc:
-        d = os.path.join(ROOT, "tests", "hostcoarse")
-        with open(os.path.join(d, ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhostcoarse.so"))
-        P = C.c_void_p
-        L.hc_quarter.argtypes = [P, C.c_int, C.c_int, P]
-        L.hc_coarse.argtypes = [P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]
-        L.hc_fine.argtypes = [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P]
-        _hc["lib"] = L
-    return _hc["lib"]
-
-
 def _random_pictures(rng, w, h, n, shift):
     """n pictures of smoothed noise, each the previous one displaced by `shift` plus fresh noise: the search has something to find and ties to break"""
     big = rng.integers(0, 256, (h + 2 * 300, w + 2 * 300)).astype(np.int32)
@@ -141,7 +119,7 @@ def _random_pictures(rng, w, h, n, shift):
     dict(w=256, h=128, n=2, R=8, reach=256, shift=(0, 0), me_early=1, tiles=(2, 1)),
 ])
 def test_host_build_of_the_device_arithmetic_matches_the_model(cfg):
-    L = hostcoarse()
+    L = hc.lib()
     rng = np.random.default_rng(0xC0A25E + cfg["w"] + cfg["reach"])
     w, h, n, R, reach, qp = cfg["w"], cfg["h"], cfg["n"], cfg["R"], cfg["reach"], cfg.get("qp", 32)
     tc, tr = cfg.get("tiles", (1, 1))

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import orc
-from test_oracle_kat import table
+from orc import table
 
 P = lambda a: a.ctypes.data_as(C.c_void_p)
 

@@ -8,14 +8,9 @@ import os
 import numpy as np
 
 import orc
+from orc import table
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def table(which, dtype, shape):
-    out = np.zeros(shape, dtype=dtype)
-    orc.lib().orc_api_tables(which, out.ctypes.data_as(C.c_void_p))
-    return out
 
 
 def test_transform_matrices():

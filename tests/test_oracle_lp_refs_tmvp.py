@@ -4,7 +4,7 @@
 * Its integer search over n references equals the numpy restatement tests/lp_refs_model.py.
 * Every stream it writes decodes to its reconstruction in oracle/hevc_dec.c (MD5 SEI checked) and, for the small sizes, in tests/pyhevc.py.
 * tmvp changes the bits and never the pictures.
-* Its merge / AMVP decisions equal the host build of the product's derivation (tests/hosttmvp ht_picture) fed the checker's own fields.
+* Its merge / AMVP decisions equal the host build of the product's derivation (tests/hostcheck ht_picture) fed the checker's own fields.
 * Recorded digests (tests/golden/lp_refs_tmvp_access_units.json) hold the statement still."""
 import hashlib
 import json
@@ -14,26 +14,14 @@ import numpy as np
 import pytest
 
 import edge_content as ec
+import enckit
+import hc
 import lp_refs_model
 import orc
+from cases import ORACLE_GUARD as GUARD
+from enckit import SEED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 0x5EED0000
-
-
-def _enc(w, h, n=None, tmvp=None, opts=(), **kw):
-    e = orc.OracleEncoder(w, h, **kw)
-    if n is not None:
-        e.set_option("lp-refs", n)
-    if tmvp is not None:
-        e.set_option("tmvp", tmvp)
-    for name, value in opts:
-        e.set_option(name, value)
-    return e
-
-
-def _frames(kind, w, h, n, seed=SEED):
-    return [orc.synth_frame(kind, seed, w, h, t) for t in range(n)]
 
 
 def test_options_are_checked():
@@ -50,21 +38,18 @@ def test_options_are_checked():
 
 
 # ---- 1. guard: lp-refs 0 / 1 and tmvp 0 are the checker of before, byte for byte
-GUARD = [dict(kw=dict()), dict(kw=dict(subme=4)), dict(kw=dict(), opts=(("intra-in-p", 2),), kind=2),
-         dict(kw=dict(tile_rows=2, tile_cols=2, slices=2, sao=1)), dict(kw=dict(bitrate=300000, rc_bands=4), frames=8),
-         dict(kw=dict(subme=2), opts=(("me-source", 1), ("intra-in-p", 1)))]
 
 
 @pytest.mark.parametrize("cfg", GUARD, ids=[str(i) for i in range(len(GUARD))])
 def test_one_reference_and_tmvp_off_are_the_checker_of_before(cfg):
     w, h = 320, 256
-    frames = _frames(cfg.get("kind", 0), w, h, cfg.get("frames", 5))
+    frames = enckit.frames(cfg.get("kind", 0), w, h, cfg.get("frames", 5))
     kw = dict(qp=30, me_range=12, period=4, **cfg["kw"])
-    base = _enc(w, h, opts=cfg.get("opts", ()), **kw)
+    base = enckit.oracle_encoder(w, h, opts=cfg.get("opts", ()), **kw)
     want = [base.encode(f) for f in frames]
     base.close()
     for n, tmvp in ((0, 0), (1, 0), (1, None), (None, 0)):
-        e = _enc(w, h, n, tmvp, opts=cfg.get("opts", ()), **kw)
+        e = enckit.oracle_encoder(w, h, n, tmvp, opts=cfg.get("opts", ()), **kw)
         got = [e.encode(f) for f in frames]
         assert got == want, (n, tmvp, [a == b for a, b in zip(got, want)])
         assert not e.debug()["cu_ref"].any()
@@ -92,14 +77,14 @@ def test_integer_search_matches_the_model(cfg):
     w, h, n, R, qp = cfg["w"], cfg["h"], cfg["n"], cfg["R"], cfg.get("qp", 32)
     tc, tr = cfg.get("tiles", (1, 1))
     period = cfg.get("period", 64)
-    e = _enc(w, h, n, cfg.get("tmvp", 0), opts=(("me-source", cfg.get("me_source", 0)),), qp=qp, me_range=R, me_early=cfg["me_early"],
+    e = enckit.oracle_encoder(w, h, n, cfg.get("tmvp", 0), opts=(("me-source", cfg.get("me_source", 0)),), qp=qp, me_range=R, me_early=cfg["me_early"],
              tile_rows=tr, tile_cols=tc, mv_frame=cfg.get("mv_frame", 0), period=period)
     if cfg.get("pattern") == "cut_runs":              # three black pictures, three white ones, ...: the first of a run has only the other colour behind it
         frames = [ec.cut_black_white(w, h, (t // 3) % 2, ec.SEED) for t in range(cfg["frames"])]
     elif cfg.get("pattern"):
         frames = [ec.PATTERNS[cfg["pattern"]](w, h, t, ec.SEED) for t in range(cfg["frames"])]
     else:
-        frames = _frames(cfg["kind"], w, h, cfg["frames"])
+        frames = enckit.frames(cfg["kind"], w, h, cfg["frames"])
     recs, older = [], 0
     for t, fr in enumerate(frames):
         e.encode(fr)
@@ -151,12 +136,12 @@ def test_closed_loop(cfg):
     w, h = cfg.get("w", 320), cfg.get("h", 192)
     nf = cfg.get("frames", 7)
     kw = dict(dict(qp=32, me_range=12), **cfg.get("kw", {}))
-    e = _enc(w, h, cfg["n"], cfg["tmvp"], opts=(("hash", 2),) + tuple(cfg.get("opts", ())), **kw)
+    e = enckit.oracle_encoder(w, h, cfg["n"], cfg["tmvp"], opts=(("hash", 2),) + tuple(cfg.get("opts", ())), **kw)
     if cfg.get("roi"):
         e.set_roi(4, 3, (np.arange(12, dtype=np.int8) % 7 - 3).astype(np.int8))
     od = orc.OracleDecoder()
     pairs = []
-    for t, f in enumerate(_frames(cfg.get("kind", 0), w, h, nf)):
+    for t, f in enumerate(enckit.frames(cfg.get("kind", 0), w, h, nf)):
         au = e.encode(f)
         rec = e.recon()
         pairs.append((au, rec))
@@ -167,7 +152,7 @@ def test_closed_loop(cfg):
     od.close(); e.close()
     if cfg.get("pyhevc"):
         import pyhevc
-        from test_python_decoder import tabs
+        from deckit import tabs
         dec = pyhevc.Decoder(tabs())
         for au, _ in pairs:
             dec.decode(au)
@@ -178,19 +163,14 @@ def test_closed_loop(cfg):
 
 
 # ---- 4. tmvp changes the bits, not the pictures
-def _pan(w, h, n):
-    from test_gpu_tmvp import _pan as pan
-    return pan(w, h, n)
-
-
 @pytest.mark.parametrize("n,kw,opts", [(1, {}, ()), (3, dict(subme=4), (("intra-in-p", 1),)), (4, dict(tile_rows=2, tile_cols=2, sao=1, period=4), ()),
                                        (2, dict(subme=2), (("me-source", 1), ("rdoq", 1)))])
 def test_tmvp_changes_bits_not_pictures(n, kw, opts):
     w, h, nf = 320, 256, 7
-    frames = _pan(w, h, nf)
+    frames = enckit.pan(w, h, nf)
     runs = {}
     for tmvp in (0, 1):
-        e = _enc(w, h, n, tmvp, opts=opts, **dict(dict(qp=30, me_range=12), **kw))
+        e = enckit.oracle_encoder(w, h, n, tmvp, opts=opts, **dict(dict(qp=30, me_range=12), **kw))
         runs[tmvp] = [(e.encode(f), e.recon()) for f in frames]
         e.close()
     for t in range(nf):
@@ -207,29 +187,24 @@ SIGNAL = [dict(n=1), dict(n=2, kw=dict(period=4, subme=4)), dict(n=3, opts=(("in
 @pytest.mark.parametrize("cfg", SIGNAL, ids=[str(i) for i in range(len(SIGNAL))])
 @pytest.mark.parametrize("tmvp", [0, 1])
 def test_signalling_matches_the_host_derivation(cfg, tmvp):
-    from test_tmvp_host import ht, col_record
     w, h, n = cfg.get("w", 320), cfg.get("h", 192), cfg["n"]
     kw = dict(dict(qp=30, me_range=12), **cfg.get("kw", {}))
     period = kw.get("period", 64)
-    e = _enc(w, h, n, tmvp, opts=cfg.get("opts", ()), **kw)
-    frames = _pan(w, h, 8) if cfg.get("pan") else _frames(0, w, h, 8)
+    e = enckit.oracle_encoder(w, h, n, tmvp, opts=cfg.get("opts", ()), **kw)
+    frames = enckit.pan(w, h, 8) if cfg.get("pan") else enckit.frames(0, w, h, 8)
     prev, checked, temporal = None, 0, 0
     for t, fr in enumerate(frames):
         e.encode(fr)
         d = e.debug()
         cw, ch = d["coded_w"], d["coded_h"]
         poc = t % period
-        col = col_record(d["cu_intra"], d["cu_mv"], d["cu_ref"]) if poc else None
+        col = hc.col_record(d["cu_intra"], d["cu_mv"], d["cu_ref"]) if poc else None
         if poc:
             nact = min(max(n, 1), poc)
             use = prev if (tmvp and poc >= 2) else None
-            b8 = (ch // 8, cw // 8)
-            want = {k: np.zeros(b8, np.uint8) for k in ("flags", "midx", "mvp")}
-            wmvd = np.zeros(b8 + (2,), np.int16)
-            out = np.zeros((ch // 16, cw // 16, 4), np.int16)
-            a = [np.ascontiguousarray(d[k]) for k in ("cu_log2", "cu_intra", "cu_mv", "cu_ref", "cu_cbf")]
-            ht().ht_picture(cw, ch, kw.get("tile_rows", 1), kw.get("tile_cols", 1), nact, *[v.ctypes.data for v in a], use.ctypes.data if use is not None else None,
-                            want["flags"].ctypes.data, want["midx"].ctypes.data, want["mvp"].ctypes.data, wmvd.ctypes.data, out.ctypes.data)
+            a = [d[k] for k in ("cu_log2", "cu_intra", "cu_mv", "cu_ref", "cu_cbf")]
+            want = {}
+            want["flags"], want["midx"], want["mvp"], wmvd, _ = hc.picture(cw, ch, kw.get("tile_rows", 1), kw.get("tile_cols", 1), nact, a, col=use)
             inter = d["cu_intra"] == 0
             for name, got, exp in (("cu_flags", d["cu_flags"], want["flags"]), ("cu_merge_idx", d["cu_merge_idx"], want["midx"]),
                                    ("cu_mvp_idx", d["cu_mvp_idx"], want["mvp"]), ("cu_mvd", d["cu_mvd"], wmvd)):
@@ -237,9 +212,8 @@ def test_signalling_matches_the_host_derivation(cfg, tmvp):
                 assert not len(bad), "picture %d: %s differs at %d units, first %s" % (t, name, len(bad), bad[0].tolist())
             checked += int(inter.sum())
             if use is not None:
-                f0 = {k: np.zeros(b8, np.uint8) for k in ("flags", "midx", "mvp")}
-                ht().ht_picture(cw, ch, kw.get("tile_rows", 1), kw.get("tile_cols", 1), nact, *[v.ctypes.data for v in a], None, f0["flags"].ctypes.data,
-                                f0["midx"].ctypes.data, f0["mvp"].ctypes.data, wmvd.ctypes.data, out.ctypes.data)
+                f0 = {}
+                f0["flags"], f0["midx"], f0["mvp"], _, _ = hc.picture(cw, ch, kw.get("tile_rows", 1), kw.get("tile_cols", 1), nact, a)
                 temporal += int((inter & ((f0["flags"] != want["flags"]) | (f0["midx"] != want["midx"]) | (f0["mvp"] != want["mvp"]))).sum())
         prev = col
     assert checked > 0
@@ -257,7 +231,7 @@ def _golden():
 def test_recorded_digests(idx):
     case = _golden()[idx]
     c = case["config"]
-    e = _enc(c["w"], c["h"], opts=[tuple(o) for o in c["opts"]], **c["enc"])
+    e = enckit.oracle_encoder(c["w"], c["h"], opts=[tuple(o) for o in c["opts"]], **c["enc"])
     for t, want in enumerate(case["frames"]):
         au = e.encode(orc.synth_frame(c["kind"], c["seed"], c["w"], c["h"], t))
         got = {"au_bytes": len(au), "au_md5": hashlib.md5(au).hexdigest(), "recon_md5": hashlib.md5(e.recon().tobytes()).hexdigest()}

@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+import enckit
 import lp_gop_model as M
 import lp_gop_stream
 import lp_refs_model
@@ -24,28 +25,10 @@ import occluder_content
 import orc
 import pan_content
 import pyhevc
+from cases import GDN, LP_REFS_SEARCH as REFS_SEARCH, ME_COARSE_SEARCH as COARSE_SEARCH, ORACLE_GUARD as GUARD
+from enckit import ROI as _ROI, SEED
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 0x5EED0000
-
-
-def _enc(w, h, n=None, tmvp=None, coarse=None, gop=None, opts=(), **kw):
-    e = orc.OracleEncoder(w, h, **kw)
-    if n is not None:
-        e.set_option("lp-refs", n)
-    if tmvp is not None:
-        e.set_option("tmvp", tmvp)
-    if coarse is not None:
-        e.set_option("me-coarse", coarse)
-    if gop is not None:
-        e.set_lp_gop(*gop)
-    for name, value in opts:
-        e.set_option(name, value)
-    return e
-
-
-def _frames(kind, w, h, n, seed=SEED):
-    return [orc.synth_frame(kind, seed, w, h, t) for t in range(n)]
 
 
 def _padded(fr, w, h):
@@ -74,22 +57,19 @@ def test_options_are_checked():
 
 
 # ---- 1. off is off: the guard cases of tests/test_oracle_lp_refs_tmvp.py
-from test_oracle_lp_refs_tmvp import GUARD  # noqa: E402
-
-
 @pytest.mark.parametrize("cfg", GUARD, ids=[str(i) for i in range(len(GUARD))])
 @pytest.mark.parametrize("n", [None, 3])
 def test_off_is_the_checker_of_before(cfg, n):
     """the options at 0 against the same build without them (the parent's bytes: the recorded digests, see the module docstring)"""
     w, h = 320, 256
-    frames = _frames(cfg.get("kind", 0), w, h, cfg.get("frames", 5))
+    frames = enckit.frames(cfg.get("kind", 0), w, h, cfg.get("frames", 5))
     kw = dict(qp=30, me_range=12, period=4, **cfg["kw"])
-    base = _enc(w, h, n, opts=cfg.get("opts", ()), **kw)
+    base = enckit.oracle_encoder(w, h, n, opts=cfg.get("opts", ()), **kw)
     want = [base.encode(f) for f in frames]
     base.close()
     # me-coarse 0; the gop string without the switch; the switch without a string; both off
     for coarse, gop in ((0, None), (None, (4, 3, 0)), (None, (0, 3, 1)), (0, (8, 4, 0))):
-        e = _enc(w, h, n, None, coarse, gop, opts=cfg.get("opts", ()), **kw)
+        e = enckit.oracle_encoder(w, h, n, None, coarse, gop, opts=cfg.get("opts", ()), **kw)
         got = [e.encode(f) for f in frames]
         d = e.debug()
         assert got == want, (coarse, gop, [a == b for a, b in zip(got, want)])
@@ -98,8 +78,6 @@ def test_off_is_the_checker_of_before(cfg, n):
 
 
 # ---- 2. the two-level integer search against the numpy statement (subme 0): the rows of tests/test_gpu_me_coarse.py SEARCH below 1080p
-from test_gpu_me_coarse import SEARCH as COARSE_SEARCH  # noqa: E402
-
 SEARCH = [c for c in COARSE_SEARCH if c.get("w", 640) <= 640]
 
 
@@ -109,8 +87,8 @@ def test_coarse_search_matches_the_model(cfg):
     tc, tr = [int(v) for v in cfg.get("tiles", "1x1").split("x")]
     me_early = cfg.get("me_early", 1)
     nf = cfg.get("frames", 3)
-    frames = _frames(cfg.get("kind", 0), w, h, nf) if cfg["clip"] == "moving" else pan_content.clip(w, h, nf, *cfg["clip"])
-    e = _enc(w, h, n, 0, reach, opts=(("me-source", cfg.get("me_source", 0)),), qp=qp, me_range=R, me_early=me_early, tile_rows=tr, tile_cols=tc,
+    frames = enckit.frames(cfg.get("kind", 0), w, h, nf) if cfg["clip"] == "moving" else pan_content.clip(w, h, nf, *cfg["clip"])
+    e = enckit.oracle_encoder(w, h, n, 0, reach, opts=(("me-source", cfg.get("me_source", 0)),), qp=qp, me_range=R, me_early=me_early, tile_rows=tr, tile_cols=tc,
              mv_frame=cfg.get("mv_frame", 0), wpp=0 if tc * tr > 1 else 1)
     srcs, recs, longest, seconds = [], [], 0, 0
     for t, fr in enumerate(frames):
@@ -143,18 +121,15 @@ def test_coarse_search_matches_the_model(cfg):
 
 
 # ---- 3. the structure of lp-gop streams: from the stream alone, and the checker's own report
-from test_gpu_lp_gop import GDN  # noqa: E402
-
-
 @pytest.mark.parametrize("period", [5, 12, 13])
 @pytest.mark.parametrize("gdn", GDN)
 def test_structure_matches_the_model(gdn, period):
     g, d, n = gdn
     w, h, qp, nf = 128, 64, 30, 2 * period + 3
-    e = _enc(w, h, n, 0, None, (g, d), qp=qp, me_range=8, period=period)
+    e = enckit.oracle_encoder(w, h, n, 0, None, (g, d), qp=qp, me_range=8, period=period)
     want = M.structure(period, nf, g, d, n, qp)
     sps = pps = None
-    for i, fr in enumerate(_frames(0, w, h, nf)):
+    for i, fr in enumerate(enckit.frames(0, w, h, nf)):
         au = e.encode(fr)
         nals = pyhevc.split_nals(au)
         if (nals[0][0] >> 1) & 63 == 32:
@@ -179,22 +154,19 @@ def test_parameter_sets_are_those_of_lp_refs_alone():
     w, h = 128, 64
     fr = orc.synth_frame(0, SEED, w, h, 0)
     for n in (1, 3):
-        a, b = _enc(w, h, n, 1, qp=30), _enc(w, h, n, 1, None, (4, 3), qp=30)
+        a, b = enckit.oracle_encoder(w, h, n, 1, qp=30), enckit.oracle_encoder(w, h, n, 1, None, (4, 3), qp=30)
         na, nb = orc.split_nals(a.encode(fr)), orc.split_nals(b.encode(fr))
         assert na[:3] == nb[:3] and na == nb          # VPS, SPS, PPS -- and the IDR picture, which keeps Q
         a.close(); b.close()
 
 
 # ---- 4. the search under lp-gop against the model: tests/test_gpu_lp_refs.py SEARCH on the blink clip
-from test_gpu_lp_refs import SEARCH as REFS_SEARCH  # noqa: E402
-
-
 @pytest.mark.parametrize("cfg", REFS_SEARCH, ids=[str(i) for i in range(len(REFS_SEARCH))])
 def test_lp_gop_search_matches_the_model(cfg):
     w, h, n, R, qp = cfg["w"], cfg["h"], cfg["n"], cfg["R"], cfg.get("qp", 32)
     g, d, nf = 4, 3, 7
     tc, tr = [int(v) for v in cfg.get("tiles", "1x1").split("x")]
-    e = _enc(w, h, n, 0, None, (g, d), opts=(("me-source", cfg.get("me_source", 0)),), qp=qp, me_range=R, me_early=cfg["me_early"], tile_rows=tr, tile_cols=tc,
+    e = enckit.oracle_encoder(w, h, n, 0, None, (g, d), opts=(("me-source", cfg.get("me_source", 0)),), qp=qp, me_range=R, me_early=cfg["me_early"], tile_rows=tr, tile_cols=tc,
              mv_frame=cfg.get("mv_frame", 0))
     frames = occluder_content.blink_clip(w, h, nf, kind=cfg["kind"])
     y0, y1, x0, x1 = occluder_content.region(w, h)
@@ -224,7 +196,6 @@ def test_lp_gop_search_matches_the_model(cfg):
 
 
 # ---- 5. the checker's own closed loop over the tool set; pan: a pan clip (vx, vy) beyond the zero window, else synthetic moving content
-_ROI = (4, 3, (np.arange(12, dtype=np.int8) % 7 - 3).astype(np.int8))
 CLOSED = [
     # me-coarse alone
     dict(coarse=128, pan=(72, -40)), dict(coarse=128, pan=(-72, 40), kw=dict(subme=2)), dict(coarse=128, pan=(40, 72), kw=dict(subme=4, sao=1)),
@@ -262,7 +233,7 @@ def _clip(cfg, w, h, nf):
         return pan_content.clip(w, h, nf, *cfg["pan"])
     if cfg.get("blink"):
         return occluder_content.blink_clip(w, h, nf)
-    return _frames(cfg.get("kind", 0), w, h, nf)
+    return enckit.frames(cfg.get("kind", 0), w, h, nf)
 
 
 @pytest.mark.parametrize("cfg", CLOSED, ids=[str(i) for i in range(len(CLOSED))])
@@ -270,7 +241,7 @@ def test_closed_loop(cfg):
     w, h = cfg.get("w", 320), cfg.get("h", 192)
     nf = cfg.get("frames", 10 if cfg.get("gop") else 6)
     kw = dict(dict(qp=32, me_range=12), **cfg.get("kw", {}))
-    e = _enc(w, h, cfg.get("n"), cfg.get("tmvp"), cfg.get("coarse"), cfg.get("gop"), opts=(("hash", 2),) + tuple(cfg.get("opts", ())), **kw)
+    e = enckit.oracle_encoder(w, h, cfg.get("n"), cfg.get("tmvp"), cfg.get("coarse"), cfg.get("gop"), opts=(("hash", 2),) + tuple(cfg.get("opts", ())), **kw)
     if cfg.get("roi"):
         e.set_roi(*_ROI)
     od = orc.OracleDecoder()
@@ -293,7 +264,7 @@ def test_closed_loop(cfg):
     if cfg.get("gop") and kw["qp"] >= 49:
         assert clipped > 0, "no picture's QP was clipped at 51"
     if cfg.get("pyhevc"):
-        from test_python_decoder import tabs
+        from deckit import tabs
         dec = pyhevc.Decoder(tabs())
         for au, _ in pairs:
             dec.decode(au)
@@ -307,10 +278,10 @@ def test_closed_loop_decodes_scaled_amvp():
     """a stream in which adjacent inter CUs hold references of different distance with a non-merged CU among them (counted from the debug arrays): the decoder
     scales a neighbour's vector by the true POC distances (8.5.3.2.7) to read the vector differences the checker's encoder wrote"""
     w, h, g, d, n = 320, 192, 4, 3, 3
-    e = _enc(w, h, n, 1, None, (g, d), qp=22, me_range=12, me_early=0)
+    e = enckit.oracle_encoder(w, h, n, 1, None, (g, d), qp=22, me_range=12, me_early=0)
     od = orc.OracleDecoder()
     count = 0
-    for t, fr in enumerate(_frames(2, w, h, 10)):
+    for t, fr in enumerate(enckit.frames(2, w, h, 10)):
         au = e.encode(fr)
         got = od.decode_au(au, t)
         assert len(got) == 1 and np.array_equal(got[0]["i420"], e.recon()), t
@@ -328,7 +299,7 @@ def test_closed_loop_decodes_scaled_amvp():
 def test_long_mvd_strings():
     """me-coarse 256 on a pan past 230 samples with subme 4: mvd components of more than 10 bins are coded, and the stream decodes"""
     w, h = 640, 384
-    e = _enc(w, h, None, None, 256, qp=32, me_range=16, subme=4)
+    e = enckit.oracle_encoder(w, h, None, None, 256, qp=32, me_range=16, subme=4)
     od = orc.OracleDecoder()
     longest = 0
     for t, fr in enumerate(pan_content.clip(w, h, 3, 236, -3)):

@@ -7,15 +7,8 @@ import pytest
 
 import orc
 import pyhevc
-from test_oracle_kat import table
-
-
-def tabs():
-    return {"range_lps": table(1, np.uint8, (64, 4)), "trans_lps": table(2, np.uint8, (64,)), "trans_mps": table(13, np.uint8, (64,)),
-            "dct": table(0, np.int8, (32, 32)).astype(int), "dst": table(5, np.int8, (4, 4)).astype(int),
-            "luma_filter": table(11, np.int8, (4, 8)).astype(int), "chroma_filter": table(12, np.int8, (8, 4)).astype(int),
-            "beta": table(6, np.uint8, (52,)).astype(int), "tc": table(7, np.uint8, (54,)).astype(int),
-            "intra_angle": table(9, np.int8, (35,)).astype(int), "inv_angle": table(10, np.int16, (35,)).astype(int)}
+from deckit import tabs
+from orc import table
 
 
 def test_context_init_values_agree_with_the_checker_and_the_product():

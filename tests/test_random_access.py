@@ -16,34 +16,8 @@ import pytest
 
 import orc
 import pyhevc
-from test_python_decoder import tabs
-
-EOS = bytes([0, 0, 0, 1, 36 << 1, 1])
-
-
-def nal_type(nal):
-    i = 0
-    while nal[i] == 0:
-        i += 1
-    return (nal[i + 1] >> 1) & 63
-
-
-def vcl_type(au):
-    return next(t for t in (nal_type(n) for n in orc.split_nals(au)) if t < 32)
-
-
-def rename(au, old, new):
-    """the access unit with its slice NAL units of type `old` called `new` (the type sits in bits 1..6 of the header's first byte)"""
-    out = bytearray()
-    for n in orc.split_nals(au):
-        n = bytearray(n)
-        i = 0
-        while n[i] == 0:
-            i += 1
-        if (n[i + 1] >> 1) & 63 == old:
-            n[i + 1] = (n[i + 1] & 0x81) | (new << 1)
-        out += n
-    return bytes(out)
+from deckit import python_pictures
+from nalkit import EOS, discard_prior, layered, nal_type, rasl_of, rename, tid_of, vcl_type
 
 
 def stream(seed, n=36, **kw):
@@ -64,17 +38,6 @@ def oracle_pictures(aus, first_pts=0):
     out += d.flush()
     d.close()
     return [(f["pts"], f["i420"]) for f in out]
-
-
-def rasl_of(types, k):
-    """indices of the RASL pictures that belong to the CRA picture at index k"""
-    out = []
-    for i in range(k + 1, len(types)):
-        if 16 <= types[i] <= 23:
-            break
-        if types[i] in (8, 9):
-            out.append(i)
-    return out
 
 
 def same(a, b):
@@ -149,14 +112,6 @@ def test_pictures_with_pic_output_flag_zero_are_referenced_but_not_shown(seed):
     assert pts == sorted(pts) and 10 < len(pts) < 30
 
 
-def python_pictures(aus):
-    d = pyhevc.Decoder(tabs())
-    for au in aus:
-        for nal in pyhevc.split_nals(au):
-            d.decode_nal(nal)
-    return d.flush()
-
-
 @pytest.mark.parametrize("seed,kw", [(1, {}), (2, {"hidden_pics": 30}), (3, {"wpp": 1, "slices": 1}), (6, {"tmvp": 1, "hidden_pics": 20})])
 def test_the_python_decoder_agrees(seed, kw):
     aus = stream(seed, n=22, **kw)
@@ -169,20 +124,6 @@ def test_the_python_decoder_agrees(seed, kw):
         assert len(want) == len(got) > 0
         for a, b in zip(want, got):
             assert np.array_equal(a, b["i420"])
-
-
-def discard_prior(au):
-    """the access unit with no_output_of_prior_pics_flag = 1 in its IDR / BLA slice NAL units (the second bit of the slice segment header)"""
-    out = bytearray()
-    for n in orc.split_nals(au):
-        n = bytearray(n)
-        i = 0
-        while n[i] == 0:
-            i += 1
-        if 16 <= (n[i + 1] >> 1) & 63 <= 20:
-            n[i + 3] |= 0x40
-        out += n
-    return bytes(out)
 
 
 @pytest.mark.parametrize("seed", (1, 2, 3, 4, 5, 6))
@@ -226,26 +167,6 @@ def test_a_bla_picture_with_no_output_of_prior_pics_flag(seed):
         assert len(py) == len(got)
         for (_, x), y in zip(got, py):
             assert np.array_equal(x, y["i420"])
-
-
-def tid_of(au):
-    """TemporalId of the access unit's slice NAL units"""
-    for n in orc.split_nals(au):
-        i = 0
-        while n[i] == 0:
-            i += 1
-        if (n[i + 1] >> 1) & 63 < 32:
-            return (n[i + 2] & 7) - 1
-    raise ValueError("no slice")
-
-
-def layered(seed, n=26, w=64, h=64, **kw):
-    cfg = dict(gop=(2, 4, 8)[seed % 3], temporal_layers=1, open_gop=seed & 1, intra_period=24, b_slices=50, num_refs=1 + seed % 4, tmvp=1)
-    cfg.update(kw)
-    g = orc.OracleGen(w, h, seed=seed, **cfg)
-    aus = [g.picture() for _ in range(n)]
-    g.close()
-    return aus
 
 
 @pytest.mark.parametrize("seed", range(1, 9))

@@ -1,45 +1,21 @@
 """CPU side of "tmvp" (temporal motion vector prediction): the option's parsing, the parameter sets and slice segment headers with
 the temporal flags read back bit by bit and with tests/pyhevc.py, byte equality of every header with tmvp off against what the encoder wrote before the
 option existed (tests/golden/tmvp_off_access_units.json), and the merge / AMVP derivation of hevc_core.h with a collocated record (host build:
-tests/hosttmvp) against pyhevc's SliceDecoder.merge_candidates / amvp_candidates / temporal on random motion fields."""
-import ctypes as C
-import fcntl
+tests/hostcheck) against pyhevc's SliceDecoder.merge_candidates / amvp_candidates / temporal on random motion fields."""
 import hashlib
 import json
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import hc
 import pyhevc
+from cases import FORMS
+from hc import col_record, motion_field
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-
-
-def ht():
-    global _LIB
-    if _LIB is None:
-        d = os.path.join(ROOT, "tests", "hosttmvp")
-        with open(os.path.join(d, ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhosttmvp.so"))
-        P = C.c_void_p
-        L.ht_access_unit.argtypes = [C.c_int] * 10 + [P, C.c_int]
-        L.ht_cands.argtypes = [C.c_int] * 5 + [P] * 6 + [C.c_int] * 3 + [P] * 3
-        L.ht_picture.argtypes = [C.c_int] * 5 + [P] * 6 + [P] * 5
-        _LIB = L
-    return _LIB
-
-
-def access_unit(w, h, lp, tmvp, sao, wpp, tr, tc, slices, poc):
-    buf = np.zeros(1 << 16, np.uint8)
-    n = ht().ht_access_unit(w, h, lp, tmvp, sao, wpp, tr, tc, slices, poc, buf.ctypes.data, len(buf))
-    assert n > 0
-    return bytes(buf[:n])
 
 
 # ---- 1. config_parse
@@ -69,16 +45,13 @@ def test_config_parse_tmvp(api):
 
 
 # ---- 2. parameter sets and slice segment headers
-FORMS = ((1, 1, 1, 0), (1, 1, 1, 1), (0, 2, 2, 2), (1, 2, 1, 2), (0, 1, 1, 0))     # (wpp, tile rows, tile columns, slices): WPP, slices=wpp, tiles 2x2 with slices=tiles, ...
-
-
 def test_headers_with_tmvp_off_are_unchanged():
     """every access unit's headers with tmvp=0 are byte for byte the ones of the encoder before the option (digests from the parent's hevc_headers.h)"""
     g = json.load(open(os.path.join(ROOT, "tests", "golden", "tmvp_off_access_units.json")))
     assert len(g["cases"]) == 700
     for *args, digest in g["cases"]:
         w, h, lp, sao, wpp, tr, tc, sl, poc = args
-        au = access_unit(w, h, lp, 0, sao, wpp, tr, tc, sl, poc)
+        au = hc.access_unit(w, h, poc, lp=lp, tmvp=0, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
         assert hashlib.sha256(au).hexdigest()[:16] == digest, args
 
 
@@ -126,7 +99,7 @@ def slice_headers(au, sps, pps, lp, sao):
             n = r.ue()
             if n:
                 ln = r.ue() + 1
-                assert all(r.u(ln) + 1 == 2 for _ in range(n))      # the 2-byte substreams hosttmvp gives every segment
+                assert all(r.u(ln) + 1 == 2 for _ in range(n))      # the 2-byte substreams the host build gives every segment
         assert r.u(1) == 1                                          # alignment_bit_equal_to_one
         r.align()
         out.append((first, dependent, f))
@@ -139,7 +112,7 @@ def test_tmvp_headers(lp, form):
     wpp, tr, tc, sl = form
     for sao in (0, 1):
         for poc in range(0, 7):
-            au = access_unit(256, 192, lp, 1, sao, wpp, tr, tc, sl, poc)
+            au = hc.access_unit(256, 192, poc, lp=lp, tmvp=1, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
             nals = pyhevc.split_nals(au)
             sps = pyhevc.parse_sps(pyhevc.unescape(nals[1]))
             pps = pyhevc.parse_pps(pyhevc.unescape(nals[2]))
@@ -159,96 +132,11 @@ def test_tmvp_headers(lp, form):
                 assert f["tmvp"] == (poc != 1), (poc, f)
                 assert f["col_idx"] == (0 if (poc != 1 and f["nact"] > 1) else None), (poc, f)
     # the off stream's SPS says 0
-    au = access_unit(256, 192, lp, 0, 0, wpp, tr, tc, sl, 0)
+    au = hc.access_unit(256, 192, 0, lp=lp, tmvp=0, sao=0, wpp=wpp, tr=tr, tc=tc, slices=sl)
     assert pyhevc.parse_sps(pyhevc.unescape(pyhevc.split_nals(au)[1]))["tmvp"] == 0
 
 
 # ---- 3. merge / AMVP with the temporal candidate against pyhevc's derivation
-class _Pic:
-    pass
-
-
-class _Ref:
-    def __init__(self, poc):
-        self.poc, self.is_lt = poc, False
-
-
-def _col_picture(poc, intra, mv, ref):
-    """pyhevc's view of the collocated picture: list-0 motion per 4x4 block, intra blocks with no list"""
-    p = _Pic()
-    p.poc, p.is_lt = poc, False
-    h4, w4 = intra.shape[0] * 2, intra.shape[1] * 2
-    up = lambda a: np.repeat(np.repeat(a, 2, 0), 2, 1)
-    p.mv = np.zeros((h4, w4, 2, 2), np.int32)
-    p.mv[:, :, 0, :] = up(mv)
-    p.ref_idx = np.full((h4, w4, 2), -1, np.int32)
-    p.ref_idx[:, :, 0] = np.where(up(intra) != 0, -1, up(ref).astype(np.int32))
-    p.ref_poc = np.zeros((h4, w4, 2), np.int32)
-    p.ref_poc[:, :, 0] = poc - 1 - up(ref).astype(np.int32)
-    p.ref_lt = np.zeros((h4, w4, 2), np.int32)
-    return p
-
-
-def col_record(intra, mv, ref):
-    """the record a picture files (hevc_core.h ColMv): its top-left 8x8 unit's motion for every 16x16 block, distance 0 for intra"""
-    i, m, r = intra[::2, ::2], mv[::2, ::2], ref[::2, ::2]
-    rec = np.zeros(i.shape + (4,), np.int16)
-    rec[..., 0] = np.where(i != 0, 0, m[..., 0])
-    rec[..., 1] = np.where(i != 0, 0, m[..., 1])
-    rec[..., 2] = np.where(i != 0, 0, r.astype(np.int16) + 1)
-    return np.ascontiguousarray(rec)
-
-
-class _Stub:
-    """the state pyhevc.SliceDecoder's merge / AMVP / temporal derivations read, filled from one motion field and the collocated picture's"""
-    merge_candidates = pyhevc.SliceDecoder.merge_candidates
-    amvp_candidates = pyhevc.SliceDecoder.amvp_candidates
-    pb_avail = pyhevc.SliceDecoder.pb_avail
-    avail = pyhevc.SliceDecoder.avail
-    zaddr = pyhevc.SliceDecoder.zaddr
-    motion = pyhevc.SliceDecoder.motion
-    temporal = pyhevc.SliceDecoder.temporal
-    scale = staticmethod(pyhevc.SliceDecoder.scale)
-
-    def __init__(self, cw, ch, tr, tc, nref, intra, mv, ref, col, poc):
-        self.w, self.h, self.ctb_log2, self.ctb, self.wc = cw, ch, 6, 64, cw // 64
-        rows, cols = ch // 64, cw // 64
-        self.tile_of_row = [next(i for i in range(tr) if (i * rows) // tr <= y < ((i + 1) * rows) // tr) for y in range(rows)]
-        self.tile_of_col = [next(i for i in range(tc) if (i * cols) // tc <= x < ((i + 1) * cols) // tc) for x in range(cols)]
-        self.ctb_slice = [-1] * (rows * cols)
-        self.sps = {"min_cb": 3}
-        self.pps = {"par_mrg": 2}
-        self.cu_pred = intra.astype(np.int32)
-        self.pic = _Pic()
-        self.pic.mv = np.zeros((ch // 4, cw // 4, 2, 2), np.int32)
-        self.pic.mv[:, :, 0, :] = np.repeat(np.repeat(mv, 2, 0), 2, 1)
-        self.pic.ref_idx = np.full((ch // 4, cw // 4, 2), -1, np.int32)
-        self.pic.ref_idx[:, :, 0] = np.repeat(np.repeat(ref, 2, 0), 2, 1)
-        self.refs = [[col if (k == 0 and col is not None) else _Ref(poc - 1 - k) for k in range(nref)], []]
-        self.sh = {"poc": poc, "max_merge": 5, "b": False, "nref": nref, "tmvp": col is not None, "col_idx": 0, "col_l0": 1}
-
-
-def motion_field(rng, cw, ch, nref, p_intra=0.12):
-    """a random quadtree of 32x32 / 16x16 / 8x8 units: some intra, vectors from a small set (so that neighbours and collocated blocks often agree), random references"""
-    b8h, b8w = ch // 8, cw // 8
-    log2 = np.zeros((b8h, b8w), np.uint8); intra = np.zeros_like(log2); ref = np.zeros_like(log2); cbf = np.zeros_like(log2)
-    mv = np.zeros((b8h, b8w, 2), np.int16)
-    pool = [(0, 0), (4, 0), (-8, 4), (12, -4), (4, 0), (3, -1), (-33, 17), (100, -60), (8, 0), (-2, 6)]
-    for y in range(0, ch, 32):
-        for x in range(0, cw, 32):
-            l = rng.choice((5, 4, 4, 3))
-            for yy in range(y, y + 32, 1 << l):
-                for xx in range(x, x + 32, 1 << l):
-                    s = (slice(yy // 8, (yy + (1 << l)) // 8), slice(xx // 8, (xx + (1 << l)) // 8))
-                    log2[s] = l
-                    intra[s] = rng.random() < p_intra
-                    mv[s] = pool[rng.randrange(len(pool))] if rng.random() < 0.8 else (rng.randrange(-300, 300), rng.randrange(-150, 150))
-                    ref[s] = rng.randrange(nref)
-                    cbf[s] = rng.random() < 0.5
-    mv[intra != 0] = 0
-    return log2, intra, mv, ref, cbf
-
-
 @pytest.mark.parametrize("seed", range(16))
 def test_merge_and_amvp_with_temporal_candidates_match_pyhevc(seed):
     rng = random.Random(0x7E40 + seed)
@@ -263,8 +151,7 @@ def test_merge_and_amvp_with_temporal_candidates_match_pyhevc(seed):
     same = np.array([[rng.random() < 0.5 for _ in range(cw // 8)] for _ in range(ch // 8)])
     cmv = np.where((same & (cintra == 0))[..., None], mv, cmv).astype(np.int16)
     col = col_record(cintra, cmv, cref)
-    stub = _Stub(cw, ch, tr, tc, nref, intra, mv, ref, _col_picture(poc - 1, cintra, cmv, cref), poc)
-    merge = np.zeros(15, np.int32); amvp = np.zeros(4, np.int32); sig = np.zeros(5, np.int32)
+    stub = hc.MotionStub(cw, ch, tr, tc, nref, intra, mv, ref, hc.col_picture(poc - 1, cintra, cmv, cref), poc)
     a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
     seen = {"merge_t": 0, "amvp_t": 0, "scaled": 0, "br_out_row": 0, "br_out_pic": 0, "col_intra": 0, "n16": 0, "n32": 0, "merged_t": 0}
     for y in range(0, ch, 8):
@@ -273,7 +160,7 @@ def test_merge_and_amvp_with_temporal_candidates_match_pyhevc(seed):
             if intra[y // 8, x // 8] or (x | y) & ((1 << l) - 1):
                 continue
             n = 1 << l
-            ht().ht_cands(cw, ch, tr, tc, nref, *[v.ctypes.data for v in a], col.ctypes.data, x, y, l, merge.ctypes.data, amvp.ctypes.data, sig.ctypes.data)
+            merge, amvp, sig = hc.cands(cw, ch, tr, tc, nref, a, x, y, l, col=col)
             want_m = [(c[0], c[1], c[2]) for c in stub.merge_candidates(x, y, n, x, y, n, n, 0, 0)]
             assert [tuple(merge[3 * k:3 * k + 3]) for k in range(5)] == want_m, (seed, x, y)
             r = int(ref[y // 8, x // 8])
@@ -307,12 +194,11 @@ def test_merge_and_amvp_with_temporal_candidates_match_pyhevc(seed):
 
 @pytest.mark.parametrize("seed", range(4))
 def test_no_record_keeps_the_derivation_of_before(seed):
-    """without a collocated record the lists are pyhevc's with slice_temporal_mvp_enabled_flag 0 (what tests/hostrefs pins for the encoder of before)"""
+    """without a collocated record the lists are pyhevc's with slice_temporal_mvp_enabled_flag 0 (what test_lp_refs_host pins for the encoder of before)"""
     rng = random.Random(seed)
     cw, ch, nref = 256, 128, 1 + seed
     log2, intra, mv, ref, cbf = motion_field(rng, cw, ch, nref)
-    stub = _Stub(cw, ch, 1, 1, nref, intra, mv, ref, None, 9)
-    merge = np.zeros(15, np.int32); amvp = np.zeros(4, np.int32); sig = np.zeros(5, np.int32)
+    stub = hc.MotionStub(cw, ch, 1, 1, nref, intra, mv, ref, None, 9)
     a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
     for y in range(0, ch, 8):
         for x in range(0, cw, 8):
@@ -320,31 +206,26 @@ def test_no_record_keeps_the_derivation_of_before(seed):
             if intra[y // 8, x // 8] or (x | y) & ((1 << l) - 1):
                 continue
             n = 1 << l
-            ht().ht_cands(cw, ch, 1, 1, nref, *[v.ctypes.data for v in a], None, x, y, l, merge.ctypes.data, amvp.ctypes.data, sig.ctypes.data)
+            merge, amvp, sig = hc.cands(cw, ch, 1, 1, nref, a, x, y, l)
             assert [tuple(merge[3 * k:3 * k + 3]) for k in range(5)] == [c[:3] for c in stub.merge_candidates(x, y, n, x, y, n, n, 0, 0)]
             assert [tuple(amvp[2 * k:2 * k + 2]) for k in range(2)] == [tuple(c) for c in stub.amvp_candidates(x, y, n, x, y, n, n, 0, 0, int(ref[y // 8, x // 8]))]
 
 
 def test_picture_restatement_files_the_record():
-    """ht_picture (what the GPU test restates k_inter_signal with) files the record col_record describes and derives what ht_cands derives"""
+    """ht_picture (what the GPU test restates k_inter_signal with) files the record col_record describes and derives what hc_cands derives"""
     rng = random.Random(5)
     cw, ch, nref = 192, 128, 2
     log2, intra, mv, ref, cbf = motion_field(rng, cw, ch, nref)
     _, cintra, cmv, cref, _ = motion_field(rng, cw, ch, 2)
     col = col_record(cintra, cmv, cref)
-    b8 = (ch // 8, cw // 8)
-    flags = np.zeros(b8, np.uint8); midx = np.zeros(b8, np.uint8); mvp = np.zeros(b8, np.uint8); mvd = np.zeros(b8 + (2,), np.int16)
-    out = np.zeros((ch // 16, cw // 16, 4), np.int16)
     a = [np.ascontiguousarray(x) for x in (log2, intra, mv, ref, cbf)]
-    ht().ht_picture(cw, ch, 1, 1, nref, *[v.ctypes.data for v in a], col.ctypes.data, flags.ctypes.data, midx.ctypes.data, mvp.ctypes.data, mvd.ctypes.data, out.ctypes.data)
+    flags, midx, mvp, mvd, out = hc.picture(cw, ch, 1, 1, nref, a, col=col)
     assert np.array_equal(out, col_record(intra, mv, ref))
-    merge = np.zeros(15, np.int32); amvp = np.zeros(4, np.int32); sig = np.zeros(5, np.int32)
     for y in range(0, ch, 8):
         for x in range(0, cw, 8):
             l = int(log2[y // 8, x // 8])
             if intra[y // 8, x // 8]:
                 continue
-            ht().ht_cands(cw, ch, 1, 1, nref, *[v.ctypes.data for v in a], col.ctypes.data, x & ~((1 << l) - 1), y & ~((1 << l) - 1), l,
-                          merge.ctypes.data, amvp.ctypes.data, sig.ctypes.data)
+            merge, amvp, sig = hc.cands(cw, ch, 1, 1, nref, a, x & ~((1 << l) - 1), y & ~((1 << l) - 1), l, col=col)
             i = (y // 8, x // 8)
             assert (flags[i], midx[i], mvp[i], mvd[i][0], mvd[i][1]) == tuple(sig), (x, y)

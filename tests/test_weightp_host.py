@@ -1,66 +1,21 @@
 """CPU side of "uvgx weighted prediction v1" (kvazaar.h weightp): the option's parsing; the statement functions of hevc_core.h (host
-build: tests/hostwp) against the restatement tests/wp_model.py -- random statistics, the extremes, every sample value under every weight --; access units whose
+build: tests/hostcheck) against the restatement tests/wp_model.py -- random statistics, the extremes, every sample value under every weight --; access units whose
 slice headers carry pred_weight_table(), read back by tests/pyhevc.py and decoded by the checker's decoder; and, with the field off, byte equality of every
 header with the encoder of before (tests/golden/tmvp_off_access_units.json)."""
-import ctypes as C
-import fcntl
 import hashlib
 import json
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
+import hc
 import orc
 import pyhevc
 import wp_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-
-
-def hw():
-    global _LIB
-    if _LIB is None:
-        d = os.path.join(ROOT, "tests", "hostwp")
-        with open(os.path.join(d, ".build.lock"), "w") as lk:
-            fcntl.flock(lk, fcntl.LOCK_EX)
-            subprocess.run(["make", "-s", "-C", d], check=True, stdout=subprocess.DEVNULL)
-        L = C.CDLL(os.path.join(d, "build", "libhostwp.so"))
-        P = C.c_void_p
-        L.hw_moments.argtypes = [C.c_uint64] * 3 + [P]
-        L.hw_isqrt.argtypes = [C.c_uint64]; L.hw_isqrt.restype = C.c_uint32
-        L.hw_candidate.argtypes = [C.c_int64] * 4 + [P]
-        L.hw_accept.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
-        L.hw_decide.argtypes = [P, P, C.c_int, C.c_int, C.c_int, P]
-        L.hw_access_unit.argtypes = [C.c_int] * 12 + [P, C.c_int, P, P, C.c_int, C.c_int, P, C.c_int]
-        _LIB = L
-    return _LIB
-
-
-def host_moments(s1, s2, n):
-    out = np.zeros(2, np.int64)
-    hw().hw_moments(s1, s2, n, out.ctypes.data)
-    return int(out[0]), int(out[1])
-
-
-def host_candidate(mc, vc, mr, vr):
-    out = np.zeros(3, np.int32)
-    hw().hw_candidate(mc, vc, mr, vr, out.ctypes.data)
-    return int(out[0]), int(out[1]), bool(out[2])
-
-
-def access_unit(w, h, lp, poc, weightp, wts=None, payload=b"", write_ps=1, tmvp=0, sao=0, wpp=1, tr=1, tc=1, slices=0, qp_delta=0, dists=()):
-    buf = np.zeros(1 << 20, np.uint8)
-    d = np.array(list(dists) + [0] * (4 - len(dists)), np.int8)
-    wa = None if wts is None else np.ascontiguousarray(np.asarray(wts, np.int32).reshape(12))
-    pl = np.frombuffer(bytes(payload) or b"\0", np.uint8)
-    n = hw().hw_access_unit(w, h, lp, tmvp, sao, wpp, tr, tc, slices, poc, qp_delta, len(dists), d.ctypes.data, weightp, None if wa is None else wa.ctypes.data,
-                            pl.ctypes.data, len(payload), write_ps, buf.ctypes.data, len(buf))
-    assert n > 0
-    return bytes(buf[:n])
 
 
 # ---- 1. config_parse
@@ -94,7 +49,7 @@ def test_isqrt():
     vals += [rng.getrandbits(rng.randrange(1, 64)) for _ in range(2000)] + [k * k + d for k in (3, 255, 65535, 4194303) for d in (-1, 0, 1)]
     import math
     for v in vals:
-        assert hw().hw_isqrt(v) == math.isqrt(v), v
+        assert hc.lib().hw_isqrt(v) == math.isqrt(v), v
 
 
 def test_moments_and_candidates_match_the_model():
@@ -112,11 +67,11 @@ def test_moments_and_candidates_match_the_model():
               (3 * 1000 + 1, 9 * 1000 + 1, 1000 + 1), (100 * 777 + 1, 100 * 100 * 777 + 201, 777)]
     mom = []
     for s1, s2, n in stats:
-        got = host_moments(s1, s2, n)
+        got = hc.wp_moments(s1, s2, n)
         assert got == M.moments_of_sums(s1, s2, n), (s1, s2, n)
         assert got[1] >= 0
         mom.append(got)
-    assert host_moments(255 * n8k, 255 * 255 * n8k, n8k) == (65280, 0)
+    assert hc.wp_moments(255 * n8k, 255 * 255 * n8k, n8k) == (65280, 0)
     assert any(v == 0 for _, v in mom) and any(v > 0 for _, v in mom)
     seen = set()
     pairs = [(rng.choice(mom), rng.choice(mom)) for _ in range(20000)]
@@ -125,14 +80,14 @@ def test_moments_and_candidates_match_the_model():
               ((50 * 256, 0), (60 * 256, 500)), ((50 * 256, 500), (60 * 256, 0)), ((50 * 256, 0), (50 * 256, 0)), ((100 * 256, 4096), (100 * 256, 4096)),
               ((100 * 256, 4356), (100 * 256, 4096)), ((100 * 256 + 128, 4096), (100 * 256, 4096)), ((100 * 256 + 127, 4096), (100 * 256, 4096))]
     for (mc, vc), (mr, vr) in pairs:
-        got = host_candidate(mc, vc, mr, vr)
+        got = hc.wp_candidate(mc, vc, mr, vr)
         assert got == M.candidate(mc, vc, mr, vr), (mc, vc, mr, vr)
         w, o, _ = got
         seen |= {("w", w) if w in (16, 64, 127) else None, ("o", o) if o in (-128, 127) else None, "cand" if got[2] else "plain"}
     assert {("w", 16), ("w", 127), ("w", 64), ("o", -128), ("o", 127), "cand", "plain"} <= seen, seen
     for cand in (0, 1):
         for plain, wt in ((0, 0), (16, 15), (16, 14), (1600, 1499), (1600, 1500), (1 << 40, (1 << 40) - (1 << 37)), (5, 100)):
-            assert hw().hw_accept(cand, plain, wt) == int(bool(cand) and 16 * wt < 15 * plain)
+            assert hc.lib().hw_accept(cand, plain, wt) == int(bool(cand) and 16 * wt < 15 * plain)
 
 
 def test_sample_prediction_matches_the_formulas():
@@ -140,17 +95,17 @@ def test_sample_prediction_matches_the_formulas():
     for w in range(16, 128):
         for o in (-128, -77, -6, -1, 0, 1, 8, 50, 127):
             want = np.clip(((s * w + 32) >> 6) + o, 0, 255)
-            got = np.array([hw().hw_sample(int(v), w, o) for v in s])
+            got = np.array([hc.lib().hw_sample(int(v), w, o) for v in s])
             assert np.array_equal(got, want) and np.array_equal(M.sample(s, w, o), want), (w, o)
     # the 14-bit form: at whole vectors (p = 64 s) the sample formula; in between, 8.5.3.3.4.3 (-8192 + ... + 8192 covers what the filters can give)
     rng = random.Random(3)
     for w in (16, 17, 63, 64, 65, 100, 127):
         for o in (-128, -6, 0, 9, 127):
-            assert all(hw().hw_pred14(64 * int(v), w, o) == hw().hw_sample(int(v), w, o) for v in s)
+            assert all(hc.lib().hw_pred14(64 * int(v), w, o) == hc.lib().hw_sample(int(v), w, o) for v in s)
             for p in [rng.randrange(-2048, 18432) for _ in range(400)] + [-2048, -1, 0, 1, 16383, 18431]:
                 want = min(255, max(0, ((p * w + 2048) >> 12) + o))
-                assert hw().hw_pred14(p, w, o) == want == int(M.pred14(p, w, o)), (p, w, o)
-    assert all(hw().hw_pred14(p, 64, 0) == min(255, max(0, (p + 32) >> 6)) for p in range(-2048, 18432, 7))      # (64, 0) is the prediction without weights
+                assert hc.lib().hw_pred14(p, w, o) == want == int(M.pred14(p, w, o)), (p, w, o)
+    assert all(hc.lib().hw_pred14(p, 64, 0) == min(255, max(0, (p + 32) >> 6)) for p in range(-2048, 18432, 7))      # (64, 0) is the prediction without weights
 
 
 def test_decision_on_pictures_matches_the_model():
@@ -168,7 +123,7 @@ def test_decision_on_pictures_matches_the_model():
                 pa[:, :w], pb[:, :w] = a, b
                 pa[:, w:], pb[:, w:] = 201, 3                # (what lies beside the visible samples must not count)
                 out = np.zeros(3, np.int32)
-                hw().hw_decide(pa.ctypes.data, pb.ctypes.data, w, h, pitch, out.ctypes.data)
+                hc.lib().hw_decide(pa.ctypes.data, pb.ctypes.data, w, h, pitch, out.ctypes.data)
                 assert tuple(int(v) for v in out) == M.decide(a, b), (w, h)
                 kinds["w" if out[0] else "p"] += 1
     assert kinds["w"] >= 20 and kinds["p"] >= 8, kinds
@@ -188,8 +143,8 @@ def test_slice_headers_carry_the_table(nact):
     recs += [[((1, rng.randrange(16, 128), rng.randrange(-128, 128)) if rng.random() < 0.6 else (0, 64, 0)) for _ in range(4)] for _ in range(12)]
     for rec in recs:
         for wpp, tr, tc, sl in ((1, 1, 1, 0), (0, 1, 1, 0), (0, 2, 2, 2), (1, 1, 1, 1)):
-            on = access_unit(256, 192, 4, nact, 1, rec, wpp=wpp, tr=tr, tc=tc, slices=sl)
-            off = access_unit(256, 192, 4, nact, 0, None, wpp=wpp, tr=tr, tc=tc, slices=sl)
+            on = hc.access_unit(256, 192, nact, lp=4, weightp=1, wts=rec, wpp=wpp, tr=tr, tc=tc, slices=sl)
+            off = hc.access_unit(256, 192, nact, lp=4, weightp=0, wts=None, wpp=wpp, tr=tr, tc=tc, slices=sl)
             non, noff = pyhevc.split_nals(on), pyhevc.split_nals(off)
             assert non[0] == noff[0] and non[1] == noff[1]                       # VPS and SPS are unchanged
             pps = pyhevc.parse_pps(pyhevc.unescape(non[2]))
@@ -226,7 +181,7 @@ def _payloads(w, h, n, frames):
             nal = [x for x in pyhevc.split_nals(au) if (x[0] >> 1) & 63 in (1, 19)]
             assert len(nal) == 1
             rbsp = pyhevc.unescape(nal[0])
-            mine = pyhevc.split_nals(access_unit(w, h, n, t, 0, None, payload=b"", write_ps=0, wpp=0))[0]
+            mine = pyhevc.split_nals(hc.access_unit(w, h, t, lp=n, weightp=0, wts=None, payload=b"", write_ps=0, wpp=0))[0]
             hdr = pyhevc.unescape(mine)[:-2]                                      # (the placeholder substream's two bytes)
             assert rbsp.startswith(hdr), t                                        # the host build's header is the checker's
             out.append((t, bytes(rbsp[len(hdr):]), oe.recon()))
@@ -239,7 +194,7 @@ def test_access_units_decode_with_the_weights_put_in():
     """A stream of the checker's encoder (lp-refs 4: pictures with 1, 2, 3 and 4 references) under new headers from the host build: weighted_pred_flag and a
     table per P picture.  tests/pyhevc.py reads back the weights put in; it and the checker's decoder make the same pictures of the stream -- the reconstruction
     of before where every flag is 0, another picture where a reference is weighted."""
-    from test_python_decoder import tabs
+    from deckit import tabs
     w, h, n = 128, 64, 4
     frames = [orc.synth_frame(0, 0x5EED0000, w, h, t) for t in range(5)]
     pay = _payloads(w, h, n, frames)
@@ -250,7 +205,7 @@ def test_access_units_decode_with_the_weights_put_in():
         try:
             for t, data, rec_plain in pay:
                 rec = recs[t] if weighted and t else [M.PLAIN] * 4
-                au = access_unit(w, h, n, t, 1, rec if t else None, payload=data, write_ps=int(t == 0), wpp=0)
+                au = hc.access_unit(w, h, t, lp=n, weightp=1, wts=rec if t else None, payload=data, write_ps=int(t == 0), wpp=0)
                 dec.decode(au)
                 if t:
                     ld, cd, wp = dec.last_sh["wp"]
@@ -278,5 +233,5 @@ def test_headers_with_the_field_off_are_the_parents_bytes():
     some = [(1, 99, -3)] * 4
     for i, (*args, digest) in enumerate(gold["cases"]):
         w, h, lp, sao, wpp, tr, tc, sl, poc = args
-        au = access_unit(w, h, lp, poc, 0, some if i & 1 else None, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
+        au = hc.access_unit(w, h, poc, lp=lp, weightp=0, wts=some if i & 1 else None, sao=sao, wpp=wpp, tr=tr, tc=tc, slices=sl)
         assert hashlib.sha256(au).hexdigest()[:16] == digest, args

@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import orc, parser_probe as PP
-from test_gpu_foreign import PLAIN
+from deckit import PLAIN
 
 feature = eval(sys.argv[1]) if len(sys.argv) > 1 else {}
 cfg = dict(PLAIN); cfg.update(feature)

@@ -7,7 +7,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(
 import numpy as np
 import orc
 from kvazzup_amd.codec import Decoder
-from test_gpu_foreign import PLAIN
+from deckit import PLAIN
 
 def seg_info(nal, nctb_bits, dep_enabled):
     # first_slice_segment_in_pic_flag, [no_output_of_prior_pics], pps id (ue), dependent flag, address

@@ -3,7 +3,7 @@ python tools/measure/b_sweep_gpu.py [first seed] [count]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_gpu_foreign as T
+import deckit as T
 first, count = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (2000, 120)
 bad = 0
 sizes = [(416, 240), (352, 288), (200, 136), (648, 360), (64, 64), (136, 72)]

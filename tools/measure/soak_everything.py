@@ -2,8 +2,8 @@
 """tools/measure/soak_everything.py [first seed] [last seed]: tests/test_gpu_everything.py's draw over many more seeds (GPU box); prints the seeds that differ."""
 import os, sys, traceback
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
-from test_gpu_everything import drawn
-from test_gpu_foreign import run_stream
+from cases import drawn
+from deckit import run_stream
 a, b = int(sys.argv[1]) if len(sys.argv) > 1 else 49, int(sys.argv[2]) if len(sys.argv) > 2 else 400
 bad = []
 for seed in range(a, b + 1):

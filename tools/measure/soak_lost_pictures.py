@@ -5,9 +5,9 @@ import os, sys
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import random
 import orc
-from test_gpu_everything import drawn
-from test_gpu_lost_pictures import run
-from test_random_access import vcl_type
+from cases import drawn
+from deckit import run
+from nalkit import vcl_type
 a, b = int(sys.argv[1]) if len(sys.argv) > 1 else 1, int(sys.argv[2]) if len(sys.argv) > 2 else 300
 bad, lost = [], 0
 for seed in range(a, b + 1):

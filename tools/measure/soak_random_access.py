@@ -5,9 +5,9 @@ prints the seeds where the HIP decoder and the checker disagree."""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import orc
-from test_gpu_everything import drawn
-from test_gpu_random_access import both
-from test_random_access import EOS, discard_prior, rename, vcl_type
+from cases import drawn
+from deckit import both
+from nalkit import EOS, discard_prior, rename, vcl_type
 a, b = int(sys.argv[1]) if len(sys.argv) > 1 else 1, int(sys.argv[2]) if len(sys.argv) > 2 else 300
 bad, cuts = [], 0
 for seed in range(a, b + 1):

@@ -4,9 +4,9 @@
 // I / P / B pictures: any coding quadtree with CTB 64 and minimum CB 8, every partitioning, transform trees down to 4x4,
 // several reference pictures, coded sizes that are multiples of 8.
 //
-// Everything lives in ONE pinned host block per picture that goes to the GPU in one copy:
-//   [ B4Rec x (ph/4 * pw/4) | region table | CTU table | SaoParams x CTUs | DecTu x ntu | level words ]
+// Everything lives in ONE pinned host block per picture that goes to the GPU in one copy: DecInputLayout, below, says where.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "hevc_core.h"
 
@@ -92,6 +92,27 @@ struct DecFrame {
   uint8_t cip;                             // constrained_intra_pred_flag: neighbouring samples of blocks that are not intra-coded are "not available" as reference samples (8.4.4.2.2)
   uint8_t tq_bypass;        // the picture may hold coding units with cu_transquant_bypass_flag (B4_BYPASS / TU_BYPASS): the loop filters look at the flags
   const uint8_t *scaling;   // KVZ_SCALING_BYTES scaling factors (scaling_list_enabled_flag), NULL: flat 16
+};
+
+// Where everything lies in a picture's input block, stated ONCE: the parser computes it, keeps it with the picture (PicJob::lay) and writes by it; the decoder uploads,
+// builds the DecFrame and digests by that copy.  Host only.  The fixed part depends on the padded size and CtbLog2SizeY alone: records | region table | per CTB:
+// transform-block range, tile id, (16) SAO parameters | (64) KVZ_SCALING_BYTES scaling factors | (64) 32 DecWt | (64) the picture's DecFrame, for launches that read it
+// from device memory (batch.h) | (16) per CTB the neighbours open to the in-loop filters (DecFrame::ctu_nb).  The variable part follows, every piece on a multiple of 16:
+// ntu DecTu | nlev level words | bi: nb4x B4L1 | CTBs < 64: ntu indices (DecFrame::tu_index; behind the B4L1s' place even without them).  upload_bytes(): the end of the last piece present.
+struct DecInputLayout {
+  size_t nctb = 0, ntu = 0, nlev = 0, nb4x = 0; bool bi = false, indexed = false;      // (nb4x: 0 without bi)
+  size_t region_off = 0, ctu_off = 0, tile_off = 0, sao_off = 0, scaling_off = 0, wt_off = 0, frame_off = 0, nb_off = 0, tu_off = 0, lev_off = 0, x_off = 0, i_off = 0, end = 0;
+  DecInputLayout(int pw = 0, int ph = 0, int ctb_log2 = 6, size_t ntu_ = 0, size_t nlev_ = 0, size_t nb4x_ = 0, bool bi_ = false)
+      : nctb((size_t)(pw >> ctb_log2) * (ph >> ctb_log2)), ntu(ntu_), nlev(nlev_), nb4x(bi_ ? nb4x_ : 0), bi(bi_), indexed(ctb_log2 < 6)
+  {
+    auto up = [](size_t v, size_t a) { return (v + a - 1) & ~(a - 1); };
+    region_off = (size_t)(pw / 4) * (ph / 4) * sizeof(B4Rec); ctu_off = region_off + (size_t)(pw / 32) * (ph / 32) * sizeof(TuRange); tile_off = ctu_off + nctb * sizeof(TuRange);
+    sao_off = up(tile_off + nctb, 16); scaling_off = up(sao_off + nctb * sizeof(SaoParams), 64); wt_off = up(scaling_off + KVZ_SCALING_BYTES, 64);
+    frame_off = up(wt_off + 32 * sizeof(DecWt), 64); nb_off = up(frame_off + sizeof(DecFrame), 16); tu_off = up(nb_off + nctb, 16);
+    lev_off = up(tu_off + ntu * sizeof(DecTu), 16); x_off = up(lev_off + nlev * sizeof(uint32_t), 16); i_off = up(x_off + nb4x * sizeof(B4L1), 16);
+    end = indexed ? i_off + ntu * sizeof(uint32_t) : (bi ? x_off + nb4x * sizeof(B4L1) : lev_off + nlev * sizeof(uint32_t));
+  }
+  size_t fixed_bytes() const { return tu_off; } size_t upload_bytes() const { return end; }
 };
 
 // Several pictures in ONE launch (batch.h: pictures of different decoder instances that are ready at the same time): the kernel argument is

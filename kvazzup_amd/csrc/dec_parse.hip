@@ -1158,16 +1158,13 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
   // offsets become picture-wide
   size_t ntu = 0, nlev = 0;
   for (auto &r : job.subs) { if (r.rc < 0) return r.rc; ntu += r.tus.size(); nlev += r.levels.size(); }
-  const size_t tu_off = fixed_bytes(), lev_off = (tu_off + ntu * sizeof(DecTu) + 15) & ~(size_t)15;
-  // (a picture with bi-predicted blocks: their second vectors ride behind the level words)
+  // The layout is decided HERE, once; everything behind the parser reads job.lay.  (bi: the second vectors ride behind the level words.  CTBs smaller than 64: a 32x32 region's transform
+  // blocks are no run of the list any more -- CTB 16: four CTBs of two CTB rows, i.e. of two substreams --, the regions get a list of INDICES into it behind everything else, DecFrame::tu_index.)
   const bool bi = (job.sh.is_b || job.sh.weighted) && job.any_bi.load(std::memory_order_relaxed) != 0;
-  const size_t x_off = (lev_off + nlev * sizeof(uint32_t) + 15) & ~(size_t)15, x_bytes = bi ? job.b4x.size() * sizeof(B4L1) : 0;
-  // CTBs smaller than 64: a 32x32 region's transform blocks are no run of the list any more (CTB 16: four CTBs of two CTB rows, i.e. of two substreams) -- the
-  // regions get a list of INDICES into it, behind everything else in the block (DecFrame::tu_index)
-  const size_t i_off = (x_off + x_bytes + 15) & ~(size_t)15, i_bytes = ctbl_ < 6 ? ntu * sizeof(uint32_t) : 0;
-  if (!grow_job_input(job, i_off + i_bytes)) return DEC_ERR_GPU;
-  if (bi) memcpy(job.h_in + x_off, job.b4x.data(), x_bytes);
-  DecTu *tus = (DecTu *)(job.h_in + tu_off); uint32_t *lev = (uint32_t *)(job.h_in + lev_off);
+  const DecInputLayout lay = job.lay = DecInputLayout(pw_, ph_, ctbl_, ntu, nlev, job.b4x.size(), bi);
+  if (!grow_job_input(job, lay.upload_bytes())) return DEC_ERR_GPU;
+  if (bi) memcpy(job.h_in + lay.x_off, job.b4x.data(), lay.nb4x * sizeof(B4L1));
+  DecTu *tus = (DecTu *)(job.h_in + lay.tu_off); uint32_t *lev = (uint32_t *)(job.h_in + lay.lev_off);
   size_t t = 0, l = 0;
   for (int r = 0; r < nsub; r++) {
     SubOut &so = job.subs[(size_t)r];
@@ -1189,7 +1186,7 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
     for (size_t k = 0; k < ntu; k++) job.region[region_of(tus[k])].count++;
     uint32_t at = 0;
     for (int g = 0; g < nreg; g++) { job.region[g].first = at; at += job.region[g].count; job.region[g].count = 0; }
-    uint32_t *idx = (uint32_t *)(job.h_in + i_off);
+    uint32_t *idx = (uint32_t *)(job.h_in + lay.i_off);
     for (size_t k = 0; k < ntu; k++) { TuRange &g = job.region[region_of(tus[k])]; idx[g.first + g.count++] = (uint32_t)k; }      // (list order = decoding order inside a region)
   }
   job.ntu = ntu; job.nlev = nlev;
@@ -1211,7 +1208,7 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
           }
       if (next != job.lf_slices.size()) return DEC_ERR_INVALID;                      // (a slice that begins where no substream's walk comes by)
     }
-    uint8_t *nb = job.h_in + off_nb();
+    uint8_t *nb = job.h_in + lay.nb_off;
     const int per = 1 << (ctbl_ - 2), b4w = pw_ / 4;
     for (int cy = 0; cy < hc; cy++)
       for (int cx = 0; cx < wc; cx++) {

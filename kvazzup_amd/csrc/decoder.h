@@ -191,6 +191,7 @@ class Decoder {
     std::shared_ptr<ColMotion> col, own;                         // collocated picture's motion (NULL: no temporal candidates); this picture's
     // the pinned input block (dec_frame.h) and the host views into it
     uint8_t *h_in = nullptr; size_t h_in_cap = 0; size_t ntu = 0, nlev = 0;
+    DecInputLayout lay;                                          // where everything lies in it: the fixed part from prepare_jobs, the whole of it once parse_job has counted the picture's blocks
     B4Rec *b4 = nullptr; TuRange *region = nullptr, *ctu = nullptr; uint8_t *ctu_tile = nullptr; SaoParams *sao = nullptr;
     // host-only syntax state per 4x4: prediction mode (0 inter, 1 intra, 2 skip, 255 not decoded yet), coding quadtree depth, intra mode
     std::vector<uint8_t> pred_mode, ct_depth, intra_mode;
@@ -256,23 +257,20 @@ class Decoder {
   void note_lf_restrictions(PicJob &job);
   int finish_oldest();
   void drop_pending();
-  // layout of the input block
-  size_t off_region() const { return (size_t)(pw_ / 4) * (ph_ / 4) * sizeof(B4Rec); }
-  size_t off_ctu() const { return off_region() + (size_t)(pw_ / 32) * (ph_ / 32) * sizeof(TuRange); }
-  // (the tables per coding tree block -- transform-block range, tile id, SAO parameters -- have one entry per CTB of the stream's size: ctbl_ = CtbLog2SizeY)
+  // (the tables per coding tree block -- transform-block range, tile id, SAO parameters -- and the intra chains' arrays have one entry per CTB of the stream's size: ctbl_ = CtbLog2SizeY)
   size_t nctb() const { return (size_t)(pw_ >> ctbl_) * (ph_ >> ctbl_); }
-  size_t off_tile() const { return off_ctu() + nctb() * sizeof(TuRange); }
-  size_t off_sao() const { return (off_tile() + nctb() + 15) & ~(size_t)15; }
-  size_t off_scaling() const { return (off_sao() + nctb() * sizeof(SaoParams) + 63) & ~(size_t)63; }     // KVZ_SCALING_BYTES scaling factors (pictures with scaling lists)
-  size_t off_wt() const { return (off_scaling() + KVZ_SCALING_BYTES + 63) & ~(size_t)63; }       // 32 DecWt (pictures with pred_weight_table())
-  size_t off_frame() const { return (off_wt() + 32 * sizeof(DecWt) + 63) & ~(size_t)63; }     // the picture's DecFrame, for launches that read it from device memory (batch.h)
-  size_t off_nb() const { return (off_frame() + sizeof(DecFrame) + 15) & ~(size_t)15; }      // per CTB: the neighbouring CTBs the in-loop filters may use (DecFrame::ctu_nb; pictures with closed boundaries)
-  size_t fixed_bytes() const { return (off_nb() + nctb() + 15) & ~(size_t)15; }
+  bool prepare_jobs(int w, int h, int ctb_log2);      // the new size takes effect; every ring entry: input block with a zeroed fixed part (PicJob::lay), per-4x4 syntax state
   bool grow_job_input(PicJob &job, size_t bytes);
   void bind_job(PicJob &job);
-  int launch_gpu(PicJob &job);
+  // launch_gpu and its stages (decoder.hip), in the order they run; the `batched` / second-chain decisions between them are launch_gpu's own
+  struct ChainSet; int launch_gpu(PicJob &job);
+  int fill_concealed(PicJob &job); uint8_t *input_buffer(PicJob &job, int ib);
+  DecFrame picture_frame(PicJob &job, const DecInputLayout &lay, const ChainSet &cs, uint8_t *d_in) const;
+  bool upload(PicJob &job, const DecInputLayout &lay, uint8_t *d_in, int ib, bool batched);
+  int post_to_batcher(PicJob &job, const DecFrame &f, uint8_t *d_in, int ib); int launch_self(PicJob &job, const DecFrame &f, uint8_t *d_in, int ib, bool alt);
+  template <class F> bool each_buffer_used(const PicJob &job, F &&visit);      // the picture's own buffer and both lists' buffers
   int complete_gpu(PicJob &job);
-  int alloc_slot();
+  int alloc_slot(); struct DpbPic; bool alloc_picture(DpbPic &p);
   void sync_main();                       // everything this decoder has submitted has run (the submission layer's queue included)
   bool batch_attached_ = false, batch_used_ = false;
 
@@ -328,16 +326,20 @@ class Decoder {
   static constexpr int kMaxGpuDepth = 8;
   int gpu_depth_ = 1; std::deque<PicJob *> gpu_q_;
   uint8_t *d_in_[kMaxGpuDepth + 1] = {}; size_t d_in_cap_[kMaxGpuDepth + 1] = {};   // device copies of PicJob::h_in: the pictures in flight take turns
-  int16_t *resid_[3] = {nullptr, nullptr, nullptr};         // intra residuals between k_dec_intra_resid and k_dec_intra
-  uint8_t *work_[3] = {nullptr, nullptr, nullptr};          // pictures with SAO: reconstruction and deblocking happen here, the filter writes into the slot
-  uint32_t *edge_col_ = nullptr; unsigned long long *edge_row_ = nullptr; uint32_t chain_gen_ = 0;      // k_dec_intra's tagged hand-off words (dec_frame.h), the generation of the last launch
-  uint32_t *progress_ = nullptr, *intra_order_ = nullptr, *err_ = nullptr; uint32_t *h_err_ = nullptr;
+  // the arrays of ONE intra chain and the stream it runs on: resid = intra residuals between k_dec_intra_resid and k_dec_intra; work = pictures with SAO are reconstructed
+  // and deblocked here, the filter writes into the picture buffer; edge_col / edge_row = k_dec_intra's tagged hand-off words (dec_frame.h); progress = its ticket counter
+  struct ChainSet { hipStream_t stream = nullptr; uint32_t *progress = nullptr, *edge_col = nullptr; unsigned long long *edge_row = nullptr; int16_t *resid[3] = {nullptr, nullptr, nullptr}; uint8_t *work[3] = {nullptr, nullptr, nullptr}; };
+  ChainSet chain_[2]; uint32_t chain_gen_ = 0;      // main (its stream is stream_) and second (below); the generation of the last launch of either
+  // per CTB of S luma samples a side: S + 2 x S / 2 column words, a quarter as many row words.  (pw_ and ph_ are multiples of 64, so the column words of a picture
+  // are a multiple of 128 -- what a 64x64 CTB has -- whatever the CTB size.)
+  size_t edge_col_words() const { return nctb() * (size_t)(2 << ctbl_); } size_t edge_row_words() const { return edge_col_words() / 4; }
+  bool build_chain(ChainSet &cs, hipStream_t clear_on); void free_chain(ChainSet &cs);      // allocates; clears on the stream that will use the set (NULL: the null stream -- only while nothing is queued anywhere, ensure_buffers)
+  uint32_t *intra_order_ = nullptr, *err_ = nullptr; uint32_t *h_err_ = nullptr;
   // A picture without inter blocks depends on no other picture, and its chain (k_dec_intra: 0.55 ms at 1080p) keeps a few dozen compute units busy: with the
   // frame-threaded decoder such pictures ALTERNATE between the decoder's stream and a second one with chain arrays of its own, so that two chains run side by
   // side (an all-intra stream, BASELINE configs[0]: the decoder's rate was 1 / chain).  Pictures that read or overwrite a buffer last used on the other stream
   // wait for that picture's event.
-  hipStream_t stream_alt_ = nullptr; char alt_prio_ = 'n'; long intra_seq_ = 0; bool alt_failed_ = false;      // (stream_alt_ is set LAST by ensure_alt: non-NULL = every array of the second chain exists)
-  uint32_t *progress_alt_ = nullptr, *edge_col_alt_ = nullptr; unsigned long long *edge_row_alt_ = nullptr; int16_t *resid_alt_[3] = {nullptr, nullptr, nullptr}; uint8_t *work_alt_[3] = {nullptr, nullptr, nullptr};
+  char alt_prio_ = 'n'; long intra_seq_ = 0; bool alt_failed_ = false;      // (chain_[1] is assigned in one piece by ensure_alt: its stream non-NULL = every array of the second chain exists)
   bool ensure_alt();
   // download mode: page-locked output buffers take turns -- one is what libOpenHevcGetOutput last handed out (valid until the next
   // decode call, openhevcfilter.cpp:218-229 copies at once), one receives the picture whose kernels are running, queued behind them on

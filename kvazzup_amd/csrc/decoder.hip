@@ -37,7 +37,7 @@ void Decoder::sync_main()
 {
   if (batch_used_) { DecBatcher::get(device_).drain(this); batch_used_ = false; }
   hipStreamSynchronize(stream_);
-  if (stream_alt_) hipStreamSynchronize(stream_alt_);
+  if (chain_[1].stream) hipStreamSynchronize(chain_[1].stream);
 }
 
 Decoder::~Decoder()
@@ -62,7 +62,7 @@ Decoder::~Decoder()
   stream_release(stream_up_, device_, 'U', prio_up_);
   for (auto &e : up_done_) if (e) hipEventDestroy(e);
   if (h_err_) hipHostFree(h_err_);
-  if (stream_alt_) stream_release(stream_alt_, device_, 'E', alt_prio_);
+  if (chain_[1].stream) stream_release(chain_[1].stream, device_, 'E', alt_prio_);
   stream_release(stream_, device_, 'D', prio_);
 }
 
@@ -80,6 +80,7 @@ bool Decoder::start(std::string *error)
     const char *prio = getenv("KVAZZUP_AMD_PRIO");
     prio_ = (prio && strlen(prio) >= 4) ? prio[3] : 'n';
     HIP_TRY(stream_acquire(&stream_, device_, 'D', prio_));        // (stream_pool.h: a re-created decoder gets its predecessor's streams)
+    chain_[0].stream = stream_;
   }
   {
     const char *prio = getenv("KVAZZUP_AMD_PRIO");          // (letters 5 and 6: the download and the upload stream)
@@ -107,28 +108,37 @@ void Decoder::free_buffers()
   for (auto &j : jobs_) { if (j.h_in) hipHostFree(j.h_in); j.h_in = nullptr; j.h_in_cap = 0; j.col.reset(); j.own.reset(); }
   if (stream_dl_) hipStreamSynchronize(stream_dl_);
   for (auto &p : h_out_) { if (p) retired_out_.emplace_back(nal_calls_, p); p = nullptr; }      // (freed kOutHold calls later: free_retired)
-  for (auto &p : d_in_) { hipFree(p); p = nullptr; }
-  for (auto &c : d_in_cap_) c = 0;
-  hipFree(progress_); hipFree(edge_col_); edge_col_ = nullptr; hipFree(edge_row_); edge_row_ = nullptr; hipFree(intra_order_); intra_order_ = nullptr;
-  if (stream_alt_) {
-    hipStreamSynchronize(stream_alt_);
-    hipFree(progress_alt_); progress_alt_ = nullptr; hipFree(edge_col_alt_); edge_col_alt_ = nullptr; hipFree(edge_row_alt_); edge_row_alt_ = nullptr;
-    for (int c = 0; c < 3; c++) { hipFree(resid_alt_[c]); resid_alt_[c] = nullptr; hipFree(work_alt_[c]); work_alt_[c] = nullptr; }
-    stream_release(stream_alt_, device_, 'E', alt_prio_); stream_alt_ = nullptr;
-  }
+  for (auto &p : d_in_) { hipFree(p); p = nullptr; } for (auto &c : d_in_cap_) c = 0;
+  free_chain(chain_[0]); hipFree(intra_order_); intra_order_ = nullptr;
+  if (chain_[1].stream) { hipStreamSynchronize(chain_[1].stream); free_chain(chain_[1]); stream_release(chain_[1].stream, device_, 'E', alt_prio_); chain_[1].stream = nullptr; }
   alt_failed_ = false;                                       // (another picture size: the second chain's arrays may fit now)
   for (auto &p : dpb_) { hipFree(p.plane[0]); p = DpbPic(); }      // (a buffer's three planes are one allocation)
-  for (int c = 0; c < 3; c++) { hipFree(work_[c]); work_[c] = nullptr; hipFree(resid_[c]); resid_[c] = nullptr; }
-  progress_ = nullptr;
   w_ = h_ = pw_ = ph_ = 0;
+}
+
+// the arrays of one intra chain (decoder.h ChainSet; the stream is the caller's).  Tagged words: generation 0 = never written
+bool Decoder::build_chain(ChainSet &cs, hipStream_t clear_on)
+{
+  const size_t npx = (size_t)pw_ * ph_;
+  auto cleared = [&](void *p, size_t bytes) { return clear_on ? hipMemsetAsync(p, 0, bytes, clear_on) : hipMemset(p, 0, bytes); };
+  HIP_TRY(hipMalloc(&cs.progress, sizeof(uint32_t) * (3 * nctb() + 1))); HIP_TRY(cleared(cs.progress, sizeof(uint32_t) * (3 * nctb() + 1)));      // (+ k_dec_intra's ticket counter)
+  HIP_TRY(hipMalloc(&cs.edge_col, edge_col_words() * sizeof(uint32_t))); HIP_TRY(cleared(cs.edge_col, edge_col_words() * sizeof(uint32_t)));
+  HIP_TRY(hipMalloc(&cs.edge_row, edge_row_words() * 8)); HIP_TRY(cleared(cs.edge_row, edge_row_words() * 8));
+  for (int c = 0; c < 3; c++) { HIP_TRY(hipMalloc(&cs.resid[c], sizeof(int16_t) * (c ? npx / 4 : npx))); HIP_TRY(hipMalloc(&cs.work[c], c ? npx / 4 : npx)); }
+  return true;
+}
+void Decoder::free_chain(ChainSet &cs)
+{
+  hipFree(cs.progress); hipFree(cs.edge_col); hipFree(cs.edge_row); for (int c = 0; c < 3; c++) { hipFree(cs.resid[c]); hipFree(cs.work[c]); }
+  cs = ChainSet{cs.stream};                                  // (the stream stays: its owner releases it)
 }
 
 // host views into a job's input block
 void Decoder::bind_job(PicJob &job)
 {
   uint8_t *p = job.h_in;
-  job.b4 = (B4Rec *)p; job.region = (TuRange *)(p + off_region()); job.ctu = (TuRange *)(p + off_ctu());
-  job.ctu_tile = p + off_tile(); job.sao = (SaoParams *)(p + off_sao());
+  job.b4 = (B4Rec *)p; job.region = (TuRange *)(p + job.lay.region_off); job.ctu = (TuRange *)(p + job.lay.ctu_off);
+  job.ctu_tile = p + job.lay.tile_off; job.sao = (SaoParams *)(p + job.lay.sao_off);
 }
 
 // pinned input block of a job: at least `bytes`; the fixed part written so far is kept.  Called from the
@@ -138,20 +148,13 @@ bool Decoder::grow_job_input(PicJob &job, size_t bytes)
   if (bytes <= job.h_in_cap) return true;
   const size_t cap = bytes + bytes / 2;
   uint8_t *p = nullptr;
-  if (parse_only_) {
-    p = (uint8_t *)aligned_alloc(64, (cap + 63) & ~(size_t)63);
-    if (!p) return false;
-    if (job.h_in) { memcpy(p, job.h_in, fixed_bytes() < job.h_in_cap ? fixed_bytes() : job.h_in_cap); free(job.h_in); }
-    job.h_in = p; job.h_in_cap = cap;
-    bind_job(job);
-    return true;
-  }
-  if (hipSetDevice(device_) != hipSuccess) return false;
-  if (hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess) return false;
+  if (parse_only_) p = (uint8_t *)aligned_alloc(64, (cap + 63) & ~(size_t)63);      // (the host half alone: plain memory)
+  else if (hipSetDevice(device_) != hipSuccess || hipHostMalloc(&p, cap, hipHostMallocDefault) != hipSuccess) return false;
+  if (!p) return false;
   if (job.h_in) {
-    memcpy(p, job.h_in, fixed_bytes() < job.h_in_cap ? fixed_bytes() : job.h_in_cap);
-    if (job.early_rows.load(std::memory_order_acquire) > 0) hipStreamSynchronize(stream_up_);      // (rows of records on their way up read the old block)
-    hipHostFree(job.h_in);
+    memcpy(p, job.h_in, job.lay.fixed_bytes() < job.h_in_cap ? job.lay.fixed_bytes() : job.h_in_cap);
+    if (!parse_only_ && job.early_rows.load(std::memory_order_acquire) > 0) hipStreamSynchronize(stream_up_);      // (rows of records on their way up read the old block)
+    if (parse_only_) free(job.h_in); else hipHostFree(job.h_in);
   }
   job.h_in = p; job.h_in_cap = cap;
   bind_job(job);
@@ -172,13 +175,7 @@ bool Decoder::ensure_buffers(int w, int h, int ctb_log2)
     for (auto &j : jobs_) { free(j.h_in); j.h_in = nullptr; j.h_in_cap = 0; }
     if (jobs_.empty()) jobs_ = std::vector<PicJob>(3);
     gpu_depth_ = 1;
-    w_ = w; h_ = h; pw_ = (w + 63) & ~63; ph_ = (h + 63) & ~63; ctbl_ = ctb_log2;
-    const size_t nb4 = (size_t)pw_ * ph_ / 16;
-    for (auto &j : jobs_) {
-      if (!grow_job_input(j, fixed_bytes() + (1 << 16))) return false;
-      memset(j.h_in, 0, fixed_bytes());
-      j.pred_mode.assign(nb4 / 4, PM_NONE); j.ct_depth.assign(nb4 / 4, 0); j.intra_mode.assign(nb4, 1);
-    }
+    if (!prepare_jobs(w, h, ctb_log2)) return false;
     for (auto &d : dpb_) { d = DpbPic(); d.plane[0] = (uint8_t *)(uintptr_t)64; }      // (never dereferenced: slots are only book-keeping here)
     seen_irap_ = false;
     return true;
@@ -194,19 +191,10 @@ bool Decoder::ensure_buffers(int w, int h, int ctb_log2)
     if (gpu_depth_ < 1 || band_nrows_ > 0) gpu_depth_ = 1;
     jobs_ = std::vector<PicJob>((size_t)frame_threads_ + 2);   // the pictures being parsed and queued on the GPU (frame_threads_ of them), the one being handed out, the one being filled
   }
-  w_ = w; h_ = h; pw_ = (w + 63) & ~63; ph_ = (h + 63) & ~63; ctbl_ = ctb_log2;
-  const size_t npx = (size_t)pw_ * ph_, nb4 = npx / 16;
-  for (auto &j : jobs_) {
-    if (!grow_job_input(j, fixed_bytes() + (1 << 16))) return false;
-    memset(j.h_in, 0, fixed_bytes());
-    j.pred_mode.assign(nb4 / 4, PM_NONE); j.ct_depth.assign(nb4 / 4, 0); j.intra_mode.assign(nb4, 1);
-  }
-  h_out_cap_ = npx * 3 / 2;                              // (allocated by the first picture that is downloaded)
-  for (int i = 0; i <= gpu_depth_; i++) { d_in_cap_[i] = fixed_bytes() + (1 << 20); HIP_TRY(hipMalloc(&d_in_[i], d_in_cap_[i])); }
-  HIP_TRY(hipMalloc(&progress_, sizeof(uint32_t) * (3 * nctb() + 1)));
-  { const size_t ec = nctb() * (size_t)(2 << ctbl_), er = nctb() * (size_t)(2 << ctbl_) / 4;          // per CTB of S luma samples a side: S + 2 x S / 2 column words, a quarter as many row words; tagged words: generation 0 = never written
-    HIP_TRY(hipMalloc(&edge_col_, ec * sizeof(uint32_t))); HIP_TRY(hipMemset(edge_col_, 0, ec * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(&edge_row_, er * 8)); HIP_TRY(hipMemset(edge_row_, 0, er * 8)); chain_gen_ = 0; }      // the CTUs' right columns (k_dec_intra)      // (+ k_dec_intra's ticket counter)
+  if (!prepare_jobs(w, h, ctb_log2)) return false;
+  h_out_cap_ = (size_t)pw_ * ph_ * 3 / 2;                // (allocated by the first picture that is downloaded)
+  for (int i = 0; i <= gpu_depth_; i++) { d_in_cap_[i] = jobs_[0].lay.fixed_bytes() + (1 << 20); HIP_TRY(hipMalloc(&d_in_[i], d_in_cap_[i])); }
+  if (!build_chain(chain_[0], nullptr)) return false; chain_gen_ = 0;
   {
     // dispatch order of k_dec_intra's workgroups: CTUs by anti-diagonal cx + 2 cy (every CTU a block depends on comes earlier)
     const int wc = ctbs_in(w_, ctbl_), hc = ctbs_in(h_, ctbl_);      // (the picture's coding tree blocks -- with CTBs smaller than 64 fewer than the padded size holds)
@@ -217,10 +205,7 @@ bool Decoder::ensure_buffers(int w, int h, int ctb_log2)
     HIP_TRY(hipMalloc(&intra_order_, sizeof(uint32_t) * order.size()));
     HIP_TRY(hipMemcpy(intra_order_, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice));
   }
-  for (int c = 0; c < 3; c++) HIP_TRY(hipMalloc(&work_[c], c ? npx / 4 : npx));
-  for (int c = 0; c < 3; c++) HIP_TRY(hipMalloc(&resid_[c], sizeof(int16_t) * (c ? npx / 4 : npx)));
-  // a picture buffer: Y | Cb | Cr back to back in one allocation (the whole picture goes to the host in ONE copy)
-  for (int s = 0; s < 6; s++) { HIP_TRY(hipMalloc(&dpb_[s].plane[0], npx * 3 / 2)); HIP_TRY(hipMemset(dpb_[s].plane[0], 128, npx * 3 / 2)); dpb_[s].plane[1] = dpb_[s].plane[0] + npx; dpb_[s].plane[2] = dpb_[s].plane[1] + npx / 4; }
+  for (int s = 0; s < 6; s++) if (!alloc_picture(dpb_[s])) return false;
   seen_irap_ = false;
   HIP_TRY(hipDeviceSynchronize());                       // (the clears above ran on the null stream: done before anything is queued on the decoder's non-blocking streams)
   return true;
@@ -240,19 +225,36 @@ int Decoder::conceal_ref(int poc, bool is_lt)
   return s;
 }
 
+// a picture buffer: Y | Cb | Cr back to back in one allocation (it goes to the host in ONE copy), mid-grey.  (The clear runs on the null stream, ordered with nothing on the decoder's non-blocking streams: the caller synchronises the device.)
+bool Decoder::alloc_picture(DpbPic &p)
+{
+  const size_t npx = (size_t)pw_ * ph_;
+  if (hipMalloc(&p.plane[0], npx * 3 / 2) != hipSuccess) { p.plane[0] = nullptr; return false; }
+  p.plane[1] = p.plane[0] + npx; p.plane[2] = p.plane[1] + npx / 4;
+  HIP_TRY(hipMemset(p.plane[0], 128, npx * 3 / 2));
+  return true;
+}
+// the new picture size takes effect: every ring entry gets its input block for it (ensure_buffers)
+bool Decoder::prepare_jobs(int w, int h, int ctb_log2)
+{
+  w_ = w; h_ = h; pw_ = (w + 63) & ~63; ph_ = (h + 63) & ~63; ctbl_ = ctb_log2;
+  const size_t nb4 = (size_t)pw_ * ph_ / 16;
+  for (auto &j : jobs_) {
+    j.lay = DecInputLayout(pw_, ph_, ctbl_, 0, 0, 0, false);
+    if (!grow_job_input(j, j.lay.fixed_bytes() + (1 << 16))) return false;
+    memset(j.h_in, 0, j.lay.fixed_bytes());
+    j.pred_mode.assign(nb4 / 4, PM_NONE); j.ct_depth.assign(nb4 / 4, 0); j.intra_mode.assign(nb4, 1);
+  }
+  return true;
+}
+
 int Decoder::alloc_slot()
 {
   for (int s = 0; s < KVZ_DEC_MAX_REFS; s++) {
     DpbPic &p = dpb_[s];
     if (p.is_ref || job_head_ - p.decode_idx <= output_hold_ + (gpu_depth_ - 1)) continue;      // (pictures queued on the GPU behind the one handed out may already write their buffers)
     if (!p.plane[0] && parse_only_) p.plane[0] = (uint8_t *)(uintptr_t)64;
-    if (!p.plane[0]) {
-      const size_t npx = (size_t)pw_ * ph_;
-      if (hipSetDevice(device_) != hipSuccess) return -1;
-      if (hipMalloc(&p.plane[0], npx * 3 / 2) != hipSuccess) { p.plane[0] = nullptr; return -1; }
-      hipMemset(p.plane[0], 128, npx * 3 / 2); p.plane[1] = p.plane[0] + npx; p.plane[2] = p.plane[1] + npx / 4;
-      hipDeviceSynchronize();                              // (a clear on the null stream is ordered with nothing on the decoder's non-blocking streams; a buffer is added at most ten times)
-    }
+    if (!p.plane[0]) { if (hipSetDevice(device_) != hipSuccess || !alloc_picture(p)) return -1; hipDeviceSynchronize(); }      // (a buffer is added at most ten times)
     return s;
   }
   return -1;
@@ -267,43 +269,27 @@ template <class F> void Decoder::timed(int id, F &&launch, hipStream_t st)
   PicJob::EvPair &p = j.ev[j.ev_used++]; p.id = id;
   hipEventRecord(p.a, st); launch(); hipEventRecord(p.b, st);
 }
-// the second chain's stream and arrays (decoder.h stream_alt_), on first use
+// the second chain's stream and arrays (decoder.h chain_[1]), on first use
 bool Decoder::ensure_alt()
 {
-  if (stream_alt_) return true;
+  if (chain_[1].stream) return true;
   if (alt_failed_) return false;                             // (it did not fit once: the intra-only pictures keep to the one chain instead of trying again for every picture)
   if (hipSetDevice(device_) != hipSuccess) return false;
-  const size_t nctu = nctb(), ecw = nctu * (size_t)(2 << ctbl_), npx = (size_t)pw_ * ph_;
   // the second chain's priority level = its pool of hardware queues: the LOWEST level, where nothing else of this library lives (measured, all-intra 1080p with
   // the encoder's second chain at the main stream's level: second decoder chain at the default level 1 563 frames/s -- the level's four queues are taken by
   // tokenizer, input, decoder and transfers --, at the high level 1 681, at the low one 1 724; one chain each side: 1 279)
   { const char *e = getenv("KVAZZUP_AMD_DEC_ALT_PRIO"); alt_prio_ = e ? e[0] : 'l'; }
-  // Everything is built in locals and handed to the members in one piece: stream_alt_ != NULL is what launch_gpu takes for "the second chain exists", so a
+  // Everything is built in a local and handed to the member in one piece: chain_[1].stream != NULL is what launch_gpu takes for "the second chain exists", so a
   // half-built state (a failed allocation at 4K) must never be visible -- on any failure what was allocated is freed and the stream released.
-  hipStream_t st = nullptr;
-  uint32_t *prog = nullptr, *ecol = nullptr; unsigned long long *erow = nullptr; int16_t *res[3] = {nullptr, nullptr, nullptr}; uint8_t *wrk[3] = {nullptr, nullptr, nullptr};
-  auto build = [&]() -> bool {
-    HIP_TRY(stream_acquire(&st, device_, 'E', alt_prio_));
-    // (cleared ON the stream that is about to use them: the decoder's streams are non-blocking, a clear on the null stream is ordered with nothing -- the first
-    // picture of the second chain had its hand-off words zeroed under its hands, every wait in it gave up: error flags 3, found by the serial suite)
-    HIP_TRY(hipMalloc(&prog, sizeof(uint32_t) * (3 * nctu + 1))); HIP_TRY(hipMemsetAsync(prog, 0, sizeof(uint32_t) * (3 * nctu + 1), st));
-    HIP_TRY(hipMalloc(&ecol, ecw * sizeof(uint32_t))); HIP_TRY(hipMemsetAsync(ecol, 0, ecw * sizeof(uint32_t), st));
-    HIP_TRY(hipMalloc(&erow, ecw / 4 * 8)); HIP_TRY(hipMemsetAsync(erow, 0, ecw / 4 * 8, st));
-    for (int c = 0; c < 3; c++) { HIP_TRY(hipMalloc(&res[c], sizeof(int16_t) * (c ? npx / 4 : npx))); HIP_TRY(hipMalloc(&wrk[c], c ? npx / 4 : npx)); }
-    return true;
-  };
+  // (Cleared ON the stream that is about to use them: a clear on the null stream is ordered with nothing on a non-blocking stream -- the second chain's first picture had its hand-off words zeroed under its hands, every wait in it gave up: error flags 3)
+  ChainSet cs;
+  auto build = [&]() -> bool { HIP_TRY(stream_acquire(&cs.stream, device_, 'E', alt_prio_)); return build_chain(cs, cs.stream); };
   if (!build()) {
-    if (st) hipStreamSynchronize(st);                        // (a clear may be queued on it)
-    hipFree(prog); hipFree(ecol); hipFree(erow);
-    for (int c = 0; c < 3; c++) { hipFree(res[c]); hipFree(wrk[c]); }
-    if (st) stream_release(st, device_, 'E', alt_prio_);
-    (void)hipGetLastError();
-    alt_failed_ = true;
-    return false;
+    if (cs.stream) hipStreamSynchronize(cs.stream);          // (a clear may be queued on it)
+    free_chain(cs); stream_release(cs.stream, device_, 'E', alt_prio_); (void)hipGetLastError();      // (stream_release: nothing to do without a stream)
+    alt_failed_ = true; return false;
   }
-  progress_alt_ = prog; edge_col_alt_ = ecol; edge_row_alt_ = erow;
-  for (int c = 0; c < 3; c++) { resid_alt_[c] = res[c]; work_alt_[c] = wrk[c]; }
-  stream_alt_ = st;
+  chain_[1] = cs;
   return true;
 }
 void Decoder::get_kernel_times(double *ms, uint64_t *launches, bool reset)
@@ -1082,7 +1068,7 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
       // (decoder.h PicJob::early_dst; the buffer is the one launch_gpu will pick -- nothing is launched between here and there)
       static const bool early_off = [] { const char *e = getenv("KVAZZUP_AMD_DEC_EARLY_UP"); return e && atoi(e) == 0; }();
       const int ib = (int)(launched_ % (gpu_depth_ + 1));
-      if (!early_off && gpu_depth_ == 1 && band_nrows_ == 0 && job.pps.tile_cols == 1 && !job.lf_restricted && !(batch_attached_ && DecBatcher::get(device_).active()) && d_in_[ib] && d_in_cap_[ib] >= fixed_bytes()) job.early_dst = d_in_[ib];      // (lf_restricted: parse_job's last step still changes records)
+      if (!early_off && gpu_depth_ == 1 && band_nrows_ == 0 && job.pps.tile_cols == 1 && !job.lf_restricted && !(batch_attached_ && DecBatcher::get(device_).active()) && d_in_[ib] && d_in_cap_[ib] >= job.lay.fixed_bytes()) job.early_dst = d_in_[ib];      // (lf_restricted: parse_job's last step still changes records)
     }
     job.rc = parse_job(job, true);
     if (job.rc == DEC_SEG_ENDS_EARLY) { if (job.early_dst) hipStreamSynchronize(stream_up_); return take_back(); }
@@ -1115,7 +1101,6 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
 // set_parse_only: what launch_gpu would upload for this picture, folded into the running digest
 void Decoder::probe_book(PicJob &job, double ms)
 {
-  const size_t tu_off = fixed_bytes(), lev_off = (tu_off + job.ntu * sizeof(DecTu) + 15) & ~(size_t)15;
   if (const char *dump = getenv("KVAZZUP_AMD_PROBE_DUMP")) {      // (debugging aid: every picture's 4x4 records and intra modes, rows of pw / 4, appended to the file)
     if (FILE *fp = fopen(dump, "ab")) {
       const int32_t hdr[4] = {pw_ / 4, ph_ / 4, w_ / 4, h_ / 4};
@@ -1125,9 +1110,9 @@ void Decoder::probe_book(PicJob &job, double ms)
   }
   uint64_t d = probe_.digest;
   auto fold = [&](const uint8_t *p, size_t n) { for (size_t i = 0; i < n; i++) { d ^= p[i]; d *= 0x100000001b3ull; } };
-  fold(job.h_in, off_scaling());                                              // records, region / CTU tables, tile ids, SAO parameters
-  fold(job.h_in + tu_off, job.ntu * sizeof(DecTu));
-  fold(job.h_in + lev_off, job.nlev * sizeof(uint32_t));
+  fold(job.h_in, job.lay.scaling_off);                                        // records, region / CTU tables, tile ids, SAO parameters
+  fold(job.h_in + job.lay.tu_off, job.ntu * sizeof(DecTu));
+  fold(job.h_in + job.lay.lev_off, job.nlev * sizeof(uint32_t));
   probe_.digest = d; probe_.pictures++; probe_.tus += job.ntu; probe_.levels += job.nlev; probe_.parse_ms += ms;
 }
 
@@ -1266,152 +1251,147 @@ int Decoder::complete_gpu(PicJob &job)
 }
 
 // ------------------------------------------------------------------------------------------ GPU reconstruction
-int Decoder::launch_gpu(PicJob &job)
+// launch_gpu's stages, in the order they run.  fill_concealed: buffers that stand in for lost reference pictures (conceal_ref) -- grey, or a copy of the nearest
+// picture -- BEFORE this picture's kernels and AFTER everything older has left the GPU: older pictures in flight may still read what the buffers held.  A loss is
+// rare: the device is simply drained (pictures handed to the submission layer are launched first).
+int Decoder::fill_concealed(PicJob &job)
 {
-  if (hipSetDevice(device_) != hipSuccess) return DEC_ERR_GPU;
-  if (!job.conceal.empty()) {
-    // buffers that stand in for lost reference pictures (conceal_ref): grey BEFORE this picture's kernels and AFTER everything older has left the GPU -- older pictures in
-    // flight may still read what the buffers held.  A loss is rare: the device is simply drained (pictures handed to the submission layer are launched first).
-    for (PicJob *j : gpu_q_) while (!j->launched.load(std::memory_order_acquire)) futex_wait(j->launched, 0);
-    if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
-    const size_t npx = (size_t)pw_ * ph_;
-    // (unconditionally: headers run ahead of launches -- by now a LATER picture may have been given the buffer, which is fine, it launches after this one and
-    // overwrites it; a list inherited from a header that failed names buffers that are still stand-ins or have become this picture's own)
-    for (const auto &c : job.conceal) {
-      uint8_t *dst = dpb_[c.first].plane[0], *src = c.second >= 0 ? dpb_[c.second].plane[0] : nullptr;
-      if (!dst) continue;
-      if ((src && src != dst ? hipMemcpy(dst, src, npx * 3 / 2, hipMemcpyDeviceToDevice) : hipMemset(dst, 128, npx * 3 / 2)) != hipSuccess) return DEC_ERR_GPU;
-    }
-    if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
-    job.conceal.clear();
+  const size_t npx = (size_t)pw_ * ph_;
+  for (PicJob *j : gpu_q_) while (!j->launched.load(std::memory_order_acquire)) futex_wait(j->launched, 0);
+  if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
+  // (unconditionally: headers run ahead of launches -- by now a LATER picture may have been given the buffer, which is fine, it launches after this one and
+  // overwrites it; a list inherited from a header that failed names buffers that are still stand-ins or have become this picture's own)
+  for (const auto &c : job.conceal) {
+    uint8_t *dst = dpb_[c.first].plane[0], *src = c.second >= 0 ? dpb_[c.second].plane[0] : nullptr;
+    if (dst && (src && src != dst ? hipMemcpy(dst, src, npx * 3 / 2, hipMemcpyDeviceToDevice) : hipMemset(dst, 128, npx * 3 / 2)) != hipSuccess) return DEC_ERR_GPU;
   }
-  const size_t ntu = job.ntu, nlev = job.nlev;
-  const size_t tu_off = fixed_bytes(), lev_off = (tu_off + ntu * sizeof(DecTu) + 15) & ~(size_t)15;
-  const bool bi = (job.sh.is_b || job.sh.weighted) && job.any_bi.load(std::memory_order_relaxed) != 0;
-  const size_t x_off = (lev_off + nlev * sizeof(uint32_t) + 15) & ~(size_t)15;
-  const size_t i_off = (x_off + (bi ? job.b4x.size() * sizeof(B4L1) : 0) + 15) & ~(size_t)15;      // (parse_job: the regions' index list of a stream with CTBs smaller than 64)
-  const size_t bytes = ctbl_ < 6 ? i_off + ntu * sizeof(uint32_t) : (bi ? x_off + job.b4x.size() * sizeof(B4L1) : lev_off + nlev * sizeof(uint32_t));
-  prof_now_ = profiling_ && (launched_ % prof_every_) == 0;
-  timed_job_ = &job; job.ev_used = 0;
-  if (!job.done && hipEventCreateWithFlags(&job.done, hipEventDisableTiming) != hipSuccess) return DEC_ERR_GPU;
-  Tick tk_api;
-  // The input block goes up on its own stream into one of gpu_depth_ + 1 device buffers: the gpu_depth_ pictures launched before this
-  // one may still be running (finish_oldest launches before it completes the oldest of them) and read the other buffers; the one before
-  // those has been completed, so this buffer is free.
-  const int ib = (int)(launched_ % (gpu_depth_ + 1));
-  uint8_t *&d_in_ = this->d_in_[ib];
+  if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
+  job.conceal.clear(); return 0;
+}
+// The input block goes up on its own stream into one of gpu_depth_ + 1 device buffers: the gpu_depth_ pictures launched before this one may still be running
+// (finish_oldest launches before it completes the oldest of them) and read the other buffers; the one before those has been completed, so this buffer is free.
+// -> buffer `ib`, grown to hold this picture's block; NULL: no memory
+uint8_t *Decoder::input_buffer(PicJob &job, int ib)
+{
+  const size_t bytes = job.lay.upload_bytes();
   if (bytes > d_in_cap_[ib]) {
     if (job.early_dst) { hipStreamSynchronize(stream_up_); job.early_dst = nullptr; }      // (the rows that went up early went into the buffer being replaced)
-    hipFree(d_in_);
-    d_in_cap_[ib] = bytes + bytes / 2;
-    if (hipMalloc(&d_in_, d_in_cap_[ib]) != hipSuccess) { d_in_ = nullptr; d_in_cap_[ib] = 0; return DEC_ERR_GPU; }
+    hipFree(d_in_[ib]); d_in_cap_[ib] = bytes + bytes / 2;
+    if (hipMalloc(&d_in_[ib], d_in_cap_[ib]) != hipSuccess) { d_in_[ib] = nullptr; d_in_cap_[ib] = 0; }
   }
+  return d_in_[ib];
+}
+// The picture's kernel argument: the one place its fields are set.  Const apart from the scaling factors and weights, which it copies into the job's input block
+// (they go up with it).  d_in: the device copy of that block, laid out by `lay`; cs: the chain the picture runs on.
+DecFrame Decoder::picture_frame(PicJob &job, const DecInputLayout &lay, const ChainSet &cs, uint8_t *d_in) const
+{
   DecFrame f; memset(&f, 0, sizeof(f));
   f.w = w_; f.h = h_; f.pw = pw_; f.ph = ph_; f.wc = (w_ + 63) / 64; f.hc = (h_ + 63) / 64;      // (wc, hc: the picture in 64x64 tiles -- what the region, deblocking and SAO grids are made of)
   f.ctb_log2 = ctbl_; f.cwc = (w_ + (1 << ctbl_) - 1) >> ctbl_; f.chc = (h_ + (1 << ctbl_) - 1) >> ctbl_;      // ... and in coding tree blocks: the intra chain's work units, the tile ids, the SAO parameters
-  f.tu_index = ctbl_ < 6 ? (const uint32_t *)(d_in_ + i_off) : nullptr;
-  f.b4 = (const B4Rec *)d_in_; f.b4x = bi ? (const B4L1 *)(d_in_ + x_off) : nullptr; f.region = (const TuRange *)(d_in_ + off_region()); f.ctu = (const TuRange *)(d_in_ + off_ctu());
-  f.ctu_tile = d_in_ + off_tile(); f.tus = (const DecTu *)(d_in_ + tu_off); f.lev = (const uint32_t *)(d_in_ + lev_off); f.ntu = (int)ntu;
-  // which chain: a picture without inter blocks, every other one of them, with the frame-threaded decoder on its own (decoder.h stream_alt_)
-  DecBatcher &batcher = DecBatcher::get(device_);
-  const bool batched = band_nrows_ == 0 && batch_attached_ && batcher.active() && !(job.pps.cip && job.any_inter && job.any_intra);      // (constrained intra prediction: the chain's own form, k_dec_intra_cip -- launched by this decoder itself)
-  static const bool alt_off = getenv("KVAZZUP_AMD_DEC_ONE_CHAIN") != nullptr;
-  bool alt = !alt_off && !batched && band_nrows_ == 0 && frame_threads_ > 1 && gpu_depth_ > 1 && job.any_intra && !job.any_inter && ((intra_seq_++) & 1);
-  if (alt && !ensure_alt()) alt = false;
-  const hipStream_t st = alt ? stream_alt_ : stream_;
-  for (int c = 0; c < 3; c++) f.resid[c] = alt ? resid_alt_[c] : resid_[c];
-  const bool sao = job.sh.sao_luma || job.sh.sao_chroma;      // the picture is then built in work_ and filtered into its buffer
-  for (int c = 0; c < 3; c++) { f.rec[c] = sao ? (alt ? work_alt_[c] : work_[c]) : dpb_[job.slot].plane[c]; f.out[c] = dpb_[job.slot].plane[c]; }
+  f.tu_index = lay.indexed ? (const uint32_t *)(d_in + lay.i_off) : nullptr;
+  f.b4 = (const B4Rec *)d_in; f.b4x = lay.bi ? (const B4L1 *)(d_in + lay.x_off) : nullptr; f.region = (const TuRange *)(d_in + lay.region_off); f.ctu = (const TuRange *)(d_in + lay.ctu_off);
+  f.ctu_tile = d_in + lay.tile_off; f.tus = (const DecTu *)(d_in + lay.tu_off); f.lev = (const uint32_t *)(d_in + lay.lev_off); f.ntu = (int)lay.ntu;
+  const bool sao = job.sh.sao_luma || job.sh.sao_chroma;      // the picture is then built in the chain's work planes and filtered into its buffer
+  for (int c = 0; c < 3; c++) { f.resid[c] = cs.resid[c]; f.rec[c] = sao ? cs.work[c] : dpb_[job.slot].plane[c]; f.out[c] = dpb_[job.slot].plane[c]; }
   for (int k = 0; k < KVZ_DEC_MAX_REFS; k++) for (int c = 0; c < 3; c++) f.ref[k][c] = dpb_[k].plane[c];
-  f.sao = sao ? (const SaoParams *)(d_in_ + off_sao()) : nullptr;
-  f.ctu_nb = job.lf_restricted ? d_in_ + off_nb() : nullptr;
-  f.progress = alt ? progress_alt_ : progress_; f.intra_order = intra_order_; f.err = err_;
-  { const size_t nctu = (size_t)f.cwc * f.chc, S = (size_t)1 << ctbl_; uint32_t *ec = alt ? edge_col_alt_ : edge_col_; unsigned long long *er = alt ? edge_row_alt_ : edge_row_;
-    f.edge_col[0] = ec; f.edge_col[1] = ec + nctu * S; f.edge_col[2] = ec + nctu * (S + S / 2);      // per CTB: S words (luma), S / 2 (Cb), S / 2 (Cr)
-    f.edge_row[0] = er; f.edge_row[1] = er + nctu * (S / 4); f.edge_row[2] = er + nctu * (S / 4 + S / 8); }
-  if (job.any_intra) {                                     // a generation of its own for every launch of the chain: 1 .. 2^24 - 1; at the wrap both arrays go back to "never written"
-    if (++chain_gen_ >= (1u << 24)) {
-      const size_t nctu = nctb() * (size_t)(2 << ctbl_) / 128;      // (in units of the 128 words a 64x64 CTB has)
-      sync_main();                                         // (everything this decoder has submitted has run: nothing reads the words while they are cleared)
-      // (on the consuming stream: the decoder's streams are non-blocking, nothing would order the next chain behind a clear on the null stream)
-      if (hipMemsetAsync(edge_col_, 0, nctu * 128 * sizeof(uint32_t), stream_) != hipSuccess || hipMemsetAsync(edge_row_, 0, nctu * 32 * 8, stream_) != hipSuccess) return DEC_ERR_GPU;
-      if (stream_alt_ && (hipMemsetAsync(edge_col_alt_, 0, nctu * 128 * sizeof(uint32_t), stream_alt_) != hipSuccess || hipMemsetAsync(edge_row_alt_, 0, nctu * 32 * 8, stream_alt_) != hipSuccess)) return DEC_ERR_GPU;
-      chain_gen_ = 1;
-    }
-    f.chain_gen = chain_gen_;
-  }
-  f.cb_qp_offset = (int8_t)job.pps.cb_qp_offset; f.cr_qp_offset = (int8_t)job.pps.cr_qp_offset;
-  f.beta_offset = (int8_t)(2 * job.sh.beta_offset_div2); f.tc_offset = (int8_t)(2 * job.sh.tc_offset_div2);
+  f.sao = sao ? (const SaoParams *)(d_in + lay.sao_off) : nullptr; f.ctu_nb = job.lf_restricted ? d_in + lay.nb_off : nullptr;
+  { f.progress = cs.progress; f.intra_order = intra_order_; f.err = err_; const size_t nctu = (size_t)f.cwc * f.chc, S = (size_t)1 << ctbl_;
+    f.edge_col[0] = cs.edge_col; f.edge_col[1] = cs.edge_col + nctu * S; f.edge_col[2] = cs.edge_col + nctu * (S + S / 2);      // per CTB: S words (luma), S / 2 (Cb), S / 2 (Cr)
+    f.edge_row[0] = cs.edge_row; f.edge_row[1] = cs.edge_row + nctu * (S / 4); f.edge_row[2] = cs.edge_row + nctu * (S / 4 + S / 8); }
+  if (job.any_intra) f.chain_gen = chain_gen_;
+  f.cb_qp_offset = (int8_t)job.pps.cb_qp_offset; f.cr_qp_offset = (int8_t)job.pps.cr_qp_offset; f.beta_offset = (int8_t)(2 * job.sh.beta_offset_div2); f.tc_offset = (int8_t)(2 * job.sh.tc_offset_div2);
   f.intra_direct = job.any_inter ? 1 : 0;                 // (a picture with inter blocks: few (CTU, plane) pairs hold intra blocks)
   f.strong_intra = (uint8_t)job.sps->strong_intra; f.tiles = job.pps.tile_rows > 1 || job.pps.tile_cols > 1 || job.slice_qps.size() > 1;
   f.general = (uint8_t)(job.pps.tile_rows > 1 || job.pps.tile_cols > 1 || job.slice_qps.size() > 1 || job.sps->pcm_depth[0] != 0);
   f.cip = (uint8_t)(job.pps.cip && job.any_inter);      // (a picture without inter blocks: every neighbour is intra)
   f.tq_bypass = (uint8_t)(job.pps.tq_bypass || (job.sps->pcm_depth[0] && job.sps->pcm_no_filter));      // (units the loop filters keep out of: B4_BYPASS records)
   // scaling lists: the picture's factors (the PPS's lists when it carries any, else the SPS's) ride in the input block
-  const std::vector<uint8_t> *sc = job.pps.scaling ? job.pps.scaling.get() : job.sps->scaling.get();
-  if (!job.sps->scaling) sc = nullptr;                     // (scaling_list_enabled_flag = 0: a PPS's lists are not used)
-  f.scaling = nullptr;
-  if (sc) { memcpy(job.h_in + off_scaling(), sc->data(), KVZ_SCALING_BYTES); f.scaling = d_in_ + off_scaling(); }
-  f.wt = nullptr;
-  if (job.sh.weighted && bi) { memcpy(job.h_in + off_wt(), job.sh.wt, sizeof(job.sh.wt)); f.wt = (const DecWt *)(d_in_ + off_wt()); f.wt_log2[0] = job.sh.wt_log2[0]; f.wt_log2[1] = job.sh.wt_log2[1]; }
-  if (band_nrows_ > 0) {
-    // a band starts and ends on tile boundaries of full-width tiles; no SAO, no temporal prediction (what the split encoder writes)
-    bool ok = !sao && !job.sps->tmvp && job.pps.tile_cols == 1 && frame_threads_ == 1, top = false, bottom = false;
-    for (int t = 0; t <= job.pps.tile_rows; t++) { top |= job.pps.row_bd[t] == band_row0_; bottom |= job.pps.row_bd[t] == band_row0_ + band_nrows_; }
-    if (!ok || !top || !bottom) return DEC_ERR_UNSUPPORTED;
-    f.row0 = band_row0_; f.nrows = band_nrows_;
-  }
-  // Several decoders open on this device: the picture goes to the device's submission layer (batch.h), which launches the waiting pictures of
-  // all of them together; its descriptor travels inside the input block.  One decoder: it launches for itself, frame by value.
-  if (!batched && batch_used_) { batcher.drain(this); batch_used_ = false; }
-  if (batched && stream_alt_) hipStreamSynchronize(stream_alt_);      // (another decoder has opened: from here on the submission layer launches on the shared stream; the second chain's last pictures first)       // (the other decoder has just closed: what this one still has queued there comes first)
-  if (batched) memcpy(job.h_in + off_frame(), &f, sizeof(f));
-  // (PicJob::early_dst: the records of every CTU row are on the device already -- queued on this stream by the row parsers -- when all rows made it)
-  const size_t up_from = (!batched && job.early_dst && job.early_dst == d_in_ && job.early_rows.load(std::memory_order_acquire) == f.chc) ? off_region() : 0;
+  const std::vector<uint8_t> *sc = !job.sps->scaling ? nullptr : (job.pps.scaling ? job.pps.scaling.get() : job.sps->scaling.get());      // (scaling_list_enabled_flag = 0: a PPS's lists are not used)
+  if (sc) { memcpy(job.h_in + lay.scaling_off, sc->data(), KVZ_SCALING_BYTES); f.scaling = d_in + lay.scaling_off; }
+  if (job.sh.weighted && lay.bi) { memcpy(job.h_in + lay.wt_off, job.sh.wt, sizeof(job.sh.wt)); f.wt = (const DecWt *)(d_in + lay.wt_off); f.wt_log2[0] = job.sh.wt_log2[0]; f.wt_log2[1] = job.sh.wt_log2[1]; }
+  if (band_nrows_ > 0) { f.row0 = band_row0_; f.nrows = band_nrows_; }
+  return f;
+}
+// the block goes up, minus the records when every CTU row of them is there already (PicJob::early_dst: queued on this stream by the row parsers -- when all rows made it)
+bool Decoder::upload(PicJob &job, const DecInputLayout &lay, uint8_t *d_in, int ib, bool batched)
+{
+  const size_t up_from = (!batched && job.early_dst && job.early_dst == d_in && job.early_rows.load(std::memory_order_acquire) == ctbs_in(h_, ctbl_)) ? lay.region_off : 0;
   job.early_dst = nullptr;
-  if (hipMemcpyAsync(d_in_ + up_from, job.h_in + up_from, bytes - up_from, hipMemcpyHostToDevice, stream_up_) != hipSuccess) return DEC_ERR_GPU;
-  if (hipEventRecord(up_done_[ib], stream_up_) != hipSuccess) return DEC_ERR_GPU;
-  if (batched) {
-    DecBatchItem it;
-    it.f = f; it.d_f = (const DecFrame *)(d_in_ + off_frame());
-    it.inter = job.any_inter; it.intra = job.any_intra; it.deblock = !job.sh.deblock_disabled; it.sao = sao;
-    it.wait0 = up_done_[ib]; it.wait1 = dpb_[job.slot].last_dl; dpb_[job.slot].last_dl = nullptr;
-    it.done = job.done; it.launched = &job.launched; it.owner = this; it.profile = prof_now_;
-    job.launched.store(0, std::memory_order_relaxed);
-    job.dl_buf = -1; job.launch_idx = launched_;
-    batcher.submit(it);
-    batch_used_ = true;
-    t_api_ += tk_api.ms();
-    launched_++;
-    gpu_q_.push_back(&job);
-    return 0;
-  }
+  if (hipMemcpyAsync(d_in + up_from, job.h_in + up_from, lay.upload_bytes() - up_from, hipMemcpyHostToDevice, stream_up_) != hipSuccess) return false;
+  return hipEventRecord(up_done_[ib], stream_up_) == hipSuccess;
+}
+// Several decoders open on this device: the picture goes to the device's submission layer (batch.h), which launches the waiting pictures of all of them together;
+// its descriptor travels inside the input block.
+int Decoder::post_to_batcher(PicJob &job, const DecFrame &f, uint8_t *d_in, int ib)
+{
+  DecBatchItem it; it.f = f; it.d_f = (const DecFrame *)(d_in + job.lay.frame_off);
+  it.inter = job.any_inter; it.intra = job.any_intra; it.deblock = !job.sh.deblock_disabled; it.sao = job.sh.sao_luma || job.sh.sao_chroma;
+  it.wait0 = up_done_[ib]; it.wait1 = dpb_[job.slot].last_dl; dpb_[job.slot].last_dl = nullptr;
+  it.done = job.done; it.launched = &job.launched; it.owner = this; it.profile = prof_now_;
+  job.launched.store(0, std::memory_order_relaxed);
+  DecBatcher::get(device_).submit(it); batch_used_ = true;
+  return 0;
+}
+template <class F> bool Decoder::each_buffer_used(const PicJob &job, F &&visit)
+{
+  bool ok = visit(dpb_[job.slot]);
+  for (int k = 0; ok && k < job.nref; k++) ok = visit(dpb_[job.ref_slot[k]]);
+  for (int k = 0; ok && k < job.nref1; k++) ok = visit(dpb_[job.ref_slot1[k]]);
+  return ok;
+}
+// One decoder: it launches for itself, frame by value, on the chain's stream.
+int Decoder::launch_self(PicJob &job, const DecFrame &f, uint8_t *d_in, int ib, bool alt)
+{
+  const hipStream_t st = chain_[alt].stream;
   if (hipStreamWaitEvent(st, up_done_[ib], 0) != hipSuccess) return DEC_ERR_GPU;
   // the buffer the picture is built in: the copy to the host of the picture last reconstructed there (queued, maybe not yet run) comes first
   if (dpb_[job.slot].last_dl) { if (hipStreamWaitEvent(st, dpb_[job.slot].last_dl, 0) != hipSuccess) return DEC_ERR_GPU; dpb_[job.slot].last_dl = nullptr; }
   // two chains: whatever this picture writes (its buffer) or reads (its reference pictures) was last touched by a picture on the OTHER stream -> after that one
-  if (stream_alt_) {
-    auto after = [&](DpbPic &d) { return !(d.last_use && d.last_use_alt != alt) || hipStreamWaitEvent(st, d.last_use, 0) == hipSuccess; };
-    if (!after(dpb_[job.slot])) return DEC_ERR_GPU;
-    for (int k = 0; k < job.nref; k++) if (!after(dpb_[job.ref_slot[k]])) return DEC_ERR_GPU;
-    for (int k = 0; k < job.nref1; k++) if (!after(dpb_[job.ref_slot1[k]])) return DEC_ERR_GPU;
-  }
+  if (chain_[1].stream && !each_buffer_used(job, [&](DpbPic &d) { return !(d.last_use && d.last_use_alt != alt) || hipStreamWaitEvent(st, d.last_use, 0) == hipSuccess; })) return DEC_ERR_GPU;
   if (job.any_inter) timed(DK_INTER, [&] { launch_dec_inter(f, st); }, st);
-  if (job.any_intra) {
-    timed(job.any_inter ? DK_INTRA_P : DK_INTRA, [&] { launch_dec_intra_resid(f, st); launch_dec_intra(f, st); }, st);
-  }
-  if (band_nrows_ > 0) { band_f_ = f; band_din_ = d_in_; }       // deblocking follows the halo exchange (band_deblock)
+  if (job.any_intra) timed(job.any_inter ? DK_INTRA_P : DK_INTRA, [&] { launch_dec_intra_resid(f, st); launch_dec_intra(f, st); }, st);
+  if (band_nrows_ > 0) { band_f_ = f; band_din_ = d_in; }       // deblocking follows the halo exchange (band_deblock)
   else if (!job.sh.deblock_disabled) timed(DK_DEBLOCK, [&] { launch_dec_deblock(f, st); }, st);
-  if (sao) timed(DK_SAO, [&] { launch_dec_sao(f, st); }, st);
+  if (f.sao) timed(DK_SAO, [&] { launch_dec_sao(f, st); }, st);
   if (hipEventRecord(job.done, st) != hipSuccess) return DEC_ERR_GPU;
   // (the picture's event now stands for the last use of its buffer and of every buffer it read; a job's event is recorded again only when its ring entry is
   // reused -- by a later picture, whose kernels are queued behind this one's on one of the two streams or wait for it through these same marks)
-  dpb_[job.slot].last_use = job.done; dpb_[job.slot].last_use_alt = alt;
-  for (int k = 0; k < job.nref; k++) { dpb_[job.ref_slot[k]].last_use = job.done; dpb_[job.ref_slot[k]].last_use_alt = alt; }
-  for (int k = 0; k < job.nref1; k++) { dpb_[job.ref_slot1[k]].last_use = job.done; dpb_[job.ref_slot1[k]].last_use_alt = alt; }
+  each_buffer_used(job, [&](DpbPic &d) { d.last_use = job.done; d.last_use_alt = alt; return true; });
+  return 0;
+}
+int Decoder::launch_gpu(PicJob &job)
+{
+  if (hipSetDevice(device_) != hipSuccess) return DEC_ERR_GPU;
+  if (!job.conceal.empty()) { const int rc = fill_concealed(job); if (rc < 0) return rc; }
+  prof_now_ = profiling_ && (launched_ % prof_every_) == 0; timed_job_ = &job; job.ev_used = 0;
+  if (!job.done && hipEventCreateWithFlags(&job.done, hipEventDisableTiming) != hipSuccess) return DEC_ERR_GPU;
+  Tick tk_api; const int ib = (int)(launched_ % (gpu_depth_ + 1));
+  uint8_t *const d_in = input_buffer(job, ib); if (!d_in) return DEC_ERR_GPU;
+  // which chain: a picture without inter blocks, every other one of them, with the frame-threaded decoder on its own (decoder.h chain_)
+  DecBatcher &batcher = DecBatcher::get(device_);
+  const bool batched = band_nrows_ == 0 && batch_attached_ && batcher.active() && !(job.pps.cip && job.any_inter && job.any_intra);      // (constrained intra prediction: the chain's own form, k_dec_intra_cip -- launched by this decoder itself)
+  static const bool alt_off = getenv("KVAZZUP_AMD_DEC_ONE_CHAIN") != nullptr;
+  bool alt = !alt_off && !batched && band_nrows_ == 0 && frame_threads_ > 1 && gpu_depth_ > 1 && job.any_intra && !job.any_inter && ((intra_seq_++) & 1);
+  if (alt && !ensure_alt()) alt = false;
+  if (job.any_intra && ++chain_gen_ >= (1u << 24)) {      // a generation of its own for every launch of a chain: 1 .. 2^24 - 1; at the wrap the hand-off words go back to "never written"
+    sync_main();                                         // (everything this decoder has submitted has run: nothing reads the words while they are cleared)
+    // (on the consuming stream: the decoder's streams are non-blocking, nothing would order the next chain behind a clear on the null stream)
+    for (const ChainSet &c : chain_) if (c.stream && (hipMemsetAsync(c.edge_col, 0, edge_col_words() * sizeof(uint32_t), c.stream) != hipSuccess || hipMemsetAsync(c.edge_row, 0, edge_row_words() * 8, c.stream) != hipSuccess)) return DEC_ERR_GPU;
+    chain_gen_ = 1;
+  }
+  if (band_nrows_ > 0) {      // a band starts and ends on tile boundaries of full-width tiles; no SAO, no temporal prediction (what the split encoder writes)
+    bool ok = !(job.sh.sao_luma || job.sh.sao_chroma) && !job.sps->tmvp && job.pps.tile_cols == 1 && frame_threads_ == 1, top = false, bottom = false;
+    for (int t = 0; t <= job.pps.tile_rows; t++) { top |= job.pps.row_bd[t] == band_row0_; bottom |= job.pps.row_bd[t] == band_row0_ + band_nrows_; }
+    if (!ok || !top || !bottom) return DEC_ERR_UNSUPPORTED;
+  }
+  const DecFrame f = picture_frame(job, job.lay, chain_[alt], d_in);
+  if (!batched && batch_used_) { batcher.drain(this); batch_used_ = false; }      // (the other decoder has just closed: what this one still has queued there comes first)
+  if (batched && chain_[1].stream) hipStreamSynchronize(chain_[1].stream);      // (another decoder has opened: from here on the submission layer launches on the shared stream; the second chain's last pictures first)
+  if (batched) memcpy(job.h_in + job.lay.frame_off, &f, sizeof(f));
+  if (!upload(job, job.lay, d_in, ib, batched)) return DEC_ERR_GPU;
   job.dl_buf = -1; job.launch_idx = launched_;
-  t_api_ += tk_api.ms();
-  launched_++;
+  if (const int rc = batched ? post_to_batcher(job, f, d_in, ib) : launch_self(job, f, d_in, ib, alt); rc < 0) return rc;
+  t_api_ += tk_api.ms(); launched_++;
   if (band_nrows_ > 0) gpu_job_ = &job; else gpu_q_.push_back(&job);
   return 0;
 }

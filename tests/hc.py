@@ -43,6 +43,7 @@ def _declare(L):
         "hw_sample": (I, [I] * 3), "hw_pred14": (I, [I] * 3), "hw_decide": (None, [P, P, I, I, I, P]),
         "hi_step": (I, [I, I]), "hi_cycle": (I, [I, I]), "hi_band": (None, [I] * 3 + [P]), "hi_position": (I, [I] * 3), "hi_forced_quarters": (I, [I] * 3),
         "hi_clean_block": (I, [I] * 3), "hi_mvx_max": (I, [I, I]), "hi_last_column": (I, [I] * 4), "hi_schedules": (None, [I, P]), "hi_bands": (I, [I, I, P]),
+        "hd_input_layout": (None, [I] * 3 + [U64] * 3 + [I, P, P]),
         # coder.cpp
         "hcr_play": (I, [I, P, P, P, I, P, P, I, P, P]), "hcr_code_picture": (I, [I, I, P, P, P] + [I] * 7 + [P, I, P, I, P]),
         "hcr_code_band": (I, [I, I, P, P, P] + [I] * 8 + [P, I, P, I, P]), "hcr_bench": (D, [P, LONG, I, I, I]),
@@ -253,3 +254,14 @@ def wp_candidate(mc, vc, mr, vr):
     out = np.zeros(3, np.int32)
     lib().hw_candidate(mc, vc, mr, vr, out.ctypes.data)
     return int(out[0]), int(out[1]), bool(out[2])
+
+
+LAYOUT_PARTS = ("region", "ctu", "tile", "sao", "scaling", "wt", "frame", "nb", "tus", "lev", "b4x", "index")
+LAYOUT_SIZES = ("B4Rec", "TuRange", "SaoParams", "scaling", "DecWt", "DecFrame", "DecTu", "B4L1")
+
+
+def input_layout(pw, ph, ctb_log2, ntu, nlev, nb4x, bi):
+    """dec_frame.h DecInputLayout -> ({part: offset}, fixed_bytes, upload_bytes, {struct: size})"""
+    out, sizes = np.zeros(14, np.uint64), np.zeros(8, np.uint64)
+    lib().hd_input_layout(pw, ph, ctb_log2, ntu, nlev, nb4x, int(bi), out.ctypes.data, sizes.ctypes.data)
+    return dict(zip(LAYOUT_PARTS, map(int, out[:12]))), int(out[12]), int(out[13]), dict(zip(LAYOUT_SIZES, map(int, sizes)))

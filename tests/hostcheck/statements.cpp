@@ -1,9 +1,11 @@
 // tests/hostcheck/statements.cpp -- host build of the statement functions the kernels share through hevc_core.h, for the CPU tests that hold them to the numpy
 // restatements: me-coarse's arithmetic (me_*: the quarter sample, the coarse stage's cost, key and centre, the admissibility rule, the second-window rule and
 // the fine stage's candidate order; the loops around them are plain C++ here, the kernels' are lanes and LDS windows; tests/me_coarse_model.py), weightp's
-// (wp_*; tests/wp_model.py) and intra-refresh's (ir_*; tests/ir_model.py).  Test infrastructure.
+// (wp_*; tests/wp_model.py) and intra-refresh's (ir_*; tests/ir_model.py); and of the decoder's input-block layout (dec_frame.h DecInputLayout;
+// tests/test_dec_input_layout.py).  Test infrastructure.
 #include <cstring>
 #include "../../kvazzup_amd/csrc/hevc_core.h"
+#include "../../kvazzup_amd/csrc/dec_frame.h"
 
 using namespace kvzx;
 
@@ -133,5 +135,17 @@ int hi_last_column(int xb, int nb, int e, int cw) { return ir_last_column(xb, nb
 void hi_schedules(int cw, int32_t *out) { for (int N = 2; N <= 255; N++) { out[2 * (N - 2)] = ir_step(cw, N); out[2 * (N - 2) + 1] = ir_cycle(cw, N); } }
 // the bands of one cycle: out[2 j] = s_j, out[2 j + 1] = e_j for j < ir_cycle(cw, N); returns the cycle's length
 int hi_bands(int cw, int N, int32_t *out) { const int n = ir_cycle(cw, N); for (int j = 0; j < n; j++) { out[2 * j] = ir_band_start(cw, N, j); out[2 * j + 1] = ir_band_end(cw, N, j); } return n; }
+
+// ---- the decoder's input block (dec_frame.h DecInputLayout).  out[0..11] = the parts' offsets in block order (region table, CTB table, tile ids, SAO parameters,
+// scaling factors, weights, frame descriptor, neighbour map, transform blocks, level words, second vectors, index list), out[12] = fixed_bytes(),
+// out[13] = upload_bytes(); sizes = {B4Rec, TuRange, SaoParams, KVZ_SCALING_BYTES, DecWt, DecFrame, DecTu, B4L1}: what a restatement needs of the product's structs
+void hd_input_layout(int pw, int ph, int ctb_log2, uint64_t ntu, uint64_t nlev, uint64_t nb4x, int bi, uint64_t *out, uint64_t *sizes)
+{
+  const DecInputLayout l(pw, ph, ctb_log2, (size_t)ntu, (size_t)nlev, (size_t)nb4x, bi != 0);
+  const size_t o[14] = {l.region_off, l.ctu_off, l.tile_off, l.sao_off, l.scaling_off, l.wt_off, l.frame_off, l.nb_off, l.tu_off, l.lev_off, l.x_off, l.i_off, l.fixed_bytes(), l.upload_bytes()};
+  const size_t z[8] = {sizeof(B4Rec), sizeof(TuRange), sizeof(SaoParams), KVZ_SCALING_BYTES, sizeof(DecWt), sizeof(DecFrame), sizeof(DecTu), sizeof(B4L1)};
+  for (int i = 0; i < 14; i++) out[i] = o[i];
+  for (int i = 0; i < 8; i++) sizes[i] = z[i];
+}
 
 }

@@ -430,3 +430,31 @@ def test_no_cropping_hands_out_the_coded_picture(gpu):
             assert np.array_equal(ua, ub[:h // 2, :w // 2])
     finally:
         plain.close(); full.close()
+
+
+@pytest.mark.gpu
+def test_second_chain_is_built_used_torn_down_and_rebuilt(gpu):
+    """all-intra pictures through the frame-threaded decoder on its own alternate between the two intra chains (its own arrays and stream each): 3 x 2 CTBs of 64,
+    one tile -- the hand-off words between CTBs travel along rows and columns --, SAO on, so the second set's work planes are read; then, through the SAME
+    decoder, another size with CTBs of 16: both sets are freed and built again with edge arrays of another size"""
+    from deckit import both
+    cut = []
+    for (w, h, ctb) in ((192, 128, 6), (128, 128, 4)):
+        g = orc.OracleGen(w, h, intra_period=1, ctb_log2=ctb, sao=1, tile_rows=1, tile_cols=1, slices=0)
+        assert (g.config["intra_period"], g.config["ctb_log2"], g.config["sao"]) == (1, ctb, 1), g.config
+        cut += [g.picture() for _ in range(8)]
+        g.close()
+    assert both(cut, list(range(16)), threads=4, frame_threads=True) == list(range(16))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("threads,frame", [(1, False), (4, True)])
+@pytest.mark.parametrize("b_slices,lf_across", [(1, 0), (100, 2)])
+@pytest.mark.parametrize("ctb_log2", [5, 4])
+def test_every_optional_part_of_the_input_block_at_once(gpu, ctb_log2, b_slices, lf_across, threads, frame):
+    """B pictures (second vectors), CTBs smaller than 64 (the regions' index list) and free slices with boundaries closed to the in-loop filters (the neighbour
+    map) in one stream, at a size that is no multiple of the CTB.  The synthesiser's b_slices is the SHARE of inter pictures that are B pictures in per cent and
+    its lf_across = 2 is what clears both loop_filter_across flags (0 leaves them set): (100, 2) is the stream in which all three parts are there; (1, 0) is kept
+    beside it -- in it the optional parts are absent and the index list sits behind the second vectors' empty place."""
+    from deckit import run_stream
+    run_stream(200, 136, 8, threads=threads, frame_threads=frame, seed=7, b_slices=b_slices, ctb_log2=ctb_log2, slices=3, lf_across=lf_across, gop=0)

@@ -133,6 +133,7 @@ typedef struct kvz_config {
   int32_t lp_gop;             /* "lp-gop" 0 / 1 (extension, "uvgx low-delay GOP v1"; statement of record: tests/lp_gop_model.py): 1 = gop=lp-g<g>d<d>t1 takes effect -- every g-th picture after an IDR picture is a key picture coded at QP + 1, the pictures between lie on the layers QP + 2 .. QP + d (g4d3: +3, +2, +3, +1), and a P picture refers to the previous picture, the most recent key picture (at most 7 pictures back) and then the pictures before the previous one, "lp-refs" pictures in all; each picture's reference picture set travels in its slice headers, the parameter sets are those of lp-refs.  0 (default, also at every preset), or no gop string / gop=0: the streams of before byte for byte.  encoder_open fails with it in band mode, with t > 1 and with d > 6 */
   int32_t weightp;            /* "weightp" 0 / 1 (extension, "uvgx weighted prediction v1"; restated in tests/wp_model.py): 1 = explicit weighted prediction of luma (PPS weighted_pred_flag, pred_weight_table() in every independent P slice segment header, denominator 6, chroma never weighted).  Per P picture and reference a weight and an offset are derived from the luma mean and variance of the two INPUT pictures and kept when a check on every fourth sample of every fourth row says they pay (16 * weighted SAD < 15 * plain SAD); the integer search then reads weighted copies of its reference planes, and the fractional refinement and the reconstruction predict luma with the weights -- brightness steps, fades, auto-exposure.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it in band mode and with lossless */
   int32_t intra_refresh;      /* "intra-refresh" 0 / 2..255 (extension, "uvgx intra refresh v1"; restated in tests/ir_model.py): N = the number of P pictures a refresh cycle may take.  A band of intra units (the step ceil(B / N) block columns of 32 samples, B = coded width / 32, plus 16 columns of overlap) walks across the P pictures, one step a picture, cycle after cycle from the first P picture behind an IDR picture; the 32x32 blocks the band has passed keep their vectors out of what it has not.  A decoder that concealed a lost picture has the encoder's pictures again, exactly, once a cycle that began after the loss is complete -- no IDR picture needed, so uvgComm users pass it beside "period=0" or a long period.  The first picture of a cycle carries a recovery point SEI (recovery_poc_cnt = cycle length - 1, exact_match_flag 1).  With "intra-in-p=0" the band's units are the only intra units.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it beside lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless and intra-chain=0 */
+  int32_t scenecut;           /* "scenecut" 0 / 1..255 (extension, "uvgx scene cut v1"; restated in tests/scenecut_model.py): N = the least distance in pictures between an IDR picture and a scene-cut IDR picture behind it.  An input picture at least N pictures behind the last IDR picture (and not an IDR picture by "period" anyway) is compared with the previous INPUT picture on their quarter-resolution pictures: the previous one is shifted by the difference of the two means, every visible 8x8 block (32x32 samples) looks for its best match within +-max(8, me-coarse / 4) quarter samples, and a block whose best SAD exceeds its own activity (sum |c - mean|) by more than 128 is new; when more than half of the blocks are new the picture is coded as an IDR picture (POC 0, parameter sets as "vps-period" says) and "period" counts from it -- slide changes, window and camera switches.  Brightness steps, fades and pans within reach are not cuts.  encoder_encode of an examined picture waits for that verdict on the GPU before the picture is planned (DESIGN.md section 9g has the cost); pictures that are not examined wait for nothing.  0 (default, also at every preset): the streams of before byte for byte.  uvgComm users pass it as a custom parameter, e.g. "scenecut=8".  encoder_open fails with it in band mode */
 } kvz_config;
 
 /* Picture.  y/u/v are planar 8-bit with stride == width (chroma width/2), as uvgComm assumes

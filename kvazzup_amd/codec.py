@@ -136,6 +136,10 @@ class Encoder:
         # intra-refresh: position in the cycle, the band's first and end column, the cycle's length -- a key of its own only with the option on
         if int(self.cfg.contents.intra_refresh):
             d["ir"] = [int(v) for v in self.debug("ir", np.int32, (4,))]
+        # scenecut: the delivered picture's record, and (S, A) of every block of the picture last examined -- keys of their own only with the option on
+        if int(self.cfg.contents.scenecut):
+            d["scenecut"] = dict(zip(("examined", "n_new", "n_b", "d", "cut"), (int(v) for v in self.debug("scenecut", np.int32, (5,)))))
+            d["sc_blocks"] = self.debug("sc_blocks", np.uint32, ((self.h + 31) // 32, (self.w + 31) // 32, 2))
         for c in range(3):
             shp = (ch, cw) if c == 0 else (ch // 2, cw // 2)
             d["coef%d" % c] = self.debug("coef%d" % c, np.int16, shp)

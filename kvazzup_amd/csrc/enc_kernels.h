@@ -40,6 +40,19 @@ void launch_wp_stats(const uint8_t *src, int cw, int width, int height, unsigned
 void launch_wp_decide(const WpArgs &a, int phase, hipStream_t st);      // phase 0: moments, candidates; phase 1: the record
 void launch_wp_check(const WpArgs &a, const uint8_t *cur, int cw, int width, int height, hipStream_t st);
 void launch_wp_plane(const WpPlaneArgs &a, int nref, int cw, int ch, hipStream_t st);      // the references' search planes
+// "scenecut" (sc_kernels.hip)
+struct ScArgs {
+  const uint8_t *qc, *qp;                            // the quarter pictures of this input picture and of the previous one (k_luma_quarter), qw x qh samples
+  int qw, qh, vw, vh;                                // ... of which vw x vh are visible
+  int bw, bh, rq;                                    // sc_visible_blocks, sc_reach
+  unsigned long long *sum_c; const unsigned long long *sum_p;   // the sums over the visible quarter samples, kept with the pictures' working sets
+  uint32_t *blocks;                                  // [block, raster][S, A] of the picture last examined
+  uint32_t *n_new;                                   // counter of new blocks: zero between pictures (k_sc_decide leaves it so)
+  int32_t *rec, *rec_host;                           // the record {examined, n_new, n_b, d, cut}: device memory / the slot's host-mapped copy
+};
+void launch_sc_sum(const ScArgs &a, hipStream_t st);      // every picture: sum_c (zero before the launch) += the visible samples of qc
+void launch_sc_blocks(const ScArgs &a, hipStream_t st);   // an examined picture: (S, A) of every block, n_new
+void launch_sc_decide(const ScArgs &a, hipStream_t st);   // ... and its record
 // k_cabac_rows (cabac_kernels.hip): the arithmetic coder proper on the GPU, one wave per substream
 struct CabacRowsArgs {
   const uint16_t *tok; const int32_t *count; const uint32_t *off;   // dense tokens (device): CTU i has count[i] tokens at tok + off[i]

@@ -74,6 +74,11 @@ struct EncoderConfig {
                               // units walks across every P picture, one step a picture and at most N pictures a pass, and the blocks it has passed keep their vectors out of
                               // what it has not -- after one pass a decoder that lost a picture has the encoder's pictures again, without an IDR picture.  The first picture
                               // of a cycle carries a recovery point SEI.  Not with lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless or intra-chain=0
+  int scenecut = 0;           // "scenecut" N (extension, "uvgx scene cut v1"; restated in tests/scenecut_model.py): 0 = off; 1 .. 255 = an input picture
+                              // at least N pictures behind the last IDR picture is compared with the previous input picture on their quarter pictures (mean shift, then per
+                              // 8x8 block the best match against the block's own activity); when more than half of the blocks are new the picture is an IDR picture and
+                              // the period counts from it.  The one option whose decision the host waits for: submit() of an examined picture waits for k_sc_decide on
+                              // the input stream before it plans the picture.  Not in band mode
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -85,6 +90,7 @@ struct EncodedPicture {
   int poc = 0, qp = 0; bool is_intra = false;
   int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop, a P picture: its QP layer and its references' POC distances in list 0 order (nref 0: the option is off)
   int32_t wp[3 * KVZ_MAX_LP_REFS] = {0, 64, 0, 0, 64, 0, 0, 64, 0, 0, 64, 0};   // weightp: the picture's record [reference][flag, w, o]
+  int32_t sc[5] = {0, 0, 0, 0, 0};  // scenecut: the picture's record {examined, n_new, n_b, d, cut}
   int32_t ir[4] = {-1, 0, 0, 0};  // intra-refresh: position j in the cycle (-1: an IDR picture, or the option is off), the band [s_j, e_j), the cycle's length n
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
@@ -136,6 +142,8 @@ class Encoder {
   //   "lp_gop" (host values, 8 int32: option active, layer, QP, number of references, their four POC distances),
   //   "wp" (weightp; host values, 12 int32: [reference][flag, w, o] as the picture's slice headers say them -- an intra picture: 0, 64, 0 throughout),
   //   "ir" (intra-refresh; host values, 4 int32: position j in the cycle, the band's s_j and e_j, the cycle's length n -- an IDR picture: -1, 0, 0, n),
+  //   "scenecut" (scenecut; 5 int32: the record {examined, n_new, n_b, d, cut} of the picture last output -- a picture that was not examined: 0, 0, n_b, 0, 0),
+  //   "sc_blocks" (scenecut; n_b pairs of uint32: (S, A) of every block of the picture last EXAMINED, raster order),
   //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
   int coded_width() const { return cw_; }
@@ -204,7 +212,7 @@ class Encoder {
   uint8_t *cu_bytes_[kSets] = {};          // 7 byte arrays back to back
   int16_t *cu_mv_[kSets] = {}, *cu_mvd_[kSets] = {};
   uint8_t *cu_ref_[kSets] = {};            // lp-refs >= 2: ref_idx_l0 per 8x8 block (EncFrame::cu_ref)
-  uint8_t *mc_q_[kSets] = {}; int16_t *mc_centres_[kSets] = {};      // me-coarse: the quarter picture of the set's input picture and the centres of the set's picture [reference][32x32 block] (EncFrame::mc_*)
+  uint8_t *mc_q_[kSets] = {}; int16_t *mc_centres_[kSets] = {};      // me-coarse (the quarter picture: also scenecut): the quarter picture of the set's input picture and the centres of the set's picture [reference][32x32 block] (EncFrame::mc_*)
   ColMv *col_[kSets] = {};                 // tmvp: the collocated record of the set's picture (EncFrame::col_out), which the next picture reads (col_prev)
   int set_ = 0, out_set_ = 0;
   int32_t out_gop_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug_copy("lp_gop") of the picture last output
@@ -217,6 +225,14 @@ class Encoder {
   int32_t out_wp_[3 * KVZ_MAX_LP_REFS] = {0, 64, 0, 0, 64, 0, 0, 64, 0, 0, 64, 0};   // debug_copy("wp") of the picture last output
   bool wp_stage(const EncFrame &f, const Plan &p, const Slot &sl);   // input stream: statistics of the picture; a P picture: candidates, check, record
   EncFrame wp_search_frame(const EncFrame &f, const Plan &p, hipStream_t st);   // the search planes of f's references built on `st`; returns f with me_ref / me_refs pointing at them
+  // scenecut (sc_kernels.hip): per working set the sum over the input picture's visible quarter samples (its quarter picture is mc_q_, me-coarse's); one array of
+  // (S, A) pairs, one counter and one device record -- an examination is over, the host has waited for it, before the next one is queued
+  unsigned long long *sc_sum_[kSets] = {}; uint32_t *sc_blocks_ = nullptr, *sc_count_ = nullptr; int32_t *sc_rec_ = nullptr; hipEvent_t ev_sc_ = nullptr;
+  bool sc_cut_ = false;                             // the verdict on the picture being submitted (sc_stage), read by plan()
+  int32_t out_sc_[5] = {0, 0, 0, 0, 0};             // debug_copy("scenecut") of the picture last output
+  bool pad_stage(int set, const uint8_t *d_i420, int in_ring);   // input stream: the picture padded into the set, its quarter picture (me-coarse, scenecut)
+  bool sc_stage(int set, const uint8_t *d_i420, int in_ring);    // pad_stage, the picture's sum; an examined picture: blocks, record, and the wait for it -- before plan()
+  bool wait_event(hipEvent_t e);                    // on the host, as finish_slot waits: naps between queries in a pipelined encoder, polling with KVAZZUP_AMD_SPIN
   char prio_[3] = {'h', 'n', 'n'};                      // priority levels of the main, tokenizer and input streams (stream_pool.h keys)
   std::vector<int8_t> roi_; int roi_w_ = 0, roi_h_ = 0;           // as set by the caller (set_roi)
   std::vector<int8_t> roi_sub_; int roi_sub_w_ = 0, roi_sub_h_ = 0;   // the map of the picture being submitted (it travels with the picture to the submitter thread)
@@ -262,6 +278,7 @@ class Encoder {
     uint32_t *h_tok_off = nullptr, *d_tok_off = nullptr;
     uint32_t *h_err = nullptr, *d_err = nullptr;
     int32_t *h_wp = nullptr, *d_wp = nullptr;            // weightp: the picture's record as k_wp_decide left it (host-mapped: the slice headers are written from it)
+    int32_t *h_sc = nullptr, *d_sc = nullptr;            // scenecut: the picture's record as k_sc_decide left it (host-mapped: submit() reads the verdict from it) or, not examined, as submit() wrote it
     // GPU arithmetic coder (cfg.entropy_gpu): dense tokens stay in device memory (d_tok_dense .. d_tok_off point there), the coder runs on the slot's own
     // stream -- a substream is a ~0.1-1 ms serial chain, so several pictures' coders must be able to run side by side
     uint16_t *g_tok = nullptr; int32_t *g_count = nullptr; uint32_t *g_off = nullptr;

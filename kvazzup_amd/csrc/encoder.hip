@@ -66,6 +66,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.me_coarse && cfg.band_rows > 0) { if (error) *error = "me-coarse is not available in band mode (the halo exchange carries a few rows)"; return false; }
   if (cfg.weightp && cfg.band_rows > 0) { if (error) *error = "weightp is not available in band mode (a band's encoder sees a part of the picture, the weights are the whole picture's)"; return false; }
   if (cfg.weightp && cfg.lossless) { if (error) *error = "weightp is not available with lossless"; return false; }
+  if (cfg.scenecut < 0 || cfg.scenecut > 255) { if (error) *error = "scenecut must be 0 .. 255"; return false; }
+  if (cfg.scenecut && cfg.band_rows > 0) { if (error) *error = "scenecut is not available in band mode (a band's encoder sees a part of the picture, the verdict is the whole picture's)"; return false; }
   if (cfg.intra_refresh) {                                 // "uvgx intra refresh v1" ("not covered")
     const char *why = nullptr;
     if (cfg.intra_refresh < 2 || cfg.intra_refresh > 255) why = "intra-refresh must be 0 or 2 .. 255";
@@ -142,8 +144,9 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     HIP_OK(hipMalloc(&cu_mvd_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mvd_[k], 0, nb8 * 2 * sizeof(int16_t)));
     if (cfg.lp_refs > 1) { HIP_OK(hipMalloc(&cu_ref_[k], nb8)); HIP_OK(hipMemset(cu_ref_[k], 0, nb8)); }
     if (cfg.tmvp) { HIP_OK(hipMalloc(&col_[k], nb8 / 4 * sizeof(ColMv))); HIP_OK(hipMemset(col_[k], 0, nb8 / 4 * sizeof(ColMv))); }
+    if (cfg.me_coarse || cfg.scenecut) { HIP_OK(hipMalloc(&mc_q_[k], npx / 16)); HIP_OK(hipMemset(mc_q_[k], 0, npx / 16)); }
+    if (cfg.scenecut) { HIP_OK(hipMalloc(&sc_sum_[k], sizeof(unsigned long long))); HIP_OK(hipMemset(sc_sum_[k], 0, sizeof(unsigned long long))); }
     if (cfg.me_coarse) {
-      HIP_OK(hipMalloc(&mc_q_[k], npx / 16)); HIP_OK(hipMemset(mc_q_[k], 0, npx / 16));
       HIP_OK(hipMalloc(&mc_centres_[k], (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t))); HIP_OK(hipMemset(mc_centres_[k], 0, (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t)));
     }
     if (cfg.weightp) {
@@ -156,6 +159,14 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.weightp) {
     HIP_OK(hipMalloc(&wp_cand_, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t))); HIP_OK(hipMalloc(&wp_acc_, 2 * KVZ_MAX_LP_REFS * sizeof(unsigned long long)));
     for (int r = 0; r < cfg.lp_refs; r++) HIP_OK(hipMalloc(&wp_plane_[r], npx));
+  }
+  if (cfg.scenecut) {
+    int bw, bh;
+    sc_visible_blocks(cfg.width, cfg.height, &bw, &bh);
+    HIP_OK(hipMalloc(&sc_blocks_, (size_t)bw * bh * 2 * sizeof(uint32_t))); HIP_OK(hipMemset(sc_blocks_, 0, (size_t)bw * bh * 2 * sizeof(uint32_t)));
+    HIP_OK(hipMalloc(&sc_count_, sizeof(uint32_t))); HIP_OK(hipMemset(sc_count_, 0, sizeof(uint32_t)));
+    HIP_OK(hipMalloc(&sc_rec_, 5 * sizeof(int32_t))); HIP_OK(hipMemset(sc_rec_, 0, 5 * sizeof(int32_t)));
+    HIP_OK(hipEventCreateWithFlags(&ev_sc_, hipEventDisableTiming));      // (the host reads what k_sc_decide wrote into host-mapped memory: an event with its system fence)
   }
   if (cfg.qp_in_cu) {
     const size_t nctu = (size_t)(cw_ / 64) * rows_;
@@ -246,6 +257,11 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
       HIP_OK(hipHostMalloc(&sl.h_wp, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t), hipHostMallocMapped));
       for (int r = 0; r < KVZ_MAX_LP_REFS; r++) { sl.h_wp[3 * r] = 0; sl.h_wp[3 * r + 1] = 64; sl.h_wp[3 * r + 2] = 0; }
       HIP_OK(hipHostGetDevicePointer(&dp, sl.h_wp, 0)); sl.d_wp = (int32_t *)dp;
+    }
+    if (cfg.scenecut) {
+      HIP_OK(hipHostMalloc(&sl.h_sc, 5 * sizeof(int32_t), hipHostMallocMapped));
+      for (int i = 0; i < 5; i++) sl.h_sc[i] = 0;
+      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_sc, 0)); sl.d_sc = (int32_t *)dp;
     }
     HIP_OK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&sl.rec_done, hipEventDisableTiming));
@@ -345,6 +361,7 @@ Encoder::~Encoder()
     if (sl.h_tok_count) hipHostFree(sl.h_tok_count);
     if (sl.h_err) hipHostFree(sl.h_err);
     if (sl.h_wp) hipHostFree(sl.h_wp);
+    if (sl.h_sc) hipHostFree(sl.h_sc);
     if (sl.h_tok_off) hipHostFree(sl.h_tok_off);
     stream_release(sl.ent_stream, cfg_.device, 'E', 'l');
     if (sl.tok_ev) hipEventDestroy(sl.tok_ev);
@@ -363,6 +380,8 @@ Encoder::~Encoder()
   for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (mc_q_[k]) hipFree(mc_q_[k]); if (mc_centres_[k]) hipFree(mc_centres_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
   for (int k = 0; k < kSets; k++) { hipFree(wp_partial_[k]); hipFree(wp_stat_[k]); hipFree(wp_rec_[k]); }
   hipFree(wp_cand_); hipFree(wp_acc_); for (int r = 0; r < KVZ_MAX_LP_REFS; r++) hipFree(wp_plane_[r]);
+  for (int k = 0; k < kSets; k++) hipFree(sc_sum_[k]);
+  hipFree(sc_blocks_); hipFree(sc_count_); hipFree(sc_rec_); if (ev_sc_) hipEventDestroy(ev_sc_);
   for (int c = 0; c < 3; c++) { hipFree(work_[c]); hipFree(work_idr_[c]); }
   hipFree(sync_idr_); hipFree(edge_col_idr_); hipFree(edge_row_); hipFree(edge_row_idr_);
   for (int k = 0; k < kSets; k++) hipFree(sao_[k]);
@@ -628,6 +647,9 @@ Encoder::Plan Encoder::plan(int set)
   set_ = set;
   const int period = cfg_.intra_period;
   p.intra = (frame_idx_ == 0) || (period > 0 && (frame_idx_ % period) == 0);
+  // scenecut: the period counts from the last IDR picture, wherever a cut put it (poc_ + 1 pictures back; without a cut that is the count above), and the
+  // picture sc_stage found to be a cut is one
+  if (cfg_.scenecut) p.intra = (frame_idx_ == 0) || (period > 0 && ((poc_ + 1) % period) == 0) || sc_cut_;
   if (p.intra) poc_ = 0; else poc_++;
   rate_control();
   // the references: the min(lp-refs, pictures since the IDR picture) pictures before this one ...
@@ -695,7 +717,7 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   // picture (which files none) the slice says slice_temporal_mvp_enabled_flag = 0 (hevc_headers.h slice_tmvp) and nothing is read
   // me-coarse: the quarter picture of this set's input and of the sets that hold input pictures t - p.dist[r] (written on the input stream, where the coarse stage
   // reads them), and the set's centres
-  if (mc_q_[k]) {
+  if (cfg_.me_coarse) {                               // (scenecut alone keeps quarter pictures too: they are sc_stage's, no frame points at them)
     f.mc_rq = cfg_.me_coarse / 4; f.mc_q = mc_q_[k]; f.mc_centres = mc_centres_[k];
     const int nr = f.cu_ref ? f.nref : 1;
     for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - (r < nr ? p.dist[r] : 1)) % kSets];
@@ -725,6 +747,9 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
   //   stream_:     motion search / intra decisions, reconstruction, deblocking: the chain picture t + 1 depends on.
   //   stream_tok_: merge/AMVP signalling, tokenizer, compaction, which only feed the host; they read set t & 1 of the
   //                level / CU arrays while stream_ already fills the other set for t + 1.
+  // scenecut: whether the picture is an IDR picture may depend on the picture itself -- the head of its input stage runs, and an examined picture's verdict is
+  // waited for, before anything is planned
+  if (cfg_.scenecut && !sc_stage((int)(submitted_ % kSets), d_i420, in_ring)) return false;
   const Plan p = plan((int)(submitted_ % kSets));
   const EncFrame f = picture_frame(p, sl, next_chain_gen());
   if (all_intra_alt_) idr_pending_ = false;                 // (alternating intra pictures: the main stream's next picture has nothing to do with the side stream's last)
@@ -732,14 +757,56 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
   return input_stage(f, p, d_i420, in_ring) && chain_stage(f, p) && hand_off(f, p, sl, in_ring);
 }
 
+// stream_in_, the head of the input stage: the picture padded into its working set, and its quarter picture where an option keeps one
+bool Encoder::pad_stage(int set, const uint8_t *d_i420, int in_ring)
+{
+  if (src_busy_[set]) { HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_src_free_[set], 0)); src_busy_[set] = false; }   // the last picture that used this set (t - kSets) has been reconstructed
+  timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[set][0], src_[set][1], src_[set][2], cw_, ch_, stream_in_); });
+  if (in_ring >= 0) { HIP_CHECK(hipEventRecord(ev_pad_[in_ring], stream_in_)); pad_pending_[in_ring] = true; }
+  // me-coarse, scenecut: every picture's quarter picture (an intra picture's is searched by / compared with the P picture behind it)
+  if (mc_q_[set]) launch_luma_quarter(src_[set][0], mc_q_[set], cw_, ch_, stream_in_);      // (no kernel id of its own: the profile's keys are the default encoder's)
+  return true;
+}
+
+// the host's wait for an event of its own stream, as finish_slot waits for a slot's
+bool Encoder::wait_event(hipEvent_t e)
+{
+  if (depth_ >= 2 && !spin_wait_) return nap_until([&] { hipError_t r = hipEventQuery(e); return r == hipSuccess ? 1 : (r == hipErrorNotReady ? 0 : -1); });
+  HIP_CHECK(hipEventSynchronize(e));
+  return true;
+}
+
+// scenecut, the input stream, in front of plan(): the picture padded, its quarter picture and that picture's sum (every picture: the next one is compared with
+// it); a picture sc_examined() names: the blocks against the previous input picture's quarter picture (the previous working set's, written on this stream),
+// the record -- and the feature's one wait on the host, for the verdict plan() needs.  A picture that is not examined waits for nothing; its record is
+// written here.
+bool Encoder::sc_stage(int set, const uint8_t *d_i420, int in_ring)
+{
+  if (!pad_stage(set, d_i420, in_ring)) return false;
+  const int prev = (set + kSets - 1) % kSets, period = cfg_.intra_period;
+  const int since = frame_idx_ == 0 ? 0 : poc_ + 1;         // pictures behind the last IDR picture
+  const bool periodic = frame_idx_ == 0 || (period > 0 && since % period == 0);
+  ScArgs a{};
+  a.qc = mc_q_[set]; a.qp = mc_q_[prev]; a.qw = cw_ / 4; a.qh = ch_ / 4; a.vw = (cfg_.width + 3) / 4; a.vh = (cfg_.height + 3) / 4;
+  sc_visible_blocks(cfg_.width, cfg_.height, &a.bw, &a.bh); a.rq = sc_reach(cfg_.me_coarse);
+  a.sum_c = sc_sum_[set]; a.sum_p = sc_sum_[prev]; a.blocks = sc_blocks_; a.n_new = sc_count_; a.rec = sc_rec_; a.rec_host = cur_slot_->d_sc;
+  HIP_CHECK(hipMemsetAsync(sc_sum_[set], 0, sizeof(unsigned long long), stream_in_));
+  launch_sc_sum(a, stream_in_);
+  volatile int32_t *h = cur_slot_->h_sc;
+  sc_cut_ = false;
+  if (!sc_examined(since, cfg_.scenecut, periodic)) { h[0] = 0; h[1] = 0; h[2] = a.bw * a.bh; h[3] = 0; h[4] = 0; return true; }
+  launch_sc_blocks(a, stream_in_);
+  launch_sc_decide(a, stream_in_);
+  HIP_CHECK(hipEventRecord(ev_sc_, stream_in_));
+  if (!wait_event(ev_sc_)) return false;                    // (the time counts as submit time: KVAZZUP_AMD_TRACE)
+  sc_cut_ = h[0] == 1 && h[4] != 0;
+  return true;
+}
+
 // stream_in_: the picture padded into its set, and what needs the source pictures only; in_done_ behind it
 bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i420, int in_ring)
 {
-  if (src_busy_[set_]) { HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_src_free_[set_], 0)); src_busy_[set_] = false; }   // the last picture that used this set (t - kSets) has been reconstructed
-  timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[set_][0], src_[set_][1], src_[set_][2], cw_, ch_, stream_in_); });
-  if (in_ring >= 0) { HIP_CHECK(hipEventRecord(ev_pad_[in_ring], stream_in_)); pad_pending_[in_ring] = true; }
-  // me-coarse: every picture's quarter picture (an intra picture's is searched by the P picture behind it)
-  if (f.mc_rq) launch_luma_quarter(src_[set_][0], f.mc_q, cw_, ch_, stream_in_);      // (no kernel id of its own: the profile's keys are the default encoder's)
+  if (!cfg_.scenecut && !pad_stage(set_, d_i420, in_ring)) return false;      // (scenecut: sc_stage has queued it)
   // weightp: every picture's luma statistics (an intra picture's are its successors' reference's), and a P picture's weights -- from input pictures alone,
   // whatever me-source says, like the coarse stage below
   if (cfg_.weightp && !wp_stage(f, p, *cur_slot_)) return false;
@@ -954,6 +1021,7 @@ bool Encoder::collect(EncodedPicture *out)
   out_gop_[0] = gop_on(); out_gop_[1] = out->layer; out_gop_[2] = out->qp; out_gop_[3] = out->nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out_gop_[4 + r] = out->dist[r];
   memcpy(out_wp_, out->wp, sizeof(out_wp_));
   memcpy(out_ir_, out->ir, sizeof(out_ir_));
+  memcpy(out_sc_, out->sc, sizeof(out_sc_));
   rc_bytes_[(collected_ - 1) & 7] = (uint32_t)out->au.size();   // (collected_ - 1 = index of this picture)
   return ok;
 }
@@ -1026,6 +1094,7 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
   out->layer = sl.layer; out->nref = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out->dist[r] = sl.dist[r];
   PicRefs pr; pr.n = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
   memcpy(out->ir, sl.ir, sizeof(out->ir));
+  if (sl.h_sc) memcpy(out->sc, sl.h_sc, sizeof(out->sc));      // scenecut: the record, final since the picture was submitted
   const int recovery = cfg_.intra_refresh && !sl.intra && sl.ir[0] == 0 ? sl.ir[3] - 1 : -1;      // intra-refresh: a cycle's first picture says when the pass is complete
   PicWeights pw{};                                         // weightp: the record k_wp_decide left in the slot (final long before the tokens are)
   for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
@@ -1222,6 +1291,8 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   if (w == "lp_gop") { if (bytes > sizeof(out_gop_)) return false; memcpy(dst, out_gop_, bytes); return true; }      // (host values: no copy from the device)
   if (w == "ir") { if (!cfg_.intra_refresh || bytes > sizeof(out_ir_)) return false; memcpy(dst, out_ir_, bytes); return true; }      // (host values)
   if (w == "wp") { if (!cfg_.weightp || bytes > sizeof(out_wp_)) return false; memcpy(dst, out_wp_, bytes); return true; }      // (host values, as the slice headers said them)
+  if (w == "scenecut") { if (!cfg_.scenecut || bytes > sizeof(out_sc_)) return false; memcpy(dst, out_sc_, bytes); return true; }      // (host values, as submit() read or wrote them)
+  if (w == "sc_blocks" && sc_blocks_) { int bw, bh; sc_visible_blocks(cfg_.width, cfg_.height, &bw, &bh); src = sc_blocks_; have = (size_t)bw * bh * 2 * sizeof(uint32_t); }      // (the picture last examined: its kernels are done, submit() waited for them)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
   if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }

@@ -214,6 +214,54 @@ KVZ_HD int wp_sample(int s, int w, int o) { return clip8(((s * w + 32) >> 6) + o
 // 8.5.3.3.4.3 with luma_log2_weight_denom 6 on the 14-bit intermediate sample
 KVZ_HD int wp_pred14(int p, int w, int o) { return clip8(((p * w + 2048) >> 12) + o); }
 
+// ---------------------------------------------------------------------------------------------
+// "uvgx scene cut v1" (scenecut; restated in tests/scenecut_model.py).  All integer.  The inputs are the quarter pictures
+// (me_quarter_sample) of two successive input pictures, qw x qh samples, of which ceil(width / 4) x ceil(height / 4) are visible.
+// ---------------------------------------------------------------------------------------------
+// reach of a block's best-match search in quarter samples: a multiple of 4, at most 64 (me-coarse is 0, 64, 128 or 256)
+KVZ_HD int sc_reach(int me_coarse) { return imax(8, me_coarse / 4); }
+// the 8x8 blocks (bx, by) of the quarter picture with 32 bx < width and 32 by < height
+KVZ_HD void sc_visible_blocks(int width, int height, int *bw, int *bh) { *bw = (width + 31) / 32; *bh = (height + 31) / 32; }
+// the mean shift d = floor((2 (Sc - Sp) + n) / (2 n)) of the sums Sc, Sp over the n visible quarter samples (true floor: the numerator may be negative)
+KVZ_HD int sc_mean_shift(int64_t sc, int64_t sp, int64_t n)
+{
+  const int64_t a = 2 * (sc - sp) + n, b = 2 * n;
+  int64_t q = a / b;
+  if (a % b != 0 && a < 0) q--;
+  return (int)q;
+}
+// a sample of the shifted previous quarter picture
+KVZ_HD int sc_ref_sample(int p, int d) { return clip8(p + d); }
+KVZ_HD int sc_block_mean(int sum) { return (sum + 32) >> 6; }
+// the block is new: its best match costs more than its own activity plus 128
+KVZ_HD bool sc_is_new(uint32_t S, uint32_t A) { return S > A + 128u; }
+// the picture is a cut: more than half of its blocks are new
+KVZ_HD bool sc_verdict(int n_new, int n_b) { return 2 * n_new > n_b; }
+// a picture since_idr pictures behind the last IDR picture is examined: the option is on (N >= 1), the period does not make it an IDR picture anyway
+// (periodic; picture 0 has since_idr 0) and it lies at least N pictures behind the last one
+KVZ_HD bool sc_examined(int since_idr, int N, bool periodic) { return N >= 1 && !periodic && since_idr >= N; }
+// block (bx, by): its activity A = sum |c - m| around its mean m, and its best match S = the smallest sum |c(x, y) - r(x + dx, y + dy)| over
+// dx, dy in [-rq, rq], r = the previous quarter picture shifted by d, coordinates clamped to the quarter picture.  The serial form of k_sc_blocks.
+KVZ_HD void sc_block_stat(const uint8_t *qc, const uint8_t *qp, int qw, int qh, int bx, int by, int rq, int d, uint32_t *S, uint32_t *A)
+{
+  int sum = 0;
+  for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) sum += qc[(size_t)(by * 8 + y) * qw + bx * 8 + x];
+  const int m = sc_block_mean(sum);
+  uint32_t act = 0, best = ~0u;
+  for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) act += (uint32_t)iabs((int)qc[(size_t)(by * 8 + y) * qw + bx * 8 + x] - m);
+  for (int dy = -rq; dy <= rq; dy++)
+    for (int dx = -rq; dx <= rq; dx++) {
+      uint32_t sad = 0;
+      for (int y = 0; y < 8; y++)
+        for (int x = 0; x < 8; x++) {
+          const int ry = clip3(0, qh - 1, by * 8 + y + dy), rx = clip3(0, qw - 1, bx * 8 + x + dx);
+          sad += (uint32_t)iabs((int)qc[(size_t)(by * 8 + y) * qw + bx * 8 + x] - sc_ref_sample(qp[(size_t)ry * qw + rx], d));
+        }
+      best = sad < best ? sad : best;
+    }
+  *S = best; *A = act;
+}
+
 // the reference planes of ref_idx k (one reference: ref[])
 KVZ_HD const uint8_t *ref_plane(const EncFrame &f, int k, int c) { return f.cu_ref ? f.refs[k][c] : f.ref[c]; }
 KVZ_HD int cu_ref_at(const EncFrame &f, int i) { return f.cu_ref ? f.cu_ref[i] : 0; }

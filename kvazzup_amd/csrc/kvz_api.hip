@@ -201,6 +201,7 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
   INT_OPT("lp-refs", lp_refs, 0, 4)              // (extension: references per P picture, "uvgx multi-reference v1"; "ref" keeps accepting 1 only)
   if (n == "me-coarse") { if (!parse_int(value, &iv) || (iv != 0 && iv != 64 && iv != 128 && iv != 256)) return 0; cfg->me_coarse = iv; return 1; }      // (extension: reach of the coarse stage of "uvgx coarse-to-fine search v1"; off by default and at every preset)
   if (n == "weightp") { if (!parse_int(value, &iv) || (iv != 0 && iv != 1)) return 0; cfg->weightp = iv; return 1; }      // (extension: "uvgx weighted prediction v1", DESIGN.md section 9e -- explicit weighted prediction of luma; off by default and at every preset)
+  if (n == "scenecut") { if (!parse_int(value, &iv) || iv < 0 || iv > 255) return 0; cfg->scenecut = iv; return 1; }      // (extension: "uvgx scene cut v1", DESIGN.md section 9g -- an input picture at least N pictures behind the last IDR picture that shares nothing with the picture before it becomes an IDR picture; off by default and at every preset)
   if (n == "intra-refresh") { if (!parse_int(value, &iv) || (iv != 0 && (iv < 2 || iv > 255))) return 0; cfg->intra_refresh = iv; return 1; }      // (extension: "uvgx intra refresh v1", DESIGN.md section 9f -- a band of intra units walks across the P pictures, N pictures a pass at most; off by default and at every preset)
   if (n == "lp-gop") { if (!parse_bool(value, &iv)) return 0; cfg->lp_gop = iv; return 1; }      // (extension: "uvgx low-delay GOP v1", DESIGN.md section 9d -- the switch that makes gop=lp-g<g>d<d>t1 take effect; off by default and at every preset)
   BOOL_OPT("tmvp", tmvp_enable)                  // (temporal motion vector prediction; off by default and at every preset, unlike Kvazaar)
@@ -354,6 +355,7 @@ kvz_encoder *encoder_open(const kvz_config *cfg)
   ec.lp_gop = cfg->lp_gop != 0; ec.gop_g = cfg->gop_len > 0 ? cfg->gop_len : 0; ec.gop_d = cfg->gop_lp_ref_depth; ec.gop_t = cfg->gop_lp_temporal_layers;
   ec.weightp = cfg->weightp != 0;
   ec.intra_refresh = cfg->intra_refresh;
+  ec.scenecut = cfg->scenecut;
   ec.hash = cfg->hash == KVZ_HASH_MD5 ? 2 : (cfg->hash == KVZ_HASH_CHECKSUM ? 1 : 0);
   ec.vaq = cfg->vaq > 0 ? cfg->vaq : 0;
   ec.qp_in_cu = (cfg->set_qp_in_cu || ec.vaq > 0) ? 1 : 0;

@@ -1,0 +1,208 @@
+"""GPU: "uvgx scene cut v1" (kvazaar.h scenecut) -- an input picture that shares nothing with the one before it becomes an IDR picture.
+
+The feature is held to: every picture's record {examined, n_new, n_b, d, cut} and every examined picture's (S, A) pairs equal tests/scenecut_model.py on the
+encoder's own padded input planes; up to the cut the stream is the option-off encoder's byte for byte, and from the cut on it is the checker's encoder's, fed the
+pictures behind the cut as a fresh stream; the period counts from the cut; the minimum distance N holds; brightness changes and a pan change no byte; every
+reconstruction equals what the checker's decoder, the library's HIP decoder and (the smallest case) tests/pyhevc.py make of the stream, over the tool set; and
+encoder_open refuses the option in band mode.  The clips are the benchmark's synthetic clip and its scene-cut form (kvazzup_amd.synth), qp 32, me-range 8."""
+import functools
+
+import numpy as np
+import pytest
+
+import enckit
+import pyhevc
+import scenecut_model as M
+import wp_model
+
+BASE = (("qp", 32), ("me-range", 8), ("vps-period", 1))
+IDR, VCL_MAX = 19, 31
+
+
+@functools.lru_cache(maxsize=None)
+def _cut_clip(w, h, n, cut):
+    return tuple(M.cut_clip(w, h, n, cut))
+
+
+@functools.lru_cache(maxsize=None)
+def _bench_clip(w, h, n):
+    return tuple(M.bench_clip(w, h, n))
+
+
+def _record(ge):
+    return dict(zip(M.FIELDS, (int(v) for v in ge.debug("scenecut", np.int32, (5,)))))
+
+
+def _vcl_types(au):
+    return sorted({(nal[0] >> 1) & 63 for nal in pyhevc.split_nals(au) if (nal[0] >> 1) & 63 <= VCL_MAX})      # (split_nals strips the start codes)
+
+
+def _is_idr(au):
+    return _vcl_types(au) == [IDR]
+
+
+def _info_and_record(ge):
+    return dict(ge.info), _record(ge)
+
+
+# ---- 1. the record and the blocks against the model
+def _check_against_model(w, h, frames, N, period=64, me_coarse=0, blocks_too=True):
+    ge = enckit.encoder(w, h, BASE + (("scenecut", N), ("period", period)) + ((("me-coarse", me_coarse),) if me_coarse else ()))
+    cw, ch = ge.coded_size()
+    model = M.Stepper(w, h, N, period, me_coarse)
+    bw, bh = M.visible_blocks(w, h)
+    cuts = examined = 0
+    try:
+        for t, fr in enumerate(frames):
+            au, _ = ge.encode(fr, want_recon=False)
+            want, wb, idr = model.step(ge.debug("src0", np.uint8, (ch, cw)))
+            got = _record(ge)
+            assert got == want, "picture %d: record %s, the model says %s" % (t, got, want)
+            assert _is_idr(au) == idr and ge.info["nal_unit_type"] == (IDR if idr else 1), (t, _vcl_types(au), idr)
+            cuts += want["cut"]; examined += want["examined"]
+            if want["examined"] and blocks_too:
+                gb = ge.debug("sc_blocks", np.uint32, (bh, bw, 2)).astype(np.int64)
+                bad = np.argwhere(gb != wb)
+                assert not len(bad), "picture %d: %d entries of sc_blocks differ, first (row, column, S / A) %s: GPU %s, model %s" % (t, len(bad), bad[0].tolist(), gb[tuple(bad[0])], wb[tuple(bad[0])])
+    finally:
+        ge.close()
+    return cuts, examined
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(64, 64), (320, 192), (416, 240)])
+def test_record_and_blocks_match_the_model(gpu, size):
+    w, h = size
+    cuts, examined = _check_against_model(w, h, _cut_clip(w, h, 7, 4), N=2)
+    assert (cuts, examined) == (1, 4)                      # pictures 2, 3, 4 (the cut: an IDR picture) and 6
+
+
+@pytest.mark.gpu
+def test_record_matches_the_model_with_me_coarse(gpu):
+    w, h = 320, 192
+    assert _check_against_model(w, h, _cut_clip(w, h, 7, 4), N=2, me_coarse=64) == (1, 4)      # rq 16
+
+
+@pytest.mark.gpu
+def test_record_matches_the_model_1080p(gpu):
+    w, h = 1920, 1080
+    assert _check_against_model(w, h, _cut_clip(w, h, 2, 1), N=1, blocks_too=False) == (1, 1)
+
+
+# ---- 2. the stream: the option-off encoder's up to the cut, the checker's from the cut on
+PINNED = {"plain": dict(), "src-subme2": dict(opts=(("me-source", 1), ("subme", 2)), okw=dict(subme=2), oopts=(("me-source", 1),)),
+          "lp-refs3": dict(opts=(("lp-refs", 3),), n=3), "tmvp": dict(opts=(("tmvp", 1),), tmvp=1)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("owf", [0, 6])
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_stream_is_pinned_to_the_checker(gpu, name, owf):
+    w, h, n, cut = 320, 192, 10, 5
+    c = PINNED[name]
+    frames = _cut_clip(w, h, n, cut)
+    opts = BASE + (("period", 64), ("owf", owf)) + tuple(c.get("opts", ()))
+    ge = enckit.encoder(w, h, opts)
+    off = enckit.encode_all(ge, frames, owf)
+    ge.close()
+    ge = enckit.encoder(w, h, opts + (("scenecut", 2),))
+    on = enckit.encode_all(ge, frames, owf, per_picture=_info_and_record)
+    ge.close()
+    for t in range(cut):
+        assert on[t][0] == off[t][0], "access unit %d differs from the option-off encoder's" % t
+    au, _, (info, rec) = on[cut]
+    assert _is_idr(au) and info["nal_unit_type"] == IDR and info["slice_type"] == 2 and info["poc"] == 0 and rec["cut"] == 1, (info, rec, _vcl_types(au))
+    assert not _is_idr(off[cut][0])
+    oe = enckit.oracle_encoder(w, h, n=c.get("n"), tmvp=c.get("tmvp"), opts=c.get("oopts", ()), qp=32, period=64, me_range=8, **c.get("okw", {}))
+    try:
+        for t in range(cut, n):
+            want = oe.encode(frames[t])
+            assert on[t][0] == want, "access unit %d: %d bytes, the checker's encoder (fed pictures %d.. as a fresh stream) makes %d" % (t, len(on[t][0]), cut, len(want))
+            assert np.array_equal(on[t][1], oe.recon()), "reconstruction %d differs from the checker's" % t
+    finally:
+        oe.close()
+
+
+# ---- 3. the period counts from the cut
+@pytest.mark.gpu
+def test_period_restarts_at_the_cut(gpu):
+    w, h = 320, 192
+    ge = enckit.encoder(w, h, BASE + (("period", 4), ("scenecut", 2)))
+    out = enckit.encode_all(ge, _cut_clip(w, h, 16, 6), per_picture=_info_and_record)
+    ge.close()
+    assert [t for t, (au, _, _) in enumerate(out) if _is_idr(au)] == [0, 4, 6, 10, 14]
+    assert [t for t, (_, _, (_, rec)) in enumerate(out) if rec["cut"]] == [6]
+    assert [info["poc"] for _, _, (info, _) in out] == [0, 1, 2, 3, 0, 1, 0, 1, 2, 3, 0, 1, 2, 3, 0, 1]
+
+
+# ---- 4. the minimum distance N
+@pytest.mark.gpu
+def test_minimum_distance(gpu):
+    w, h = 320, 192
+    ge = enckit.encoder(w, h, BASE + (("period", 64), ("scenecut", 8)))
+    out = enckit.encode_all(ge, _cut_clip(w, h, 12, 3), per_picture=_info_and_record)
+    ge.close()
+    assert [t for t, (au, _, _) in enumerate(out) if _is_idr(au)] == [0]      # picture 3 lies closer than 8 pictures to the IDR picture
+    assert [t for t, (_, _, (_, rec)) in enumerate(out) if rec["examined"]] == [8, 9, 10, 11] and not any(rec["cut"] for _, _, (_, rec) in out)
+
+
+# ---- 5. no false cuts: brightness changes and a pan change no byte
+@pytest.mark.gpu
+@pytest.mark.parametrize("clip", ["bench", "offset", "gain", "flash", "pan"])
+def test_no_false_cuts(gpu, clip):
+    w, h, n = 320, 192, 10
+    frames = enckit.pan(w, h, n) if clip == "pan" else (list(_bench_clip(w, h, n)) if clip == "bench" else wp_model.change(_bench_clip(w, h, n), w, h, clip))
+    runs = []
+    for N in (0, 1):
+        ge = enckit.encoder(w, h, BASE + (("period", 64), ("scenecut", N)))
+        runs.append(enckit.encode_all(ge, frames, per_picture=_record if N else None))
+        ge.close()
+    for t in range(n):
+        assert runs[1][t][0] == runs[0][t][0], "access unit %d differs from the option-off encoder's" % t
+        assert runs[1][t][2]["cut"] == 0 and runs[1][t][2]["examined"] == (1 if t else 0), (t, runs[1][t][2])
+
+
+# ---- 6. closed loop over the tool set
+CLOSED = {
+    "subme4-sao": dict(opts=(("subme", 4), ("sao", "full"))),
+    "lp-gop-refs3": dict(opts=(("gop", "lp-g4d3t1"), ("lp-gop", 1), ("lp-refs", 3))),
+    "weightp": dict(opts=(("weightp", 1),)),
+    "intra-refresh": dict(opts=(("intra-refresh", 6), ("period", 0))),
+    "bitrate-oba": dict(bitrate=400000, opts=(("rc-algorithm", "oba"),)),
+    "tiles2x2": dict(opts=(("tiles", "2x2"),)),
+    "slices-wpp": dict(opts=(("slices", "wpp"),)),
+    "owf0": dict(owf=0), "owf2": dict(owf=2), "owf6": dict(owf=6),
+    "frame-threaded": dict(owf=2, frame_threaded=True),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CLOSED))
+def test_closed_loop_decodes_to_the_reconstruction(gpu, name):
+    c = CLOSED[name]
+    w, h, n, cut, owf, br = 320, 192, 8, 4, c.get("owf", 0), c.get("bitrate", 0)
+    opts = BASE + (("owf", owf), ("scenecut", 2)) + tuple(c.get("opts", ())) + ((("bitrate", br),) if br else ())
+    ge = enckit.encoder(w, h, opts, fields={"target_bitrate": br} if br else None)
+    out = enckit.encode_all(ge, _cut_clip(w, h, n, cut), owf, per_picture=_info_and_record)
+    ge.close()
+    assert [t for t, (au, _, _) in enumerate(out) if _is_idr(au)] == [0, cut] and out[cut][2][1]["cut"] == 1 and out[cut][2][0]["nal_unit_type"] == IDR
+    enckit.closed_loop([(au, rec) for au, rec, _ in out], frame_threaded=c.get("frame_threaded", False))
+
+
+@pytest.mark.gpu
+def test_closed_loop_smallest_case_also_matches_pyhevc(gpu):
+    w, h, n, cut = 64, 64, 6, 3
+    ge = enckit.encoder(w, h, BASE + (("scenecut", 2), ("subme", 2)))
+    out = enckit.encode_all(ge, _cut_clip(w, h, n, cut), per_picture=_info_and_record)
+    ge.close()
+    assert [t for t, (au, _, _) in enumerate(out) if _is_idr(au)] == [0, cut]
+    enckit.closed_loop([(au, rec) for au, rec, _ in out], pyhevc_too=True)
+
+
+# ---- 7. what encoder_open refuses
+@pytest.mark.gpu
+def test_encoder_open_refuses_band_mode(gpu, capfd):
+    from kvazzup_amd.codec import Encoder
+    with pytest.raises(RuntimeError):
+        Encoder(256, 256, options=(("scenecut", 4), ("tiles", "1x2"), ("band-row0", 0), ("band-rows", 2)))
+    assert "scenecut" in capfd.readouterr().err

@@ -67,6 +67,7 @@ enum kvz_ime_algorithm { KVZ_IME_HEXBS = 0, KVZ_IME_TZ = 1, KVZ_IME_FULL = 2, KV
 enum kvz_nal_unit_type { KVZ_NAL_TRAIL_N = 0, KVZ_NAL_TRAIL_R = 1, KVZ_NAL_IDR_W_RADL = 19, KVZ_NAL_IDR_N_LP = 20,
                          KVZ_NAL_CRA_NUT = 21, KVZ_NAL_VPS_NUT = 32, KVZ_NAL_SPS_NUT = 33, KVZ_NAL_PPS_NUT = 34 };
 enum kvz_slice_type { KVZ_SLICE_B = 0, KVZ_SLICE_P = 1, KVZ_SLICE_I = 2 };
+enum kvz_input_format { KVZ_INPUT_I420 = 0, KVZ_INPUT_RGB32 = 1, KVZ_INPUT_RGB32_SSE41 = 2, KVZ_INPUT_YUYV = 3 };   /* kvz_config.input_format ("input-format", kvazzup_amd extension) */
 
 /* Encoder configuration.  Fields uvgComm touches keep Kvazaar's names; the rest record what
  * config_parse() understood.  Initialise with kvz_api.config_init(). */
@@ -134,6 +135,7 @@ typedef struct kvz_config {
   int32_t weightp;            /* "weightp" 0 / 1 (extension, "uvgx weighted prediction v1"; restated in tests/wp_model.py): 1 = explicit weighted prediction of luma (PPS weighted_pred_flag, pred_weight_table() in every independent P slice segment header, denominator 6, chroma never weighted).  Per P picture and reference a weight and an offset are derived from the luma mean and variance of the two INPUT pictures and kept when a check on every fourth sample of every fourth row says they pay (16 * weighted SAD < 15 * plain SAD); the integer search then reads weighted copies of its reference planes, and the fractional refinement and the reconstruction predict luma with the weights -- brightness steps, fades, auto-exposure.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it in band mode and with lossless */
   int32_t intra_refresh;      /* "intra-refresh" 0 / 2..255 (extension, "uvgx intra refresh v1"; restated in tests/ir_model.py): N = the number of P pictures a refresh cycle may take.  A band of intra units (the step ceil(B / N) block columns of 32 samples, B = coded width / 32, plus 16 columns of overlap) walks across the P pictures, one step a picture, cycle after cycle from the first P picture behind an IDR picture; the 32x32 blocks the band has passed keep their vectors out of what it has not.  A decoder that concealed a lost picture has the encoder's pictures again, exactly, once a cycle that began after the loss is complete -- no IDR picture needed, so uvgComm users pass it beside "period=0" or a long period.  The first picture of a cycle carries a recovery point SEI (recovery_poc_cnt = cycle length - 1, exact_match_flag 1).  With "intra-in-p=0" the band's units are the only intra units.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it beside lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless and intra-chain=0 */
   int32_t scenecut;           /* "scenecut" 0 / 1..255 (extension, "uvgx scene cut v1"; restated in tests/scenecut_model.py): N = the least distance in pictures between an IDR picture and a scene-cut IDR picture behind it.  An input picture at least N pictures behind the last IDR picture (and not an IDR picture by "period" anyway) is compared with the previous INPUT picture on their quarter-resolution pictures: the previous one is shifted by the difference of the two means, every visible 8x8 block (32x32 samples) looks for its best match within +-max(8, me-coarse / 4) quarter samples, and a block whose best SAD exceeds its own activity (sum |c - mean|) by more than 128 is new; when more than half of the blocks are new the picture is coded as an IDR picture (POC 0, parameter sets as "vps-period" says) and "period" counts from it -- slide changes, window and camera switches.  Brightness steps, fades and pans within reach are not cuts.  encoder_encode of an examined picture waits for that verdict on the GPU before the picture is planned (DESIGN.md section 9g has the cost); pictures that are not examined wait for nothing.  0 (default, also at every preset): the streams of before byte for byte.  uvgComm users pass it as a custom parameter, e.g. "scenecut=8".  encoder_open fails with it in band mode */
+  int32_t input_format;       /* "input-format" i420 / rgb32 / rgb32-sse41 / yuyv (extension; enum kvz_input_format): what the pictures handed to the encoder are.  i420 (default, also at every preset): planar pictures as ever, the encoder of before byte for byte.  Otherwise the encoder takes PACKED pictures through kvzx_encoder_encode_packed_host / _device (kvazzup_amd.h) -- rgb32: width * height * 4 bytes, rows top to bottom, converted with the arithmetic of uvgComm's rgb_to_yuv420_i_c; rgb32-sse41: the same bytes with the arithmetic of rgb_to_yuv420_i_sse41, which turns the picture upside down; yuyv: width * height * 2 bytes Y0 U Y1 V, converted as yuyv_to_yuv420_c does -- and converts them in its input stage on the GPU, in the pass that pads the picture: the stream and the reconstructions are those of an i420 encoder fed the converted pictures, byte for byte.  The format is fixed per encoder; encoder_encode (a kvz_picture carries planes) and the I420 entry points return 0 on such an encoder.  encoder_open fails with it beside input-hold and in band mode, and for rgb32 / rgb32-sse41 when the width is no multiple of 4 */
 } kvz_config;
 
 /* Picture.  y/u/v are planar 8-bit with stride == width (chroma width/2), as uvgComm assumes

@@ -27,6 +27,15 @@ KVZ_PUBLIC int kvzx_encoder_encode_device(kvz_encoder *enc, const void *d_i420, 
 /* Same with host planes (stride = width), without going through kvz_picture / chunk lists. */
 KVZ_PUBLIC int kvzx_encoder_encode_host(kvz_encoder *enc, const uint8_t *y, const uint8_t *u, const uint8_t *v,
                                         uint8_t *au_buf, uint32_t au_cap, uint32_t *len_out, kvz_frame_info *info_out);
+/* Encoders opened with "input-format" rgb32 / rgb32-sse41 / yuyv (kvazaar.h kvz_config.input_format) take their pictures here, as ONE packed block:
+ * RGB32 width * height * 4 bytes, rows top to bottom; YUYV width * height * 2 bytes (Y0 U Y1 V).  The block's length is implied by the encoder's format --
+ * the caller vouches for it as it does for the planes of the calls above -- and a device block of RGB32 must start at a multiple of 16 bytes.  The picture
+ * is converted on the GPU in the encoder's input stage; the stream is that of an i420 encoder fed the converted picture.  A host block that starts a
+ * page-locked kvz_picture (picture_alloc of a size that holds it) is read in place by the copy engine and must then stay unchanged until its access unit
+ * has come back; any other host block is copied before the call returns.  NULL returns the picture in flight (owf >= 1).  On an i420 encoder both return
+ * 0, as the two calls above (and encoder_encode) do on a packed one. */
+KVZ_PUBLIC int kvzx_encoder_encode_packed_host(kvz_encoder *enc, const void *packed, uint8_t *au_buf, uint32_t au_cap, uint32_t *len_out, kvz_frame_info *info_out);
+KVZ_PUBLIC int kvzx_encoder_encode_packed_device(kvz_encoder *enc, const void *d_packed, uint8_t *au_buf, uint32_t au_cap, uint32_t *len_out, kvz_frame_info *info_out);
 KVZ_PUBLIC int kvzx_encoder_coded_size(kvz_encoder *enc, int *coded_w, int *coded_h);
 /* cropped reconstruction of the last coded picture into host planes (stride = width) */
 KVZ_PUBLIC int kvzx_encoder_download_recon(kvz_encoder *enc, uint8_t *y, uint8_t *u, uint8_t *v);
@@ -138,6 +147,8 @@ KVZ_PUBLIC int kvzx_decoder_output_rgb32_device(OpenHevc_Handle h, void *d_rgb32
  * down).  width % 4 == 0, height % 2 == 0.  Output: packed I420 (width * height * 3 / 2 bytes). */
 KVZ_PUBLIC int kvzx_rgb32_to_yuv420_device(const void *d_rgb32, void *d_i420, int width, int height, int variant, void *hip_stream);
 KVZ_PUBLIC int kvzx_rgb32_to_yuv420(const uint8_t *rgb32, uint8_t *i420, int width, int height, int variant);
+/* measurement aid: `reps` launches of kvzx_rgb32_to_yuv420_device on the default stream, each timed with a pair of HIP events; ms_out[reps] */
+KVZ_PUBLIC int kvzx_rgb32_to_yuv420_device_timed(const void *d_rgb32, void *d_i420, int width, int height, int variant, int reps, float *ms_out);
 
 /* ---- filter-graph harness (kvazzup_amd/csrc/filters.h): KvazaarFilter -> [WireAdapter -> OpenHEVCFilter] ----
  * A Qt-free restatement of the two uvgComm filters on this path, each on its own thread with the
@@ -147,6 +158,10 @@ KVZ_PUBLIC int kvzx_rgb32_to_yuv420(const uint8_t *rgb32, uint8_t *i420, int wid
 KVZ_PUBLIC void *uvgx_pipeline_create(const char *settings_text, int loopback_decode, int keep_outputs);
 KVZ_PUBLIC int uvgx_pipeline_push_host(void *p, const uint8_t *i420, int w, int h, int fps_num, int fps_den, int64_t pts);
 KVZ_PUBLIC int uvgx_pipeline_push_device(void *p, const void *d_i420, int w, int h, int fps_num, int fps_den, int64_t pts);
+/* a packed RGB32 / YUYV picture (type: uvgx::DataType, DT_RGB32VIDEO = 1 << 10 or DT_YUYVVIDEO = 1 << 4) for a graph whose settings say
+ * uvgx/inputFormat = rgb32 | rgb32-sse41 | yuyv: the encoder filter hands it over without a host conversion; 0 = rejected */
+KVZ_PUBLIC int uvgx_pipeline_push_packed_host(void *p, const uint8_t *packed, int type, int w, int h, int fps_num, int fps_den, int64_t pts);
+KVZ_PUBLIC int uvgx_pipeline_push_packed_device(void *p, const void *d_packed, int type, int w, int h, int fps_num, int fps_den, int64_t pts);
 KVZ_PUBLIC int uvgx_pipeline_wait(void *p, uint64_t n_outputs, int timeout_ms);
 /* push_device for a source that paces itself: sleeps until the encoder filter buffers fewer than max_backlog pictures (uvgComm filters
  * drop inputs at 10 buffered, filter.cpp:151-222); 0 = timed out or rejected */

@@ -102,6 +102,45 @@ class Encoder:
             raise RuntimeError("kvzx_encoder_encode_device failed")
         return bytes(self._au[:n.value])
 
+    # -- "input-format" rgb32 / rgb32-sse41 / yuyv: the picture as one packed block, converted in the encoder's input stage
+    def packed_bytes(self):
+        """bytes of one input picture in the encoder's format"""
+        return self.w * self.h * (3, 8, 8, 4)[int(self.cfg.contents.input_format)] // 2
+
+    def _packed_out(self, ok, n, info, want_recon, what):
+        if not ok:
+            raise RuntimeError("%s failed" % what)
+        if not n.value:
+            return None, None
+        self.info = {"poc": info.poc, "qp": info.qp, "nal_unit_type": info.nal_unit_type, "slice_type": info.slice_type,
+                     "ref_list": [int(info.ref_list[0][k]) for k in range(int(info.ref_list_len[0]))]}
+        rec = None
+        if want_recon:
+            ny = self.w * self.h
+            rec = np.empty(ny * 3 // 2, dtype=np.uint8)
+            if not self.lib.kvzx_encoder_download_recon(self.enc, rec.ctypes.data, rec.ctypes.data + ny, rec.ctypes.data + ny + ny // 4):
+                raise RuntimeError("kvzx_encoder_download_recon failed")
+        return bytes(self._au[:n.value]), rec
+
+    def encode_packed(self, buf, want_recon=True):
+        """a packed host picture (uint8, packed_bytes() long); None flushes.  Returns (access unit, reconstruction) like encode(), (None, None)
+        when the call produced no output"""
+        if buf is not None:
+            buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+            if buf.size != self.packed_bytes():
+                raise ValueError("a packed picture of %d bytes, the encoder's format has %d" % (buf.size, self.packed_bytes()))
+        n = C.c_uint32(0)
+        info = N.KvzFrameInfo()
+        ok = self.lib.kvzx_encoder_encode_packed_host(self.enc, buf.ctypes.data if buf is not None else None, self._au.ctypes.data, len(self._au), C.byref(n), C.byref(info))
+        return self._packed_out(ok, n, info, want_recon, "kvzx_encoder_encode_packed_host")
+
+    def encode_packed_device(self, dptr, want_recon=True):
+        """the same for a packed picture in device memory (an address; None flushes)"""
+        n = C.c_uint32(0)
+        info = N.KvzFrameInfo()
+        ok = self.lib.kvzx_encoder_encode_packed_device(self.enc, dptr, self._au.ctypes.data, len(self._au), C.byref(n), C.byref(info))
+        return self._packed_out(ok, n, info, want_recon, "kvzx_encoder_encode_packed_device")
+
     def coded_size(self):
         a, b = C.c_int(), C.c_int()
         self.lib.kvzx_encoder_coded_size(self.enc, C.byref(a), C.byref(b))

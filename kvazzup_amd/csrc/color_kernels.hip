@@ -190,6 +190,25 @@ KVZ_PUBLIC int kvzx_rgb32_to_yuv420_device(const void *d_rgb32, void *d_i420, in
   return kvzx::convert_rgb32_to_i420((const uint8_t *)d_rgb32, (uint8_t *)d_i420, width, height, variant, (hipStream_t)hip_stream);
 }
 
+// measurement aid (tools/measure/input_format_ab.py): `reps` launches of the converter on the default stream, each between two events of its own as the encoder's
+// profiling times its kernels; ms_out[reps]
+KVZ_PUBLIC int kvzx_rgb32_to_yuv420_device_timed(const void *d_rgb32, void *d_i420, int width, int height, int variant, int reps, float *ms_out)
+{
+  if (reps < 1 || !ms_out) return 0;
+  hipEvent_t a, b;
+  if (hipEventCreate(&a) != hipSuccess) return 0;
+  if (hipEventCreate(&b) != hipSuccess) { hipEventDestroy(a); return 0; }
+  int ok = 1;
+  for (int i = 0; i < reps && ok; i++) {
+    hipEventRecord(a, nullptr);
+    ok = kvzx::convert_rgb32_to_i420((const uint8_t *)d_rgb32, (uint8_t *)d_i420, width, height, variant, nullptr);
+    hipEventRecord(b, nullptr);
+    ok = ok && hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&ms_out[i], a, b) == hipSuccess;
+  }
+  hipEventDestroy(a); hipEventDestroy(b);
+  return ok;
+}
+
 // host buffers in and out, like rgb_to_yuv420_i_*(input, output, width, height): upload, convert, download
 KVZ_PUBLIC int kvzx_rgb32_to_yuv420(const uint8_t *rgb32, uint8_t *i420, int width, int height, int variant)
 {

@@ -15,6 +15,7 @@
 #include "hevc_headers.h"
 #include "entropy_host.h"
 #include "enc_kernels.h"
+#include "input_kernels.h"
 
 namespace kvzx {
 
@@ -79,6 +80,9 @@ struct EncoderConfig {
                               // 8x8 block the best match against the block's own activity); when more than half of the blocks are new the picture is an IDR picture and
                               // the period counts from it.  The one option whose decision the host waits for: submit() of an examined picture waits for k_sc_decide on
                               // the input stream before it plans the picture.  Not in band mode
+  int input_format = 0;       // "input-format" (extension; enum kvz_input_format): 0 = I420 pictures (the encoder of before); rgb32 / rgb32-sse41 / yuyv = PACKED pictures
+                              // (encode_packed_host / _device), converted with the reference's arithmetic in the input stage -- k_input_rgb32 / k_input_yuyv (input_kernels.hip)
+                              // write the working set's padded planes in k_pad_input's place, and everything behind them is as ever.  Not with input-hold, not in band mode
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -106,6 +110,11 @@ class Encoder {
   bool encode_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, EncodedPicture *out, bool pinned = false);
   // picture as packed I420 in device memory (w*h*3/2 bytes)
   bool encode_device(const uint8_t *d_i420, EncodedPicture *out);
+  // input-format other than i420: the picture as ONE packed block (input_bytes() long) in host / device memory; the I420 calls above fail on such an
+  // encoder and these fail on an I420 encoder.  pinned: page-locked and left alone until the access unit has been returned, as for encode_host
+  bool encode_packed_host(const uint8_t *packed, EncodedPicture *out, bool pinned = false);
+  bool encode_packed_device(const uint8_t *d_packed, EncodedPicture *out);
+  size_t input_bytes() const;            // bytes of one input picture in the encoder's format
   // owf >= 1: outputs the picture still in flight, if any (kvz_api encoder_encode with pic_in == NULL)
   bool flush(EncodedPicture *out);
   // like flush, but never waits: outputs the oldest picture in flight only if it has already been finished
@@ -315,7 +324,9 @@ class Encoder {
   void submitter();
   void drain_submitter();
   bool enqueue(const uint8_t *src, bool host, EncodedPicture *out);
-  bool upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_t *v, bool pinned);
+  bool upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_t *v, bool pinned);      // (a packed format: y is the whole picture)
+  bool host_picture(const uint8_t *y, const uint8_t *u, const uint8_t *v, EncodedPicture *out, bool pinned);      // what encode_host and encode_packed_host share
+  bool device_picture(const uint8_t *d_in, EncodedPicture *out);
   hipEvent_t in_done_ = nullptr; bool in_pending_ = false;   // input picture consumed (staging buffer / caller's device buffer reusable)
   // owf >= 2: two background workers, each with its own coder pool, finish two pictures side by side (the substreams of one
   // picture start one after the other -- WPP context hand-over -- so one picture alone cannot keep the pool busy)

@@ -68,6 +68,14 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.weightp && cfg.lossless) { if (error) *error = "weightp is not available with lossless"; return false; }
   if (cfg.scenecut < 0 || cfg.scenecut > 255) { if (error) *error = "scenecut must be 0 .. 255"; return false; }
   if (cfg.scenecut && cfg.band_rows > 0) { if (error) *error = "scenecut is not available in band mode (a band's encoder sees a part of the picture, the verdict is the whole picture's)"; return false; }
+  if (cfg.input_format != KVZ_INPUT_I420) {                // "input-format" 
+    const char *why = nullptr;
+    if (cfg.input_format != KVZ_INPUT_RGB32 && cfg.input_format != KVZ_INPUT_RGB32_SSE41 && cfg.input_format != KVZ_INPUT_YUYV) why = "input-format must be i420, rgb32, rgb32-sse41 or yuyv";
+    else if (cfg.input_hold) why = "input-format other than i420 is not available with input-hold (held pictures are I420)";
+    else if (cfg.band_rows > 0) why = "input-format other than i420 is not available in band mode";
+    else if (cfg.input_format != KVZ_INPUT_YUYV && (cfg.width & 3)) why = "input-format rgb32 / rgb32-sse41 needs a width that is a multiple of 4";
+    if (why) { if (error) *error = why; return false; }
+  }
   if (cfg.intra_refresh) {                                 // "uvgx intra refresh v1" ("not covered")
     const char *why = nullptr;
     if (cfg.intra_refresh < 2 || cfg.intra_refresh > 255) why = "intra-refresh must be 0 or 2 .. 255";
@@ -429,7 +437,8 @@ void Encoder::get_kernel_times(double *ms, uint64_t *launches, bool reset)
 // Nothing here waits on the calling thread except a staging buffer coming free (callers without page-locked planes).
 bool Encoder::upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_t *v, bool pinned)
 {
-  const size_t ny = (size_t)cfg_.width * cfg_.height, bytes = ny * 3 / 2;
+  const size_t ny = (size_t)cfg_.width * cfg_.height, bytes = input_bytes();
+  const bool packed = cfg_.input_format != KVZ_INPUT_I420;
   const int k = (int)(in_count_++ % kInRing);
   // The copy rides on the input stream itself, ahead of the picture's input kernel.  HIP spreads the streams of one priority level over four
   // hardware queues, and at the default level those are taken (tokenizer, input, decoder, decoder transfers): a fifth stream there shares a
@@ -444,7 +453,8 @@ bool Encoder::upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_
   if (!pinned) {
     if (!h_in_[k]) HIP_CHECK(hipHostMalloc(&h_in_[k], bytes, hipHostMallocDefault));
     if (h2d_pending_[k]) { Tick tk; HIP_CHECK(hipEventSynchronize(ev_h2d_[k])); h2d_pending_[k] = false; t_in_ += tk.ms(); }   // the staging buffer's last upload
-    memcpy(h_in_[k], y, ny); memcpy(h_in_[k] + ny, u, ny / 4); memcpy(h_in_[k] + ny + ny / 4, v, ny / 4);
+    if (packed) memcpy(h_in_[k], y, bytes);
+    else { memcpy(h_in_[k], y, ny); memcpy(h_in_[k] + ny, u, ny / 4); memcpy(h_in_[k] + ny + ny / 4, v, ny / 4); }
     src = h_in_[k];
   }
   if (pad_pending_[k]) {                             // d_in_[k]'s last reader: done long ago, normally
@@ -458,12 +468,26 @@ bool Encoder::upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_
   return true;
 }
 
+size_t Encoder::input_bytes() const { return kvzx::input_bytes(cfg_.input_format, cfg_.width, cfg_.height); }
+
 bool Encoder::encode_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, EncodedPicture *out, bool pinned)
 {
   const size_t ny = (size_t)cfg_.width * cfg_.height;
-  HIP_CHECK(hipSetDevice(cfg_.device));
   out->valid = false; out->au.clear();
-  pinned = pinned && u == y + ny && v == u + ny / 4;
+  if (cfg_.input_format != KVZ_INPUT_I420) return false;      // (a packed encoder takes encode_packed_host)
+  return host_picture(y, u, v, out, pinned && u == y + ny && v == u + ny / 4);
+}
+
+bool Encoder::encode_packed_host(const uint8_t *packed, EncodedPicture *out, bool pinned)
+{
+  out->valid = false; out->au.clear();
+  if (cfg_.input_format == KVZ_INPUT_I420 || !packed) return false;
+  return host_picture(packed, nullptr, nullptr, out, pinned);
+}
+
+bool Encoder::host_picture(const uint8_t *y, const uint8_t *u, const uint8_t *v, EncodedPicture *out, bool pinned)
+{
+  HIP_CHECK(hipSetDevice(cfg_.device));
   if (pinned && sub_thread_.joinable()) return enqueue(y, true, out);
   drain_submitter();
   accepted_++;
@@ -477,8 +501,21 @@ bool Encoder::encode_host(const uint8_t *y, const uint8_t *u, const uint8_t *v, 
 
 bool Encoder::encode_device(const uint8_t *d_i420, EncodedPicture *out)
 {
-  HIP_CHECK(hipSetDevice(cfg_.device));
   out->valid = false; out->au.clear();
+  return cfg_.input_format == KVZ_INPUT_I420 && device_picture(d_i420, out);      // (a packed encoder takes encode_packed_device)
+}
+
+bool Encoder::encode_packed_device(const uint8_t *d_packed, EncodedPicture *out)
+{
+  out->valid = false; out->au.clear();
+  // (the RGB32 kernels read 16 bytes at a time: rows are multiples of 16 bytes, the picture must start at one)
+  if (cfg_.input_format == KVZ_INPUT_I420 || !d_packed || (cfg_.input_format != KVZ_INPUT_YUYV && (((uintptr_t)d_packed) & 15))) return false;
+  return device_picture(d_packed, out);
+}
+
+bool Encoder::device_picture(const uint8_t *d_i420, EncodedPicture *out)
+{
+  HIP_CHECK(hipSetDevice(cfg_.device));
   if (cfg_.input_hold && sub_thread_.joinable()) return enqueue(d_i420, false, out);
   drain_submitter();
   accepted_++;
@@ -761,7 +798,13 @@ bool Encoder::submit(const uint8_t *d_i420, int in_ring)
 bool Encoder::pad_stage(int set, const uint8_t *d_i420, int in_ring)
 {
   if (src_busy_[set]) { HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_src_free_[set], 0)); src_busy_[set] = false; }   // the last picture that used this set (t - kSets) has been reconstructed
-  timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[set][0], src_[set][1], src_[set][2], cw_, ch_, stream_in_); });
+  // input-format: a packed picture is converted in the pass that pads it, under the input stage's kernel id
+  if (cfg_.input_format == KVZ_INPUT_I420) timed(K_PAD, stream_in_, [&] { launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[set][0], src_[set][1], src_[set][2], cw_, ch_, stream_in_); });
+  else {
+    bool ok = true;
+    timed(K_PAD, stream_in_, [&] { ok = launch_input_packed(cfg_.input_format, d_i420, cfg_.width, cfg_.height, src_[set][0], src_[set][1], src_[set][2], cw_, ch_, stream_in_); });
+    if (!ok) return false;
+  }
   if (in_ring >= 0) { HIP_CHECK(hipEventRecord(ev_pad_[in_ring], stream_in_)); pad_pending_[in_ring] = true; }
   // me-coarse, scenecut: every picture's quarter picture (an intra picture's is searched by / compared with the P picture behind it)
   if (mc_q_[set]) launch_luma_quarter(src_[set][0], mc_q_[set], cw_, ch_, stream_in_);      // (no kernel id of its own: the profile's keys are the default encoder's)

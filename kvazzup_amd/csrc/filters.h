@@ -29,7 +29,7 @@
 
 namespace uvgx {
 
-enum DataType { DT_NONE = 0, DT_YUV420VIDEO = 1, DT_RGB32VIDEO = (1 << 10), DT_HEVCVIDEO = (1 << 14) };
+enum DataType { DT_NONE = 0, DT_YUV420VIDEO = 1, DT_YUYVVIDEO = (1 << 4), DT_RGB32VIDEO = (1 << 10), DT_HEVCVIDEO = (1 << 14) };      // (filter.h:27-45: the values of the reference's enum)
 enum DataSource { DS_UNKNOWN, DS_LOCAL, DS_REMOTE };
 enum HEVC_NAL_UNIT_TYPE { TRAIL_R = 1, IDR_W_RADL = 19, VPS_NUT = 32, SPS_NUT = 33, PPS_NUT = 34 };
 
@@ -52,7 +52,7 @@ struct Data {
   // filter.cpp initializeData): what the delay statistics below are computed from; travels with the picture through encoder, wire and decoder
   int64_t creationUs = -1;
   std::unique_ptr<VideoInfo> vInfo;
-  // extension (not in the reference): picture already resident in HBM (packed I420); data stays empty
+  // extension (not in the reference): picture already resident in HBM (packed I420; with uvgx/inputFormat the packed RGB32 / YUYV picture `type` names); data stays empty
   const void *device_data = nullptr;
   const void *device_planes[3] = {nullptr, nullptr, nullptr}; int device_pitch[3] = {0, 0, 0};   // decoded I420 left in HBM
   // extension (harness only): the payload lies in memory the source keeps alive and unchanged until the picture has left the encoder
@@ -169,6 +169,11 @@ class KvazaarFilter : public Filter {
   std::vector<uint8_t> au_;                        // device-input path: access unit buffer
   bool lastInputOnDevice_ = false;
   void drain();
+  // harness setting uvgx/inputFormat = rgb32 | rgb32-sse41 | yuyv ("input-format", kvazaar.h): the filter takes DT_RGB32VIDEO / DT_YUYVVIDEO pictures and hands
+  // them to the encoder as they are -- where uvgComm's graph puts a conversion filter in front of this one, the encoder's input stage converts on the GPU
+  bool packedInput() const { return config_ && config_->input_format != KVZ_INPUT_I420; }
+  int encodeRaw(const void *ptr, bool device, uint32_t *n, kvz_frame_info *info);      // the extension entry point for the encoder's format; ptr NULL: the picture in flight
+  void sendRaw(uint32_t n);
 };
 
 class OpenHEVCFilter : public Filter {

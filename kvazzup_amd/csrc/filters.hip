@@ -264,6 +264,10 @@ bool KvazaarFilter::init()                                 // kvazaarfilter.cpp:
   const int vaq = atoi(setting("video/vaq", "0").c_str());
   if (vaq > 0 && vaq <= 20) api_->config_parse(config_, "vaq", setting("video/vaq").c_str());
   customParameters();
+  {                                                        // extension: packed RGB32 / YUYV input, converted by the encoder (filters.h)
+    const std::string fmt = setting("uvgx/inputFormat", "");
+    if (!fmt.empty() && api_->config_parse(config_, "input-format", fmt.c_str()) != 1) { fprintf(stderr, "KvazaarFilter: invalid uvgx/inputFormat %s\n", fmt.c_str()); return false; }
+  }
   config_->hash = KVZ_HASH_NONE;
   enc_ = api_->encoder_open(config_);
   if (!enc_) { fprintf(stderr, "KvazaarFilter: failed to open the encoder\n"); return false; }
@@ -320,10 +324,26 @@ void KvazaarFilter::feedInput(std::unique_ptr<Data> input) // kvazaarfilter.cpp:
     return;
   }
   if (nextInputPic_ == -1 || nextInputPic_ >= (int)inputPics_.size()) return;
+  if (packedInput()) {
+    // extension: where kvazaarfilter.cpp:410-418 copies I420 planes into a kvz_picture, a packed picture goes to the encoder as it is (host or HBM)
+    const DataType want = config_->input_format == KVZ_INPUT_YUYV ? DT_YUYVVIDEO : DT_RGB32VIDEO;
+    const size_t px = (size_t)config_->width * config_->height, bytes = want == DT_YUYVVIDEO ? px * 2 : px * 4;
+    const void *ptr = input->device_data ? input->device_data : (input->data ? input->data.get() : input->host_view);
+    if (input->type != want || !ptr || (!input->device_data && input->data_size != bytes)) { fprintf(stderr, "KvazaarFilter: input is not the packed picture uvgx/inputFormat names\n"); return; }
+    const bool device = input->device_data != nullptr;
+    input->device_data = nullptr;
+    uint32_t n = 0;
+    ++pts_;
+    lastInputOnDevice_ = true;                             // (drain() collects through the extension entry point)
+    encodingFrames_.push_front({std::move(input), nullptr});
+    if (!encodeRaw(ptr, device, &n, &frame_info)) { encodingFrames_.pop_front(); return; }
+    encodingFrames_.front().data->host_view = nullptr;     // (a host picture has been copied: the caller's buffer is free)
+    if (n) sendRaw(n);
+    return;
+  }
+  if (input->type == DT_RGB32VIDEO || input->type == DT_YUYVVIDEO) { fprintf(stderr, "KvazaarFilter: a packed picture, but uvgx/inputFormat is not set\n"); return; }
   if (input->device_data) {
     // extension: the picture is already in HBM -- no kvz_picture copy, no chunk list (include/kvazzup_amd.h)
-    const size_t cap = (size_t)config_->width * config_->height * 3 + (1 << 20);
-    if (au_.size() < cap) au_.resize(cap);
     uint32_t n = 0;
     ++pts_;
     const void *dptr = input->device_data;
@@ -331,14 +351,8 @@ void KvazaarFilter::feedInput(std::unique_ptr<Data> input) // kvazaarfilter.cpp:
     lastInputOnDevice_ = true;
     encodingFrames_.push_front({std::move(input), nullptr});
     // with video/OWF >= 1 the access unit that comes back belongs to the previous picture (n == 0 on the first call)
-    if (!kvzx_encoder_encode_device(enc_, dptr, au_.data(), (uint32_t)au_.size(), &n, &frame_info)) { encodingFrames_.pop_front(); return; }
-    if (n == 0) return;
-    FrameInfo info = std::move(encodingFrames_.back());
-    encodingFrames_.pop_back();
-    std::unique_ptr<uint8_t[]> hevc_frame(new uint8_t[n]);
-    memcpy(hevc_frame.get(), au_.data(), n);
-    if (getStats()) { getStats()->encodingDelaySumMs += (uint64_t)(now_ms() - info.data->creationTimestamp); if (info.data->creationUs >= 0) getStats()->encodingDelayUs.add(now_us() - info.data->creationUs); getStats()->encodedPackets++; getStats()->encodedBytes += n; }
-    sendEncodedFrame(std::move(info.data), std::move(hevc_frame), n);
+    if (!encodeRaw(dptr, true, &n, &frame_info)) { encodingFrames_.pop_front(); return; }
+    if (n) sendRaw(n);
     return;
   }
   lastInputOnDevice_ = false;
@@ -375,6 +389,27 @@ void KvazaarFilter::feedInput(std::unique_ptr<Data> input) // kvazaarfilter.cpp:
   }
 }
 
+// the extension entry points (include/kvazzup_amd.h): no kvz_picture, no chunk list -- the access unit lands in au_
+int KvazaarFilter::encodeRaw(const void *ptr, bool device, uint32_t *n, kvz_frame_info *info)
+{
+  const size_t cap = (size_t)config_->width * config_->height * 3 + (1 << 20);
+  if (au_.size() < cap) au_.resize(cap);
+  if (!packedInput()) return kvzx_encoder_encode_device(enc_, ptr, au_.data(), (uint32_t)au_.size(), n, info);
+  if (device || !ptr) return kvzx_encoder_encode_packed_device(enc_, ptr, au_.data(), (uint32_t)au_.size(), n, info);
+  return kvzx_encoder_encode_packed_host(enc_, ptr, au_.data(), (uint32_t)au_.size(), n, info);
+}
+
+// the oldest picture in flight leaves with the n bytes in au_
+void KvazaarFilter::sendRaw(uint32_t n)
+{
+  FrameInfo info = std::move(encodingFrames_.back());
+  encodingFrames_.pop_back();
+  std::unique_ptr<uint8_t[]> hevc_frame(new uint8_t[n]);
+  memcpy(hevc_frame.get(), au_.data(), n);
+  if (getStats()) { getStats()->encodingDelaySumMs += (uint64_t)(now_ms() - info.data->creationTimestamp); if (info.data->creationUs >= 0) getStats()->encodingDelayUs.add(now_us() - info.data->creationUs); getStats()->encodedPackets++; getStats()->encodedBytes += n; }
+  sendEncodedFrame(std::move(info.data), std::move(hevc_frame), n);
+}
+
 // flush marker (harness extension): the pictures the encoder still holds (video/OWF) come out, like the reference's
 // encoder_encode(NULL) loop at kvazaarfilter.cpp:440-448 run to the end
 void KvazaarFilter::drain()
@@ -383,13 +418,8 @@ void KvazaarFilter::drain()
   while (!encodingFrames_.empty()) {
     if (lastInputOnDevice_) {
       uint32_t n = 0;
-      if (!kvzx_encoder_encode_device(enc_, nullptr, au_.data(), (uint32_t)au_.size(), &n, &frame_info) || n == 0) break;
-      FrameInfo info = std::move(encodingFrames_.back());
-      encodingFrames_.pop_back();
-      std::unique_ptr<uint8_t[]> hevc_frame(new uint8_t[n]);
-      memcpy(hevc_frame.get(), au_.data(), n);
-      if (getStats()) { getStats()->encodingDelaySumMs += (uint64_t)(now_ms() - info.data->creationTimestamp); if (info.data->creationUs >= 0) getStats()->encodingDelayUs.add(now_us() - info.data->creationUs); getStats()->encodedPackets++; getStats()->encodedBytes += n; }
-      sendEncodedFrame(std::move(info.data), std::move(hevc_frame), n);
+      if (!encodeRaw(nullptr, true, &n, &frame_info) || n == 0) break;
+      sendRaw(n);
     } else {
       kvz_picture *recon_pic = nullptr; kvz_data_chunk *data_out = nullptr; uint32_t len_out = 0;
       api_->encoder_encode(enc_, nullptr, &data_out, &len_out, &recon_pic, nullptr, &frame_info);
@@ -781,21 +811,25 @@ KVZ_PUBLIC void *uvgx_pipeline_create(const char *settings_text, int loopback_de
   return p;
 }
 
-static int push(UvgxPipeline *p, const uint8_t *host, const void *dev, int w, int h, int fn, int fd, int64_t pts, bool borrow = false)
+static int push(UvgxPipeline *p, const uint8_t *host, const void *dev, int w, int h, int fn, int fd, int64_t pts, bool borrow = false, DataType type = DT_YUV420VIDEO)
 {
   std::unique_ptr<Data> d(new Data);
-  d->source = DS_LOCAL; d->type = DT_YUV420VIDEO;
+  const size_t bytes = type == DT_RGB32VIDEO ? (size_t)w * h * 4 : (type == DT_YUYVVIDEO ? (size_t)w * h * 2 : (size_t)w * h * 3 / 2);
+  d->source = DS_LOCAL; d->type = type;
   d->creationTimestamp = now_ms(); d->creationUs = now_us(); d->presentationTimestamp = pts;
   d->vInfo.reset(new VideoInfo);
   d->vInfo->width = (int16_t)w; d->vInfo->height = (int16_t)h; d->vInfo->framerateNumerator = fn; d->vInfo->framerateDenominator = fd;
-  if (host && borrow) { d->data_size = (uint32_t)(w * h * 3 / 2); d->host_view = host; }
-  else if (host) { d->data_size = (uint32_t)(w * h * 3 / 2); d->data.reset(new uint8_t[d->data_size]); memcpy(d->data.get(), host, d->data_size); }
+  if (host && borrow) { d->data_size = (uint32_t)bytes; d->host_view = host; }
+  else if (host) { d->data_size = (uint32_t)bytes; d->data.reset(new uint8_t[d->data_size]); memcpy(d->data.get(), host, d->data_size); }
   d->device_data = dev;
   p->enc->putInput(std::move(d));
   return 1;
 }
 KVZ_PUBLIC int uvgx_pipeline_push_host(void *pp, const uint8_t *i420, int w, int h, int fn, int fd, int64_t pts) { return pp && i420 ? push((UvgxPipeline *)pp, i420, nullptr, w, h, fn, fd, pts) : 0; }
 KVZ_PUBLIC int uvgx_pipeline_push_device(void *pp, const void *d_i420, int w, int h, int fn, int fd, int64_t pts) { return pp && d_i420 ? push((UvgxPipeline *)pp, nullptr, d_i420, w, h, fn, fd, pts) : 0; }
+static bool packed_type(int type) { return type == DT_RGB32VIDEO || type == DT_YUYVVIDEO; }
+KVZ_PUBLIC int uvgx_pipeline_push_packed_host(void *pp, const uint8_t *packed, int type, int w, int h, int fn, int fd, int64_t pts) { return pp && packed && packed_type(type) ? push((UvgxPipeline *)pp, packed, nullptr, w, h, fn, fd, pts, false, (DataType)type) : 0; }
+KVZ_PUBLIC int uvgx_pipeline_push_packed_device(void *pp, const void *d_packed, int type, int w, int h, int fn, int fd, int64_t pts) { return pp && d_packed && packed_type(type) ? push((UvgxPipeline *)pp, nullptr, d_packed, w, h, fn, fd, pts, false, (DataType)type) : 0; }
 
 // measurement aid: an access unit straight into the receiving side (WireAdapter -> OpenHEVCFilter), paced like the sources above; size 0 = flush marker
 KVZ_PUBLIC int uvgx_pipeline_push_encoded(void *pp, const uint8_t *au, uint32_t size, int64_t pts, uint32_t max_backlog, int timeout_ms)

@@ -11,6 +11,7 @@
 #include "../../include/kvazzup_amd.h"
 #include <deque>
 #include <mutex>
+#include <unordered_map>
 #include <unordered_set>
 #include "encoder.h"
 
@@ -203,6 +204,11 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
   if (n == "weightp") { if (!parse_int(value, &iv) || (iv != 0 && iv != 1)) return 0; cfg->weightp = iv; return 1; }      // (extension: "uvgx weighted prediction v1", DESIGN.md section 9e -- explicit weighted prediction of luma; off by default and at every preset)
   if (n == "scenecut") { if (!parse_int(value, &iv) || iv < 0 || iv > 255) return 0; cfg->scenecut = iv; return 1; }      // (extension: "uvgx scene cut v1", DESIGN.md section 9g -- an input picture at least N pictures behind the last IDR picture that shares nothing with the picture before it becomes an IDR picture; off by default and at every preset)
   if (n == "intra-refresh") { if (!parse_int(value, &iv) || (iv != 0 && (iv < 2 || iv > 255))) return 0; cfg->intra_refresh = iv; return 1; }      // (extension: "uvgx intra refresh v1", DESIGN.md section 9f -- a band of intra units walks across the P pictures, N pictures a pass at most; off by default and at every preset)
+  if (n == "input-format") {                     // (extension, DESIGN.md section 9h: packed RGB32 / YUYV pictures converted in the encoder's input stage; i420 by default and at every preset)
+    static const char *formats[] = {"i420", "rgb32", "rgb32-sse41", "yuyv"};
+    for (int i = 0; i < 4; i++) if (!strcmp(value, formats[i])) { cfg->input_format = i; return 1; }
+    return 0;
+  }
   if (n == "lp-gop") { if (!parse_bool(value, &iv)) return 0; cfg->lp_gop = iv; return 1; }      // (extension: "uvgx low-delay GOP v1", DESIGN.md section 9d -- the switch that makes gop=lp-g<g>d<d>t1 take effect; off by default and at every preset)
   BOOL_OPT("tmvp", tmvp_enable)                  // (temporal motion vector prediction; off by default and at every preset, unlike Kvazaar)
   if (n == "null-input") {
@@ -254,9 +260,16 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
 // no second host copy into a staging buffer.  Without a device (header-only use, the CPU test suite) they are ordinary memory.
 // Freed page-locked pictures are kept (up to 16) for the next picture_alloc of the same size: encoder_encode hands out a fresh reconstruction
 // picture per access unit and uvgComm frees it at once (kvazaarfilter.cpp:476) -- page-locking memory costs milliseconds, a list look-up nothing.
-struct PinnedSet { std::mutex m; std::unordered_set<const void *> s; std::vector<std::pair<size_t, void *>> spare; };
+struct PinnedSet { std::mutex m; std::unordered_set<const void *> s; std::vector<std::pair<size_t, void *>> spare; std::unordered_map<const void *, size_t> room; };      // (room: bytes of each page-locked picture handed out)
 PinnedSet &pinned_set() { static PinnedSet *p = new PinnedSet(); return *p; }      // (never destroyed: pictures may be freed during exit)
 bool is_pinned(const void *buf) { PinnedSet &ps = pinned_set(); std::lock_guard<std::mutex> l(ps.m); return ps.s.count(buf) != 0; }
+// a packed input picture ("input-format") of `bytes` bytes that a caller keeps in a page-locked kvz_picture (one allocated large enough): it starts the picture and fits in it
+bool is_pinned_packed(const void *buf, size_t bytes)
+{
+  PinnedSet &ps = pinned_set(); std::lock_guard<std::mutex> l(ps.m);
+  auto it = ps.room.find(buf);
+  return it != ps.room.end() && it->second >= bytes;
+}
 
 kvz_picture *picture_alloc_csp(enum kvz_chroma_format csp, int32_t width, int32_t height)
 {
@@ -272,7 +285,7 @@ kvz_picture *picture_alloc_csp(enum kvz_chroma_format csp, int32_t width, int32_
   }
   if (pin || (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0 && hipHostMalloc(&pin, ny * 3 / 2 + 64, hipHostMallocPortable | hipHostMallocMapped) == hipSuccess && pin)) {
     p->fulldata_buf = (kvz_pixel *)pin;
-    PinnedSet &ps = pinned_set(); std::lock_guard<std::mutex> l(ps.m); ps.s.insert(pin);
+    PinnedSet &ps = pinned_set(); std::lock_guard<std::mutex> l(ps.m); ps.s.insert(pin); ps.room[pin] = ny * 3 / 2 + 64;
   } else {
     (void)hipGetLastError();
     p->fulldata_buf = (kvz_pixel *)malloc(ny * 3 / 2 + 64);
@@ -293,7 +306,7 @@ void picture_free(kvz_picture *pic)
   void *evicted = nullptr;
   {
     PinnedSet &ps = pinned_set(); std::lock_guard<std::mutex> l(ps.m);
-    pinned = ps.s.erase(pic->fulldata_buf) != 0;
+    pinned = ps.s.erase(pic->fulldata_buf) != 0; ps.room.erase(pic->fulldata_buf);
     if (pinned) {
       // newest last; the OLDEST spare goes when there are sixteen (round 5: a full list of 1080p spares left by earlier encoders kept every 4K picture of a
       // later one out -- each reconstruction picture was page-locked and released again, 3 ms apiece: 4K at uvgComm's defaults 421 -> 235 frames/s)
@@ -356,6 +369,7 @@ kvz_encoder *encoder_open(const kvz_config *cfg)
   ec.weightp = cfg->weightp != 0;
   ec.intra_refresh = cfg->intra_refresh;
   ec.scenecut = cfg->scenecut;
+  ec.input_format = cfg->input_format;
   ec.hash = cfg->hash == KVZ_HASH_MD5 ? 2 : (cfg->hash == KVZ_HASH_CHECKSUM ? 1 : 0);
   ec.vaq = cfg->vaq > 0 ? cfg->vaq : 0;
   ec.qp_in_cu = (cfg->set_qp_in_cu || ec.vaq > 0) ? 1 : 0;
@@ -441,6 +455,7 @@ int encoder_encode(kvz_encoder *e, kvz_picture *pic_in, kvz_data_chunk **data_ou
     // return only pictures that are already finished -- the loop then collects what is there and the pipeline stays full.
     if (!(e->cfg.null_input_poll ? e->impl->poll(&ep) : e->impl->flush(&ep))) { drop_failed(c0); return 0; }
   } else {
+    if (e->impl->config().input_format != KVZ_INPUT_I420) return 0;      // (a kvz_picture carries planes: packed pictures go in through kvzx_encoder_encode_packed_host / _device)
     if (pic_in->width != e->cfg.width || pic_in->height != e->cfg.height || !pic_in->y || !pic_in->u || !pic_in->v) return 0;
     // delta-QP map of this picture (kvazaarfilter.cpp:423-431); honoured when set-qp-in-cu enabled the signalling
     if (pic_in->roi.roi_array && pic_in->roi.width > 0 && pic_in->roi.height > 0) e->impl->set_roi(pic_in->roi.width, pic_in->roi.height, pic_in->roi.roi_array);
@@ -516,7 +531,7 @@ static int finish_raw(kvz_encoder *e, const EncodedPicture &ep, uint8_t *au_buf,
 }
 int kvzx_encoder_encode_device(kvz_encoder *e, const void *d_i420, uint8_t *au_buf, uint32_t au_cap, uint32_t *len_out, kvz_frame_info *info)
 {
-  if (!e) return 0;
+  if (!e || e->impl->config().input_format != KVZ_INPUT_I420) return 0;      // (a packed encoder: kvzx_encoder_encode_packed_device)
   EncodedPicture ep;
   if (!d_i420) { if (!e->impl->flush(&ep)) return 0; }          // NULL input: return the picture in flight (owf >= 1)
   else if (!e->impl->encode_device((const uint8_t *)d_i420, &ep)) return 0;
@@ -525,9 +540,27 @@ int kvzx_encoder_encode_device(kvz_encoder *e, const void *d_i420, uint8_t *au_b
 int kvzx_encoder_encode_host(kvz_encoder *e, const uint8_t *y, const uint8_t *u, const uint8_t *v, uint8_t *au_buf, uint32_t au_cap,
                              uint32_t *len_out, kvz_frame_info *info)
 {
-  if (!e || !y || !u || !v) return 0;
+  if (!e || !y || !u || !v || e->impl->config().input_format != KVZ_INPUT_I420) return 0;      // (a packed encoder: kvzx_encoder_encode_packed_host)
   EncodedPicture ep;
   if (!e->impl->encode_host(y, u, v, &ep)) return 0;
+  return finish_raw(e, ep, au_buf, au_cap, len_out, info);
+}
+// input-format other than i420: one packed picture (RGB32: w * h * 4 bytes, YUYV: w * h * 2) from host / device memory; NULL returns the picture in flight.
+// A host picture inside a page-locked kvz_picture from picture_alloc is recognised as encoder_encode recognises its planes: the copy engine reads it in place
+int kvzx_encoder_encode_packed_host(kvz_encoder *e, const void *packed, uint8_t *au_buf, uint32_t au_cap, uint32_t *len_out, kvz_frame_info *info)
+{
+  if (!e || e->impl->config().input_format == KVZ_INPUT_I420) return 0;
+  EncodedPicture ep;
+  if (!packed) { if (!e->impl->flush(&ep)) return 0; }
+  else if (!e->impl->encode_packed_host((const uint8_t *)packed, &ep, is_pinned_packed(packed, e->impl->input_bytes()))) return 0;
+  return finish_raw(e, ep, au_buf, au_cap, len_out, info);
+}
+int kvzx_encoder_encode_packed_device(kvz_encoder *e, const void *d_packed, uint8_t *au_buf, uint32_t au_cap, uint32_t *len_out, kvz_frame_info *info)
+{
+  if (!e || e->impl->config().input_format == KVZ_INPUT_I420) return 0;
+  EncodedPicture ep;
+  if (!d_packed) { if (!e->impl->flush(&ep)) return 0; }
+  else if (!e->impl->encode_packed_device((const uint8_t *)d_packed, &ep)) return 0;
   return finish_raw(e, ep, au_buf, au_cap, len_out, info);
 }
 int kvzx_encoder_coded_size(kvz_encoder *e, int *cw, int *ch)

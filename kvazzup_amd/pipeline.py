@@ -13,6 +13,8 @@ def _bind(lib):
     lib.uvgx_pipeline_create.argtypes = [C.c_char_p, C.c_int, C.c_int]
     lib.uvgx_pipeline_push_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
     lib.uvgx_pipeline_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
+    lib.uvgx_pipeline_push_packed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
+    lib.uvgx_pipeline_push_packed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]
     lib.uvgx_pipeline_wait.argtypes = [C.c_void_p, C.c_uint64, C.c_int]
     lib.uvgx_pipeline_push_device_paced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint32, C.c_int]
     lib.uvgx_pipeline_push_host_paced.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_uint32, C.c_int, C.c_int]
@@ -44,6 +46,9 @@ DEFAULT_SETTINGS = {            # uvgComm defaults with rate control off (defaul
 }
 
 
+PACKED_TYPES = {"rgb32": 1 << 10, "rgb32-sse41": 1 << 10, "yuyv": 1 << 4}      # uvgx::DataType (csrc/filters.h): DT_RGB32VIDEO, DT_YUYVVIDEO
+
+
 class Pipeline:
     def __init__(self, width, height, fps=(30, 1), settings=None, custom=(), loopback=True, keep_outputs=True):
         self.lib = N.load_library()
@@ -73,6 +78,20 @@ class Pipeline:
     def push_device(self, dptr, pts=None):
         self.lib.uvgx_pipeline_push_device(self.p, dptr, self.w, self.h, self.fps[0], self.fps[1], self.pushed if pts is None else pts)
         self.pushed += 1
+
+    def push_packed(self, packed, fmt, pts=None, device=False):
+        """a packed picture for a graph whose settings say uvgx/inputFormat: fmt "rgb32" (also for rgb32-sse41) or "yuyv"; packed is a contiguous uint8
+        array, or with device=True an address in device memory.  False: rejected"""
+        kind = PACKED_TYPES[fmt]
+        if device:
+            ok = self.lib.uvgx_pipeline_push_packed_device(self.p, packed, kind, self.w, self.h, self.fps[0], self.fps[1], self.pushed if pts is None else pts)
+        else:
+            packed = np.ascontiguousarray(packed, dtype=np.uint8)
+            if packed.size != self.w * self.h * (2 if fmt == "yuyv" else 4):
+                raise ValueError("a %s picture of %d bytes at %dx%d" % (fmt, packed.size, self.w, self.h))
+            ok = self.lib.uvgx_pipeline_push_packed_host(self.p, packed.ctypes.data, kind, self.w, self.h, self.fps[0], self.fps[1], self.pushed if pts is None else pts)
+        self.pushed += 1 if ok else 0
+        return bool(ok)
 
     def push_device_paced(self, dptr, max_backlog=6, timeout_ms=60000, pts=None):
         """push_device that sleeps (in C) until the encoder filter buffers fewer than max_backlog pictures"""

@@ -116,3 +116,35 @@ def scene_cut_frame(seed, w, h, t, cut):
     u = f[w * h:w * h + w * h // 4].reshape(h // 2, w // 2)[::-1, ::-1]
     v = f[w * h + w * h // 4:].reshape(h // 2, w // 2)[::-1, ::-1]
     return np.concatenate([y.reshape(-1), u.reshape(-1), v.reshape(-1)]).astype(np.uint8)
+
+
+def to_rgb32(i420, w, h):
+    """a deterministic packed RGB32 picture (w*h*4 bytes: B G R X, rows top to bottom) made of a packed I420 picture with fixed integer arithmetic --
+    test and benchmark input for "input-format" rgb32 / rgb32-sse41, not a statement of any converter"""
+    i420 = np.asarray(i420, dtype=np.uint8)
+    y = i420[:w * h].reshape(h, w).astype(np.int32)
+    u = np.repeat(np.repeat(i420[w * h:w * h + w * h // 4].reshape(h // 2, w // 2), 2, 0), 2, 1).astype(np.int32) - 128
+    v = np.repeat(np.repeat(i420[w * h + w * h // 4:].reshape(h // 2, w // 2), 2, 0), 2, 1).astype(np.int32) - 128
+    out = np.empty((h, w, 4), dtype=np.uint8)
+    out[..., 0] = np.clip(y + ((454 * u) >> 8), 0, 255)
+    out[..., 1] = np.clip(y - ((88 * u + 183 * v) >> 8), 0, 255)
+    out[..., 2] = np.clip(y + ((359 * v) >> 8), 0, 255)
+    out[..., 3] = 255
+    return out.reshape(-1)
+
+
+def to_yuyv(i420, w, h):
+    """a deterministic packed YUYV picture (w*h*2 bytes: Y0 U Y1 V) made of a packed I420 picture: luma as it is, a chroma sample on its two rows as
+    c and c ^ 1 -- so the two rows differ and the converter's mean has something to round; test and benchmark input for "input-format" yuyv"""
+    i420 = np.asarray(i420, dtype=np.uint8)
+    y = i420[:w * h].reshape(h, w)
+    u = np.repeat(i420[w * h:w * h + w * h // 4].reshape(h // 2, w // 2), 2, 0)
+    v = np.repeat(i420[w * h + w * h // 4:].reshape(h // 2, w // 2), 2, 0)
+    u[1::2] ^= 1
+    v[0::2] ^= 1
+    out = np.empty((h, w // 2, 4), dtype=np.uint8)
+    out[..., 0] = y[:, 0::2]
+    out[..., 1] = u
+    out[..., 2] = y[:, 1::2]
+    out[..., 3] = v
+    return out.reshape(-1)

@@ -1,4 +1,4 @@
-// kvazzup_amd/csrc/enc_kernels.h -- launch wrappers of the encoder kernels (enc_kernels.hip)
+// kvazzup_amd/csrc/enc_kernels.h -- launch wrappers of the encoder kernels (each defined in the file of its kernel: enc_kernels.hip, recon_kernels.hip, loop_kernels.hip, ...)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hevc_core.h"

@@ -1020,6 +1020,11 @@ KVZ_HD int mvd_bits(int q)
   return 2 + len + 1 + k + 1;
 }
 
+// the split and intra-in-P prices of the statement (oracle/hevc_enc.c), which k_me and k_intra_analyse both apply
+#define SPLIT_BITS 8          // rate charged for splitting a CU one level, in bins
+#define INTRA_P_GATE 24       // intra-in-P: a quarter is a candidate when its inter cost exceeds this many lambda_q4
+#define INTRA_P_BITS 16       // ... and goes intra when the intra cost plus this many bins is below the inter cost
+
 // ---------------------------------------------------------------------------------------------
 // "uvgx coarse-to-fine search v1" (kvazaar.h me-coarse; statement of record: tests/me_coarse_model.py).  The arithmetic the
 // kernels k_luma_quarter, k_me_coarse and k_me<.., true> share with the host build tests/hostcheck/statements.cpp.

@@ -35,6 +35,10 @@ struct orc_encoder {
   int rc_qp;                           /* Q: the constant QP, or rate control v1's current QP (its state: lp-gop's layer offset is never written back into it) */
   int lp_gop, gop_g, gop_d;            /* "lp-gop" with "lp-gop-g" / "lp-gop-d": "uvgx low-delay GOP v1"  */
   int me_coarse;                       /* "me-coarse" 0 / 64 / 128 / 256: "uvgx coarse-to-fine search v1"  */
+  int weightp;                         /* "weightp" 0 / 1: "uvgx weighted prediction v1"  */
+  int wp[ORC_MAX_LP_REFS][3];          /* weightp: the record of the picture being coded, (flag, w, o) per reference; (0, 64, 0) where nothing is weighted */
+  int intra_refresh;                   /* "intra-refresh" 0 / 2 .. 255: "uvgx intra refresh v1"  */
+  int ir_j, ir_s, ir_e;                /* intra-refresh: position in the cycle and the band [ir_s, ir_e) of the P picture being coded (ir_e 0: no band -- an IDR picture, or the option off) */
   int layer;                           /* lp-gop: QP layer of the picture being coded (0: an IDR picture, or the option off) */
   int dist[ORC_MAX_LP_REFS];           /* reference k of the picture being coded lies dist[k] pictures back (k + 1 without lp-gop) */
   int64_t rc_debt; uint32_t rc_bytes[8];  /* rate control: bits spent above target so far; sizes of the last access units */
@@ -50,7 +54,7 @@ struct orc_encoder {
   int nref;                            /* max(lp_refs, 1): references a P picture has at most */
   int nact;                            /* m: active references of the picture being coded (P: min(nref, pictures since the IDR picture)) */
   pixel *src[3];
-  pixel *prev_src[ORC_MAX_REF_DIST];   /* cfg.me_source: the luma planes of the previous input pictures, [j] = picture t-1-j (padded to the coded size), NULL until needed */
+  pixel *prev_src[ORC_MAX_REF_DIST];   /* cfg.me_source, weightp: the luma planes of the previous input pictures, [j] = picture t-1-j (padded to the coded size), NULL until needed */
   pixel *qcur, *qprev[ORC_MAX_REF_DIST];   /* me-coarse: quarter picture of the input picture being coded and of the input pictures t-1-j */
   int16_t *centres;                    /* me-coarse: [reference][32x32 block, raster][x, y] the coarse stage's centres, full samples */
   int16_t *coef[3];
@@ -330,6 +334,8 @@ static void intra_analyse_size(orc_encoder *e, int n, uint8_t *best_mode, uint32
         const uint64_t tr = n == 16 ? 0x7f9f80001ull : 0x7f8000001ull, bl = n == 16 ? 0x3f3fdull : 0x3fdull;      /* luma 16x16 / 8x8: modes reading p[x][-1], x >= n / p[-1][y], y >= n */
         if ((y0 & 63) == 0 && ((x0 + n) & 63) == 0 && orc_available(&e->av, x0, y0, x0 + n, y0 - 1)) excl |= tr;
         if ((x0 & 63) == 0 && orc_available(&e->av, x0, y0, x0 - 1, y0 + n)) excl |= bl;
+        /* intra-refresh: a unit on the band's last unit column reads no above-right samples -- beyond the band the reference picture is not clean yet */
+        if (e->ir_e && x0 + n == e->ir_e && e->ir_e < e->cw && orc_available(&e->av, x0, y0, x0 + n, y0 - 1)) excl |= tr;
       }
       for (int m = 0; m < 35; m++) {
         if ((excl >> m) & 1) continue;
@@ -418,6 +424,79 @@ static void encode_intra_picture(orc_encoder *e)
 }
 
 /* ------------------------------------------------------------------ inter pictures */
+/* ---- "uvgx weighted prediction v1" (option weightp; the same statement in python: tests/wp_model.py).  Luma only, one (w, o) per
+ * reference and picture, luma_log2_weight_denom 6.  All integer; the divisions and shifts round towards minus infinity. */
+static int64_t floor_div64(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
+static uint64_t isqrt64(uint64_t v)
+{
+  uint64_t r = 0;
+  for (uint64_t bit = (uint64_t)1 << 62; bit; bit >>= 2) { if (v >= r + bit) { v -= r + bit; r = (r >> 1) + bit; } else r >>= 1; }
+  return r;
+}
+/* 1. the moments of a padded luma plane over its visible samples: mean in 1/256, variance in 1/65536 (never below zero) */
+static void wp_moments(const orc_encoder *e, const pixel *plane, int64_t *m, int64_t *v)
+{
+  const int64_t n = (int64_t)e->cfg.width * e->cfg.height;
+  uint64_t s1 = 0, s2 = 0;
+  for (int y = 0; y < e->cfg.height; y++) for (int x = 0; x < e->cfg.width; x++) { const uint64_t a = plane[(size_t)y * e->cw + x]; s1 += a; s2 += a * a; }
+  *m = (int64_t)((256 * s1 + (uint64_t)(n / 2)) / (uint64_t)n);
+  const int64_t q = (int64_t)((256 * s2 + (uint64_t)(n / 2)) / (uint64_t)n), d = 256 * q - *m * *m;
+  *v = d > 0 ? d : 0;
+}
+/* 4. a full sample of a weighted reference, and the same on the 14-bit intermediate of a fractional vector (8.5.3.3.4.3, log2WD = 6 + 6) */
+static inline int wp_full(int s, int w, int o) { return orc_clip3(0, 255, ((s * w + 32) >> 6) + o); }
+static void wp_pred14(const int16_t *src, int ss, pixel *dst, int ds, int n, int w, int o)
+{
+  for (int y = 0; y < n; y++) for (int x = 0; x < n; x++)
+    dst[y * ds + x] = (pixel)orc_clip3(0, 255, (int)floor_div64((int64_t)src[y * ss + x] * w + 2048, 4096) + o);
+}
+/* 2. and 3.: the record of P picture t -- per active reference k the candidate from the moments of INPUT pictures t and t - dist[k] (whatever me-source says), kept
+ * when it is one (|w - 64| >= 2 or o != 0) and the check over the samples at (4i, 4j) of the two visible pictures says 16 wt < 15 plain */
+static void wp_decide(orc_encoder *e)
+{
+  int64_t mc, vc;
+  wp_moments(e, e->src[0], &mc, &vc);
+  for (int k = 0; k < e->nact; k++) {
+    const pixel *ref = e->prev_src[e->dist[k] - 1];
+    int64_t mr, vr;
+    wp_moments(e, ref, &mr, &vr);
+    int w = 64;
+    if (vc != 0 && vr != 0) w = orc_clip3(16, 127, (int)((isqrt64((uint64_t)(16384 * vc) / (uint64_t)vr) + 1) >> 1));
+    const int o = orc_clip3(-128, 127, (int)floor_div64(64 * mc - (int64_t)w * mr + 8192, 16384));
+    if (orc_abs(w - 64) < 2 && o == 0) continue;
+    uint64_t plain = 0, wt = 0;
+    for (int y = 0; y < e->cfg.height; y += 4) for (int x = 0; x < e->cfg.width; x += 4) {
+      const int c = e->src[0][(size_t)y * e->cw + x], r = ref[(size_t)y * e->cw + x];
+      plain += (uint64_t)orc_abs(c - r); wt += (uint64_t)orc_abs(c - wp_full(r, w, o));
+    }
+    if (16 * wt < 15 * plain) { e->wp[k][0] = 1; e->wp[k][1] = w; e->wp[k][2] = o; }
+  }
+}
+
+/* ---- "uvgx intra refresh v1" (option intra-refresh = N; the same statement in python: tests/ir_model.py).  B = cw / 32 block columns, a
+ * picture advances m = ceil(B / N) of them, a cycle takes n = ceil(B / m) pictures; the P picture poc pictures behind its IDR picture stands at j = (poc - 1) % n and
+ * its band is the luma columns [32 m j, min(cw, 32 m j + 32 m + 16)). */
+static int ir_cycle(const orc_encoder *e) { const int B = e->cw / 32, m = (B + e->intra_refresh - 1) / e->intra_refresh; return (B + m - 1) / m; }
+static void ir_plan(orc_encoder *e)
+{
+  e->ir_j = -1; e->ir_s = e->ir_e = 0;
+  if (!e->intra_refresh || e->is_intra) return;
+  const int B = e->cw / 32, m = (B + e->intra_refresh - 1) / e->intra_refresh;
+  e->ir_j = (e->poc - 1) % ir_cycle(e);
+  e->ir_s = 32 * m * e->ir_j;
+  e->ir_e = ORC_MIN(e->cw, e->ir_s + 32 * m + 16);
+}
+/* bit k: the 16x16 quarter k (raster of 2 x 2) of the 32x32 block at x0 lies inside the band and is coded as intra units */
+static int ir_forced(const orc_encoder *e, int x0)
+{
+  int q = 0;
+  for (int k = 0; k < 4; k++) { const int x = x0 + 16 * (k & 1); if (e->ir_e && e->ir_s <= x && x + 16 <= e->ir_e) q |= 1 << k; }
+  return q;
+}
+/* a clean block: a 32x32 block left of the band at j >= 1; it and its quarters keep every vector to 4 (x0 + 32) + mvx <= 4 ir_s (mvx in quarter samples) */
+static int ir_clean(const orc_encoder *e, int x0) { return e->ir_e && e->ir_j >= 1 && x0 + 32 <= e->ir_s; }
+static int ir_mvx_max(const orc_encoder *e, int x0) { return 4 * (e->ir_s - x0 - 32); }
+
 /* The picture the integer search looks at: the reference picture's reconstruction, or -- "uvgx search pipelining v1", option me-source -- the previous
  * INPUT picture: then the search of picture t + 1 depends on nothing picture t's reconstruction loop produces and the two run side by side (what hardware
  * encoders do).  Only the search moves: early termination, the 32x32 / 16x16 costs and the intra-in-P gate are priced on that picture; fractional
@@ -433,6 +512,8 @@ static void build_refpad(orc_encoder *e, int k)
     const pixel *srow = plane + (size_t)orc_clip3(0, e->ch - 1, y) * pstride;
     pixel *drow = e->refpad[k] + (size_t)(y + ME_PAD) * st;
     for (int x = -ME_PAD; x < e->cw + ME_PAD; x++) drow[x + ME_PAD] = srow[orc_clip3(0, e->cw - 1, x)];
+    /* weightp: a weighted reference is searched through the whole-vector form of its prediction (wp_full) */
+    if (e->wp[k][0]) for (int x = 0; x < e->cw + 2 * ME_PAD; x++) drow[x] = (pixel)wp_full(drow[x], e->wp[k][1], e->wp[k][2]);
   }
 }
 
@@ -479,14 +560,19 @@ static int subme_allowed(const orc_encoder *e, int x0, int y0, int n, int mvx, i
     if (e->cfg.mv_frame == 1) { mx = (mvx & 3) ? 4 : 0; my = (mvy & 3) ? 4 : 0; }     /* plain frame constraint: integer vectors may touch the edge */
     if (x0 + ix - mx < 0 || x0 + ix + n + mx > e->cw || y0 + iy - my < 0 || y0 + iy + n + my > e->ch) return 0;
   }
+  if (ir_clean(e, x0 & ~31) && mvx > ir_mvx_max(e, x0 & ~31)) return 0;      /* intra-refresh: a clean block's units keep the block's bound */
   return 1;
 }
 static uint32_t subme_cost(orc_encoder *e, int x0, int y0, int n, int mvx, int mvy)
 {
   int16_t tmp[32 * 32]; pixel pred[32 * 32];
-  const orc_pic *r = e->refs[e->cu_ref[b8i(e, x0, y0)]];          /* the CU's own reference: the refinement never changes it */
+  const int rk = e->cu_ref[b8i(e, x0, y0)];
+  const orc_pic *r = e->refs[rk];                                  /* the CU's own reference: the refinement never changes it */
   orc_mc_luma(r->plane[0], r->stride[0], r->w, r->h, x0, y0, n, n, mvx, mvy, tmp, 32);
-  orc_pred_uni(tmp, 32, pred, 32, n, n);
+  if (e->wp[rk][0]) {                                              /* weightp: priced on the weighted prediction, Clip1(((pred14 w + 2048) >> 12) + o) */
+    for (int y = 0; y < n; y++) for (int x = 0; x < n; x++)
+      pred[y * 32 + x] = (pixel)orc_clip3(0, 255, (int)floor_div64((int64_t)tmp[y * 32 + x] * e->wp[rk][1] + 2048, 4096) + e->wp[rk][2]);
+  } else orc_pred_uni(tmp, 32, pred, 32, n, n);
   uint32_t rate = ((uint32_t)orc_lambda_q4[e->qp] * (uint32_t)(orc_mvd_bits(mvx) + orc_mvd_bits(mvy))) >> 4;
   return satd_block(e->src[0] + y0 * e->cw + x0, e->cw, pred, 32, n) + rate;
 }
@@ -579,6 +665,48 @@ static void coarse_stage(orc_encoder *e)
   free(bits);
 }
 
+/* "uvgx intra-in-P v1" for the 32x32 block at (x0, y0).  ic[k]: inter cost of 16x16 quarter k = what the search found for it (split) or a quarter of the 32x32
+ * block's cost; quarters above the gate are priced as intra blocks by the intra picture's analysis (source neighbours: nothing depends on other
+ * blocks' decisions) and go intra when that is cheaper by INTRA_P_BITS bins (lam: the picture's lambda, also under rate control v2).  A block with an intra quarter is coded as four 16x16
+ * units (the inter ones keep their vectors; an intra quarter is one 16x16 or four 8x8 intra units).
+ * intra-refresh: a quarter of `forced` passes the gate and beats every intra price (its cost counts as 0xffffffff); with intra-in-p 0 the band's quarters are the
+ * only ones priced, as 16x16 units (level 1). */
+static void intra_p_block(orc_encoder *e, int x0, int y0, const uint32_t ic_in[4], int forced)
+{
+  const uint32_t lam = orc_lambda_q4[e->qp], pen = (lam * SPLIT_BITS) >> 4;
+  const int level = e->cfg.intra_in_p ? e->cfg.intra_in_p : 1;
+  uint32_t ic[4]; int any = 0, cand[4];
+  for (int k = 0; k < 4; k++) {
+    ic[k] = ((forced >> k) & 1) ? 0xffffffffu : ic_in[k];
+    cand[k] = ((forced >> k) & 1) || (e->cfg.intra_in_p && ic[k] > INTRA_P_GATE * lam); any |= cand[k];
+  }
+  if (!any) return;
+  if (!e->intra_p_ready) { if (level >= 2) intra_analyse_size(e, 8, e->im8, e->ic8); intra_analyse_size(e, 16, e->im16, e->ic16); e->intra_p_ready = 1; }
+  int w8 = e->cw / 8, w16 = e->cw / 16, chosen = 0, sp16[4];
+  for (int k = 0; k < 4; k++) {
+    int x16 = x0 / 16 + (k & 1), y16 = y0 / 16 + (k >> 1);
+    uint32_t c8 = pen;
+    if (level >= 2) for (int j = 0; j < 4; j++) c8 += e->ic8[(y16 * 2 + (j >> 1)) * w8 + x16 * 2 + (j & 1)];
+    uint32_t c16 = e->ic16[y16 * w16 + x16];
+    sp16[k] = level >= 2 && c8 < c16;          /* level 1: one 16x16 intra unit per quarter, no 8x8 units (the fast presets: a CTU of 8x8 intra units is twice the wavefront steps in the encoder's and the decoder's chain) */
+    uint32_t cintra = (sp16[k] ? c8 : c16) + ((lam * INTRA_P_BITS) >> 4);
+    cand[k] = cand[k] && cintra < ic[k];
+    chosen |= cand[k];
+  }
+  if (!chosen) return;
+  for (int k = 0; k < 4; k++) {
+    int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16, x16 = bx / 16, y16 = by / 16;
+    if (!cand[k]) { set_cu(e, e->cu_log2, bx, by, 16, 4); continue; }
+    set_cu(e, e->cu_intra, bx, by, 16, 1);
+    for (int y = by; y < by + 16; y += 8) for (int x = bx; x < bx + 16; x += 8) { e->cu_mv[b8i(e, x, y) * 2] = 0; e->cu_mv[b8i(e, x, y) * 2 + 1] = 0; }
+    if (!sp16[k]) { set_cu(e, e->cu_log2, bx, by, 16, 4); set_cu(e, e->cu_intra_mode, bx, by, 16, e->im16[y16 * w16 + x16]); }
+    else for (int j = 0; j < 4; j++) {
+      int x8 = x16 * 2 + (j & 1), y8 = y16 * 2 + (j >> 1);
+      e->cu_log2[y8 * w8 + x8] = 3; e->cu_intra_mode[y8 * w8 + x8] = e->im8[y8 * w8 + x8];
+    }
+  }
+}
+
 /* Full search for one 32x32 block over the m active references (reference k: refpad[k]), each with candidates in raster order (dy outer,
  * dx inner), cost = SAD + (lambda * (bits(mv as mvd from zero) + ref_bins(k, m))) >> 4, key = cost << 16 | k << 13 | candidate index:
  * lower cost, then lower reference, then lower candidate (with one reference the order of cost << 13 | candidate).
@@ -589,7 +717,18 @@ static void me_block32(orc_encoder *e, int x0, int y0)
   int R = e->cfg.search_range, st = e->refpad_stride, m = e->nact;
   uint32_t lam = orc_lambda_q4[e->qp];
   uint64_t best16[4] = { UINT64_MAX, UINT64_MAX, UINT64_MAX, UINT64_MAX }, best32 = UINT64_MAX;
-  if (e->cfg.me_early) {                              /* early termination: static content is not searched (against reference 0, which it then takes) */
+  /* intra-refresh: the quarters inside the band go intra whatever the search finds.  A block all of whose quarters are forced is not searched; one whose left
+   * quarters alone are forced is searched as ever, never left early, and its right quarters stay free */
+  const int forced = ir_forced(e, x0);
+  if (forced == 15) {
+    static const uint32_t all[4] = { 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu };
+    set_cu(e, e->cu_log2, x0, y0, 32, 5); set_cu(e, e->cu_intra, x0, y0, 32, 0); set_cu(e, e->cu_ref, x0, y0, 32, 0);
+    for (int y = y0; y < y0 + 32; y += 8) for (int x = x0; x < x0 + 32; x += 8) { e->cu_mv[b8i(e, x, y) * 2] = 0; e->cu_mv[b8i(e, x, y) * 2 + 1] = 0; }
+    intra_p_block(e, x0, y0, all, forced);
+    return;
+  }
+  const int ir_dx = ir_clean(e, x0) ? ir_mvx_max(e, x0) >> 2 : INT32_MAX;      /* a clean block's largest horizontal displacement, full samples */
+  if (e->cfg.me_early && !forced) {                   /* early termination: static content is not searched (against reference 0, which it then takes) */
     uint32_t s0 = 0;
     for (int k = 0; k < 4; k++) {
       int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16;
@@ -621,7 +760,8 @@ static void me_block32(orc_encoder *e, int x0, int y0)
       int myt = (dy & 1) ? 4 : 0, mxt = (dx & 1) ? 4 : 0;
       if ((ty0 > 0 && y0 + dy - myt < ty0) || (ty1 < e->ch && y0 + dy + 32 + myt > ty1)) continue;
       if ((tx0 > 0 && x0 + dx - mxt < tx0) || (tx1 < e->cw && x0 + dx + 32 + mxt > tx1)) continue;
-      if (e->cfg.mv_frame) {                                   /* mv-constraint frame: the displaced block stays inside the picture */
+      if (dx > ir_dx) continue;                                /* intra-refresh: a clean block stays out of what the reference picture has not cleaned */
+      if (e->cfg.mv_frame) {                                  /* mv-constraint frame: the displaced block stays inside the picture */
         int my = (e->cfg.mv_frame == 2 && (dy & 1)) ? 4 : 0, mx = (e->cfg.mv_frame == 2 && (dx & 1)) ? 4 : 0;
         if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > e->cw || y0 + dy - my < 0 || y0 + dy + 32 + my > e->ch) continue;
       }
@@ -665,43 +805,10 @@ static void me_block32(orc_encoder *e, int x0, int y0)
     }
   }
   set_cu(e, e->cu_intra, x0, y0, 32, 0);
-  if (e->cfg.intra_in_p) {
-    /* "uvgx intra-in-P v1".  Inter cost of a 16x16 quarter = what the search found for it (split) or a quarter of the 32x32 block's cost;
-     * quarters above the gate are priced as intra blocks by the intra picture's analysis (source neighbours: nothing depends on other
-     * blocks' decisions) and go intra when that is cheaper by INTRA_P_BITS bins (lam: the picture's lambda, also under rate control v2).  A block with an intra quarter is coded as four 16x16
-     * units (the inter ones keep their vectors; an intra quarter is one 16x16 or four 8x8 intra units). */
-    uint32_t ic[4]; int any = 0, cand[4];
-    for (int k = 0; k < 4; k++) {
-      ic[k] = csplit < c32 ? (uint32_t)(best16[k] >> 17) : (c32 + 2) >> 2;      /* (the chosen costs: reference bins included) */
-      cand[k] = ic[k] > INTRA_P_GATE * lam; any |= cand[k];
-    }
-    if (any) {
-      if (!e->intra_p_ready) { if (e->cfg.intra_in_p >= 2) intra_analyse_size(e, 8, e->im8, e->ic8); intra_analyse_size(e, 16, e->im16, e->ic16); e->intra_p_ready = 1; }
-      int w8 = e->cw / 8, w16 = e->cw / 16, chosen = 0, sp16[4];
-      for (int k = 0; k < 4; k++) {
-        int x16 = x0 / 16 + (k & 1), y16 = y0 / 16 + (k >> 1);
-        uint32_t c8 = pen;
-        if (e->cfg.intra_in_p >= 2) for (int j = 0; j < 4; j++) c8 += e->ic8[(y16 * 2 + (j >> 1)) * w8 + x16 * 2 + (j & 1)];
-        uint32_t c16 = e->ic16[y16 * w16 + x16];
-        sp16[k] = e->cfg.intra_in_p >= 2 && c8 < c16;          /* level 1: one 16x16 intra unit per quarter, no 8x8 units (the fast presets: a CTU of 8x8 intra units is twice the wavefront steps in the encoder's and the decoder's chain) */
-        uint32_t cintra = (sp16[k] ? c8 : c16) + ((lam * INTRA_P_BITS) >> 4);
-        cand[k] = cand[k] && cintra < ic[k];
-        chosen |= cand[k];
-      }
-      if (chosen) {
-        for (int k = 0; k < 4; k++) {
-          int bx = x0 + (k & 1) * 16, by = y0 + (k >> 1) * 16, x16 = bx / 16, y16 = by / 16;
-          if (!cand[k]) { set_cu(e, e->cu_log2, bx, by, 16, 4); continue; }
-          set_cu(e, e->cu_intra, bx, by, 16, 1);
-          for (int y = by; y < by + 16; y += 8) for (int x = bx; x < bx + 16; x += 8) { e->cu_mv[b8i(e, x, y) * 2] = 0; e->cu_mv[b8i(e, x, y) * 2 + 1] = 0; }
-          if (!sp16[k]) { set_cu(e, e->cu_log2, bx, by, 16, 4); set_cu(e, e->cu_intra_mode, bx, by, 16, e->im16[y16 * w16 + x16]); }
-          else for (int j = 0; j < 4; j++) {
-            int x8 = x16 * 2 + (j & 1), y8 = y16 * 2 + (j >> 1);
-            e->cu_log2[y8 * w8 + x8] = 3; e->cu_intra_mode[y8 * w8 + x8] = e->im8[y8 * w8 + x8];
-          }
-        }
-      }
-    }
+  if (e->cfg.intra_in_p || e->ir_e) {
+    uint32_t ic[4];
+    for (int k = 0; k < 4; k++) ic[k] = csplit < c32 ? (uint32_t)(best16[k] >> 17) : (c32 + 2) >> 2;      /* (the chosen costs: reference bins included) */
+    intra_p_block(e, x0, y0, ic, forced);
   }
   if (e->cfg.subme > 0) {                                        /* fractional-sample refinement of the (inter) CUs just decided */
     if (e->cu_log2[b8i(e, x0, y0)] == 5) subme_refine(e, x0, y0, 32, ty0, ty1);
@@ -737,7 +844,8 @@ static void inter_recon_cu(orc_encoder *e, int x0, int y0, int log2)
     m->mv[0] = mv[0]; m->mv[1] = mv[1]; m->ref_idx = (int8_t)rk;
   }
   orc_mc_luma(r->plane[0], r->stride[0], r->w, r->h, x0, y0, n, n, mv[0], mv[1], tmp, 32);
-  orc_pred_uni(tmp, 32, p->plane[0] + y0 * p->stride[0] + x0, p->stride[0], n, n);
+  if (e->wp[rk][0]) wp_pred14(tmp, 32, p->plane[0] + y0 * p->stride[0] + x0, p->stride[0], n, e->wp[rk][1], e->wp[rk][2]);      /* weightp: luma alone; chroma is never weighted */
+  else orc_pred_uni(tmp, 32, p->plane[0] + y0 * p->stride[0] + x0, p->stride[0], n, n);
   int cbf = code_block(e, 0, x0, y0, n, ctu_target_qp(e, x0, y0), 0, 0);
   fill_b4(p, p->tu_nz, x0, y0, n, cbf);
   for (int c = 1; c <= 2; c++) {
@@ -1202,6 +1310,21 @@ static void write_picture(orc_encoder *e, int write_ps)
   sh.slice_deblocking_disabled = !e->cfg.deblock;
   sh.loop_filter_across_slices = 1;
   sh.sao_luma = sh.sao_chroma = e->cfg.sao ? 1 : 0;
+  if (e->weightp && !e->is_intra) {                               /* weightp: pred_weight_table() in every independent P slice segment header -- denominators 6 / +0, no chroma weights */
+    sh.luma_log2_weight_denom = 6; sh.delta_chroma_log2_weight_denom = 0;
+    for (int k = 0; k < e->nact; k++) if (e->wp[k][0]) { sh.luma_weight_flag[0][k] = 1; sh.delta_luma_weight[0][k] = (int16_t)(e->wp[k][1] - 64); sh.luma_offset[0][k] = (int16_t)e->wp[k][2]; }
+  }
+  if (e->ir_e && e->ir_j == 0) {
+    /* intra-refresh: recovery point SEI (D.2.8: prefix SEI NAL unit, payload type 6) in front of a cycle's first slice segment -- recovery_poc_cnt = n - 1,
+     * exact_match_flag 1, broken_link_flag 0; a payload that does not end on a byte is filled with a one and zeros */
+    orc_bitw body, sei; orc_bw_init(&body); orc_bw_init(&sei);
+    orc_bw_se(&body, ir_cycle(e) - 1); orc_bw_put(&body, 1, 1); orc_bw_put(&body, 0, 1);
+    if (body.nbits) orc_bw_trailing(&body);
+    orc_bw_put(&sei, 6, 8); orc_bw_put(&sei, (uint32_t)body.len, 8); orc_bw_bytes(&sei, body.buf, body.len);
+    orc_bw_trailing(&sei);
+    orc_write_nal(&e->au, 39, 0, sei.buf, sei.len, 1);
+    orc_bw_free(&body); orc_bw_free(&sei);
+  }
   /* slice segments, one NAL unit each: the whole picture; or a dependent segment per CTU row (its header: address and entry points
    * only); or an independent slice per tile (the same header with its own address) */
   for (int s0 = 0; s0 < nsub; ) {
@@ -1347,6 +1470,9 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
   for (int k = 0; k < ORC_MAX_LP_REFS; k++) e->refs[k] = e->hist[e->dist[k] <= e->nkeep ? e->dist[k] - 1 : 0];
   rc_picture_start(e);
   load_input(e, y, u, v);
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) { e->wp[k][0] = 0; e->wp[k][1] = 64; e->wp[k][2] = 0; }
+  if (e->weightp && !e->is_intra) wp_decide(e);
+  ir_plan(e);
   roi_targets(e);
   orc_pic_reset_side(e->cur);
   e->cur->poc = e->poc;
@@ -1370,7 +1496,12 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
     for (int i = 0; i < 3; i++) { memcpy(e->sao_in[i], e->cur->plane[i], (size_t)e->cur->stride[i] * (i ? e->ch / 2 : e->ch)); deb[i] = e->sao_in[i]; org[i] = e->src[i]; }
     if (e->cur->stride[0] != e->cw || e->cur->stride[1] != e->cw / 2) abort();
     for (int cy = 0; cy < hc; cy++) for (int cx = 0; cx < wc; cx++)
-      orc_sao_decide_ctu(deb, org, e->cur->stride, e->cw, e->ch, cx, cy, orc_lambda_q4[e->qp], &e->sao[cy * wc + cx]);
+    {
+      orc_sao_params *sp = &e->sao[cy * wc + cx];
+      orc_sao_decide_ctu(deb, org, e->cur->stride, e->cw, e->ch, cx, cy, orc_lambda_q4[e->qp], sp);
+      /* intra-refresh: luma SAO is off in the CTBs that hold column ir_e - 5 -- an edge class would carry what deblocking the band's end lets in one column further */
+      if (e->ir_e && e->ir_e < e->cw && cx == ((e->ir_e - 5) >> 6)) { sp->type[0] = 0; sp->eo_class[0] = 0; sp->band_pos[0] = 0; memset(sp->offset[0], 0, sizeof(sp->offset[0])); }
+    }
     orc_sao_ctx sc; memset(&sc, 0, sizeof(sc));
     sc.w = e->cw; sc.h = e->ch; sc.ctb_log2 = 6; sc.pic_w_ctbs = wc; sc.params = e->sao; sc.across_slices = sc.across_tiles = 1;
     for (int i = 0; i < 3; i++) { sc.src[i] = e->sao_in[i]; sc.dst[i] = e->cur->plane[i]; sc.stride[i] = e->cur->stride[i]; }
@@ -1403,7 +1534,7 @@ size_t orc_enc_encode(orc_encoder *e, const pixel *y, const pixel *u, const pixe
     for (int k = e->nkeep - 1; k > 0; k--) e->hist[k] = e->hist[k - 1];
     e->hist[0] = e->cur; e->cur = t;
   }
-  if (e->cfg.me_source) {                               /* the next picture's search looks at this input picture (and its references at the ones before) */
+  if (e->cfg.me_source || e->weightp) {                 /* the next picture's search looks at this input picture (and its references at the ones before); weightp weighs against it */
     pixel *t = e->prev_src[e->nkeep - 1];
     if (!t) t = (pixel *)malloc((size_t)e->cw * e->ch);
     for (int k = e->nkeep - 1; k > 0; k--) e->prev_src[k] = e->prev_src[k - 1];
@@ -1445,6 +1576,20 @@ int orc_enc_set_option(orc_encoder *e, const char *name, int value)
     for (int sz = 0; sz < 4; sz++) for (int mi = 0; mi < (sz == 3 ? 2 : 6); mi++) orc_scaling_factor(&e->sps.scaling, sz, mi, e->sfac[sz][mi]);
     return 1;
   }
+  /* weightp (before the first picture; not with lossless): the PPS says weighted_pred_flag */
+  if (!strcmp(name, "weightp")) {
+    if (value < 0 || value > 1 || e->frame_idx > 0 || (value && e->cfg.lossless)) return 0;
+    e->weightp = value; e->pps.weighted_pred = value; return 1;
+  }
+  /* intra-refresh N = 0, 2 .. 255 (before the first picture); what it is not stated with is refused, here and where the other option is set */
+  if (!strcmp(name, "intra-refresh")) {
+    if (value < 0 || value == 1 || value > 255 || e->frame_idx > 0) return 0;
+    if (value && (e->nref > 1 || e->lp_gop || e->cfg.tmvp || e->me_coarse || e->cfg.tile_rows != 1 || e->cfg.tile_cols != 1 || e->cfg.lossless || !e->cfg.intra_chain)) return 0;
+    e->intra_refresh = value; return 1;
+  }
+  if (e->intra_refresh && value && (!strcmp(name, "lossless") || !strcmp(name, "tmvp") || !strcmp(name, "me-coarse") || !strcmp(name, "lp-gop") || (!strcmp(name, "lp-refs") && value > 1))) return 0;
+  if (e->intra_refresh && !value && !strcmp(name, "intra-chain")) return 0;
+  if (e->weightp && value && !strcmp(name, "lossless")) return 0;
   if (!strcmp(name, "intra-chain")) { e->cfg.intra_chain = value != 0; return 1; }
   if (!strcmp(name, "lossless")) {                     /* (set it before the first picture: the PPS says transquant_bypass_enabled_flag) */
     if (!value) return e->cfg.lossless == 0;
@@ -1504,6 +1649,16 @@ void orc_enc_debug_gop(orc_encoder *e, int out[8])
   for (int k = 0; k < ORC_MAX_LP_REFS; k++) out[4 + k] = !e->is_intra && k < e->nact ? e->dist[k] : 0;
 }
 const int16_t *orc_enc_debug_centres(orc_encoder *e) { return e->me_coarse && !e->is_intra ? e->centres : NULL; }
+int orc_enc_debug_wp(orc_encoder *e, int out[12])
+{
+  for (int k = 0; k < ORC_MAX_LP_REFS; k++) for (int i = 0; i < 3; i++) out[3 * k + i] = e->wp[k][i];
+  return e->weightp;
+}
+int orc_enc_debug_ir(orc_encoder *e, int out[4])
+{
+  out[0] = e->ir_j; out[1] = e->ir_s; out[2] = e->ir_e; out[3] = e->intra_refresh ? ir_cycle(e) : 0;
+  return e->intra_refresh != 0;
+}
 
 void orc_enc_get_recon(orc_encoder *e, pixel *y, pixel *u, pixel *v)
 {

@@ -103,6 +103,10 @@ void orc_enc_default_config(orc_enc_config *c);
 /* options added after the packed open calls ran out of bits: by name, before the first picture.  "hash" 0/1/2, "rdoq" 0/1, "signhide" 0/1, "intra-in-p" 0/1,
  * "lp-refs" 0..4, "tmvp" 0/1, "me-coarse" 0/64/128/256, "lp-gop-g" >= 0 and "lp-gop-d" 1..6 (the numbers of gop=lp-g<g>d<d>t1; g 0 = no string) followed by
  * "lp-gop" 0/1 (without a g the switch has nothing to say).  "lp-refs", "tmvp", "me-coarse" and the three of lp-gop are refused after the first picture.
+ * "weightp" 0/1 ("uvgx weighted prediction v1", DESIGN.md section 9e: explicit weighted prediction of luma, one (w, o) per reference and picture from the input
+ * pictures' moments; refused with "lossless") and "intra-refresh" 0 / 2..255 ("uvgx intra refresh v1", section 9f: a band of intra units walks across the P
+ * pictures; refused with "lp-refs" >= 2, "lp-gop", "tmvp", "me-coarse", tiles other than 1x1, "lossless" and "intra-chain" 0, whichever of the two is set
+ * second), both before the first picture.
  * Returns 1 when known (0 also for a value out of range). */
 int orc_enc_set_option(orc_encoder *e, const char *name, int value);
 orc_encoder *orc_enc_open(const orc_enc_config *c);
@@ -124,6 +128,11 @@ const int16_t *orc_enc_debug_cu_mvd(orc_encoder *e);
  * raster][x, y] in full samples (references >= m hold zeros); NULL for an intra picture or without the option */
 void orc_enc_debug_gop(orc_encoder *e, int out[8]);
 const int16_t *orc_enc_debug_centres(orc_encoder *e);
+/* weightp: the record of the picture just coded, [4 references][flag, w, o] ((0, 64, 0) where nothing is weighted: intra pictures, references beyond m).
+ * intra-refresh: out = { position j in the cycle (-1: an IDR picture), the band's first column, its end column, the cycle's length n }.  Both return whether the
+ * option is on */
+int orc_enc_debug_wp(orc_encoder *e, int out[12]);
+int orc_enc_debug_ir(orc_encoder *e, int out[4]);
 /* copy cropped reconstruction (width x height I420, packed) */
 void orc_enc_get_recon(orc_encoder *e, pixel *y, pixel *u, pixel *v);
 

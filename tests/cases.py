@@ -113,3 +113,27 @@ LP_GOP_ROWS = LP_REFS_CLOSED + LP_GOP_EXTRA
 ORACLE_GUARD = [dict(kw=dict()), dict(kw=dict(subme=4)), dict(kw=dict(), opts=(("intra-in-p", 2),), kind=2),
          dict(kw=dict(tile_rows=2, tile_cols=2, slices=2, sao=1)), dict(kw=dict(bitrate=300000, rc_bands=4), frames=8),
          dict(kw=dict(subme=2), opts=(("me-source", 1), ("intra-in-p", 1)))]
+
+
+# ---- weightp (tests/test_gpu_weightp.py: closed loops on the benchmark clip with wp_model.change(kind), 320x192 unless the row says otherwise, me-range 12, 8 pictures)
+# and intra-refresh (tests/test_gpu_intra_refresh.py: size = (w, h, N), 2 n + 4 pictures); tests/test_gpu_weightp_ir_oracle.py holds every row to the checker
+WEIGHTP_CLOSED = [
+    dict(kind="offset"), dict(kind="gain", opts=(("subme", 2),)), dict(kind="flash", opts=(("subme", 4), ("sao", "full"))),
+    dict(kind="gain", opts=(("lp-refs", 3), ("tmvp", 1), ("subme", 2))), dict(kind="offset", opts=(("lp-refs", 2), ("intra-in-p", 1), ("subme", 2), ("me-source", 1))),
+    dict(kind="offset", opts=(("tiles", "2x2"), ("wpp", 0), ("lp-refs", 3))), dict(kind="flash", opts=(("tiles", "2x2"), ("slices", "tiles"), ("subme", 2))),
+    dict(kind="gain", owf=3, opts=(("lp-refs", 4), ("subme", 2), ("sao", "full"), ("me-source", 1))), dict(kind="offset", owf=3, opts=(("period", 4),)),
+    dict(kind="offset", bitrate=400000, opts=(("rc-algorithm", "lambda"), ("subme", 2))), dict(kind="gain", bitrate=400000, opts=(("rc-algorithm", "lambda"), ("rdoq", 1))),
+    dict(kind="flash", w=384, h=256, opts=(("me-coarse", 64), ("lp-refs", 2))), dict(kind="gain", opts=(("rdoq", 1), ("signhide", 1), ("subme", 4))),
+    dict(kind="offset", opts=(("rdoq", 1),)), dict(kind="gain", opts=(("lp-refs", 3), ("gop", "lp-g4d3t1"), ("lp-gop", 1), ("tmvp", 1), ("subme", 2))),
+    dict(kind="offset", w=200, h=120, opts=(("subme", 2), ("slices", "wpp"))), dict(kind="none", opts=(("subme", 2), ("lp-refs", 2))),
+]
+
+INTRA_REFRESH_CLOSED = [
+    dict(), dict(opts=(("subme", 2),)), dict(opts=(("subme", 4), ("sao", "full"))), dict(opts=(("rdoq", 1), ("signhide", 1), ("subme", 2))),
+    dict(opts=(("weightp", 1), ("subme", 2)), change="offset"), dict(opts=(("me-source", 1), ("subme", 2), ("intra-in-p", 1))),
+    dict(bitrate=400000, opts=(("rc-algorithm", "lambda"), ("subme", 2))), dict(owf=3, opts=(("subme", 2), ("sao", "full"), ("me-source", 1))),
+    dict(opts=(("slices", "wpp"), ("subme", 2))), dict(opts=(("intra-in-p", 0), ("subme", 4))), dict(opts=(("intra-in-p", 1), ("sao", "full"))),
+    dict(opts=(("intra-in-p", 2), ("subme", 2), ("rdoq", 1))), dict(opts=(("period", 4), ("subme", 2), ("intra-in-p", 1))), dict(owf=3, opts=(("period", 4),)),
+    dict(size=(320, 192, 10), opts=(("preset", "veryfast"),)), dict(size=(200, 120, 8), opts=(("subme", 2), ("sao", "full"))), dict(size=(640, 384, 4), opts=(("subme", 2),)),
+    dict(opts=(("wpp", 0), ("subme", 2))), dict(opts=(("deblock", 0), ("intra-in-p", 1))),
+]

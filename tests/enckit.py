@@ -159,6 +159,10 @@ def checker(w, h, c):
         oe.set_option("me-coarse", c["coarse"])
     if c.get("gop"):
         oe.set_lp_gop(*c["gop"])
+    if c.get("weightp"):                              # "weightp"  and "intra-refresh" N (section 9f): tests/test_gpu_weightp_ir_oracle.py
+        oe.set_option("weightp", c["weightp"])
+    if c.get("intra_refresh"):
+        oe.set_option("intra-refresh", c["intra_refresh"])
     for name, key in (("intra-in-p", "intra_in_p"), ("rdoq", "rdoq"), ("signhide", "signhide"), ("me-source", "me_source"), ("hash", "hash"),
                       ("scaling-list", "scaling_list"), ("lossless", "lossless")):     # (lossless last: it switches tools off)
         if c.get(key):
@@ -180,6 +184,7 @@ def hip(w, h, c):
     o += ((("vaq", c["vaq"]),) if c.get("vaq") else ()) + ((("bitrate", br),) if br else ()) + ((("rc-algorithm", "lambda"),) if c.get("rc_lambda") else ())
     o += ((("scaling-list", "default"),) if c.get("scaling_list") else ()) + ((("lossless", 1),) if c.get("lossless") else ())
     o += ((("me-coarse", c["coarse"]),) if c.get("coarse") else ()) + ((("gop", "lp-g%dd%dt1" % tuple(c["gop"])), ("lp-gop", 1)) if c.get("gop") else ())
+    o += ((("weightp", c["weightp"]),) if c.get("weightp") else ()) + ((("intra-refresh", c["intra_refresh"]),) if c.get("intra_refresh") else ())
     fields = dict(({"target_bitrate": br} if br else {}), **({"hash": c["hash"]} if c.get("hash") else {}))
     return encoder(w, h, o, fields=fields or None)
 
@@ -195,6 +200,11 @@ def first_stage(do, dg):
         if len(bad):
             i = tuple(bad[0])
             return "first stage that differs: me_coarse (centres) at %d blocks, first (reference, block row, column) %s: checker %s, HIP %s" % (len(bad), list(i), a[i], b[i])
+    for k in ("wp", "ir"):                              # weightp's record (flag, w, o per reference), then intra-refresh's (j, s, e, n): in front of every decision
+        if k in do and k in dg:
+            a, b = np.asarray(do[k]).tolist(), np.asarray(dg[k]).tolist()
+            if a != b:
+                return "first stage that differs: %s (the record): checker %s, HIP %s" % (k, a, b)
     if "lp_gop" in do and "lp_gop" in dg:
         for k in ("layer", "qp", "dists"):              # the layer and the QP, then the reference distances
             if do["lp_gop"][k] != dg["lp_gop"][k]:
@@ -219,6 +229,15 @@ def first_stage(do, dg):
 
 
 def case_frames(c):
+    w, h = c["w"], c["h"]
+    fr = _case_clip(c)
+    if c.get("change"):                                # a brightness change on the luma of whatever clip the case names (tests/wp_model.py change())
+        import wp_model
+        fr = wp_model.change(fr, w, h, c["change"])
+    return fr
+
+
+def _case_clip(c):
     w, h, nf = c["w"], c["h"], c.get("frames", 5)
     if c.get("pattern"):
         return [ec.PATTERNS[c["pattern"]](w, h, t, ec.SEED) for t in range(nf)]
@@ -292,6 +311,48 @@ def hip_debug(ge):
     cw, ch = ge.coded_size()
     d["cu_mvd"] = ge.debug("cu_mvd", np.int16, (ch // 8, cw // 8, 2))
     return d
+
+
+_NAMES = {"subme": "subme", "rdoq": "rdoq", "signhide": "signhide", "intra-in-p": "intra_in_p", "lp-refs": "n", "tmvp": "tmvp", "wpp": "wpp", "period": "period",
+          "vaq": "vaq", "lossless": "lossless", "gpu-entropy": "gpu_entropy", "deblock": "deblock", "me-source": "me_source", "qp": "qp", "owf": "owf",
+          "me-coarse": "coarse", "weightp": "weightp", "intra-refresh": "intra_refresh"}
+
+
+def case_from_opts(opts, fields=None):
+    """a row's kvazaar options in the vocabulary of checker() / hip(); an option without a mapping is an error, not a dropped row"""
+    c = {}
+    for k, v in opts:
+        if k in _NAMES:
+            c[_NAMES[k]] = int(v)
+        elif k == "sao":
+            c["sao"] = int(v == "full")
+        elif k == "tiles":
+            c["tiles"] = tuple(int(x) for x in v.split("x"))
+        elif k == "slices":
+            c["slices"] = {"none": 0, "wpp": 1, "tiles": 2}[v]
+        elif k == "rc-algorithm":
+            c["rc_lambda"] = int(v == "lambda")
+        elif k == "scaling-list":
+            c["scaling_list"] = int(v == "default")
+        elif k == "me-early-termination":
+            c["me_early"] = int(v == "on")
+        elif k == "preset":
+            c["preset"] = v                           # (hip() states every tool a preset touches after it, so the checker's options are the case's)
+        elif k == "gop":
+            g, d = v[len("lp-g"):-len("t1")].split("d")
+            assert v == "lp-g%sd%st1" % (g, d), v
+            c["gop"] = (int(g), int(d))
+        elif k == "lp-gop":
+            assert int(v) == 1, v                     # (the switch: the numbers come with "gop")
+        elif k == "set-qp-in-cu":
+            pass                                      # (checker() / hip() switch it on with the ROI map)
+        else:
+            raise KeyError("no checker mapping for option %s" % k)
+    for k, v in (fields or {}).items():
+        if k != "hash":
+            raise KeyError(k)
+        c["hash"] = v
+    return c
 
 
 ROI = (4, 3, (np.arange(12, dtype=np.int8) % 7 - 3).astype(np.int8))

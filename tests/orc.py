@@ -130,6 +130,13 @@ class OracleEncoder:
         g = (C.c_int * 8)()
         lib().orc_enc_debug_gop(self.p, g)
         out["lp_gop"] = {"active": g[0], "layer": g[1], "qp": g[2], "dists": [int(v) for v in g[4:4 + g[3]]]}
+        # weightp / intra-refresh: keys of their own only with the option on, as the HIP encoder's debug_all()
+        rec = (C.c_int * 12)()
+        lib().orc_enc_debug_wp.argtypes = lib().orc_enc_debug_ir.argtypes = [C.c_void_p, C.c_void_p]
+        if lib().orc_enc_debug_wp(self.p, rec):
+            out["wp"] = np.array(rec[:12], dtype=np.int32).reshape(4, 3)
+        if lib().orc_enc_debug_ir(self.p, rec):
+            out["ir"] = [int(v) for v in rec[:4]]
         cen = lib().orc_enc_debug_centres(self.p)
         if cen:
             out["me_coarse"] = _arr(cen, (4, ch // 32, cw // 32, 2), np.int16)

@@ -17,41 +17,7 @@ import pytest
 import lp_gop_model as M
 import lp_refs_model
 from cases import LP_GOP_ROWS as GOP_ROWS, ME_COARSE_CLOSED as COARSE_ROWS
-from enckit import ROI as _ROI, case_id as _id, run_case, sweep_case
-
-_NAMES = {"subme": "subme", "rdoq": "rdoq", "signhide": "signhide", "intra-in-p": "intra_in_p", "lp-refs": "n", "tmvp": "tmvp", "wpp": "wpp", "period": "period",
-          "vaq": "vaq", "lossless": "lossless", "gpu-entropy": "gpu_entropy", "deblock": "deblock", "me-source": "me_source", "qp": "qp", "owf": "owf",
-          "me-coarse": "coarse"}
-
-
-def case_from_opts(opts, fields=None):
-    """a row's kvazaar options in the vocabulary of checker() / hip() (tests/enckit.py); an option without a mapping is an error, not a dropped row"""
-    c = {}
-    for k, v in opts:
-        if k in _NAMES:
-            c[_NAMES[k]] = int(v)
-        elif k == "sao":
-            c["sao"] = int(v == "full")
-        elif k == "tiles":
-            c["tiles"] = tuple(int(x) for x in v.split("x"))
-        elif k == "slices":
-            c["slices"] = {"none": 0, "wpp": 1, "tiles": 2}[v]
-        elif k == "rc-algorithm":
-            c["rc_lambda"] = int(v == "lambda")
-        elif k == "scaling-list":
-            c["scaling_list"] = int(v == "default")
-        elif k == "me-early-termination":
-            c["me_early"] = int(v == "on")
-        elif k == "set-qp-in-cu":
-            pass                                      # (checker() / hip() switch it on with the ROI map)
-        else:
-            raise KeyError("no checker mapping for option %s" % k)
-    for k, v in (fields or {}).items():
-        if k != "hash":
-            raise KeyError(k)
-        c["hash"] = v
-    return c
-
+from enckit import ROI as _ROI, case_from_opts, case_id as _id, run_case, sweep_case
 
 def coverage(c):
     """what the checker's pictures of case c must contain for the case to exercise its subject; returns run_case's check"""

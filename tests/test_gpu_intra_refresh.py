@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 
 import enckit
+from cases import INTRA_REFRESH_CLOSED as CLOSED
 import ir_model as M
+from ir_model import check_structure as _check_structure
 import orc
 import pyhevc
 
@@ -46,52 +48,6 @@ def _stream(w, h, N, opts=(), npics=0):
     out = enckit.encode_all(ge, _clip(w, h, npics or _npics(w, N)))
     ge.close()
     return out
-
-
-def _avail(x, y, xn, yn, cw):
-    """z-scan availability of the sample (xn, yn) for the block at (x, y): one slice, no tiles, 64x64 coding tree blocks, 8x8 granularity"""
-    if xn < 0 or yn < 0 or xn >= cw:
-        return False
-    if (xn >> 6, yn >> 6) != (x >> 6, y >> 6):
-        return (yn >> 6, xn >> 6) < (y >> 6, x >> 6)
-    z = lambda a, b: sum((((a >> 3) >> k) & 1) << (2 * k) | (((b >> 3) >> k) & 1) << (2 * k + 1) for k in range(3))
-    return z(xn & 63, yn & 63) < z(x & 63, y & 63)
-
-
-def _check_structure(d, poc, cw, N, free):
-    """one picture's debug_all() against the statement; returns how many cells it looked at per rule"""
-    seen = {"band": 0, "clean": 0, "last": 0, "excluded_matter": 0}
-    assert d["ir"] == M.record(cw, N, poc), (poc, d["ir"])
-    if poc == 0:
-        return seen
-    j, s, e, _ = d["ir"]
-    intra, log2, mode, mv = d["cu_intra"], d["cu_log2"], d["cu_intra_mode"], d["cu_mv"]
-    rows = intra.shape[0]
-    band = intra[:, s // 8:e // 8]
-    assert band.all(), "picture %d: %d cells of the band [%d, %d) are not intra" % (poc, int((band == 0).sum()), s, e)
-    seen["band"] += band.size
-    assert set(np.unique(log2[:, s // 8:e // 8])) <= ({4} if free < 2 else {3, 4})
-    if not free:
-        outside = np.concatenate([intra[:, :s // 8], intra[:, e // 8:]], axis=1)
-        assert not outside.any(), "picture %d: intra-in-p=0 and %d intra cells outside the band" % (poc, int(outside.sum()))
-    if j >= 1:
-        for x0 in range(0, s, 32):
-            assert M.clean_block(x0, s, j)
-            blk_mv, blk_in = mv[:, x0 // 8:x0 // 8 + 4, 0].astype(np.int64), intra[:, x0 // 8:x0 // 8 + 4]
-            bad = (blk_in == 0) & (4 * (x0 + 32) + blk_mv > 4 * s)
-            assert not bad.any(), "picture %d: a clean block at x0 = %d has a vector beyond the bound (mvx %d, limit %d)" % (poc, x0, int(blk_mv[bad].max()), M.mvx_max(x0, s))
-            seen["clean"] += int((blk_in == 0).sum())
-    if e < cw:
-        cx = e // 8 - 1
-        for cy in range(rows):
-            l2 = int(log2[cy, cx]); nb = 1 << l2
-            xb, yb = e - nb, (cy * 8) & ~(nb - 1)
-            assert M.last_column(xb, nb, e, cw)
-            seen["last"] += 1
-            if _avail(xb, yb, xb + nb, yb - 1, cw):
-                seen["excluded_matter"] += 1
-                assert not (M.ABOVE_RIGHT[l2] >> int(mode[cy, cx])) & 1, "picture %d: the unit at (%d, %d) size %d takes mode %d, which reads above-right samples" % (poc, xb, yb, nb, int(mode[cy, cx]))
-    return seen
 
 
 # ---- 1. structure
@@ -146,16 +102,7 @@ def test_the_bound_bites_on_a_pan(gpu):
     assert counts[0] >= 1 and counts[1] == 0, counts
 
 
-# ---- 2. closed loop over the tool set
-CLOSED = [
-    dict(), dict(opts=(("subme", 2),)), dict(opts=(("subme", 4), ("sao", "full"))), dict(opts=(("rdoq", 1), ("signhide", 1), ("subme", 2))),
-    dict(opts=(("weightp", 1), ("subme", 2)), change="offset"), dict(opts=(("me-source", 1), ("subme", 2), ("intra-in-p", 1))),
-    dict(bitrate=400000, opts=(("rc-algorithm", "lambda"), ("subme", 2))), dict(owf=3, opts=(("subme", 2), ("sao", "full"), ("me-source", 1))),
-    dict(opts=(("slices", "wpp"), ("subme", 2))), dict(opts=(("intra-in-p", 0), ("subme", 4))), dict(opts=(("intra-in-p", 1), ("sao", "full"))),
-    dict(opts=(("intra-in-p", 2), ("subme", 2), ("rdoq", 1))), dict(opts=(("period", 4), ("subme", 2), ("intra-in-p", 1))), dict(owf=3, opts=(("period", 4),)),
-    dict(size=(320, 192, 10), opts=(("preset", "veryfast"),)), dict(size=(200, 120, 8), opts=(("subme", 2), ("sao", "full"))), dict(size=(640, 384, 4), opts=(("subme", 2),)),
-    dict(opts=(("wpp", 0), ("subme", 2))), dict(opts=(("deblock", 0), ("intra-in-p", 1))),
-]
+# ---- 2. closed loop over the tool set (the rows: tests/cases.py INTRA_REFRESH_CLOSED; tests/test_gpu_weightp_ir_oracle.py holds every one of them to the checker)
 
 
 @pytest.mark.gpu

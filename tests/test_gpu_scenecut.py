@@ -91,7 +91,10 @@ def test_record_matches_the_model_1080p(gpu):
 
 # ---- 2. the stream: the option-off encoder's up to the cut, the checker's from the cut on
 PINNED = {"plain": dict(), "src-subme2": dict(opts=(("me-source", 1), ("subme", 2)), okw=dict(subme=2), oopts=(("me-source", 1),)),
-          "lp-refs3": dict(opts=(("lp-refs", 3),), n=3), "tmvp": dict(opts=(("tmvp", 1),), tmvp=1)}
+          "lp-refs3": dict(opts=(("lp-refs", 3),), n=3), "tmvp": dict(opts=(("tmvp", 1),), tmvp=1),
+          # weightp: the table in every P slice header behind the cut; intra-refresh: the cycle restarts behind the cut's IDR picture (positions 0 .. 3 of 5)
+          "weightp": dict(opts=(("weightp", 1), ("subme", 2)), okw=dict(subme=2), oopts=(("weightp", 1),)),
+          "intra-refresh": dict(opts=(("intra-refresh", 5), ("subme", 2)), okw=dict(subme=2), oopts=(("intra-refresh", 5),))}
 
 
 @pytest.mark.gpu

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import enckit
+from cases import WEIGHTP_CLOSED as CLOSED
 import lp_gop_model
 import lp_refs_model
 import orc
@@ -75,17 +76,7 @@ def test_record_and_search_match_the_models(gpu, size, kind, setup):
         assert weighted0 == 0
 
 
-# ---- 2. closed loop over the tool set
-CLOSED = [
-    dict(kind="offset"), dict(kind="gain", opts=(("subme", 2),)), dict(kind="flash", opts=(("subme", 4), ("sao", "full"))),
-    dict(kind="gain", opts=(("lp-refs", 3), ("tmvp", 1), ("subme", 2))), dict(kind="offset", opts=(("lp-refs", 2), ("intra-in-p", 1), ("subme", 2), ("me-source", 1))),
-    dict(kind="offset", opts=(("tiles", "2x2"), ("wpp", 0), ("lp-refs", 3))), dict(kind="flash", opts=(("tiles", "2x2"), ("slices", "tiles"), ("subme", 2))),
-    dict(kind="gain", owf=3, opts=(("lp-refs", 4), ("subme", 2), ("sao", "full"), ("me-source", 1))), dict(kind="offset", owf=3, opts=(("period", 4),)),
-    dict(kind="offset", bitrate=400000, opts=(("rc-algorithm", "lambda"), ("subme", 2))), dict(kind="gain", bitrate=400000, opts=(("rc-algorithm", "lambda"), ("rdoq", 1))),
-    dict(kind="flash", w=384, h=256, opts=(("me-coarse", 64), ("lp-refs", 2))), dict(kind="gain", opts=(("rdoq", 1), ("signhide", 1), ("subme", 4))),
-    dict(kind="offset", opts=(("rdoq", 1),)), dict(kind="gain", opts=(("lp-refs", 3), ("gop", "lp-g4d3t1"), ("lp-gop", 1), ("tmvp", 1), ("subme", 2))),
-    dict(kind="offset", w=200, h=120, opts=(("subme", 2), ("slices", "wpp"))), dict(kind="none", opts=(("subme", 2), ("lp-refs", 2))),
-]
+# ---- 2. closed loop over the tool set (the rows: tests/cases.py WEIGHTP_CLOSED; tests/test_gpu_weightp_ir_oracle.py holds every one of them to the checker)
 
 
 @pytest.mark.gpu

@@ -59,6 +59,14 @@ KVZ_PUBLIC int kvzx_encoder_pending(kvz_encoder *enc);         /* pictures hande
  * or the environment variable KVAZZUP_AMD_DEVICE) */
 KVZ_PUBLIC int kvzx_decoder_set_device(OpenHevc_Handle h, int device);
 KVZ_PUBLIC int kvzx_decoder_last_error(OpenHevc_Handle h);
+/* What stands in for a reference picture that never arrived (a lost access unit): mode 2 (default) a copy of the nearest reference picture the decoder holds,
+ * mode 3 that picture moved block by block along its own motion, continued to the lost picture's place in time (whole samples) -- the
+ * better guess under camera motion and scrolling, an opt-in because it can lose about 1 dB where moving objects are as small as a block.  Either way grey
+ * when there is no picture to take, and the stand-in is never handed out.  Call before the first picture.  Returns 1, or 0 for any other mode, for a call
+ * after the first picture and for mode 3 on a band decoder (kvzx_decoder_set_band, which in turn is refused in mode 3).
+ * kvzx_decoder_debug_copy: "standin" = the buffer of the stand-in filled last (mode 3; Y | Cb | Cr, pitch = the coded width rounded up to 64),
+ * "standin_mv" = its displacements, int16 [ceil(h / 16)][ceil(w / 16)][4]: luma dx, dy, chroma dx, dy. */
+KVZ_PUBLIC int kvzx_decoder_set_concealment(OpenHevc_Handle h, int mode);
 /* Test / measurement hook, not a decoding mode: before libOpenHevcStartDecoder.  The decoder then runs its HOST half only (NAL units, parameter sets, slice
  * headers, the CABAC slice-data parser with `parse_threads` row threads), touches no device and never outputs a picture (libOpenHevcDecode returns 0 or an
  * error).  kvzx_decoder_parse_probe_stats: out5 = pictures parsed, transform blocks, level words, FNV-1a digest of everything the parser produced, 0;

@@ -237,12 +237,18 @@ class Decoder:
 
     OH_THREAD_FRAME, OH_THREAD_SLICE = 1, 2
 
-    def __init__(self, threads=1, download=True, device=None, frame_threads=False, temporal_layer=7, no_cropping=False):
+    def __init__(self, threads=1, download=True, device=None, frame_threads=False, temporal_layer=7, no_cropping=False, concealment=2):
+        """concealment: what stands in for a lost reference picture -- 2 a copy of the nearest one, 3 that picture moved along its own motion (kvazzup_amd.h
+        kvzx_decoder_set_concealment)"""
         self.lib = N.load_library()
         self.threads, self.frame_threads = threads, bool(frame_threads) and threads > 1
         self.h = self.lib.libOpenHevcInit(threads, self.OH_THREAD_FRAME if frame_threads else self.OH_THREAD_SLICE)
         if device is not None:
             self.lib.kvzx_decoder_set_device(self.h, device)
+        if concealment != 2 and not self.set_concealment(concealment):
+            self.lib.libOpenHevcClose(self.h)
+            self.h = None
+            raise ValueError("concealment mode %r (2 or 3)" % (concealment,))
         if self.lib.libOpenHevcStartDecoder(self.h) == -1:
             self.lib.libOpenHevcClose(self.h)
             self.h = None
@@ -315,6 +321,23 @@ class Decoder:
                 if misses > ring:
                     break
         return out
+
+    def set_concealment(self, mode):
+        """False: refused (a mode other than 2 and 3, or the first picture has been decoded)"""
+        return bool(self.lib.kvzx_decoder_set_concealment(self.h, int(mode)))
+
+    def standin(self, w, h):
+        """concealment 3: the stand-in filled last, (Y, Cb, Cr) at the coded size w x h, and its displacements [ceil(h / 16)][ceil(w / 16)][4]
+        (luma dx, dy, chroma dx, dy); None before the first one"""
+        pw, ph = (w + 63) & ~63, (h + 63) & ~63
+        buf = np.empty(pw * ph * 3 // 2, np.uint8)
+        mv = np.empty(((h + 15) // 16, (w + 15) // 16, 4), np.int16)
+        if not self.lib.kvzx_decoder_debug_copy(self.h, b"standin", buf.ctypes.data, buf.nbytes) or not self.lib.kvzx_decoder_debug_copy(self.h, b"standin_mv", mv.ctypes.data, mv.nbytes):
+            return None
+        y = buf[:pw * ph].reshape(ph, pw)[:h, :w]
+        u = buf[pw * ph:pw * ph * 5 // 4].reshape(ph // 2, pw // 2)[:h // 2, :w // 2]
+        v = buf[pw * ph * 5 // 4:].reshape(ph // 2, pw // 2)[:h // 2, :w // 2]
+        return (y.copy(), u.copy(), v.copy()), mv
 
     def output_device(self):
         planes = (C.c_void_p * 3)()

@@ -14,4 +14,7 @@ void launch_dec_inter_n(const DecFrame *const *h, const DecFrame *const *d, int 
 void launch_dec_intra_n(const DecFrame *const *h, const DecFrame *const *d, int n, hipStream_t st);     // residuals + chain (two launches)
 void launch_dec_deblock_n(const DecFrame *const *h, const DecFrame *const *d, int n, hipStream_t st);
 void launch_dec_sao_n(const DecFrame *const *h, const DecFrame *const *d, int n, hipStream_t st);
+// ---- conceal_kernels.hip: concealment v3's stand-in (decoder.h) -- the three planes of src (coded size w x h, luma pitch `pitch`) moved into dst by the table's
+// whole-sample displacements, one row (luma dx, dy, chroma dx, dy) per 16x16 luma block, d_tab in device memory
+void launch_dec_standin(uint8_t *const dst[3], uint8_t *const src[3], const int16_t *d_tab, int w, int h, int pitch, hipStream_t st);
 }  // namespace kvzx

@@ -1100,9 +1100,27 @@ int Decoder::parse_substream(PicJob &job, int sub, const uint8_t *data, size_t l
       if (hipSetDevice(device_) == hipSuccess && hipMemcpyAsync(job.early_dst + off, job.h_in + off, rowb, hipMemcpyHostToDevice, stream_up_) == hipSuccess)
         job.early_rows.fetch_add(1, std::memory_order_acq_rel);
     }
+    const int per16 = 1 << (ctbl_ - 4);                     // 16x16 blocks a CTB is wide
+    if (ConcealMotion *cm = job.cown.get()) {
+      // concealment v3 (decoder.h): this CTB row's motion, should the picture become the source of a stand-in -- list 0's if that list predicts the block, else list 1's
+      for (int y16 = cy * per16; y16 < (cy + 1) * per16 && y16 < cm->h16; y16++)
+        for (int x16 = cx0 * per16; x16 < cx1 * per16 && x16 < cm->w16; x16++) {
+          const size_t i4 = (size_t)(y16 * 4) * (pw_ / 4) + x16 * 4;
+          const B4Rec &m = job.b4[i4];
+          ConcealMotion::E &o = cm->e[(size_t)y16 * cm->w16 + x16];
+          o.none = 1;
+          if (m.ref_idx < 0) continue;                         // intra
+          if (sh.is_b) {
+            const PicJob::MvF &f = job.mvf[i4];
+            const int L = f.ref[0] >= 0 ? 0 : 1;
+            if (f.ref[L] < 0) continue;
+            o.mv[0] = f.mv[L][0]; o.mv[1] = f.mv[L][1]; o.ref_poc = L ? job.ref_poc1[f.ref[L] & 15] : job.ref_poc[f.ref[L] & 15]; o.lt = (L ? job.ref_lt1 : job.ref_lt)[f.ref[L] & 15] ? 1 : 0;
+          } else { o.mv[0] = m.mvx; o.mv[1] = m.mvy; o.ref_poc = job.ref_poc[m.ref_idx & 15]; o.lt = job.ref_lt[m.ref_idx & 15] ? 1 : 0; }
+          o.none = 0;
+        }
+    }
     // this CTB row's motion (the tile's columns of it) as later pictures see it (one entry per 16x16 block)
     if (!own) continue;
-    const int per16 = 1 << (ctbl_ - 4);                     // 16x16 blocks a CTB is wide
     for (int y16 = cy * per16; y16 < (cy + 1) * per16 && y16 < own->h16; y16++)
       for (int x16 = cx0 * per16; x16 < cx1 * per16 && x16 < own->w16; x16++) {
         const size_t i4 = (size_t)(y16 * 4) * (pw_ / 4) + x16 * 4;

@@ -98,9 +98,22 @@ struct ColMotion {
   int cols = 1;
 };
 
+// motion of a decoded picture as concealment v3 reads it (Decoder, below): one entry per 16x16 luma block of the coded picture (the last column and row may be
+// partial), the motion of its top-left 4x4 -- list 0's when that list predicts the block, else list 1's.  Filled by the picture's parser row by row, and only in
+// mode 3; read when a stand-in is filled from the picture, by which time the parse has finished (fill_concealed).  A plain array: no ordering state.
+struct ConcealMotion {
+  struct E { int16_t mv[2]; int32_t ref_poc; uint8_t lt, none, pad[2]; };      // vector (quarter samples), POC of the picture it points into, that picture was a long-term reference then, none: intra / not parsed
+  int w16 = 0, h16 = 0;
+  std::vector<E> e;
+};
+
 class Decoder {
  public:
   explicit Decoder(int device) : device_(device) {}
+  // what stands in for a reference picture that never arrived: 2 = a copy of the nearest reference picture (default), 3 = that picture moved along its own motion
+  // ("Concealment v2" / "v3" below); before the first picture, and 3 not in band mode.  false: refused
+  bool set_concealment(int mode) { if ((mode != 2 && mode != 3) || !jobs_.empty() || (mode == 3 && band_nrows_ > 0)) return false; conceal_mode_ = mode; return true; }
+  int concealment() const { return conceal_mode_; }
   // frame threading: up to n pictures are parsed concurrently while one more is reconstructed on the GPU; the output is delayed by n pictures
   // (libOpenHevcInit(nb_threads, OH_THREAD_FRAME / OH_THREAD_FRAMESLICE)); call before the first picture
   void set_frame_threads(int n) { if (jobs_.empty()) frame_threads_ = n < 1 ? 1 : (n > 32 ? 32 : n); }
@@ -168,13 +181,15 @@ class Decoder {
     // some boundary inside the picture is closed to the in-loop filters (loop_filter_across_tiles_enabled_flag = 0 with tiles; a slice with
     // slice_loop_filter_across_slices_enabled_flag = 0): lf_slices = the picture's independent slices (first block, flag)
     bool lf_restricted = false; std::vector<std::pair<int, uint8_t>> lf_slices;
-    struct Undo { int poc = 0, prev_poc = 0; bool is_ref = false, used = false, seen_irap = false; long decode_idx = 0; std::shared_ptr<ColMotion> motion; std::vector<std::pair<uint64_t, int>> vwait; } undo;      // what submit_job changed
+    struct Undo { int poc = 0, prev_poc = 0; bool is_ref = false, used = false, seen_irap = false; long decode_idx = 0; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion; std::vector<std::pair<uint64_t, int>> vwait; } undo;      // what submit_job changed
     SliceHdr sh; std::shared_ptr<const DecSps> sps; DecPps pps;  // (a later SPS / PPS NAL may replace the table entry while this picture is still being parsed: the job keeps the SPS it was coded with alive, the PPS by value)
     int64_t pts = 0; int crop[4] = {0, 0, 0, 0}; uint32_t fps_num = 0, fps_den = 0;
     int slot = 0;                                                // picture buffer this picture is reconstructed into
     int cvs = 0;                                                 // the coded video sequence it belongs to (output order)
     uint64_t serial = 0;                                         // number in decoding order
-    std::vector<std::pair<int, int>> conceal;                    // (buffer, source buffer or -1): buffers that stand in for reference pictures that never arrived, filled before this picture's kernels (launch_gpu)
+    // (mode 3: the stand-in's and the source's picture order counts and the source's motion, taken when the source is chosen)
+    struct Conceal { int first, second; int poc = 0, src_poc = 0; std::shared_ptr<const ConcealMotion> motion; Conceal(int buf, int src) : first(buf), second(src) {} };
+    std::vector<Conceal> conceal;                                // (buffer, source buffer or -1): buffers that stand in for reference pictures that never arrived, filled before this picture's kernels (launch_gpu)
     bool starts_cvs = false, discard_prior = false;              // NoRaslOutputFlag (8.1.3); ... and no_output_of_prior_pics_flag in force (C.5.2.2)
     int nref = 0; int ref_poc[16]; uint8_t ref_slot[16];        // RefPicList0
     int nref1 = 0; int ref_poc1[16]; uint8_t ref_slot1[16];     // RefPicList1 (B slices)
@@ -189,6 +204,7 @@ class Decoder {
     // levels.  early_dst: the input buffer this picture will be launched from (nullptr: no early upload); early_rows: rows whose copy was queued.
     uint8_t *early_dst = nullptr; std::atomic<int> early_rows{0};
     std::shared_ptr<ColMotion> col, own;                         // collocated picture's motion (NULL: no temporal candidates); this picture's
+    std::shared_ptr<ConcealMotion> cown;                         // this picture's motion for concealment v3 (NULL in mode 2)
     // the pinned input block (dec_frame.h) and the host views into it
     uint8_t *h_in = nullptr; size_t h_in_cap = 0; size_t ntu = 0, nlev = 0;
     DecInputLayout lay;                                          // where everything lies in it: the fixed part from prepare_jobs, the whole of it once parse_job has counted the picture's blocks
@@ -215,7 +231,7 @@ class Decoder {
   // Synchronous decoder only (one frame thread), no SAO, no temporal motion prediction.  Per picture: decode_nal (returns 0: the band is
   // reconstructed) -> band_export(0) -> [to rank + 1 / from rank - 1] -> band_import(0) -> band_deblock -> band_export(1) ->
   // [to rank - 1 / from rank + 1] -> band_import(1) -> band_finish (the picture is the output; its band's rows are valid).
-  void set_band(int row0, int nrows) { if (jobs_.empty()) { band_row0_ = row0; band_nrows_ = nrows; } }
+  bool set_band(int row0, int nrows) { if (conceal_mode_ == 3 && nrows > 0) return false; if (jobs_.empty()) { band_row0_ = row0; band_nrows_ = nrows; } return true; }      // (false: refused -- concealment v3 has no band form)
   size_t band_halo_bytes() const { return (size_t)pw_ * 8; }
   bool band_export(int stage, uint8_t *d_buf);     // stage 0: this band's LAST four luma rows (+ chroma) before deblocking and their 4x4 records, for the band below; stage 1: the four rows above this band, final, for the band above
   bool band_import(int stage, const uint8_t *d_buf);   // stage 0: from the band above, into the rows above this band; stage 1: from the band below, this band's last four rows, final
@@ -315,7 +331,7 @@ class Decoder {
   std::unique_ptr<FrameWorkers> workers_;
   // decoded picture buffer: slot = device planes + what reference marking needs
   struct DpbPic { uint8_t *plane[3] = {nullptr, nullptr, nullptr}; int poc = 0; bool is_ref = false, used = false, is_lt = false;      // is_lt: marked "used for long-term reference" (8.3.2)
-                  long decode_idx = -1000; std::shared_ptr<ColMotion> motion;
+                  long decode_idx = -1000; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion;      // (cmotion: concealment v3's record, NULL in mode 2 and for a stand-in)
                   hipEvent_t last_dl = nullptr;
                   hipEvent_t last_use = nullptr; bool last_use_alt = false; };      // (two chains, below: the last picture that read or wrote the buffer, and the stream it ran on)     // download mode: the copy of the picture last reconstructed here (a later picture's kernels wait for it before they write the buffer)
   DpbPic dpb_[KVZ_DEC_MAX_REFS];
@@ -367,7 +383,25 @@ class Decoder {
   // picture order count stands in -- no motion, never output -- and decoding goes on.  Its samples: a copy of the reference picture nearest in output order among
   // those the DPB held when the current picture arrived (of two equally near the earlier one), mid-grey when there is none (libavcodec's generate_missing_ref always takes grey).
   // The checker follows the same rule (oracle/hevc_dec.c missing_ref).  The buffers wait here for the picture that needed them; its launch fills them.
-  int conceal_ref(int poc, bool is_lt); std::vector<std::pair<int, int>> pending_conceal_; uint64_t concealed_ = 0;
+  //
+  // Concealment v3 (set_concealment(3); off by default, and with it off nothing below exists): the stand-in is the same source picture S (order count s), moved along
+  // S's own motion continued to the missing picture's order count p.  All integer, >> arithmetic:
+  //  1. Block vectors.  Per 16x16 luma block B of the coded picture: the motion of the 4x4 block at B's top-left corner in S, list 0 if that list predicts it, else
+  //     list 1 (ConcealMotion).  Zero when that block is intra, when the picture the vector points into (order count r) was a long-term reference then, when S is
+  //     itself a stand-in, or when td = 0; else td = clip3(-128, 127, s - r), tb = clip3(-128, 127, p - s) and the vector is scaled as 8.5.3.2.12 scales one:
+  //     tx = (16384 + (|td| >> 1)) / td, f = clip3(-4096, 4095, (tb * tx + 32) >> 6), v = clip3(-32768, 32767, sign(f * mv) * ((|f * mv| + 127) >> 8)).
+  //  2. Neighbour test.  B keeps v only if at least two of its four edge neighbours inside the block grid carry a vector of step 1 within 4 quarter samples of v in
+  //     both components; else its vector is zero.
+  //  3. Fetch, whole samples: luma (x, y) of B = S's luma at (clip(x + ((vx + 2) >> 2)), clip(y + ((vy + 2) >> 2))); B's 8x8 chroma samples = S's chroma at
+  //     (clip(xc + ((vx + 4) >> 3)), clip(yc + ((vy + 4) >> 3))); clipped to the coded plane.
+  // Steps 1 and 2 run on the host when the stand-in is filled (conceal_displacements: one row of four displacements per block), step 3 is k_dec_standin
+  // (conceal_kernels.hip).  Everything else is v2's: no motion, never output, grey without a source.  The checker stays at v2; tests/conceal_model.py states v3.
+  int conceal_ref(int poc, bool is_lt); std::vector<PicJob::Conceal> pending_conceal_; uint64_t concealed_ = 0;
+  int conceal_mode_ = 2;
+  static std::vector<int16_t> conceal_displacements(const ConcealMotion *m, int w16, int h16, int p, int s);      // [h16][w16][4]: luma dx, dy, chroma dx, dy
+  int16_t *d_standin_tab_ = nullptr; size_t standin_tab_cap_ = 0;      // the table on the device, allocated with the first stand-in of mode 3
+  int standin_slot_ = -1; std::vector<int16_t> standin_tab_;          // debug_copy "standin" / "standin_mv": the stand-in filled last and its table
+  float standin_ms_ = -1;                                              // debug_copy "standin_ms": time of the last stand-in's fill (either mode; set_profiling only)
   bool cur_discard_ = false;     // the picture whose headers are being read empties the buffer without output (decided with its first segment)
   bool cur_no_rasl_ = false;     // NoRaslOutputFlag of the picture whose slice headers are being read (decided with its first segment)
   bool skip_rasl_ = false;       // NoRaslOutputFlag of the last IRAP picture: the RASL pictures that belong to it refer to pictures that are not there -- their NAL units are dropped

@@ -105,7 +105,8 @@ bool Decoder::start(std::string *error)
 
 void Decoder::free_buffers()
 {
-  for (auto &j : jobs_) { if (j.h_in) hipHostFree(j.h_in); j.h_in = nullptr; j.h_in_cap = 0; j.col.reset(); j.own.reset(); }
+  for (auto &j : jobs_) { if (j.h_in) hipHostFree(j.h_in); j.h_in = nullptr; j.h_in_cap = 0; j.col.reset(); j.own.reset(); j.cown.reset(); }
+  hipFree(d_standin_tab_); d_standin_tab_ = nullptr; standin_tab_cap_ = 0; standin_slot_ = -1; standin_tab_.clear();
   if (stream_dl_) hipStreamSynchronize(stream_dl_);
   for (auto &p : h_out_) { if (p) retired_out_.emplace_back(nal_calls_, p); p = nullptr; }      // (freed kOutHold calls later: free_retired)
   for (auto &p : d_in_) { hipFree(p); p = nullptr; } for (auto &c : d_in_cap_) c = 0;
@@ -219,7 +220,7 @@ int Decoder::conceal_ref(int poc, bool is_lt)
   const int s = alloc_slot();
   if (s < 0) return -1;
   DpbPic &d = dpb_[s];
-  d.poc = poc; d.is_ref = true; d.used = true; d.is_lt = is_lt; d.motion.reset();      // (decode_idx stays: the buffer was old enough to be taken and is no picture anybody waits for -- free again the moment no set names it)
+  d.poc = poc; d.is_ref = true; d.used = true; d.is_lt = is_lt; d.motion.reset(); d.cmotion.reset();      // (decode_idx stays: the buffer was old enough to be taken and is no picture anybody waits for -- free again the moment no set names it)
   pending_conceal_.emplace_back(s, -2);                           // (-2: the source is chosen once the reference picture set has been applied, decode_slice)
   if (concealed_++ < 3) fprintf(stderr, "kvazzup_amd: decoder: reference picture with POC %d never arrived -- the nearest reference picture (or a grey one) stands in\n", poc);
   return s;
@@ -770,6 +771,7 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
         if (best < 0 || dq < db || (dq == db && dpb_[q].poc < dpb_[best].poc)) best = q;
       }
       pc.second = best;                                            // (-1: none -- grey)
+      if (conceal_mode_ == 3 && best >= 0) { pc.poc = dpb_[pc.first].poc; pc.src_poc = dpb_[best].poc; pc.motion = dpb_[best].cmotion; }      // (v3: the source's motion goes with the entry -- the buffer may be another picture's by the time it is filled; NULL: the source is a stand-in)
     }
     for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) if (!keep[q]) dpb_[q].is_ref = false;
     if (!sh.is_intra) {
@@ -831,8 +833,15 @@ Decoder::PicJob &Decoder::open_job(const SliceCtx &c, const DecPps &pp, int slot
     const size_t nb4 = (size_t)(pw_ / 4) * (ph_ / 4);
     if (job.b4x.size() != nb4) job.b4x.assign(nb4, B4L1());
   }
+  job.cown.reset();
+  if (conceal_mode_ == 3) {                                      // concealment v3: the picture's motion per 16x16 block, should it become the source of a stand-in
+    job.cown = std::make_shared<ConcealMotion>();
+    job.cown->w16 = (s.width + 15) / 16; job.cown->h16 = (s.height + 15) / 16;
+    ConcealMotion::E none; memset(&none, 0, sizeof(none)); none.none = 1;
+    job.cown->e.assign((size_t)job.cown->w16 * job.cown->h16, none);
+  }
   job.own.reset();
-  if (s.tmvp) {                                                  // (only streams with temporal prediction ever read it)
+  if (s.tmvp) {                                                 // (only streams with temporal prediction ever read it)
     job.own = std::make_shared<ColMotion>();
     job.own->w16 = (s.width + 15) / 16; job.own->h16 = (s.height + 15) / 16; job.own->hc = hc; job.own->poc = sh.poc;
     job.own->mv.resize((size_t)job.own->w16 * job.own->h16);
@@ -1000,9 +1009,9 @@ int Decoder::append_segment_tiles(PicJob &job, const SliceCtx &c, int address)
 void Decoder::take_back_job(PicJob &job)
 {
   DpbPic &d = dpb_[job.slot];
-  d.poc = job.undo.poc; d.is_ref = job.undo.is_ref; d.used = job.undo.used; d.decode_idx = job.undo.decode_idx; d.motion = job.undo.motion; prev_poc_ = job.undo.prev_poc; seen_irap_ = job.undo.seen_irap;
+  d.poc = job.undo.poc; d.is_ref = job.undo.is_ref; d.used = job.undo.used; d.decode_idx = job.undo.decode_idx; d.motion = job.undo.motion; d.cmotion = job.undo.cmotion; prev_poc_ = job.undo.prev_poc; seen_irap_ = job.undo.seen_irap;
   vwait_ = std::move(job.undo.vwait);
-  job.undo.motion.reset();
+  job.undo.motion.reset(); job.undo.cmotion.reset();
   job_head_--; job.state.store(0, std::memory_order_relaxed); job.rc = 0; job.early_dst = nullptr;
   asm_.active = true; asm_.free = free_stream_ = true;
 }
@@ -1027,9 +1036,9 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
   // (PicJob::ambiguous_end: when the picture's last segment ends before the picture does, more segments are to come -- everything is put back as it was before
   // the call and the picture is open again, as one of free slices; append_segment collects the rest, the end of the access unit closes it.  The synchronous decoder
   // knows at once; with frame threads the worker finds out and decode_slice looks when the next segment arrives.)
-  job.undo.poc = d.poc; job.undo.prev_poc = prev_poc_; job.undo.is_ref = d.is_ref; job.undo.used = d.used; job.undo.seen_irap = seen_irap_; job.undo.decode_idx = d.decode_idx; job.undo.motion = d.motion;
+  job.undo.poc = d.poc; job.undo.prev_poc = prev_poc_; job.undo.is_ref = d.is_ref; job.undo.used = d.used; job.undo.seen_irap = seen_irap_; job.undo.decode_idx = d.decode_idx; job.undo.motion = d.motion; job.undo.cmotion = d.cmotion;
   auto take_back = [&] { take_back_job(job); return 0; };
-  d.poc = sh.poc; d.is_ref = true; d.used = true; d.is_lt = false; d.decode_idx = job_head_; d.motion = job.own;
+  d.poc = sh.poc; d.is_ref = true; d.used = true; d.is_lt = false; d.decode_idx = job_head_; d.motion = job.own; d.cmotion = job.cown;
   if (cur_tid_ == 0 && (nal_type > 9 || ((nal_type & 1) && nal_type < 6))) prev_poc_ = sh.poc;   // prevTid0Pic (8.3.1): TemporalId 0, not RASL / RADL / sub-layer non-reference
   if (irap) seen_irap_ = true;
   {
@@ -1254,6 +1263,35 @@ int Decoder::complete_gpu(PicJob &job)
 // launch_gpu's stages, in the order they run.  fill_concealed: buffers that stand in for lost reference pictures (conceal_ref) -- grey, or a copy of the nearest
 // picture -- BEFORE this picture's kernels and AFTER everything older has left the GPU: older pictures in flight may still read what the buffers held.  A loss is
 // rare: the device is simply drained (pictures handed to the submission layer are launched first).
+// Concealment v3, steps 1 and 2 (decoder.h): the source's motion per 16x16 block, continued from its order count s to the missing picture's p, kept where the
+// neighbours agree -> per block the whole-sample displacements of luma (x, y) and chroma (x, y).  m = NULL: the source is a stand-in -- no motion, all zero.
+std::vector<int16_t> Decoder::conceal_displacements(const ConcealMotion *m, int w16, int h16, int p, int s)
+{
+  std::vector<int16_t> tab((size_t)w16 * h16 * 4, 0);
+  if (!m || m->w16 != w16 || m->h16 != h16) return tab;
+  auto clip3 = [](long long lo, long long hi, long long v) { return (int)(v < lo ? lo : (v > hi ? hi : v)); };      // (64 bits: the difference of two order counts of a hostile stream)
+  std::vector<int> v((size_t)w16 * h16 * 2, 0);
+  const int tb = clip3(-128, 127, (long long)p - s);
+  for (size_t b = 0; b < (size_t)w16 * h16; b++) {
+    const ConcealMotion::E &e = m->e[b];
+    const int td = clip3(-128, 127, (long long)s - e.ref_poc);
+    if (e.none || e.lt || td == 0) continue;
+    const int tx = (16384 + (abs(td) >> 1)) / td, f = clip3(-4096, 4095, (tb * tx + 32) >> 6);
+    for (int k = 0; k < 2; k++) { const int q = f * e.mv[k], a = (abs(q) + 127) >> 8; v[2 * b + k] = clip3(-32768, 32767, q < 0 ? -a : a); }
+  }
+  for (int y = 0; y < h16; y++)
+    for (int x = 0; x < w16; x++) {
+      const size_t b = (size_t)y * w16 + x;
+      const int vx = v[2 * b], vy = v[2 * b + 1];
+      int agree = 0;
+      auto near = [&](int nx, int ny) { if (nx < 0 || ny < 0 || nx >= w16 || ny >= h16) return; const size_t n = (size_t)ny * w16 + nx; agree += abs(v[2 * n] - vx) <= 4 && abs(v[2 * n + 1] - vy) <= 4; };
+      near(x - 1, y); near(x + 1, y); near(x, y - 1); near(x, y + 1);
+      if (agree < 2) continue;
+      tab[4 * b] = (int16_t)((vx + 2) >> 2); tab[4 * b + 1] = (int16_t)((vy + 2) >> 2); tab[4 * b + 2] = (int16_t)((vx + 4) >> 3); tab[4 * b + 3] = (int16_t)((vy + 4) >> 3);
+    }
+  return tab;
+}
+
 int Decoder::fill_concealed(PicJob &job)
 {
   const size_t npx = (size_t)pw_ * ph_;
@@ -1261,11 +1299,36 @@ int Decoder::fill_concealed(PicJob &job)
   if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
   // (unconditionally: headers run ahead of launches -- by now a LATER picture may have been given the buffer, which is fine, it launches after this one and
   // overwrites it; a list inherited from a header that failed names buffers that are still stand-ins or have become this picture's own)
+  // (set_profiling: the fill itself -- v2's copy or v3's kernel -- between two events, debug_copy "standin_ms"; a loss is rare, the events are made here)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  auto stamp = [&](int k, hipStream_t st) { if (profiling_ && (ev[k] || hipEventCreate(&ev[k]) == hipSuccess)) hipEventRecord(ev[k], st); };
+  auto elapsed = [&] { float ms = 0; if (profiling_ && ev[0] && ev[1] && hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) standin_ms_ = ms; };
   for (const auto &c : job.conceal) {
     uint8_t *dst = dpb_[c.first].plane[0], *src = c.second >= 0 ? dpb_[c.second].plane[0] : nullptr;
+    if (conceal_mode_ == 3 && dst) {
+      // v3 (decoder.h): steps 1 and 2 here -- the source's parse has finished, its picture was launched before this one --, the table goes up, step 3 is the kernel
+      const int w16 = (w_ + 15) / 16, h16 = (h_ + 15) / 16;
+      const bool moved = src && src != dst;
+      standin_slot_ = c.first;
+      standin_tab_ = moved ? conceal_displacements(c.motion.get(), w16, h16, c.poc, c.src_poc) : std::vector<int16_t>((size_t)w16 * h16 * 4, 0);
+      if (moved) {
+        const size_t bytes = standin_tab_.size() * sizeof(int16_t);
+        if (bytes > standin_tab_cap_) { hipFree(d_standin_tab_); standin_tab_cap_ = 0; if (hipMalloc(&d_standin_tab_, bytes) != hipSuccess) { d_standin_tab_ = nullptr; return DEC_ERR_GPU; } standin_tab_cap_ = bytes; }
+        if (hipMemcpy(d_standin_tab_, standin_tab_.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return DEC_ERR_GPU;
+        stamp(0, stream_);
+        launch_dec_standin(dpb_[c.first].plane, dpb_[c.second].plane, d_standin_tab_, w_, h_, pw_, stream_);
+        stamp(1, stream_);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) return DEC_ERR_GPU;      // (the next entry overwrites the table)
+        elapsed();
+        continue;
+      }
+    }
+    stamp(0, nullptr);
     if (dst && (src && src != dst ? hipMemcpy(dst, src, npx * 3 / 2, hipMemcpyDeviceToDevice) : hipMemset(dst, 128, npx * 3 / 2)) != hipSuccess) return DEC_ERR_GPU;
+    stamp(1, nullptr); elapsed();
   }
   if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
+  for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
   job.conceal.clear(); return 0;
 }
 // The input block goes up on its own stream into one of gpu_depth_ + 1 device buffers: the gpu_depth_ pictures launched before this one may still be running
@@ -1449,6 +1512,10 @@ bool Decoder::debug_copy(const char *what, void *dst, size_t bytes)
   if (!w_) return false;
   const size_t npx = (size_t)pw_ * ph_;
   std::string w(what);
+  // concealment v3: the stand-in filled last (its buffer as it lies in memory: Y | Cb | Cr, pitch = the padded width) and its table of displacements
+  if (w == "standin") { if (standin_slot_ < 0 || bytes > npx * 3 / 2) return false; return hipDeviceSynchronize() == hipSuccess && hipMemcpy(dst, dpb_[standin_slot_].plane[0], bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+  if (w == "standin_ms") { if (bytes != sizeof(float) || standin_ms_ < 0) return false; memcpy(dst, &standin_ms_, sizeof(float)); return true; }      // (either mode, with set_profiling: the last stand-in's fill, ms)
+  if (w == "standin_mv") { if (standin_slot_ < 0 || bytes > standin_tab_.size() * sizeof(int16_t)) return false; memcpy(dst, standin_tab_.data(), bytes); return true; }
   for (int c = 0; c < 3; c++) {
     size_t n = c ? npx / 4 : npx;
     if (w == std::string("rec") + char('0' + c)) { if (bytes > n) return false; return hipMemcpy(dst, dpb_[out_slot_].plane[c], bytes, hipMemcpyDeviceToHost) == hipSuccess; }

@@ -491,6 +491,9 @@ bool OpenHEVCFilter::init()                                // openhevcfilter.cpp
   else handle_ = libOpenHevcInit(threads_, OH_THREAD_FRAMESLICE);
   const std::string dev = get("uvgx/gpu", "");
   if (!dev.empty()) kvzx_decoder_set_device(handle_, atoi(dev.c_str()));
+  // harness setting uvgx/concealment = 2 | 3 (kvazzup_amd.h kvzx_decoder_set_concealment): what stands in for a picture lost on the way; absent = 2
+  const std::string conceal = get("uvgx/concealment", "");
+  if (!conceal.empty() && !kvzx_decoder_set_concealment(handle_, atoi(conceal.c_str()))) { fprintf(stderr, "OpenHEVCFilter: invalid uvgx/concealment %s\n", conceal.c_str()); return false; }
   if (libOpenHevcStartDecoder(handle_) == -1) { fprintf(stderr, "OpenHEVCFilter: failed to start decoder\n"); return false; }
   libOpenHevcSetTemporalLayer_id(handle_, 0);
   libOpenHevcSetActiveDecoders(handle_, 0);

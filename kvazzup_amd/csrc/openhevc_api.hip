@@ -111,10 +111,10 @@ int kvzx_decoder_set_device(OpenHevc_Handle hh, int device)
 {
   Handle *h = H(hh);
   if (!h || h->started || device < 0) return 0;
-  int ft = h->dec->frame_threads();
+  int ft = h->dec->frame_threads(), cm = h->dec->concealment();
   delete h->dec;
   h->dec = new Decoder(device);
-  h->dec->set_frame_threads(ft);
+  h->dec->set_frame_threads(ft); h->dec->set_concealment(cm);
   return 1;
 }
 void kvzx_decoder_hash_stats(OpenHevc_Handle hh, int *checked, int *mismatch) { Handle *h = H(hh); if (h) h->dec->hash_stats(checked, mismatch); }
@@ -136,6 +136,8 @@ int kvzx_decoder_parse_probe_stats(OpenHevc_Handle hh, uint64_t *out5, double *p
   if (parse_ms) *parse_ms = st.parse_ms;
   return 1;
 }
+// what stands in for a lost reference picture (decoder.h "Concealment v2" / "v3"): before the first picture
+int kvzx_decoder_set_concealment(OpenHevc_Handle hh, int mode) { Handle *h = H(hh); return h && h->dec->set_concealment(mode) ? 1 : 0; }
 int kvzx_decoder_last_error(OpenHevc_Handle hh) { Handle *h = H(hh); return h ? h->dec->last_error() : -1; }
 int kvzx_decoder_output_device(OpenHevc_Handle hh, const void **planes, int *pitches)
 {
@@ -153,7 +155,7 @@ int kvzx_decoder_output_rgb32_device(OpenHevc_Handle hh, void *d_rgb32, int vari
   return hipStreamSynchronize(nullptr) == hipSuccess ? 1 : 0;
 }
 // ---- tile-row split decoder (decoder.h "band mode")
-int kvzx_decoder_set_band(OpenHevc_Handle hh, int row0, int nrows) { Handle *h = H(hh); if (!h || row0 < 0 || nrows < 0) return 0; h->dec->set_band(row0, nrows); return 1; }
+int kvzx_decoder_set_band(OpenHevc_Handle hh, int row0, int nrows) { Handle *h = H(hh); if (!h || row0 < 0 || nrows < 0) return 0; return h->dec->set_band(row0, nrows) ? 1 : 0; }
 size_t kvzx_decoder_band_halo_bytes(OpenHevc_Handle hh) { Handle *h = H(hh); return h ? h->dec->band_halo_bytes() : 0; }
 int kvzx_decoder_band_export(OpenHevc_Handle hh, int stage, void *d_buf) { Handle *h = H(hh); return h && h->dec->band_export(stage, (uint8_t *)d_buf) ? 1 : 0; }
 int kvzx_decoder_band_import(OpenHevc_Handle hh, int stage, const void *d_buf) { Handle *h = H(hh); return h && h->dec->band_import(stage, (const uint8_t *)d_buf) ? 1 : 0; }

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import orc
+from deckit import batch_stats
 
 SEED = 0x5EED0040
 
@@ -29,15 +30,6 @@ def _stream(w, h, n, seed, scene_cut=None, **enc):
         recs.append(oe.recon())
     oe.close()
     return aus, recs
-
-
-def _batch_stats(lib, reset=False):
-    lib.kvzx_batch_stats.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
-                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int]
-    b, p = C.c_uint64(), C.c_uint64()
-    sizes, ms, ln, fr = (C.c_uint64 * 9)(), (C.c_double * 4)(), (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
-    k = lib.kvzx_batch_stats(0, C.byref(b), C.byref(p), sizes, ms, ln, fr, int(reset))
-    return {"batches": b.value, "pictures": p.value, "sizes": list(sizes), "ms": list(ms)[:k], "launches": list(ln)[:k], "frames": list(fr)[:k]}
 
 
 def _decode_all(dec, aus, out, err, k):
@@ -77,7 +69,7 @@ def test_three_decoders_beside_an_encoder_in_one_process(gpu, coded, frame_threa
     from kvazzup_amd.codec import Decoder, Encoder
     decs = [Decoder(threads=frame_threads, frame_threads=frame_threads > 1) for _ in coded]
     lib = decs[0].lib
-    _batch_stats(lib, reset=True)
+    batch_stats(lib, reset=True)
     out, err = [None] * len(coded), [None] * len(coded)
     ths = [threading.Thread(target=_decode_all, args=(decs[k], coded[k][2], out, err, k)) for k in range(len(coded))]
     w, h, n = 832, 480, 6
@@ -95,7 +87,7 @@ def test_three_decoders_beside_an_encoder_in_one_process(gpu, coded, frame_threa
         for t in ths:
             t.join()
         ge.close(); oe.close()
-    st = _batch_stats(lib)
+    st = batch_stats(lib)
     for d in decs:
         d.close()
     for k, (w, h, aus, recs) in enumerate(coded):
@@ -118,7 +110,7 @@ def test_full_batches_are_bit_exact(gpu, coded):
     decs = [Decoder(threads=4, frame_threads=True) for _ in plan]
     lib = decs[0].lib
     lib.kvzx_batch_hold.argtypes = [C.c_int, C.c_int]
-    _batch_stats(lib, reset=True)
+    batch_stats(lib, reset=True)
     for d in decs:
         d.set_profiling(1)
     out, err = [None] * len(plan), [None] * len(plan)
@@ -132,7 +124,7 @@ def test_full_batches_are_bit_exact(gpu, coded):
         lib.kvzx_batch_hold(0, 0)
         for t in ths:
             t.join()
-    st = _batch_stats(lib)
+    st = batch_stats(lib)
     for d in decs:
         d.close()
     for k, s in enumerate(plan):

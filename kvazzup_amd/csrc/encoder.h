@@ -16,6 +16,8 @@
 #include "entropy_host.h"
 #include "enc_kernels.h"
 #include "input_kernels.h"
+#include "enc_layout.h"
+#include "hip_owner.h"
 
 namespace kvzx {
 
@@ -99,6 +101,9 @@ struct EncodedPicture {
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
 };
+
+// the arrays of one intra chain (Encoder::chain_, chain_idr_); work, SAO on: the picture up to deblocking (rec_[] then holds the filtered pictures)
+struct EncChain { uint32_t *sync = nullptr, *edge_col = nullptr; unsigned long long *edge_row = nullptr; uint8_t *work[3] = {nullptr, nullptr, nullptr}; };
 
 class Encoder {
  public:
@@ -189,12 +194,14 @@ class Encoder {
 
   EncoderConfig cfg_;
   int cw_ = 0, ch_ = 0, rows_ = 0;
+  EncLayout lay_;                        // how long the arrays are and where their parts lie (enc_layout.h); cw_, ch_, rows_ are its
+  HipOwner mem_;                         // every array and event below is a view of what it holds (init and the lazy sites); ~Encoder releases it explicitly, behind the last wait and in front of the streams' release
   hipStream_t stream_ = nullptr;
   EncFrame base_{};                      // what does not change from picture to picture: geometry, options, scratch, tokenizer buffers, the main chain's arrays (written by init only)
   // Host pictures (kvz_api->encoder_encode, kvazaarfilter.cpp:435-438): a ring of packed device buffers filled by the copy engine ahead of
   // each picture's input stage -- picture t + 1 travels over PCIe while the kernels of picture t run -- and, for callers whose planes are not
-  // page-locked, a ring of pinned staging buffers (allocated on first use).  Twelve entries: more than the pictures that can be in flight
-  // (owf <= 8 plus the submitter's hand), so a copy never waits in the copy engine's queue for its buffer's previous reader.
+  // page-locked, a ring of pinned staging buffers (allocated on first use).  kInRing entries: more than the pictures that can be in flight
+  // (owf <= kMaxDepth plus the submitter's hand), so a copy never waits in the copy engine's queue for its buffer's previous reader.
   static constexpr int kInRing = 20;
   uint8_t *d_in_[kInRing] = {};          // packed input (device)
   uint8_t *h_in_[kInRing] = {};          // pinned host staging
@@ -215,10 +222,10 @@ class Encoder {
   int rc_delay_ = 3;            // rate control: pictures between a picture and the access unit size booked before it (3 .. 7)
   int nrec_ = 3;                // reconstruction ring: the picture being written, its reference, and the ones whose output is still owed (owf)
   int cur_idx_ = 0, ref_idx_ = 2, out_idx_ = 2;
-  // Two sets of everything the tokenizer reads (levels and CU records): picture t is tokenised on the second stream
-  // from set t & 1 while the kernels of picture t + 1 fill the other one.
+  // What the tokenizer reads (levels and CU records) is the working set's too: picture t is tokenised on the second stream
+  // from its set while the kernels of the pictures behind it fill the others.
   int16_t *coef_[kSets][3] = {};
-  uint8_t *cu_bytes_[kSets] = {};          // 7 byte arrays back to back
+  uint8_t *cu_bytes_[kSets] = {};          // 7 byte arrays back to back (EncLayout::cu_off)
   int16_t *cu_mv_[kSets] = {}, *cu_mvd_[kSets] = {};
   uint8_t *cu_ref_[kSets] = {};            // lp-refs >= 2: ref_idx_l0 per 8x8 block (EncFrame::cu_ref)
   uint8_t *mc_q_[kSets] = {}; int16_t *mc_centres_[kSets] = {};      // me-coarse (the quarter picture: also scenecut): the quarter picture of the set's input picture and the centres of the set's picture [reference][32x32 block] (EncFrame::mc_*)
@@ -261,25 +268,24 @@ class Encoder {
   hipStream_t stream_tok_ = nullptr;     // signalling decisions, tokenizer, compaction
   hipStream_t stream_in_ = nullptr;      // input padding (runs ahead of the previous picture's kernels)
   hipEvent_t ev_src_free_[kSets] = {}; bool src_busy_[kSets] = {};
-  uint8_t *work_[3] = {nullptr, nullptr, nullptr};   // SAO on: the picture up to deblocking (rec_[] then holds the filtered pictures)
   SaoParams *sao_[kSets] = {};            // per CTU, one array per set
 
   // An intra picture depends on no other picture: its chain (1.6 ms at 1080p, twenty picture intervals) is queued on a stream of its own the moment the
   // picture is accepted, beside the P pictures in front of it that the main stream is still working through; the next P picture waits for ev_idr_done_.
   hipStream_t stream_idr_ = nullptr; hipEvent_t ev_idr_done_ = nullptr; bool idr_pending_ = false, idr_side_ = false, all_intra_alt_ = false;
   // ... with its own copies of what the P pictures' kernels also use while it runs beside them (round 4: the side chain also with SAO, intra units in P
-  // pictures, per-CTU QPs and rate control v2 -- uvgComm's default mode): progress counters + ticket word, the CTUs' edge columns, the SAO work picture
-  uint32_t *sync_idr_ = nullptr; uint32_t *edge_col_idr_ = nullptr; uint32_t chain_gen_ = 0; unsigned long long *edge_row_ = nullptr, *edge_row_idr_ = nullptr; uint8_t *work_idr_[3] = {nullptr, nullptr, nullptr};
+  // pictures, per-CTU QPs and rate control v2 -- uvgComm's default mode): progress counters + ticket word, the CTUs' edge columns and rows, the SAO work picture
+  EncChain chain_, chain_idr_; uint32_t chain_gen_ = 0;      // the main stream's; the side chain's (idr_side_ || all_intra_alt_, else empty)
+  bool build_chain(EncChain &c, std::string *error);
   hipEvent_t ev_signalled_ = nullptr, ev_tok_done_[kSets] = {}; bool tok_pending_[kSets] = {};
   uint8_t *intra_scratch_ = nullptr;
   uint8_t *d_scaling_ = nullptr;          // scaling-list default: KVZ_SCALING_BYTES scaling factors
-  uint16_t *tok_buf_ = nullptr; int tok_cap_ = 0; int32_t *tok_count_ = nullptr; uint32_t *tok_seg_ = nullptr; uint32_t *tok_list_ = nullptr; int tok_nctu_ = 0;
-  size_t tok_dense_cap_ = 0;
+  uint16_t *tok_buf_ = nullptr; int32_t *tok_count_ = nullptr; uint32_t *tok_seg_ = nullptr; uint32_t *tok_list_ = nullptr;
   std::vector<std::vector<uint8_t>> band_subs_; uint64_t band_bins_ = 0; bool band_coded_ = false;   // band mode: between phase 2a and 2b
   // me-source: k_me and k_intra_analyse<P> of the pictures ahead run on the input stream while the main stream is still in an earlier picture's chain, so what
   // they write -- the 16x16 costs, the candidate list, the quarters' scratch, the P pictures' progress counters with the "has intra units" word -- exists per working set
   bool me_ahead_ = false; uint32_t *me_block_[kSets] = {}; uint32_t *sync_set_[kSets] = {}; int prev_set_ = 0;
-  uint32_t *sync_ = nullptr; uint32_t *me_cost16_ = nullptr; uint32_t *edge_col_ = nullptr; uint32_t *intra_order_ = nullptr; uint32_t *err_ = nullptr; unsigned long long *trace_ = nullptr;
+  uint32_t *me_cost16_ = nullptr; uint32_t *intra_order_ = nullptr; uint32_t *err_ = nullptr; unsigned long long *trace_ = nullptr;
   // one slot per picture in flight: the host-visible results of its kernels and what collect() needs to finish it
   struct EvPair { hipEvent_t a, b; KernelId id; };
   struct Slot {
@@ -304,7 +310,6 @@ class Encoder {
     EncFrame f_tok{}; bool prof = false, tok_failed = false;                    // tok_deferred_: what the tokenizer's launches need, kept until the launcher thread makes them
   };
   Slot slot_[kMaxDepth + 2]; Slot *cur_slot_ = nullptr; int nslots_ = 1, depth_ = 0;
-  size_t stage_cap_ = 0, out_cap_ = 0;
   std::thread bg_[2]; std::mutex bm_; std::condition_variable bcv_; std::deque<int> bq_; bool bquit_ = false;
   // SAO (owf 2..7): the tokenizer of a picture needs the filter's parameters, i.e. the END of the picture's chain.  An event on the main stream that another
   // stream is already waiting for costs the stream's next kernel -- the next picture's k_me -- 12-25 us; one that only the host looks at costs 1-2 us

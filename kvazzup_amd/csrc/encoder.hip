@@ -20,20 +20,25 @@ static const unsigned kDeviceEvent = hipEventDisableTiming | hipEventDisableSyst
 #define HIP_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { fprintf(stderr, "kvazzup_amd: %s failed: %s\n", #expr, hipGetErrorString(e_)); return false; } } while (0)
 
 // the me-source block of one working set, or the shared one: k_me's 16x16 costs, the candidate list with the intra pricing's arrival counters and scratch
-static void point_me_block(EncFrame &f, uint32_t *block)
+static void point_me_block(EncFrame &f, const EncLayout &L, uint32_t *block)
 {
-  const size_t n16 = (size_t)(f.cw / 16) * (f.ch / 16);
-  f.me_cost16 = block; f.me_cand = block + n16;
-  f.ip_arrive = f.me_cand + 1 + n16 / 4; f.ip_scratch = (uint64_t *)(block + ((n16 + 1 + n16 / 4 + n16 / 4 + 1) & ~(size_t)1));      // (8-byte aligned)
+  f.me_cost16 = block; f.me_cand = block + L.me_cand_off;
+  f.ip_arrive = block + L.ip_arrive_off; f.ip_scratch = (uint64_t *)(block + L.ip_scratch_off);
 }
 
 // the arrays of one intra chain: progress counters, and per plane the CTUs' right columns and bottom rows
-static void point_chain(EncFrame &f, uint32_t *sync, uint32_t *col, unsigned long long *row)
+static void point_chain(EncFrame &f, const EncLayout &L, const EncChain &c)
 {
-  const size_t nctu = (size_t)(f.cw / 64) * (f.ch / 64);
-  f.sync = sync;
-  f.edge_col[0] = col; f.edge_col[1] = col + nctu * 64; f.edge_col[2] = col + nctu * 96;
-  f.edge_row[0] = row; f.edge_row[1] = row + nctu * 16; f.edge_row[2] = row + nctu * 24;
+  f.sync = c.sync;
+  for (int p = 0; p < 3; p++) { f.edge_col[p] = c.edge_col + L.edge_col_off(p); f.edge_row[p] = c.edge_row + L.edge_row_off(p); }
+}
+
+// ... allocated and cleared (tagged words: generation 0 = never written); SAO: the chain's work picture too
+bool Encoder::build_chain(EncChain &c, std::string *error)
+{
+  HIP_OK(mem_.dev(&c.sync, lay_.sync, true)); HIP_OK(mem_.dev(&c.edge_col, lay_.edge_col, true)); HIP_OK(mem_.dev(&c.edge_row, lay_.edge_row, true));
+  if (cfg_.sao) for (int p = 0; p < 3; p++) HIP_OK(mem_.dev(&c.work[p], lay_.plane(p)));
+  return true;
 }
 
 Encoder *Encoder::create(const EncoderConfig &cfg, std::string *error)
@@ -119,9 +124,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     if (error) *error = "no usable HIP device (this library has no CPU fallback)"; return false;
   }
   HIP_OK(hipSetDevice(cfg.device));
-  cw_ = (cfg.width + 63) & ~63; ch_ = (cfg.height + 63) & ~63;
-  if (cw_ < 128) cw_ = 128;
-  rows_ = ch_ / 64;
+  lay_ = EncLayout(cfg.width, cfg.height, cfg.band_rows); const EncLayout &L = lay_;
+  cw_ = L.cw; ch_ = L.ch; rows_ = L.rows;
   // pictures in flight behind the one being submitted (output lag).  Rate control books picture t - 3 before picture t: lag <= 2.  Beyond
   // 3 the gain is buffering: while an intra picture's chain holds the main stream (1.6 ms at 1080p, ten picture intervals) the coder threads
   // work off the pictures queued before it (1080p, host-bound: owf 3 -> 4 measured +4 %; more changes nothing).  The GPU arithmetic coder
@@ -138,62 +142,43 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   nrec_ = depth_ + 1 + keep < 2 + keep ? 2 + keep : depth_ + 1 + keep;
   prio_[0] = prio[0]; prio_[1] = prio[1]; prio_[2] = prio[2];
   HIP_OK(stream_acquire(&stream_, cfg.device, 'M', prio_[0]));
-  const size_t npx = (size_t)cw_ * ch_, nb8 = npx / 64, in_bytes = (size_t)cfg.width * cfg.height * 3 / 2;
-  (void)in_bytes;                                          // (the host-picture ring is allocated by the first encode_host)
   for (int c = 0; c < 3; c++) {
-    size_t n = c ? npx / 4 : npx;
-    for (int k = 0; k < kSets; k++) HIP_OK(hipMalloc(&src_[k][c], n));
-    for (int b = 0; b < nrec_; b++) { HIP_OK(hipMalloc(&rec_[b][c], n)); HIP_OK(hipMemset(rec_[b][c], 0, n)); }
-    for (int k = 0; k < kSets; k++) { HIP_OK(hipMalloc(&coef_[k][c], n * sizeof(int16_t))); HIP_OK(hipMemset(coef_[k][c], 0, n * sizeof(int16_t))); }
+    for (int k = 0; k < kSets; k++) HIP_OK(mem_.dev(&src_[k][c], L.plane(c)));
+    for (int b = 0; b < nrec_; b++) HIP_OK(mem_.dev(&rec_[b][c], L.plane(c), true));
+    for (int k = 0; k < kSets; k++) HIP_OK(mem_.dev(&coef_[k][c], L.plane(c), true));
   }
   for (int k = 0; k < kSets; k++) {
-    HIP_OK(hipMalloc(&cu_bytes_[k], nb8 * 7)); HIP_OK(hipMemset(cu_bytes_[k], 0, nb8 * 7));
-    HIP_OK(hipMalloc(&cu_mv_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mv_[k], 0, nb8 * 2 * sizeof(int16_t)));
-    HIP_OK(hipMalloc(&cu_mvd_[k], nb8 * 2 * sizeof(int16_t))); HIP_OK(hipMemset(cu_mvd_[k], 0, nb8 * 2 * sizeof(int16_t)));
-    if (cfg.lp_refs > 1) { HIP_OK(hipMalloc(&cu_ref_[k], nb8)); HIP_OK(hipMemset(cu_ref_[k], 0, nb8)); }
-    if (cfg.tmvp) { HIP_OK(hipMalloc(&col_[k], nb8 / 4 * sizeof(ColMv))); HIP_OK(hipMemset(col_[k], 0, nb8 / 4 * sizeof(ColMv))); }
-    if (cfg.me_coarse || cfg.scenecut) { HIP_OK(hipMalloc(&mc_q_[k], npx / 16)); HIP_OK(hipMemset(mc_q_[k], 0, npx / 16)); }
-    if (cfg.scenecut) { HIP_OK(hipMalloc(&sc_sum_[k], sizeof(unsigned long long))); HIP_OK(hipMemset(sc_sum_[k], 0, sizeof(unsigned long long))); }
-    if (cfg.me_coarse) {
-      HIP_OK(hipMalloc(&mc_centres_[k], (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t))); HIP_OK(hipMemset(mc_centres_[k], 0, (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t)));
-    }
-    if (cfg.weightp) {
-      HIP_OK(hipMalloc(&wp_partial_[k], (size_t)wp_stat_blocks(cfg.height) * 2 * sizeof(unsigned long long)));
-      HIP_OK(hipMalloc(&wp_stat_[k], 2 * sizeof(int64_t))); HIP_OK(hipMemset(wp_stat_[k], 0, 2 * sizeof(int64_t)));
-      HIP_OK(hipMalloc(&wp_rec_[k], 3 * KVZ_MAX_LP_REFS * sizeof(int32_t))); HIP_OK(hipMemset(wp_rec_[k], 0, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t)));
-    }
-    HIP_OK(hipEventCreateWithFlags(&ev_tok_done_[k], kDeviceEvent));
+    HIP_OK(mem_.dev(&cu_bytes_[k], L.cu_bytes, true));
+    HIP_OK(mem_.dev(&cu_mv_[k], L.cu_mv, true)); HIP_OK(mem_.dev(&cu_mvd_[k], L.cu_mv, true));
+    if (cfg.lp_refs > 1) HIP_OK(mem_.dev(&cu_ref_[k], L.nb8, true));
+    if (cfg.tmvp) HIP_OK(mem_.dev(&col_[k], L.col, true));
+    if (cfg.me_coarse || cfg.scenecut) HIP_OK(mem_.dev(&mc_q_[k], L.mc_q, true));
+    if (cfg.scenecut) HIP_OK(mem_.dev(&sc_sum_[k], 1, true));
+    if (cfg.me_coarse) HIP_OK(mem_.dev(&mc_centres_[k], L.mc_centres, true));
+    if (cfg.weightp) { HIP_OK(mem_.dev(&wp_partial_[k], (size_t)wp_stat_blocks(cfg.height) * 2)); HIP_OK(mem_.dev(&wp_stat_[k], 2, true)); HIP_OK(mem_.dev(&wp_rec_[k], 3 * KVZ_MAX_LP_REFS, true)); }
+    HIP_OK(mem_.event(&ev_tok_done_[k], kDeviceEvent));
   }
   if (cfg.weightp) {
-    HIP_OK(hipMalloc(&wp_cand_, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t))); HIP_OK(hipMalloc(&wp_acc_, 2 * KVZ_MAX_LP_REFS * sizeof(unsigned long long)));
-    for (int r = 0; r < cfg.lp_refs; r++) HIP_OK(hipMalloc(&wp_plane_[r], npx));
+    HIP_OK(mem_.dev(&wp_cand_, 3 * KVZ_MAX_LP_REFS)); HIP_OK(mem_.dev(&wp_acc_, 2 * KVZ_MAX_LP_REFS));
+    for (int r = 0; r < cfg.lp_refs; r++) HIP_OK(mem_.dev(&wp_plane_[r], L.npx));
   }
   if (cfg.scenecut) {
-    int bw, bh;
-    sc_visible_blocks(cfg.width, cfg.height, &bw, &bh);
-    HIP_OK(hipMalloc(&sc_blocks_, (size_t)bw * bh * 2 * sizeof(uint32_t))); HIP_OK(hipMemset(sc_blocks_, 0, (size_t)bw * bh * 2 * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&sc_count_, sizeof(uint32_t))); HIP_OK(hipMemset(sc_count_, 0, sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&sc_rec_, 5 * sizeof(int32_t))); HIP_OK(hipMemset(sc_rec_, 0, 5 * sizeof(int32_t)));
-    HIP_OK(hipEventCreateWithFlags(&ev_sc_, hipEventDisableTiming));      // (the host reads what k_sc_decide wrote into host-mapped memory: an event with its system fence)
+    HIP_OK(mem_.dev(&sc_blocks_, L.sc_blocks, true)); HIP_OK(mem_.dev(&sc_count_, 1, true)); HIP_OK(mem_.dev(&sc_rec_, 5, true));
+    HIP_OK(mem_.event(&ev_sc_, hipEventDisableTiming));      // (the host reads what k_sc_decide wrote into host-mapped memory: an event with its system fence)
   }
   if (cfg.qp_in_cu) {
-    const size_t nctu = (size_t)(cw_ / 64) * rows_;
     for (int k = 0; k < kSets; k++) {
-      HIP_OK(hipMalloc(&ctu_qt_[k], nctu)); HIP_OK(hipMalloc(&ctu_qy_[k], nctu)); HIP_OK(hipMalloc(&ctu_delta_[k], nctu)); HIP_OK(hipMalloc(&ctu_first_[k], nctu));
-      HIP_OK(hipHostMalloc(&h_ctu_qt_[k], nctu, hipHostMallocDefault));
-      HIP_OK(hipMalloc(&ctu_roi_[k], nctu));
+      HIP_OK(mem_.dev(&ctu_qt_[k], L.nctu)); HIP_OK(mem_.dev(&ctu_qy_[k], L.nctu)); HIP_OK(mem_.dev(&ctu_delta_[k], L.nctu)); HIP_OK(mem_.dev(&ctu_first_[k], L.nctu));
+      HIP_OK(mem_.pinned(&h_ctu_qt_[k], L.nctu, hipHostMallocDefault)); HIP_OK(mem_.dev(&ctu_roi_[k], L.nctu));
     }
-    if (cfg.vaq > 0) { HIP_OK(hipMalloc(&vaq_act_, nctu * sizeof(int))); HIP_OK(hipMalloc(&vaq_sum_, sizeof(int))); }
+    if (cfg.vaq > 0) { HIP_OK(mem_.dev(&vaq_act_, L.nctu)); HIP_OK(mem_.dev(&vaq_sum_, 1)); }
   }
-  if (cfg.sao) {
-    for (int c = 0; c < 3; c++) HIP_OK(hipMalloc(&work_[c], c ? npx / 4 : npx));
-    for (int k = 0; k < kSets; k++) HIP_OK(hipMalloc(&sao_[k], sizeof(SaoParams) * (size_t)(cw_ / 64) * rows_));
-  }
-  if (cfg.rc_bands > 0) { HIP_OK(hipMalloc(&rc_state_, sizeof(RcState))); HIP_OK(hipMemset(rc_state_, 0, sizeof(RcState))); }
+  if (cfg.sao) for (int k = 0; k < kSets; k++) HIP_OK(mem_.dev(&sao_[k], L.nctu));
+  if (cfg.rc_bands > 0) HIP_OK(mem_.dev(&rc_state_, 1, true));
   HIP_OK(stream_acquire(&stream_tok_, cfg.device, 'T', prio_[1]));
   HIP_OK(stream_acquire(&stream_in_, cfg.device, 'I', prio_[2]));
-  for (int k = 0; k < kSets; k++) HIP_OK(hipEventCreateWithFlags(&ev_src_free_[k], kDeviceEvent));
-  HIP_OK(hipEventCreateWithFlags(&ev_signalled_, kDeviceEvent));
+  for (int k = 0; k < kSets; k++) HIP_OK(mem_.event(&ev_src_free_[k], kDeviceEvent));
+  HIP_OK(mem_.event(&ev_signalled_, kDeviceEvent));
   // the intra pictures' own stream: where the chain shares nothing with the P pictures' kernels (no SAO work picture, no intra units in P pictures
   // -- they use the same progress counters --, no per-CTU QP upload, no row groups) and pictures are queued ahead at all
   // (round 4: SAO, intra units in P pictures, per-CTU QPs and the row groups of rate control v2 no longer keep it on the main stream -- the side chain has its own
@@ -205,95 +190,61 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   // the pictures ALTERNATE between the main stream with its arrays and a second stream with the side chain's (round 5: all-intra 1080p was bound by
   // one chain after the other, 1 / (0.67 + 0.03 ms)).  The second stream is one of its own here: the input stream carries every picture's analysis.
   all_intra_alt_ = depth_ >= 2 && cfg.vaq == 0 && cfg.band_rows == 0 && cfg.intra_period == 1;
+  if (!build_chain(chain_, error)) return false;
   if (idr_side_ || all_intra_alt_) {
-    const size_t nsync = ((size_t)rows_ * (cw_ / 64) * 3 + 2 + 3) & ~(size_t)3, nctu_ = (size_t)(cw_ / 64) * rows_;
-    HIP_OK(hipMalloc(&sync_idr_, sizeof(uint32_t) * nsync)); HIP_OK(hipMemset(sync_idr_, 0, sizeof(uint32_t) * nsync));
-    HIP_OK(hipMalloc(&edge_col_idr_, nctu_ * 128 * sizeof(uint32_t))); HIP_OK(hipMemset(edge_col_idr_, 0, nctu_ * 128 * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&edge_row_idr_, nctu_ * 32 * 8)); HIP_OK(hipMemset(edge_row_idr_, 0, nctu_ * 32 * 8));
-    if (cfg.sao) { const size_t npx_ = (size_t)cw_ * ch_; for (int c = 0; c < 3; c++) HIP_OK(hipMalloc(&work_idr_[c], c ? npx_ / 4 : npx_)); }
+    if (!build_chain(chain_idr_, error)) return false;
     // ... which is the INPUT stream: the pictures behind an intra picture need it anyway, so their input stages lose nothing by queueing behind
     // its chain, and a further stream would share a hardware queue with one that matters (HIP spreads a priority level's streams over four;
     // measured with a stream of its own: no gain at the default level, half the rate at any other)
     if (all_intra_alt_) HIP_OK(stream_acquire(&stream_idr_, cfg.device, 'X', prio_[0])); else stream_idr_ = stream_in_;
-    HIP_OK(hipEventCreateWithFlags(&ev_idr_done_, kDeviceEvent));
+    HIP_OK(mem_.event(&ev_idr_done_, kDeviceEvent));
   }
-  // intra scratch: ic8 (nb8 u32) | ic16 (nb8/4 u32) | ic32 (nb8/16 u32) | im8 | im16 | im32
-  size_t isz = nb8 * 4 + nb8 + nb8 / 4 + nb8 + nb8 / 4 + nb8 / 16 + 64;
-  HIP_OK(hipMalloc(&intra_scratch_, isz));
-  const int nctu = (cw_ / 64) * rows_;
-  tok_cap_ = 49152;                                // tokens per CTU slot (worst case of a 64x64 CTU is ~43k)
-  HIP_OK(hipMalloc(&tok_buf_, (size_t)nctu * tok_cap_ * sizeof(uint16_t)));
-  HIP_OK(hipMalloc(&tok_count_, sizeof(uint32_t) * nctu * 2));        // two sets of cursors take turns (k_tok_compact)
-  HIP_OK(hipMalloc(&tok_seg_, sizeof(uint32_t) * nctu * 16 * 17 * 2));       // [ctu][unit][piece] {offset, length}
-  HIP_OK(hipMemset(tok_seg_, 0, sizeof(uint32_t) * nctu * 16 * 17 * 2));     // (all "no tokens": the list form of k_tokenize writes only the entries that have some; k_tok_compact zeroes behind itself)
-  if (cfg.band_rows == 0) { HIP_OK(hipMalloc(&tok_list_, sizeof(uint32_t) * (1 + (size_t)nctu * 16 * 4))); HIP_OK(hipMemset(tok_list_, 0, sizeof(uint32_t) * (1 + (size_t)nctu * 16 * 4))); }      // (unit, role) pairs with something to say, P pictures (hevc_core.h EncFrame::tok_list)
-  HIP_OK(hipMemset(tok_count_, 0, sizeof(uint32_t) * nctu * 2)); tok_nctu_ = nctu;
-  tok_dense_cap_ = (size_t)nctu * tok_cap_;
-  if (tok_dense_cap_ > ((size_t)1 << 27)) tok_dense_cap_ = (size_t)1 << 27;
+  HIP_OK(mem_.dev(&intra_scratch_, L.intra_scratch));
+  HIP_OK(mem_.dev(&tok_buf_, L.tok_buf)); HIP_OK(mem_.dev(&tok_count_, L.tok_count, true));
+  HIP_OK(mem_.dev(&tok_seg_, L.tok_seg, true));            // (all "no tokens": the list form of k_tokenize writes only the entries that have some; k_tok_compact zeroes behind itself)
+  if (cfg.band_rows == 0) HIP_OK(mem_.dev(&tok_list_, L.tok_list, true));      // (unit, role) pairs with something to say, P pictures (hevc_core.h EncFrame::tok_list)
   spin_wait_ = getenv("KVAZZUP_AMD_SPIN") != nullptr;
   nslots_ = depth_ + 1;
-  stage_cap_ = tok_dense_cap_ * 2 + 256 * (size_t)rows_; if (stage_cap_ > 0xfff00000u) stage_cap_ = 0xfff00000u;
-  out_cap_ = (size_t)cw_ * ch_ * 3 + 4096; if (out_cap_ > stage_cap_) out_cap_ = stage_cap_;       // twice the raw picture: a larger access unit is not a picture this encoder makes
   for (int i = 0; i < nslots_; i++) {
     Slot &sl = slot_[i];
-    void *dp = nullptr;
     if (cfg.entropy_gpu) {
-      HIP_OK(hipMalloc(&sl.g_tok, tok_dense_cap_ * sizeof(uint16_t)));
-      HIP_OK(hipMalloc(&sl.g_count, sizeof(int32_t) * nctu)); HIP_OK(hipMalloc(&sl.g_off, sizeof(uint32_t) * nctu));
+      HIP_OK(mem_.dev(&sl.g_tok, L.tok_dense_cap)); HIP_OK(mem_.dev(&sl.g_count, L.nctu)); HIP_OK(mem_.dev(&sl.g_off, L.nctu));
       sl.d_tok_dense = sl.g_tok; sl.d_tok_count = sl.g_count; sl.d_tok_off = sl.g_off;
-      HIP_OK(hipMalloc(&sl.g_stage, stage_cap_));
-      HIP_OK(hipMalloc(&sl.g_cursors, 2 * sizeof(uint32_t))); HIP_OK(hipMemset(sl.g_cursors, 0, 2 * sizeof(uint32_t)));
-      HIP_OK(hipMalloc(&sl.g_ctx_save, sizeof(uint32_t) * 40 * rows_));
-      HIP_OK(hipMalloc(&sl.g_ctx_ready, sizeof(uint32_t) * rows_)); HIP_OK(hipMemset(sl.g_ctx_ready, 0, sizeof(uint32_t) * rows_));
-      HIP_OK(hipHostMalloc(&sl.h_out, out_cap_, hipHostMallocMapped));
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_out, 0)); sl.d_out = (uint8_t *)dp;
-      HIP_OK(hipHostMalloc(&sl.h_sub, sizeof(uint32_t) * 3 * rows_, hipHostMallocMapped));
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_sub, 0)); sl.d_sub = (uint32_t *)dp;
+      HIP_OK(mem_.dev(&sl.g_stage, L.stage_cap));
+      HIP_OK(mem_.dev(&sl.g_cursors, 2, true)); HIP_OK(mem_.dev(&sl.g_ctx_save, L.ctx_save)); HIP_OK(mem_.dev(&sl.g_ctx_ready, (size_t)rows_, true));
+      HIP_OK(mem_.pinned(&sl.h_out, L.out_cap, hipHostMallocMapped, &sl.d_out)); HIP_OK(mem_.pinned(&sl.h_sub, L.sub, hipHostMallocMapped, &sl.d_sub));
       HIP_OK(stream_acquire(&sl.ent_stream, cfg.device, 'E', 'l'));           // (streams of one priority level share that level's hardware queues: the long coder kernels get the lowest level to themselves)
-      HIP_OK(hipEventCreateWithFlags(&sl.tok_ev, hipEventDisableTiming));
+      HIP_OK(mem_.event(&sl.tok_ev, hipEventDisableTiming));
     } else {
-      HIP_OK(hipHostMalloc(&sl.h_tok_dense, tok_dense_cap_ * sizeof(uint16_t), hipHostMallocMapped));
-      HIP_OK(hipHostMalloc(&sl.h_tok_count, sizeof(int32_t) * nctu, hipHostMallocMapped));
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_tok_dense, 0)); sl.d_tok_dense = (uint16_t *)dp;
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_tok_count, 0)); sl.d_tok_count = (int32_t *)dp;
-      HIP_OK(hipHostMalloc(&sl.h_tok_off, sizeof(uint32_t) * nctu, hipHostMallocMapped));
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_tok_off, 0)); sl.d_tok_off = (uint32_t *)dp;
+      HIP_OK(mem_.pinned(&sl.h_tok_dense, L.tok_dense_cap, hipHostMallocMapped, &sl.d_tok_dense));
+      HIP_OK(mem_.pinned(&sl.h_tok_count, L.nctu, hipHostMallocMapped, &sl.d_tok_count)); HIP_OK(mem_.pinned(&sl.h_tok_off, L.nctu, hipHostMallocMapped, &sl.d_tok_off));
     }
-    HIP_OK(hipHostMalloc(&sl.h_err, sizeof(uint32_t), hipHostMallocMapped)); *sl.h_err = 0;
-    HIP_OK(hipHostGetDevicePointer(&dp, sl.h_err, 0)); sl.d_err = (uint32_t *)dp;
+    HIP_OK(mem_.pinned(&sl.h_err, 1, hipHostMallocMapped, &sl.d_err)); *sl.h_err = 0;
     if (cfg.weightp) {
-      HIP_OK(hipHostMalloc(&sl.h_wp, 3 * KVZ_MAX_LP_REFS * sizeof(int32_t), hipHostMallocMapped));
+      HIP_OK(mem_.pinned(&sl.h_wp, 3 * KVZ_MAX_LP_REFS, hipHostMallocMapped, &sl.d_wp));
       for (int r = 0; r < KVZ_MAX_LP_REFS; r++) { sl.h_wp[3 * r] = 0; sl.h_wp[3 * r + 1] = 64; sl.h_wp[3 * r + 2] = 0; }
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_wp, 0)); sl.d_wp = (int32_t *)dp;
     }
     if (cfg.scenecut) {
-      HIP_OK(hipHostMalloc(&sl.h_sc, 5 * sizeof(int32_t), hipHostMallocMapped));
+      HIP_OK(mem_.pinned(&sl.h_sc, 5, hipHostMallocMapped, &sl.d_sc));
       for (int i = 0; i < 5; i++) sl.h_sc[i] = 0;
-      HIP_OK(hipHostGetDevicePointer(&dp, sl.h_sc, 0)); sl.d_sc = (int32_t *)dp;
     }
-    HIP_OK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&sl.rec_done, hipEventDisableTiming));
+    HIP_OK(mem_.event(&sl.done, hipEventDisableTiming)); HIP_OK(mem_.event(&sl.rec_done, hipEventDisableTiming));
   }
-  HIP_OK(hipEventCreateWithFlags(&in_done_, kDeviceEvent));
-  HIP_OK(hipMalloc(&sync_, sizeof(uint32_t) * ((rows_ * (cw_ / 64) * 3 + 2 + 3) & ~3))); HIP_OK(hipMemset(sync_, 0, sizeof(uint32_t) * ((rows_ * (cw_ / 64) * 3 + 2 + 3) & ~3)));      // (a multiple of 16 bytes: k_picture_begin zeroes it in 16-byte pieces)       // one progress counter per CTU and colour plane, and the ticket counter of k_intra_recon's workgroups
-  if (cfg.intra_in_p) { const size_t n16 = (size_t)(cw_ / 16) * (ch_ / 16); HIP_OK(hipMalloc(&me_cost16_, sizeof(uint32_t) * (n16 + 2 + n16 / 4 + n16 / 4 + (n16 / 4) * 40))); HIP_OK(hipMemset(me_cost16_, 0, sizeof(uint32_t) * (n16 + 2 + n16 / 4 + n16 / 4 + (n16 / 4) * 40))); }      // k_me's inter cost per 16x16 block (intra-in-P)
+  HIP_OK(mem_.event(&in_done_, kDeviceEvent));
+  if (cfg.intra_in_p) HIP_OK(mem_.dev(&me_cost16_, L.me_block, true));      // k_me's inter cost per 16x16 block (intra-in-P)
   me_ahead_ = cfg.me_source != 0;
-  if (me_ahead_ && cfg.intra_in_p) {                       // (encoder.h me_block_: one block of these and one array of progress counters per working set)
-    const size_t n16 = (size_t)(cw_ / 16) * (ch_ / 16), nme = sizeof(uint32_t) * (n16 + 2 + n16 / 4 + n16 / 4 + (n16 / 4) * 40), nsy = sizeof(uint32_t) * ((rows_ * (cw_ / 64) * 3 + 2 + 3) & ~3);
-    for (int k = 0; k < kSets; k++) { HIP_OK(hipMalloc(&me_block_[k], nme)); HIP_OK(hipMemset(me_block_[k], 0, nme)); HIP_OK(hipMalloc(&sync_set_[k], nsy)); HIP_OK(hipMemset(sync_set_[k], 0, nsy)); }
-  }
+  if (me_ahead_ && cfg.intra_in_p)                         // (encoder.h me_block_: one block of these and one array of progress counters per working set)
+    for (int k = 0; k < kSets; k++) { HIP_OK(mem_.dev(&me_block_[k], L.me_block, true)); HIP_OK(mem_.dev(&sync_set_[k], L.sync, true)); }
   {
     // dispatch order of the intra reconstruction's workgroups: the CTUs of the rows this instance codes, by anti-diagonal cx + 2 cy
     const int wc = cw_ / 64, r0 = cfg.band_rows > 0 ? cfg.band_row0 : 0, nr = cfg.band_rows > 0 ? cfg.band_rows : rows_;
     std::vector<uint32_t> order;
     for (int d = 0; d < wc + 2 * nr; d++) for (int cy = 0; cy < nr; cy++) { const int cx = d - 2 * cy; if (cx >= 0 && cx < wc) order.push_back((uint32_t)((r0 + cy) * wc + cx)); }
-    HIP_OK(hipMalloc(&intra_order_, sizeof(uint32_t) * order.size()));
+    HIP_OK(mem_.dev(&intra_order_, L.intra_order));
     HIP_OK(hipMemcpy(intra_order_, order.data(), sizeof(uint32_t) * order.size(), hipMemcpyHostToDevice));
   }
-  { const size_t nctu = (size_t)(cw_ / 64) * rows_; HIP_OK(hipMalloc(&edge_col_, nctu * 128 * sizeof(uint32_t))); HIP_OK(hipMemset(edge_col_, 0, nctu * 128 * sizeof(uint32_t)));
-    HIP_OK(hipMalloc(&edge_row_, nctu * 32 * 8)); HIP_OK(hipMemset(edge_row_, 0, nctu * 32 * 8)); }      // (tagged words: generation 0 = never written)      // the CTUs' right columns (k_intra_recon)
-  HIP_OK(hipMalloc(&err_, sizeof(uint32_t))); HIP_OK(hipMemset(err_, 0, sizeof(uint32_t)));
-  if (getenv("KVAZZUP_AMD_INTRA_TRACE")) { HIP_OK(hipMalloc(&trace_, sizeof(unsigned long long) * (rows_ * (cw_ / 64) * 72))); HIP_OK(hipMemset(trace_, 0, sizeof(unsigned long long) * (rows_ * (cw_ / 64) * 72))); }
+  HIP_OK(mem_.dev(&err_, 1, true));
+  if (getenv("KVAZZUP_AMD_INTRA_TRACE")) HIP_OK(mem_.dev(&trace_, L.trace, true));
   int eth = cfg.entropy_threads;
   if (const char *e = getenv("KVAZZUP_AMD_ENTROPY_THREADS")) eth = atoi(e) < 1 ? 1 : atoi(e);     // tuning knob (containers with a small CPU quota)
   if (cfg.entropy_gpu) { entropy_ = nullptr; entropy2_ = nullptr; }
@@ -305,7 +256,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.scaling_list) {                                 // `scaling-list default`: the default lists' factors, once
     uint8_t tab[KVZ_SCALING_BYTES];
     scaling_factors(scaling_defaults(), tab);
-    HIP_OK(hipMalloc(&d_scaling_, KVZ_SCALING_BYTES)); HIP_OK(hipMemcpy(d_scaling_, tab, KVZ_SCALING_BYTES, hipMemcpyHostToDevice));
+    HIP_OK(mem_.dev(&d_scaling_, KVZ_SCALING_BYTES)); HIP_OK(hipMemcpy(d_scaling_, tab, KVZ_SCALING_BYTES, hipMemcpyHostToDevice));
   }
   // what every picture's frame starts from (picture_frame)
   EncFrame &b = base_;
@@ -314,13 +265,12 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   b.row0 = cfg.band_rows > 0 ? cfg.band_row0 : 0; b.nrows = cfg.band_rows > 0 ? cfg.band_rows : 0;
   b.range = cfg.me_range; b.scaling = d_scaling_; b.intra_chain = cfg.intra_chain;
   b.lossless = cfg.lossless; b.rdoq = cfg.rdoq; b.signhide = cfg.signhide; b.intra_p = cfg.intra_in_p;
-  if (me_cost16_) point_me_block(b, me_cost16_);
+  if (me_cost16_) point_me_block(b, L, me_cost16_);
   b.wpp = cfg.wpp; b.mv_frame = cfg.mv_frame; b.me_early = cfg.me_early; b.satd = cfg.satd; b.subme = cfg.subme; b.slices = cfg.slices;
   uint8_t *p = intra_scratch_;
-  b.ic8 = (uint32_t *)p; p += nb8 * 4; b.ic16 = (uint32_t *)p; p += nb8; b.ic32 = (uint32_t *)p; p += nb8 / 4;
-  b.im8 = p; p += nb8; b.im16 = p; p += nb8 / 4; b.im32 = p;
-  b.tok_buf = tok_buf_; b.tok_cap = tok_cap_; b.tok_seg = tok_seg_; b.tok_list = tok_list_; b.tok_dense_cap = (uint32_t)tok_dense_cap_;
-  point_chain(b, sync_, edge_col_, edge_row_);
+  b.ic8 = (uint32_t *)p; b.ic16 = (uint32_t *)(p + L.ic16_off); b.ic32 = (uint32_t *)(p + L.ic32_off); b.im8 = p + L.im8_off; b.im16 = p + L.im16_off; b.im32 = p + L.im32_off;
+  b.tok_buf = tok_buf_; b.tok_cap = L.tok_cap; b.tok_seg = tok_seg_; b.tok_list = tok_list_; b.tok_dense_cap = (uint32_t)L.tok_dense_cap;
+  point_chain(b, L, chain_);
   b.err = err_; b.trace = trace_; b.intra_order = intra_order_;
   // (a synchronous encoder: the cap that keeps the search from holding every wave slot protects nobody -- 185 -> 142 us of an intra picture's encoding delay
   // at 1080p; band mode keeps the cap)
@@ -349,60 +299,19 @@ namespace { struct Tick { std::chrono::steady_clock::time_point t0 = std::chrono
 Encoder::~Encoder()
 {
   if (getenv("KVAZZUP_AMD_TRACE")) fprintf(stderr, "kvazzup_amd encoder thread ms: submit %.1f  wait_gpu %.1f  arith %.1f  assemble %.1f  wait_input %.1f  (pictures %ld)\n", t_submit_, t_wait_, t_arith_, t_asm_, t_in_, collected_);
-  { std::lock_guard<std::mutex> l(sm_); squit_ = true; }
-  scv_.notify_all();
-  if (sub_thread_.joinable()) sub_thread_.join();
-  { std::lock_guard<std::mutex> l(tm_); tquit_ = true; }
-  tcv_.notify_all();
-  if (tok_thread_.joinable()) tok_thread_.join();           // (what it still had queued has gone to the workers)
-  { std::lock_guard<std::mutex> l(bm_); bquit_ = true; }
-  bcv_.notify_all();
-  for (auto &t : bg_) if (t.joinable()) t.join();
-  if (stream_) hipStreamSynchronize(stream_);
-  if (stream_idr_ && stream_idr_ != stream_in_) hipStreamSynchronize(stream_idr_);
-  if (stream_tok_) hipStreamSynchronize(stream_tok_);
-  if (stream_in_) hipStreamSynchronize(stream_in_);
-  for (Slot &sl : slot_) {
-    for (auto &e : sl.ev) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
-    if (sl.sink_done) { hipEventSynchronize(sl.sink_done); hipEventDestroy(sl.sink_done); }
-    if (sl.h_tok_dense) hipHostFree(sl.h_tok_dense);
-    if (sl.h_tok_count) hipHostFree(sl.h_tok_count);
-    if (sl.h_err) hipHostFree(sl.h_err);
-    if (sl.h_wp) hipHostFree(sl.h_wp);
-    if (sl.h_sc) hipHostFree(sl.h_sc);
-    if (sl.h_tok_off) hipHostFree(sl.h_tok_off);
-    stream_release(sl.ent_stream, cfg_.device, 'E', 'l');
-    if (sl.tok_ev) hipEventDestroy(sl.tok_ev);
-    hipFree(sl.g_tok); hipFree(sl.g_count); hipFree(sl.g_off); hipFree(sl.g_stage); hipFree(sl.g_cursors); hipFree(sl.g_ctx_save); hipFree(sl.g_ctx_ready);
-    if (sl.h_out) hipHostFree(sl.h_out);
-    if (sl.h_sub) hipHostFree(sl.h_sub);
-    if (sl.done) hipEventDestroy(sl.done);
-    if (sl.rec_done) hipEventDestroy(sl.rec_done);
-  }
-  if (in_done_) hipEventDestroy(in_done_);
-  for (int k = 0; k < kInRing; k++) { hipFree(d_in_[k]); if (h_in_[k]) hipHostFree(h_in_[k]); if (ev_h2d_[k]) hipEventDestroy(ev_h2d_[k]); if (ev_pad_[k]) hipEventDestroy(ev_pad_[k]); }
+  auto stop = [](std::mutex &m, bool &quit, std::condition_variable &cv) { { std::lock_guard<std::mutex> l(m); quit = true; } cv.notify_all(); };
+  stop(sm_, squit_, scv_); if (sub_thread_.joinable()) sub_thread_.join();
+  stop(tm_, tquit_, tcv_); if (tok_thread_.joinable()) tok_thread_.join();           // (what it still had queued has gone to the workers)
+  stop(bm_, bquit_, bcv_); for (auto &t : bg_) if (t.joinable()) t.join();
+  for (hipStream_t st : {stream_, stream_idr_ != stream_in_ ? stream_idr_ : nullptr, stream_tok_, stream_in_}) if (st) hipStreamSynchronize(st);
+  for (Slot &sl : slot_) { if (sl.ent_stream) hipStreamSynchronize(sl.ent_stream); if (sl.sink_done) hipEventSynchronize(sl.sink_done); }      // (the coders' streams; the copies into the caller's pictures)
+  mem_.release();
+  delete entropy_; delete entropy2_;
+  for (Slot &sl : slot_) stream_release(sl.ent_stream, cfg_.device, 'E', 'l');
   stream_release(stream_rec_, cfg_.device, 'R', 'n');
-  for (int c = 0; c < 3; c++) { for (int k = 0; k < kSets; k++) { hipFree(src_[k][c]); hipFree(coef_[k][c]); } for (int b = 0; b < kRecRing; b++) hipFree(rec_[b][c]); }
-  hipFree(vaq_act_); hipFree(vaq_sum_); hipFree(rc_state_);
-  for (int k = 0; k < kSets; k++) { hipFree(ctu_qt_[k]); hipFree(ctu_qy_[k]); hipFree(ctu_delta_[k]); hipFree(ctu_first_[k]); if (h_ctu_qt_[k]) hipHostFree(h_ctu_qt_[k]); hipFree(ctu_roi_[k]); }
-  for (int k = 0; k < kSets; k++) { hipFree(cu_bytes_[k]); hipFree(cu_mv_[k]); hipFree(cu_mvd_[k]); if (cu_ref_[k]) hipFree(cu_ref_[k]); if (col_[k]) hipFree(col_[k]); if (mc_q_[k]) hipFree(mc_q_[k]); if (mc_centres_[k]) hipFree(mc_centres_[k]); if (ev_tok_done_[k]) hipEventDestroy(ev_tok_done_[k]); }
-  for (int k = 0; k < kSets; k++) { hipFree(wp_partial_[k]); hipFree(wp_stat_[k]); hipFree(wp_rec_[k]); }
-  hipFree(wp_cand_); hipFree(wp_acc_); for (int r = 0; r < KVZ_MAX_LP_REFS; r++) hipFree(wp_plane_[r]);
-  for (int k = 0; k < kSets; k++) hipFree(sc_sum_[k]);
-  hipFree(sc_blocks_); hipFree(sc_count_); hipFree(sc_rec_); if (ev_sc_) hipEventDestroy(ev_sc_);
-  for (int c = 0; c < 3; c++) { hipFree(work_[c]); hipFree(work_idr_[c]); }
-  hipFree(sync_idr_); hipFree(edge_col_idr_); hipFree(edge_row_); hipFree(edge_row_idr_);
-  for (int k = 0; k < kSets; k++) hipFree(sao_[k]);
-  if (ev_signalled_) hipEventDestroy(ev_signalled_);
-  for (int k = 0; k < kSets; k++) if (ev_src_free_[k]) hipEventDestroy(ev_src_free_[k]);
   stream_release(stream_tok_, cfg_.device, 'T', prio_[1]);
   stream_release(stream_in_, cfg_.device, 'I', prio_[2]);
   if (stream_idr_ && stream_idr_ != stream_in_) stream_release(stream_idr_, cfg_.device, 'X', prio_[0]);
-  if (ev_idr_done_) hipEventDestroy(ev_idr_done_);
-  hipFree(intra_scratch_); hipFree(d_scaling_);
-  delete entropy_; delete entropy2_;
-  for (int k = 0; k < kSets; k++) { hipFree(me_block_[k]); hipFree(sync_set_[k]); }
-  hipFree(trace_); hipFree(intra_order_); hipFree(tok_buf_); hipFree(tok_count_); hipFree(tok_seg_); hipFree(tok_list_); hipFree(sync_); hipFree(me_cost16_); hipFree(edge_col_); hipFree(err_);
   stream_release(stream_, cfg_.device, 'M', prio_[0]);
 }
 
@@ -411,7 +320,7 @@ void Encoder::timed_slot(Slot &sl, bool prof, KernelId id, hipStream_t st, const
 {
   if (!prof) { launch(); return; }
   if (sl.ev_used == sl.ev.size()) {
-    EvPair p; hipEventCreate(&p.a); hipEventCreate(&p.b); p.id = id; sl.ev.push_back(p);
+    EvPair p; mem_.event(&p.a, hipEventDefault); mem_.event(&p.b, hipEventDefault); p.id = id; sl.ev.push_back(p);
   }
   EvPair &p = sl.ev[sl.ev_used++]; p.id = id;
   hipEventRecord(p.a, st);
@@ -446,12 +355,12 @@ bool Encoder::upload_and_submit(const uint8_t *y, const uint8_t *u, const uint8_
   // of 5200 frames/s at 1080p); a stream at the lowest level has a queue to itself and measured no better for the encoder alone, worse with
   // the decoder beside it.
   if (!d_in_[k]) {
-    HIP_CHECK(hipMalloc(&d_in_[k], bytes));
-    HIP_CHECK(hipEventCreateWithFlags(&ev_h2d_[k], hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ev_pad_[k], hipEventDisableTiming));
+    HIP_CHECK(mem_.dev(&d_in_[k], bytes));
+    HIP_CHECK(mem_.event(&ev_h2d_[k], hipEventDisableTiming)); HIP_CHECK(mem_.event(&ev_pad_[k], hipEventDisableTiming));
   }
   const uint8_t *src = y;
   if (!pinned) {
-    if (!h_in_[k]) HIP_CHECK(hipHostMalloc(&h_in_[k], bytes, hipHostMallocDefault));
+    if (!h_in_[k]) HIP_CHECK(mem_.pinned(&h_in_[k], bytes, hipHostMallocDefault));
     if (h2d_pending_[k]) { Tick tk; HIP_CHECK(hipEventSynchronize(ev_h2d_[k])); h2d_pending_[k] = false; t_in_ += tk.ms(); }   // the staging buffer's last upload
     if (packed) memcpy(h_in_[k], y, bytes);
     else { memcpy(h_in_[k], y, ny); memcpy(h_in_[k] + ny, u, ny / 4); memcpy(h_in_[k] + ny + ny / 4, v, ny / 4); }
@@ -629,9 +538,9 @@ bool Encoder::stage_roi(hipStream_t st)
 uint32_t Encoder::next_chain_gen()
 {
   if (++chain_gen_ >= (1u << 24)) {
-    const size_t bytes = (size_t)(cw_ / 64) * rows_ * 128 * sizeof(uint32_t);
-    hipMemsetAsync(edge_col_, 0, bytes, stream_); hipMemsetAsync(edge_row_, 0, bytes / 2, stream_);
-    if (edge_col_idr_) { hipMemsetAsync(edge_col_idr_, 0, bytes, stream_idr_); hipMemsetAsync(edge_row_idr_, 0, bytes / 2, stream_idr_); }
+    const size_t col = lay_.edge_col * sizeof(uint32_t), row = lay_.edge_row * sizeof(unsigned long long);
+    hipMemsetAsync(chain_.edge_col, 0, col, stream_); hipMemsetAsync(chain_.edge_row, 0, row, stream_);
+    if (chain_idr_.edge_col) { hipMemsetAsync(chain_idr_.edge_col, 0, col, stream_idr_); hipMemsetAsync(chain_idr_.edge_row, 0, row, stream_idr_); }
     chain_gen_ = 1;
   }
   return chain_gen_;
@@ -651,7 +560,7 @@ bool Encoder::picture_begin(const EncFrame &f, hipStream_t qt_stream, EncFrame *
   // (an intra picture, `zero`: the launch also takes the chain's two arrays back to zero -- the ticket counter's array with the "has intra units" word of the
   // P pictures behind it, which no P picture has pending while an intra picture starts on these arrays, and the CU cbf bits)
   void *za = zero ? (void *)f.sync : nullptr, *zb = zero ? (void *)f.cu_cbf : nullptr;
-  const size_t na = zero ? sizeof(uint32_t) * (((size_t)rows_ * (cw_ / 64) * 3 + 2 + 3) & ~(size_t)3) : 0, nb = zero ? (size_t)f.b8w * f.b8h : 0;
+  const size_t na = zero ? sizeof(uint32_t) * lay_.sync : 0, nb = zero ? (size_t)f.b8w * f.b8h : 0;
   if (qt_stream == stream_) launch_picture_begin(rc_state_, bits3, slot3, have ? 1 : 0, qt, roi_dev_, n, f.qp, cfg_.vaq > 0 ? 1 : 0, stream_, za, na, zb, nb);
   else {
     // an intra picture on its side stream: the rate control state is updated in PICTURE ORDER on the main stream (between the P pictures' row groups, which
@@ -723,18 +632,17 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
 {
   EncFrame f = base_;
   const int k = set_;
-  const size_t nb8 = (size_t)cw_ * ch_ / 64;
   uint8_t *cu = cu_bytes_[k];
   for (int c = 0; c < 3; c++) { f.coef[c] = coef_[k][c]; f.src[c] = src_[k][c]; }
-  f.cu_log2 = cu; f.cu_intra = cu + nb8; f.cu_flags = cu + 2 * nb8; f.cu_merge_idx = cu + 3 * nb8;
-  f.cu_mvp_idx = cu + 4 * nb8; f.cu_intra_mode = cu + 5 * nb8; f.cu_cbf = cu + 6 * nb8;
+  f.cu_log2 = cu; f.cu_intra = cu + lay_.cu_off(1); f.cu_flags = cu + lay_.cu_off(2); f.cu_merge_idx = cu + lay_.cu_off(3);
+  f.cu_mvp_idx = cu + lay_.cu_off(4); f.cu_intra_mode = cu + lay_.cu_off(5); f.cu_cbf = cu + lay_.cu_off(6);
   f.cu_mv = cu_mv_[k]; f.cu_mvd = cu_mvd_[k];
   f.cu_ref = cu_ref_[k];                              // NULL with one reference
   f.sao = sao_[k];                                    // NULL without SAO
   f.ctu_qt = ctu_qt_[k]; f.ctu_qy = ctu_qy_[k]; f.ctu_delta = ctu_delta_[k]; f.ctu_first = ctu_first_[k];     // all NULL without qp_in_cu
   f.qp = p.qp; f.qpc = kChromaQp[p.qp]; f.lambda_q4 = kLambdaQ4[p.qp];
   f.is_intra = p.intra; f.poc = poc_;
-  for (int c = 0; c < 3; c++) { f.rec[c] = cfg_.sao ? work_[c] : rec_[cur_idx_][c]; f.sao_out[c] = rec_[cur_idx_][c]; f.ref[c] = rec_[ref_idx_][c]; }
+  for (int c = 0; c < 3; c++) { f.rec[c] = cfg_.sao ? chain_.work[c] : rec_[cur_idx_][c]; f.sao_out[c] = rec_[cur_idx_][c]; f.ref[c] = rec_[ref_idx_][c]; }
   // me-source: the search looks at the previous input picture (still in its working set: the set is not padded into again before kSets - 1 more pictures have
   // gone through the input stream, behind this picture's k_me), and what the search and the intra pricing behind it write is the set's own
   f.me_ref = p.ahead ? src_[prev_set_][0] : f.ref[0];
@@ -762,14 +670,14 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   if (p.ir_e) { f.ir_j = p.ir_j; f.ir_s = p.ir_s; f.ir_e = p.ir_e; f.ir_free = ir_free_ ? 1 : 0; }      // intra-refresh: the picture's band
   if (wp_rec_[k] && !p.intra) f.wp = wp_rec_[k];       // weightp: the record k_wp_decide writes on the input stream, in front of everything that reads it
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
-  if (p.ahead && me_block_[k]) { point_me_block(f, me_block_[k]); f.sync = sync_set_[k]; }
+  if (p.ahead && me_block_[k]) { point_me_block(f, lay_, me_block_[k]); f.sync = sync_set_[k]; }
   f.tok_dense = sl.d_tok_dense; f.tok_count_out = sl.d_tok_count; f.tok_off_out = sl.d_tok_off; f.err_out = sl.d_err; f.ent_cursors = sl.g_cursors;
-  f.tok_cursor = (uint32_t *)tok_count_ + (size_t)(frame_idx_ & 1) * tok_nctu_; f.tok_cursor_next = (uint32_t *)tok_count_ + (size_t)((frame_idx_ + 1) & 1) * tok_nctu_;
+  f.tok_cursor = (uint32_t *)tok_count_ + (size_t)(frame_idx_ & 1) * lay_.nctu; f.tok_cursor_next = (uint32_t *)tok_count_ + (size_t)((frame_idx_ + 1) & 1) * lay_.nctu;
   f.chain_gen = chain_gen;
   if (p.side) {                                       // beside the P pictures still on the main stream: nothing of theirs is touched
-    point_chain(f, sync_idr_, edge_col_idr_, edge_row_idr_);
+    point_chain(f, lay_, chain_idr_);
     f.me_cand = nullptr;                              // (me_cand NULL: the picture's deblocking kernel leaves the P pictures' candidate list and "has intra units" word alone)
-    if (cfg_.sao) for (int c = 0; c < 3; c++) f.rec[c] = work_idr_[c];
+    if (cfg_.sao) for (int c = 0; c < 3; c++) f.rec[c] = chain_idr_.work[c];
   }
   return f;
 }
@@ -966,7 +874,7 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
     HIP_CHECK(hipStreamWaitEvent(sl.ent_stream, sl.tok_ev, 0));
     const int nsub = cfg_.wpp ? rows_ : cfg_.tile_rows;
     CabacRowsArgs a;
-    a.tok = sl.g_tok; a.count = sl.g_count; a.off = sl.g_off; a.stage = sl.g_stage; a.stage_cap = (uint32_t)stage_cap_; a.out = sl.d_out; a.out_cap = (uint32_t)out_cap_;
+    a.tok = sl.g_tok; a.count = sl.g_count; a.off = sl.g_off; a.stage = sl.g_stage; a.stage_cap = (uint32_t)lay_.stage_cap; a.out = sl.d_out; a.out_cap = (uint32_t)lay_.out_cap;
     a.cursors = sl.g_cursors; a.sub_off = sl.d_sub; a.sub_len = sl.d_sub + rows_; a.sub_bins = sl.d_sub + 2 * rows_;
     a.ctx_save = sl.g_ctx_save; a.ctx_ready = sl.g_ctx_ready; a.gen = ++sl.gen; a.err = err_;
     a.wc = cw_ / 64; a.hc = rows_; a.wpp = cfg_.wpp; a.tile_rows = cfg_.tile_rows; a.init_type = p.intra ? 0 : 1; a.qp = f.qp; a.first_sub = 0;
@@ -980,7 +888,7 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
   if (sink_sub_[0] && in_ring >= 0) {                      // (host pictures only: set_recon_sink)
     // the reconstruction is final behind the chain's last kernel: rec_done, with SAO the event behind the filter
     if (!stream_rec_) HIP_CHECK(stream_acquire(&stream_rec_, cfg_.device, 'R', 'n'));
-    if (!sl.sink_done) HIP_CHECK(hipEventCreateWithFlags(&sl.sink_done, hipEventDisableTiming));
+    if (!sl.sink_done) HIP_CHECK(mem_.event(&sl.sink_done, hipEventDisableTiming));
     HIP_CHECK(hipStreamWaitEvent(stream_rec_, cfg_.sao ? ev_src_free_[set_] : sl.rec_done, 0));
     for (int c = 0; c < 3; c++) {
       const int pw = c ? cfg_.width / 2 : cfg_.width, ph = c ? cfg_.height / 2 : cfg_.height, cp = c ? cw_ / 2 : cw_;
@@ -1119,7 +1027,7 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
     rows_out.resize((size_t)nsub);
     const uint32_t *off = sl.h_sub, *len = sl.h_sub + rows_, *nb = sl.h_sub + 2 * rows_;
     for (int k = 0; k < nsub; k++) {
-      if (len[k] == ~0u || (size_t)off[k] + len[k] > out_cap_) { fprintf(stderr, "kvazzup_amd: substream %d was not coded (token or output buffer overflow)\n", k); return false; }
+      if (len[k] == ~0u || (size_t)off[k] + len[k] > lay_.out_cap) { fprintf(stderr, "kvazzup_amd: substream %d was not coded (token or output buffer overflow)\n", k); return false; }
       rows_out[(size_t)k].assign(sl.h_out + off[k], sl.h_out + off[k] + len[k]);
       bins += nb[k];
     }
@@ -1210,7 +1118,7 @@ bool Encoder::band_phase1(const uint8_t *d_i420)
   launch_pad_input(d_i420, cfg_.width, cfg_.height, src_[0][0], src_[0][1], src_[0][2], cw_, ch_, stream_);
   if (f.is_intra) {
     launch_intra_analyse(f, stream_);
-    HIP_CHECK(hipMemsetAsync(sync_, 0, sizeof(uint32_t) * (rows_ * (cw_ / 64) * 3 + 1), stream_));
+    HIP_CHECK(hipMemsetAsync(chain_.sync, 0, sizeof(uint32_t) * (rows_ * (cw_ / 64) * 3 + 1), stream_));
     HIP_CHECK(hipMemsetAsync(f.cu_cbf + (size_t)f.row0 * 8 * f.b8w, 0, (size_t)f.b8w * 8 * band_rows(f), stream_));
     launch_intra_recon(f, stream_);
   } else {
@@ -1326,24 +1234,23 @@ bool Encoder::download_recon(uint8_t *y, uint8_t *u, uint8_t *v)
 
 bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
 {
-  const size_t npx = (size_t)cw_ * ch_, nb8 = npx / 64;
   const void *src = nullptr; size_t have = 0;
   std::string w(what);
   static const char *names[7] = {"cu_log2", "cu_intra", "cu_flags", "cu_merge_idx", "cu_mvp_idx", "cu_intra_mode", "cu_cbf"};
-  for (int i = 0; i < 7; i++) if (w == names[i]) { src = cu_bytes_[out_set_] + i * nb8; have = nb8; }
+  for (int i = 0; i < 7; i++) if (w == names[i]) { src = cu_bytes_[out_set_] + lay_.cu_off(i); have = lay_.nb8; }
   if (w == "lp_gop") { if (bytes > sizeof(out_gop_)) return false; memcpy(dst, out_gop_, bytes); return true; }      // (host values: no copy from the device)
   if (w == "ir") { if (!cfg_.intra_refresh || bytes > sizeof(out_ir_)) return false; memcpy(dst, out_ir_, bytes); return true; }      // (host values)
   if (w == "wp") { if (!cfg_.weightp || bytes > sizeof(out_wp_)) return false; memcpy(dst, out_wp_, bytes); return true; }      // (host values, as the slice headers said them)
   if (w == "scenecut") { if (!cfg_.scenecut || bytes > sizeof(out_sc_)) return false; memcpy(dst, out_sc_, bytes); return true; }      // (host values, as submit() read or wrote them)
-  if (w == "sc_blocks" && sc_blocks_) { int bw, bh; sc_visible_blocks(cfg_.width, cfg_.height, &bw, &bh); src = sc_blocks_; have = (size_t)bw * bh * 2 * sizeof(uint32_t); }      // (the picture last examined: its kernels are done, submit() waited for them)
-  if (w == "cu_mv") { src = cu_mv_[out_set_]; have = nb8 * 4; }
-  if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = nb8 * 4; }
-  if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? nb8 : 0; }
-  if (w == "me_coarse") { src = mc_centres_[out_set_]; have = mc_centres_[out_set_] ? (size_t)KVZ_MAX_LP_REFS * (nb8 / 16) * 2 * sizeof(int16_t) : 0; }
-  if (w == "col") { src = col_[out_set_]; have = col_[out_set_] ? nb8 / 4 * sizeof(ColMv) : 0; }
-  if (w == "trace" && trace_) { src = trace_; have = sizeof(unsigned long long) * (rows_ * (cw_ / 64) * 72); }
+  if (w == "sc_blocks" && sc_blocks_) { src = sc_blocks_; have = lay_.sc_blocks * sizeof(uint32_t); }      // (the picture last examined: its kernels are done, submit() waited for them)
+  if (w == "cu_mv") { src = cu_mv_[out_set_]; have = lay_.cu_mv * sizeof(int16_t); }
+  if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = lay_.cu_mv * sizeof(int16_t); }
+  if (w == "cu_ref") { src = cu_ref_[out_set_]; have = cu_ref_[out_set_] ? lay_.nb8 : 0; }
+  if (w == "me_coarse") { src = mc_centres_[out_set_]; have = mc_centres_[out_set_] ? lay_.mc_centres * sizeof(int16_t) : 0; }
+  if (w == "col") { src = col_[out_set_]; have = col_[out_set_] ? lay_.col * sizeof(ColMv) : 0; }
+  if (w == "trace" && trace_) { src = trace_; have = lay_.trace * sizeof(unsigned long long); }
   for (int c = 0; c < 3; c++) {
-    size_t n = c ? npx / 4 : npx;
+    size_t n = lay_.plane(c);
     if (w == std::string("coef") + char('0' + c)) { src = coef_[out_set_][c]; have = n * 2; }
     if (w == std::string("rec") + char('0' + c)) { src = rec_[out_idx_][c]; have = n; }
     if (w == std::string("src") + char('0' + c)) { src = src_[out_set_][c]; have = n; }

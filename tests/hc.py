@@ -43,7 +43,7 @@ def _declare(L):
         "hw_sample": (I, [I] * 3), "hw_pred14": (I, [I] * 3), "hw_decide": (None, [P, P, I, I, I, P]),
         "hi_step": (I, [I, I]), "hi_cycle": (I, [I, I]), "hi_band": (None, [I] * 3 + [P]), "hi_position": (I, [I] * 3), "hi_forced_quarters": (I, [I] * 3),
         "hi_clean_block": (I, [I] * 3), "hi_mvx_max": (I, [I, I]), "hi_last_column": (I, [I] * 4), "hi_schedules": (None, [I, P]), "hi_bands": (I, [I, I, P]),
-        "hd_input_layout": (None, [I] * 3 + [U64] * 3 + [I, P, P]),
+        "hd_input_layout": (None, [I] * 3 + [U64] * 3 + [I, P, P]), "he_layout": (None, [I] * 3 + [P]),
         # coder.cpp
         "hcr_play": (I, [I, P, P, P, I, P, P, I, P, P]), "hcr_code_picture": (I, [I, I, P, P, P] + [I] * 7 + [P, I, P, I, P]),
         "hcr_code_band": (I, [I, I, P, P, P] + [I] * 8 + [P, I, P, I, P]), "hcr_bench": (D, [P, LONG, I, I, I]),
@@ -265,3 +265,19 @@ def input_layout(pw, ph, ctb_log2, ntu, nlev, nb4x, bi):
     out, sizes = np.zeros(14, np.uint64), np.zeros(8, np.uint64)
     lib().hd_input_layout(pw, ph, ctb_log2, ntu, nlev, nb4x, int(bi), out.ctypes.data, sizes.ctypes.data)
     return dict(zip(LAYOUT_PARTS, map(int, out[:12]))), int(out[12]), int(out[13]), dict(zip(LAYOUT_SIZES, map(int, sizes)))
+
+
+ENC_LAYOUT = ("cw", "ch", "rows", "npx", "nb8", "n16", "nctu", "plane0", "plane1", "cu_bytes", "cu_mv", "col", "mc_q", "mc_centres", "sc_blocks", "sync", "edge_col", "edge_row",
+              "me_block", "intra_scratch", "intra_order", "trace", "tok_cap", "tok_buf", "tok_count", "tok_seg", "tok_list", "tok_dense_cap", "stage_cap", "out_cap",
+              "ctx_save", "sub", "me_cand_off", "ip_arrive_off", "ip_scratch_off", "ic16_off", "ic32_off", "im8_off", "im16_off", "im32_off", "edge_col_off1", "edge_col_off2")
+
+
+def enc_layout(width, height, band_rows=0):
+    """enc_layout.h EncLayout -> {name: count, cap or offset}; "edge_col_off" / "edge_row_off": the three planes' offsets, "cu_off": the seven CU arrays'"""
+    out = np.zeros(52, np.uint64)
+    lib().he_layout(width, height, band_rows, out.ctypes.data)
+    d = dict(zip(ENC_LAYOUT, map(int, out[:42])))
+    d["edge_col_off"] = [0, d.pop("edge_col_off1"), d.pop("edge_col_off2")]
+    d["edge_row_off"] = [int(v) for v in out[42:45]]
+    d["cu_off"] = [int(v) for v in out[45:52]]
+    return d

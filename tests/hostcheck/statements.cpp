@@ -2,10 +2,11 @@
 // restatements: me-coarse's arithmetic (me_*: the quarter sample, the coarse stage's cost, key and centre, the admissibility rule, the second-window rule and
 // the fine stage's candidate order; the loops around them are plain C++ here, the kernels' are lanes and LDS windows; tests/me_coarse_model.py), weightp's
 // (wp_*; tests/wp_model.py) and intra-refresh's (ir_*; tests/ir_model.py); and of the decoder's input-block layout (dec_frame.h DecInputLayout;
-// tests/test_dec_input_layout.py).  Test infrastructure.
+// tests/test_dec_input_layout.py) and the encoder's array lengths and partitions (enc_layout.h EncLayout; tests/test_enc_layout.py).  Test infrastructure.
 #include <cstring>
 #include "../../kvazzup_amd/csrc/hevc_core.h"
 #include "../../kvazzup_amd/csrc/dec_frame.h"
+#include "../../kvazzup_amd/csrc/enc_layout.h"
 
 using namespace kvzx;
 
@@ -146,6 +147,21 @@ void hd_input_layout(int pw, int ph, int ctb_log2, uint64_t ntu, uint64_t nlev, 
   const size_t z[8] = {sizeof(B4Rec), sizeof(TuRange), sizeof(SaoParams), KVZ_SCALING_BYTES, sizeof(DecWt), sizeof(DecFrame), sizeof(DecTu), sizeof(B4L1)};
   for (int i = 0; i < 14; i++) out[i] = o[i];
   for (int i = 0; i < 8; i++) sizes[i] = z[i];
+}
+
+// ---- the encoder's arrays (enc_layout.h EncLayout) of a width x height encoder, band_rows > 0: a band of that many CTU rows.  out[0..41], in the order of
+// tests/hc.py ENC_LAYOUT: the coded size, the counts (elements of each array's type), the caps, and the offsets of the parts of the arrays that are cut up;
+// out[42..44] the three planes' edge-row offsets, out[45..51] the seven CU arrays' offsets
+void he_layout(int width, int height, int band_rows, uint64_t *out)
+{
+  const EncLayout l(width, height, band_rows);
+  const size_t o[42] = {(size_t)l.cw, (size_t)l.ch, (size_t)l.rows, l.npx, l.nb8, l.n16, l.nctu, l.plane(0), l.plane(1), l.cu_bytes, l.cu_mv, l.col, l.mc_q, l.mc_centres,
+                        l.sc_blocks, l.sync, l.edge_col, l.edge_row, l.me_block, l.intra_scratch, l.intra_order, l.trace, (size_t)l.tok_cap, l.tok_buf, l.tok_count, l.tok_seg,
+                        l.tok_list, l.tok_dense_cap, l.stage_cap, l.out_cap, l.ctx_save, l.sub,
+                        l.me_cand_off, l.ip_arrive_off, l.ip_scratch_off, l.ic16_off, l.ic32_off, l.im8_off, l.im16_off, l.im32_off, l.edge_col_off(1), l.edge_col_off(2)};
+  for (int i = 0; i < 42; i++) out[i] = o[i];
+  for (int c = 0; c < 3; c++) out[42 + c] = l.edge_row_off(c);
+  for (int i = 0; i < 7; i++) out[45 + i] = l.cu_off(i);
 }
 
 }

@@ -9,12 +9,21 @@ from enckit import diagnose as _diagnose
 SEED = 0x5EED0000
 
 
-def run_clip(w, h, frames, qp, period, me_range, kind, wpp=1, deblock=1, via_picture=True, tile_rows=1, sao=0, mv_frame=0, vaq=0, gpu_entropy=0, subme=0, me_early=1, slices=0):
+def run_clip(w, h, frames, qp, period, me_range, kind, wpp=1, deblock=1, via_picture=True, tile_rows=1, sao=0, mv_frame=0, vaq=0, gpu_entropy=0, subme=0, me_early=1, slices=0, profiling=0, trace=0):
+    """profiling: kernel times taken between event pairs (set_profiling); trace: the encoder opened with KVAZZUP_AMD_INTRA_TRACE set, its kernels stamping into the trace array"""
+    import os
     from kvazzup_amd.codec import Encoder
     oe = orc.OracleEncoder(w, h, qp=qp, period=period, me_range=me_range, wpp=wpp, deblock=deblock, tile_rows=tile_rows, sao=sao, mv_frame=mv_frame, vaq=vaq, subme=subme, me_early=me_early, slices=slices)
-    ge = Encoder(w, h, options=(("qp", qp), ("period", period), ("me-range", me_range), ("wpp", wpp), ("deblock", deblock), ("tiles", "1x%d" % tile_rows),
-                                ("sao", "full" if sao else "off"), ("mv-constraint", ("none", "frame", "frametilemargin")[mv_frame]), ("gpu-entropy", gpu_entropy), ("slices", ("none", "wpp", "tiles")[slices]), ("subme", subme), ("me-early-termination", "on" if me_early else "off")) + ((('vaq', vaq),) if vaq else ()))
+    if trace:
+        os.environ["KVAZZUP_AMD_INTRA_TRACE"] = "1"       # (read when the encoder is opened)
+    try:
+        ge = Encoder(w, h, options=(("qp", qp), ("period", period), ("me-range", me_range), ("wpp", wpp), ("deblock", deblock), ("tiles", "1x%d" % tile_rows),
+                                    ("sao", "full" if sao else "off"), ("mv-constraint", ("none", "frame", "frametilemargin")[mv_frame]), ("gpu-entropy", gpu_entropy), ("slices", ("none", "wpp", "tiles")[slices]), ("subme", subme), ("me-early-termination", "on" if me_early else "off")) + ((('vaq', vaq),) if vaq else ()))
+    finally:
+        os.environ.pop("KVAZZUP_AMD_INTRA_TRACE", None)
     assert not ge.rejected, ge.rejected
+    if profiling:
+        ge.set_profiling(1)
     try:
         for t in range(frames):
             frame = orc.synth_frame(kind, SEED, w, h, t)
@@ -26,6 +35,10 @@ def run_clip(w, h, frames, qp, period, me_range, kind, wpp=1, deblock=1, via_pic
                     t, "I" if dbg_o["is_intra"] else "P", len(au_o), len(au_g), au_o == au_g,
                     np.array_equal(rec_g, oe.recon()), _diagnose(dbg_o, ge.debug_all())))
             assert ge.last_bins() == dbg_o["bins"]
+        if profiling:
+            assert sum(n for _, n in ge.kernel_times().values()) > 0, "profiling on, no kernel was timed"
+        if trace:
+            assert ge.debug("trace", np.uint64, (8,)).any(), "the IDR picture's chain left no stamp for its first CTU in the trace array"
     finally:
         ge.close()
         oe.close()
@@ -45,6 +58,8 @@ def run_clip(w, h, frames, qp, period, me_range, kind, wpp=1, deblock=1, via_pic
     dict(w=130, h=70, frames=3, qp=0, period=64, me_range=1, kind=2),
     dict(w=16, h=16, frames=3, qp=30, period=64, me_range=8, kind=0),        # smallest input the ABI accepts (coded 128x64)
     dict(w=3840, h=2160, frames=2, qp=32, period=64, me_range=16, kind=0),  # BASELINE configs[2] size: one IDR + one P against the checker
+    dict(w=192, h=128, frames=3, qp=32, period=64, me_range=8, kind=0, profiling=1),     # every launch between a pair of timing events (allocated on first use)
+    dict(w=192, h=128, frames=3, qp=32, period=64, me_range=8, kind=0, trace=1),         # KVAZZUP_AMD_INTRA_TRACE: the kernels stamp into the trace array
 ])
 def test_encoder_matches_oracle(gpu, cfg):
     run_clip(**cfg)

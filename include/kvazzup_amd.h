@@ -67,6 +67,21 @@ KVZ_PUBLIC int kvzx_decoder_last_error(OpenHevc_Handle h);
  * kvzx_decoder_debug_copy: "standin" = the buffer of the stand-in filled last (mode 3; Y | Cb | Cr, pitch = the coded width rounded up to 64),
  * "standin_mv" = its displacements, int16 [ceil(h / 16)][ceil(w / 16)][4]: luma dx, dy, chroma dx, dy. */
 KVZ_PUBLIC int kvzx_decoder_set_concealment(OpenHevc_Handle h, int mode);
+/* Partial pictures v1 (off by default): a picture that lost slice segments on the way is not thrown away -- the coding tree blocks that arrived
+ * are decoded, the others are filled from the nearest reference picture the way kvzx_decoder_set_concealment says (2: copied, 3: moved along its motion), and the
+ * picture is handed out in its turn and kept as a reference.  Built for one-tile pictures: the form a Kvazaar peer's slices=wpp sends (WPP, a dependent slice segment per CTU row: the
+ * rows before the lost one stay) and every other cut, free slices with or without WPP (gaps anywhere); pictures with tiles keep today's behaviour.  Call before the first picture; returns 1, or 0 after the first picture and on a band decoder
+ * (kvzx_decoder_set_band, which in turn is refused while this is on).
+ * kvzx_decoder_damage: the picture of the last libOpenHevcGetOutput -- coding tree blocks that were filled in, and how many it has (0 missing: whole); what an
+ * application needs to ask the sender for a refresh.  Returns 0 when there is no such picture.
+ * kvzx_decoder_damage_log: the runs (POC, first coding tree block, count) of all damaged pictures so far, in decoding order, up to `cap` triples; returns how many there
+ * are (also under kvzx_decoder_set_parse_only).
+ * kvzx_decoder_debug_copy: "partial_layout" = four bytes per coding tree block of the damaged picture filed last -- before the first one, of the picture parsed last -- (missing, its ctu_tile byte, its ctu_nb byte or 0xff,
+ * min(255, transform blocks)), "fill_mv" = the displacements used last, laid out like "standin_mv"; "take_backs" = uint32, pictures whose first segments looked complete, ended early and were
+ * opened again so far. */
+KVZ_PUBLIC int kvzx_decoder_set_partial_pictures(OpenHevc_Handle h, int on);
+KVZ_PUBLIC int kvzx_decoder_damage(OpenHevc_Handle h, int *missing_ctbs, int *total_ctbs);
+KVZ_PUBLIC int kvzx_decoder_damage_log(OpenHevc_Handle h, int32_t *triples, int cap);
 /* Test / measurement hook, not a decoding mode: before libOpenHevcStartDecoder.  The decoder then runs its HOST half only (NAL units, parameter sets, slice
  * headers, the CABAC slice-data parser with `parse_threads` row threads), touches no device and never outputs a picture (libOpenHevcDecode returns 0 or an
  * error).  kvzx_decoder_parse_probe_stats: out5 = pictures parsed, transform blocks, level words, FNV-1a digest of everything the parser produced, 0;

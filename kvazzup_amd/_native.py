@@ -108,7 +108,7 @@ DECODER_EXPORTS = ["libOpenHevcInit", "libOpenHevcStartDecoder", "libOpenHevcDec
                    "libOpenHevcSetDebugMode", "libOpenHevcSetTemporalLayer_id", "libOpenHevcSetNoCropping", "libOpenHevcSetActiveDecoders",
                    "libOpenHevcSetViewLayers", "libOpenHevcClose", "libOpenHevcFlush", "libOpenHevcVersion",
                    "kvzx_decoder_set_device", "kvzx_decoder_last_error", "kvzx_decoder_hash_stats", "kvzx_decoder_output_device", "kvzx_decoder_set_download", "kvzx_decoder_set_output_hold", "kvzx_decoder_set_profiling",
-                   "kvzx_decoder_kernel_times", "kvzx_decoder_kernel_name", "kvzx_decoder_debug_copy", "kvzx_decoder_set_concealment",
+                   "kvzx_decoder_kernel_times", "kvzx_decoder_kernel_name", "kvzx_decoder_debug_copy", "kvzx_decoder_set_concealment", "kvzx_decoder_set_partial_pictures", "kvzx_decoder_damage", "kvzx_decoder_damage_log",
                    "kvzx_decoder_set_band", "kvzx_decoder_band_halo_bytes", "kvzx_decoder_band_export", "kvzx_decoder_band_import", "kvzx_decoder_band_deblock", "kvzx_decoder_band_finish", "kvzx_decoder_band_ready"]
 
 
@@ -175,5 +175,8 @@ def load_library():
         L.kvzx_decoder_kernel_name.argtypes = [C.c_int]
         L.kvzx_decoder_debug_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]
         L.kvzx_decoder_set_concealment.argtypes = [C.c_void_p, C.c_int]
+        L.kvzx_decoder_set_partial_pictures.argtypes = [C.c_void_p, C.c_int]
+        L.kvzx_decoder_damage.argtypes = [C.c_void_p, _P(C.c_int), _P(C.c_int)]
+        L.kvzx_decoder_damage_log.argtypes = [C.c_void_p, _P(C.c_int32), C.c_int]
     _LIB = L
     return L

@@ -237,9 +237,10 @@ class Decoder:
 
     OH_THREAD_FRAME, OH_THREAD_SLICE = 1, 2
 
-    def __init__(self, threads=1, download=True, device=None, frame_threads=False, temporal_layer=7, no_cropping=False, concealment=2):
+    def __init__(self, threads=1, download=True, device=None, frame_threads=False, temporal_layer=7, no_cropping=False, concealment=2, partial_pictures=False):
         """concealment: what stands in for a lost reference picture -- 2 a copy of the nearest one, 3 that picture moved along its own motion (kvazzup_amd.h
-        kvzx_decoder_set_concealment)"""
+        kvzx_decoder_set_concealment); partial_pictures: a picture that lost slice segments keeps what arrived (kvzx_decoder_set_partial_pictures) -- every
+        picture handed out then carries "missing_ctbs" and "total_ctbs" """
         self.lib = N.load_library()
         self.threads, self.frame_threads = threads, bool(frame_threads) and threads > 1
         self.h = self.lib.libOpenHevcInit(threads, self.OH_THREAD_FRAME if frame_threads else self.OH_THREAD_SLICE)
@@ -249,6 +250,11 @@ class Decoder:
             self.lib.libOpenHevcClose(self.h)
             self.h = None
             raise ValueError("concealment mode %r (2 or 3)" % (concealment,))
+        self.partial_pictures = bool(partial_pictures)
+        if partial_pictures and not self.lib.kvzx_decoder_set_partial_pictures(self.h, 1):
+            self.lib.libOpenHevcClose(self.h)
+            self.h = None
+            raise ValueError("partial pictures were refused")
         if self.lib.libOpenHevcStartDecoder(self.h) == -1:
             self.lib.libOpenHevcClose(self.h)
             self.h = None
@@ -288,6 +294,10 @@ class Decoder:
         info = fr.frameInfo
         w, h = info.nWidth, info.nHeight
         out = {"width": w, "height": h, "fps": (info.frameRate.num, info.frameRate.den), "pts": info.nTimeStamp}
+        if getattr(self, "partial_pictures", False):                # (tests build a Decoder around a handle of their own, without __init__)
+            missing, total = C.c_int(), C.c_int()
+            if self.lib.kvzx_decoder_damage(self.h, C.byref(missing), C.byref(total)):
+                out["missing_ctbs"], out["total_ctbs"] = missing.value, total.value
         if self.download:
             ys, qs = info.nYPitch, info.nUPitch // 2
             y = np.empty((h, w), np.uint8)
@@ -325,6 +335,18 @@ class Decoder:
     def set_concealment(self, mode):
         """False: refused (a mode other than 2 and 3, or the first picture has been decoded)"""
         return bool(self.lib.kvzx_decoder_set_concealment(self.h, int(mode)))
+
+    def damage_log(self):
+        """[(POC, first coding tree block, count)] of every damaged picture so far, in decoding order (partial_pictures)"""
+        n = self.lib.kvzx_decoder_damage_log(self.h, None, 0)
+        buf = (C.c_int32 * (3 * max(n, 1)))()
+        n = min(n, self.lib.kvzx_decoder_damage_log(self.h, buf, n))
+        return [tuple(buf[3 * i:3 * i + 3]) for i in range(n)]
+
+    def fill_mv(self, w, h):
+        """partial pictures: the displacements the last fill used, laid out like standin()'s table; None before the first one"""
+        mv = np.empty(((h + 15) // 16, (w + 15) // 16, 4), np.int16)
+        return mv if self.lib.kvzx_decoder_debug_copy(self.h, b"fill_mv", mv.ctypes.data, mv.nbytes) else None
 
     def standin(self, w, h):
         """concealment 3: the stand-in filled last, (Y, Cb, Cr) at the coded size w x h, and its displacements [ceil(h / 16)][ceil(w / 16)][4]

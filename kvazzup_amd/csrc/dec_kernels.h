@@ -17,4 +17,5 @@ void launch_dec_sao_n(const DecFrame *const *h, const DecFrame *const *d, int n,
 // ---- conceal_kernels.hip: concealment v3's stand-in (decoder.h) -- the three planes of src (coded size w x h, luma pitch `pitch`) moved into dst by the table's
 // whole-sample displacements, one row (luma dx, dy, chroma dx, dy) per 16x16 luma block, d_tab in device memory
 void launch_dec_standin(uint8_t *const dst[3], uint8_t *const src[3], const int16_t *d_tab, int w, int h, int pitch, hipStream_t st);
+void launch_dec_fill_ctbs(uint8_t *const dst[3], uint8_t *const *src, const int16_t *d_tab, const uint32_t *d_ctbs, int n, int ctb_log2, int w, int h, int pitch, hipStream_t st);
 }  // namespace kvzx

@@ -1008,9 +1008,34 @@ int Decoder::parse_substream(PicJob &job, int sub, const uint8_t *data, size_t l
   };
   const int init_type = sh.is_intra ? 0 : (sh.is_b ? (sh.cabac_init_flag ? 1 : 2) : (sh.cabac_init_flag ? 2 : 1));      // 9.3.2.2: cabac_init_flag swaps the P and the B tables
   CabacDec &c = sp.c;
-  c.start(data, len);
   // free slices (PicJob::ctb_cut; one tile): the slice of every coding tree block, its SliceQpY
   const bool free_slices = !job.ctb_cut.empty();
+  // partial pictures v1, one tile (PicJob::scan_gaps): where a segment ends is known only here.  `skipping`: the blocks at hand belong to no decoded segment -- in front of
+  // the first segment that arrived, or behind a segment that ended before the next one's address (the gap), a dependent successor included (its predecessor is gone: it is
+  // skipped, with its bytes) -- until an INDEPENDENT segment begins.  A skipped block gets what makes every kernel do nothing there (rule 3), the slice byte 255 (no decoded
+  // slice has it: close_free_picture) and a mark in job.miss_map; parse_job makes PicJob::missing of the marks.  Without WPP one thread walks the picture.  With WPP (free
+  // slices; `data` is then the whole of the picture's bytes, every start of the arithmetic decoder names its own offset) a row learns from the row above whether it begins
+  // inside a gap: an independent segment at its start decodes; a dependent one decodes if the last block of the row above was decoded (that row is waited for); a row that
+  // continues a segment (an entry point) decodes if that segment's first block was decoded -- a block of the row above, waited for, or of a row further up, which the row
+  // above has looked at before its own first block; a row without bytes skips.  A skipped block's progress is published like a decoded one's: nothing waits in vain.
+  const bool scan = job.scan_gaps && cols == 1 && (!wpp || free_slices);
+  bool skipping = false;
+  size_t first_off = 0;                                   // scan with WPP: where this row's bytes begin in `data`
+  if (scan && free_slices) {
+    const int a0 = first_cy * wc + cx0;
+    const uint8_t cut0 = job.ctb_cut[(size_t)a0];
+    if (cut0 & 1) skipping = false;
+    else if (a0 == 0) skipping = true;
+    else if (cut0 & 2) { if (!wait_above(first_cy, tw)) return DEC_ERR_INVALID; skipping = job.miss_map[(size_t)a0 - 1] != 0; }
+    else if (job.sub_start[(size_t)first_cy] == SIZE_MAX || job.row_seg_start[(size_t)first_cy] < 0) skipping = true;
+    else {
+      const int s0 = job.row_seg_start[(size_t)first_cy];
+      if (!wait_above(first_cy, s0 / wc == first_cy - 1 ? imax(2, s0 % wc + 1) : 2)) return DEC_ERR_INVALID;
+      skipping = job.miss_map[(size_t)s0] != 0;
+    }
+    if (wpp && !skipping) { first_off = job.sub_start[(size_t)first_cy]; if (first_off == SIZE_MAX || first_off >= len) return DEC_ERR_INVALID; }
+  }
+  c.start(data + first_off, len - first_off);
   sp.slice_qp = sh.slice_qp;
   if (free_slices) { sp.slice_of = job.ctb_slice.data(); sp.cur_slice = job.ctb_slice[(size_t)first_cy * wc + cx0]; sp.slice_qp = job.slice_qps[(size_t)sp.cur_slice]; }
   auto init_contexts = [&] { uint8_t init[CTX_COUNT]; cabac_init_contexts(init, init_type, sp.slice_qp); c.load_ctx(init); };
@@ -1018,7 +1043,9 @@ int Decoder::parse_substream(PicJob &job, int sub, const uint8_t *data, size_t l
   // CTB when that CTB exists (pictures one CTB wide: it does not, and the row initialises afresh) -- and is AVAILABLE: with free slices it may
   // belong to another slice; then a dependent segment that begins with this row goes on where the segment before it stopped (the end of the row
   // above), anything else initialises
-  if (!wpp || tile_starts_at(first_cy) || tw < 2) init_contexts();
+  if (skipping) init_contexts();                        // (whatever: the next block decoded begins an independent slice)
+  else if (!wpp || tile_starts_at(first_cy) || tw < 2) init_contexts();
+  else if (scan && !wait_above(first_cy, 2)) return DEC_ERR_INVALID;      // (the row above may have found its second block missing: its slice byte is read below)
   else if (free_slices && job.ctb_slice[(size_t)(first_cy - 1) * wc + cx0 + 1] != sp.cur_slice) {
     if (job.ctb_cut[(size_t)first_cy * wc + cx0] & 2) {
       if (!wait_above(first_cy, tw)) return DEC_ERR_INVALID;
@@ -1035,6 +1062,15 @@ int Decoder::parse_substream(PicJob &job, int sub, const uint8_t *data, size_t l
     if (band_row0_ + band_nrows_ < (h_ + 63) / 64) sp.ref_y1 = (band_row0_ + band_nrows_) * 64;
   }
   ColMotion *own = job.own.get();
+  auto mark_missing = [&](int ctu) {
+    const int per = 1 << (ctbl_ - 2), b4w = pw_ / 4, mx = ctu % wc, my = ctu / wc;
+    B4Rec none; memset(&none, 0, sizeof(none)); none.ref_idx = -1;
+    for (int k = 0; k < per; k++) for (int x = 0; x < per; x++) job.b4[(size_t)(my * per + k) * b4w + mx * per + x] = none;
+    job.ctu_tile[ctu] = 255; if (free_slices) job.ctb_slice[(size_t)ctu] = 255;
+    memset(&job.sao[ctu], 0, sizeof(SaoParams));
+    job.miss_map[(size_t)ctu] = 1;
+    if (wpp) job.row_progress[(size_t)(ctu / wc) * cols + g.tc].v.store(ctu % wc - cx0 + 1, std::memory_order_release);
+  };
   for (int cy = first_cy; cy < first_cy + ncy; cy++) {
     if (cy > first_cy && job.row_restart[(size_t)cy] != SIZE_MAX) {
       // a dependent slice segment begins inside this substream: new arithmetic codeword, the contexts go on (9.3.1)
@@ -1046,6 +1082,10 @@ int Decoder::parse_substream(PicJob &job, int sub, const uint8_t *data, size_t l
       if (!wait_above(cy, cx - cx0 + 2)) return DEC_ERR_INVALID;
       const int ctu = cy * wc + cx;
       const uint8_t cut = free_slices ? job.ctb_cut[(size_t)ctu] : 0;
+      if (skipping) {
+        if (!(cut & 1)) { mark_missing(ctu); continue; }
+        skipping = false;                                  // an independent segment begins: decoding goes on
+      }
       if (cut & 3) {
         // a slice segment begins with this block: its own arithmetic codeword (the substream's first block: started above); an independent slice is a new
         // slice for every availability rule, starts from the initial context states and from its own SliceQpY; a dependent one goes on with the states at hand
@@ -1085,14 +1125,17 @@ int Decoder::parse_substream(PicJob &job, int sub, const uint8_t *data, size_t l
       job.ctu[ctu].count = ((uint32_t)out.tus.size() - tu0) | (sp.ctu_intra_mask << 24);
       if (out.tus.size() - tu0 >= (1u << 24)) return DEC_ERR_INVALID;
       if (wpp && cx == cx0 + 1) c.save_ctx(&job.wpp_saved[((size_t)cy * cols + g.tc) * CTX_COUNT]);
-      if ((cut & 4) && wpp && cx == cx1 - 1) c.save_ctx(&job.ds_saved[(size_t)cy * CTX_COUNT]);      // (a segment ends with the row: what a dependent segment that begins the next row may have to go on with)
+      if (((cut & 4) || scan) && wpp && free_slices && cx == cx1 - 1) c.save_ctx(&job.ds_saved[(size_t)cy * CTX_COUNT]);      // (a segment ends with the row: what a dependent segment that begins the next row may have to go on with)
       if (wpp) job.row_progress[(size_t)cy * cols + g.tc].v.store(cx - cx0 + 1, std::memory_order_release);
       // end_of_slice_segment_flag: 1 exactly where the picture's slice segments end (decode_slice noted the rows; one segment: the
       // last CTU of the picture); inside a segment a substream ends with end_of_subset_one_bit
       const bool seg_last = free_slices ? (cut & 4) != 0 : cx == cx1 - 1 && (cols > 1 ? (cy == g.cy1 - 1 && job.seg_end_sub[(size_t)sub]) : job.seg_end_row[(size_t)cy] != 0);
       const int end = c.terminate();
-      if (end != (seg_last ? 1 : 0)) return seg_last ? DEC_ERR_INVALID : (job.ambiguous_end ? DEC_SEG_ENDS_EARLY : DEC_ERR_UNSUPPORTED);      // (a segment that ends elsewhere: not whole CTU rows / tiles)
-      if (!seg_last && cx == cx1 - 1 && (wpp || tile_ends_at(cy)) && !c.terminate()) return DEC_ERR_INVALID;   // end_of_subset_one_bit
+      if (end != (seg_last ? 1 : 0)) {
+        if (scan && end == 1 && !job.ambiguous_end) skipping = true;      // (partial pictures: it ends before the next segment's address -- what lies between never arrived)
+        else return seg_last ? DEC_ERR_INVALID : (job.ambiguous_end ? DEC_SEG_ENDS_EARLY : DEC_ERR_UNSUPPORTED);      // (a segment that ends elsewhere: not whole CTU rows / tiles)
+      }
+      if (!skipping && !seg_last && cx == cx1 - 1 && (wpp || tile_ends_at(cy)) && !c.terminate()) return DEC_ERR_INVALID;   // end_of_subset_one_bit
     }
     if (job.early_dst) {
       // the row's 4x4 records are final (a coding unit writes inside its own CTU only): up they go, from whichever thread parsed the row
@@ -1143,8 +1186,23 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
   const uint8_t *data = job.rbsp.data() + job.data_off; const size_t len = job.data_len;
   const int wc = ctbs_in(w_, ctbl_), hc = ctbs_in(h_, ctbl_), nsub = (int)job.geom.size(), cols = job.pps.tile_cols;
   auto release_all = [&] { if (job.own) for (int r = 0; r < hc; r++) job.own->row_done[(size_t)r].store(1, std::memory_order_release); };   // never leave a later picture's parser waiting
-  if ((int)job.sub_start.size() != nsub) { release_all(); return DEC_ERR_INVALID; }
-  for (int r = 0; r < nsub; r++) if (job.sub_start[(size_t)r] >= len) { release_all(); return DEC_ERR_INVALID; }
+  // partial pictures v1 (decoder.h): the coding tree blocks that never arrived.  What is built lays out whole trailing CTB rows of a one-tile picture with WPP: their
+  // substreams have no bytes and are not parsed -- skip_row gives the row the records that make every kernel do nothing there and publishes it
+  std::vector<uint8_t> miss;
+  int nrecv = nsub;
+  const bool scan_rows = job.scan_gaps && job.pps.wpp != 0 && !job.ctb_cut.empty();      // (free slices with WPP: rows may have no bytes, every row gets the whole of the picture's)
+  if (job.scan_gaps) { job.missing.clear(); job.miss_map.assign((size_t)wc * hc, 0); }      // (the parser finds what is missing -- parse_substream; a picture parsed again starts afresh)
+  if (!job.missing.empty()) {
+    miss.assign((size_t)wc * hc, 0);
+    if (job.missing.size() != 1 || !job.pps.wpp || cols != 1 || nsub != hc || band_nrows_ > 0) { release_all(); return DEC_ERR_INVALID; }
+    const int a = job.missing[0].first, n = job.missing[0].second;
+    if (a <= 0 || a % wc != 0 || a + n != wc * hc) { release_all(); return DEC_ERR_INVALID; }
+    memset(miss.data() + a, 1, (size_t)n);
+    nrecv = a / wc;
+  }
+  if ((int)job.sub_start.size() != nrecv) { release_all(); return DEC_ERR_INVALID; }
+  for (int r = 0; r < nrecv; r++) if (job.sub_start[(size_t)r] >= len && !(scan_rows && job.sub_start[(size_t)r] == SIZE_MAX)) { release_all(); return DEC_ERR_INVALID; }
+  if (scan_rows && (int)job.row_seg_start.size() != hc) { release_all(); return DEC_ERR_INVALID; }
   job.subs.resize((size_t)nsub);
   for (auto &r : job.subs) { r.levels.clear(); r.tus.clear(); r.rc = 0; }
   job.wpp_saved.resize((size_t)hc * cols * CTX_COUNT);
@@ -1153,9 +1211,27 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
   memset(job.region, 0, (size_t)(pw_ / 32) * (ph_ / 32) * sizeof(TuRange));
   memset(job.ctu, 0, nctb() * sizeof(TuRange));
   memset(job.pred_mode.data(), PM_NONE, job.pred_mode.size());
+  auto skip_row = [&](int cy) {
+    // rule 3: no coding units (PM_NONE stays: available to nothing), no transform blocks (job.ctu stays zero), records that are intra to the inter kernel and carry no
+    // edge, SAO off, a slice byte of their own, no motion filed (ColMotion: like intra; ConcealMotion: none, as open_job left it)
+    const int per = 1 << (ctbl_ - 2), b4w = pw_ / 4;
+    B4Rec none; memset(&none, 0, sizeof(none)); none.ref_idx = -1;
+    for (int k = 0; k < per; k++) for (int x = 0; x < b4w; x++) job.b4[(size_t)(cy * per + k) * b4w + x] = none;
+    memset(job.ctu_tile + (size_t)cy * wc, 255, (size_t)wc);
+    memset(&job.sao[(size_t)cy * wc], 0, (size_t)wc * sizeof(SaoParams));
+    job.subs[(size_t)cy].rc = 0;
+    job.row_progress[(size_t)cy].v.store(wc, std::memory_order_release);
+    if (ColMotion *own = job.own.get()) {
+      const int per16 = 1 << (ctbl_ - 4);
+      for (int y16 = cy * per16; y16 < (cy + 1) * per16 && y16 < own->h16; y16++) memset(&own->mv[(size_t)y16 * own->w16], 0, (size_t)own->w16 * sizeof(ColMotion::Mv));
+      own->row_cols[(size_t)cy].store((uint8_t)own->cols, std::memory_order_release); own->row_done[(size_t)cy].store(1, std::memory_order_release);
+    }
+  };
   auto one = [&](int r) {
+    if (r >= nrecv) { skip_row(job.geom[(size_t)r].cy0); return; }
     if (band_nrows_ > 0 && (job.geom[(size_t)r].cy0 < band_row0_ || job.geom[(size_t)r].cy1 > band_row0_ + band_nrows_)) { job.subs[(size_t)r].rc = 0; return; }   // another decoder's rows
-    size_t start = job.sub_start[(size_t)r], end = (r + 1 < nsub) ? job.sub_start[(size_t)r + 1] : len;
+    size_t start = job.sub_start[(size_t)r], end = (r + 1 < nrecv) ? job.sub_start[(size_t)r + 1] : len;
+    if (scan_rows) { start = 0; end = len; }
     int rc = end > start ? parse_substream(job, r, data + start, end - start, job.subs[(size_t)r]) : DEC_ERR_INVALID;
     job.subs[(size_t)r].rc = rc;
     if (rc < 0 && job.pps.wpp) job.row_progress[(size_t)job.geom[(size_t)r].cy0 * cols + job.geom[(size_t)r].tc].v.store(1 << 30, std::memory_order_release);   // release any waiter
@@ -1208,6 +1284,10 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
     for (size_t k = 0; k < ntu; k++) { TuRange &g = job.region[region_of(tus[k])]; idx[g.first + g.count++] = (uint32_t)k; }      // (list order = decoding order inside a region)
   }
   job.ntu = ntu; job.nlev = nlev;
+  if (job.scan_gaps) {      // gaps found by the parser: the runs, in raster order; their boundaries are closed like the row form's
+    for (int a = 0; a < wc * hc; a++) if (job.miss_map[(size_t)a]) { if (!job.missing.empty() && job.missing.back().first + job.missing.back().second == a) job.missing.back().second++; else job.missing.emplace_back(a, 1); }
+    if (!job.missing.empty()) { miss = job.miss_map; job.lf_restricted = true; }
+  }
   if (job.lf_restricted) {
     // ---- closed slice / tile boundaries (PicJob::lf_restricted).  Every coding tree block's slice: the slices are runs of the DECODING order (tile after tile), so the
     // walk goes through the substreams' geometry; then per block which of its eight neighbours the in-loop filters may use -- not across a tile boundary when the
@@ -1237,7 +1317,8 @@ int Decoder::parse_job(PicJob &job, bool row_parallel)
             if ((!dx && !dy) || nx < 0 || ny < 0 || nx >= wc || ny >= hc) continue;
             const int q = ny * wc + nx, later = order[(size_t)q] > order[(size_t)c] ? q : c;
             const bool closed = (job.ctu_tile[c] != job.ctu_tile[q] && !job.pps.across_tiles && job.ctb_cut.empty()) ||      // (free slices: the byte holds the slice, there is one tile)
-                                (slice[(size_t)c] != slice[(size_t)q] && !job.lf_slices[(size_t)slice[(size_t)later]].second);
+                                (!miss.empty() && (miss[(size_t)c] || miss[(size_t)q])) ||                                     // (partial pictures: a missing block is closed on every side, and on the neighbours' side)
+                                (!job.lf_slices.empty() && slice[(size_t)c] != slice[(size_t)q] && !job.lf_slices[(size_t)slice[(size_t)later]].second);
             const int k = (dy + 1) * 3 + (dx + 1);
             if (closed) m &= (uint8_t)~(1u << (k > 4 ? k - 1 : k));
           }

@@ -27,6 +27,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <string>
 #include <atomic>
 #include <condition_variable>
@@ -58,6 +59,7 @@ struct DecodedPicture {
   int poc = 0; int64_t pts = 0; uint32_t fps_num = 0, fps_den = 0; bool is_intra = false;
   int cvs = 0, num_reorder = 0;       // coded video sequence the picture belongs to (a running count); its SPS's sps_max_num_reorder_pics
   uint64_t serial = 0;                // the picture's number in decoding order (Decoder::vwait_: which waiting pictures an IDR / BLA picture discards)
+  int missing_ctbs = 0, total_ctbs = 0;      // partial pictures: coding tree blocks of the picture that never arrived and were filled in (0: the picture is whole)
 };
 
 // a finished picture that owns its samples: what is still in the frame-threaded ring when the stream changes its resolution is
@@ -114,6 +116,11 @@ class Decoder {
   // ("Concealment v2" / "v3" below); before the first picture, and 3 not in band mode.  false: refused
   bool set_concealment(int mode) { if ((mode != 2 && mode != 3) || !jobs_.empty() || (mode == 3 && band_nrows_ > 0)) return false; conceal_mode_ = mode; return true; }
   int concealment() const { return conceal_mode_; }
+  // "Partial pictures v1" (below): a picture that lost slice segments keeps the coding tree blocks that arrived; off by default; before the first picture, not in band mode.  false: refused
+  bool set_partial_pictures(bool on) { if (!jobs_.empty() || (on && band_nrows_ > 0)) return false; partial_ = on; return true; }
+  bool partial_pictures() const { return partial_; }
+  // the runs of missing coding tree blocks of every damaged picture so far, in decoding order: (POC, first block, count) triples; -> the number of triples there are
+  int damage_log(int32_t *triples, int cap) const { const int n = (int)(damage_log_.size() / 3); for (int i = 0; triples && i < n && i < cap; i++) memcpy(triples + 3 * i, &damage_log_[(size_t)3 * i], 3 * sizeof(int32_t)); return n; }
   // frame threading: up to n pictures are parsed concurrently while one more is reconstructed on the GPU; the output is delayed by n pictures
   // (libOpenHevcInit(nb_threads, OH_THREAD_FRAME / OH_THREAD_FRAMESLICE)); call before the first picture
   void set_frame_threads(int n) { if (jobs_.empty()) frame_threads_ = n < 1 ? 1 : (n > 32 ? 32 : n); }
@@ -181,7 +188,7 @@ class Decoder {
     // some boundary inside the picture is closed to the in-loop filters (loop_filter_across_tiles_enabled_flag = 0 with tiles; a slice with
     // slice_loop_filter_across_slices_enabled_flag = 0): lf_slices = the picture's independent slices (first block, flag)
     bool lf_restricted = false; std::vector<std::pair<int, uint8_t>> lf_slices;
-    struct Undo { int poc = 0, prev_poc = 0; bool is_ref = false, used = false, seen_irap = false; long decode_idx = 0; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion; std::vector<std::pair<uint64_t, int>> vwait; } undo;      // what submit_job changed
+    struct Undo { int poc = 0, prev_poc = 0; bool is_ref = false, used = false, seen_irap = false; long decode_idx = 0; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion; std::vector<std::pair<uint64_t, int>> vwait; bool standin = false; } undo;      // what submit_job changed
     SliceHdr sh; std::shared_ptr<const DecSps> sps; DecPps pps;  // (a later SPS / PPS NAL may replace the table entry while this picture is still being parsed: the job keeps the SPS it was coded with alive, the PPS by value)
     int64_t pts = 0; int crop[4] = {0, 0, 0, 0}; uint32_t fps_num = 0, fps_den = 0;
     int slot = 0;                                                // picture buffer this picture is reconstructed into
@@ -189,6 +196,11 @@ class Decoder {
     uint64_t serial = 0;                                         // number in decoding order
     // (mode 3: the stand-in's and the source's picture order counts and the source's motion, taken when the source is chosen)
     struct Conceal { int first, second; int poc = 0, src_poc = 0; std::shared_ptr<const ConcealMotion> motion; Conceal(int buf, int src) : first(buf), second(src) {} };
+    // partial pictures v1: the runs (first coding tree block, count) that never arrived -- the parser gives them records that make every kernel do nothing, fill_missing
+    // their samples; the source picture S chosen when the picture's first segment arrived (buffer or -1: grey, its order count, its motion for mode 3 -- NULL: a stand-in)
+    bool scan_gaps = false;      // one tile, without WPP or as free slices: the parser itself finds what is missing (dec_parse.hip parse_substream; miss_map, a byte per block) and parse_job files the runs here
+    std::vector<uint8_t> miss_map; std::vector<int> row_seg_start;      // (row_seg_start: WPP, per CTB row the address of the segment that goes on into it through an entry point, -1: none)
+    std::vector<std::pair<int, int>> missing; int fill_src = -1, fill_src_poc = 0; std::shared_ptr<const ConcealMotion> fill_motion;
     std::vector<Conceal> conceal;                                // (buffer, source buffer or -1): buffers that stand in for reference pictures that never arrived, filled before this picture's kernels (launch_gpu)
     bool starts_cvs = false, discard_prior = false;              // NoRaslOutputFlag (8.1.3); ... and no_output_of_prior_pics_flag in force (C.5.2.2)
     int nref = 0; int ref_poc[16]; uint8_t ref_slot[16];        // RefPicList0
@@ -231,7 +243,7 @@ class Decoder {
   // Synchronous decoder only (one frame thread), no SAO, no temporal motion prediction.  Per picture: decode_nal (returns 0: the band is
   // reconstructed) -> band_export(0) -> [to rank + 1 / from rank - 1] -> band_import(0) -> band_deblock -> band_export(1) ->
   // [to rank - 1 / from rank + 1] -> band_import(1) -> band_finish (the picture is the output; its band's rows are valid).
-  bool set_band(int row0, int nrows) { if (conceal_mode_ == 3 && nrows > 0) return false; if (jobs_.empty()) { band_row0_ = row0; band_nrows_ = nrows; } return true; }      // (false: refused -- concealment v3 has no band form)
+  bool set_band(int row0, int nrows) { if ((conceal_mode_ == 3 || partial_) && nrows > 0) return false; if (jobs_.empty()) { band_row0_ = row0; band_nrows_ = nrows; } return true; }      // (false: refused -- concealment v3 and partial pictures have no band form)
   size_t band_halo_bytes() const { return (size_t)pw_ * 8; }
   bool band_export(int stage, uint8_t *d_buf);     // stage 0: this band's LAST four luma rows (+ chroma) before deblocking and their 4x4 records, for the band below; stage 1: the four rows above this band, final, for the band above
   bool band_import(int stage, const uint8_t *d_buf);   // stage 0: from the band above, into the rows above this band; stage 1: from the band below, this band's last four rows, final
@@ -253,7 +265,7 @@ class Decoder {
   int parse_substream(PicJob &job, int sub, const uint8_t *data, size_t len, SubOut &out);
   int close_open_picture();
   int close_free_picture(PicJob &job);
-  void take_back_job(PicJob &job);
+  void take_back_job(PicJob &job); void file_damage(const PicJob &job); std::vector<uint8_t> layout_of(const PicJob &job) const; std::vector<uint8_t> damaged_layout_; uint32_t take_backs_ = 0;
   // ---- a picture arriving in several slice segment NAL units: its job is filled segment by segment and submitted with the last one.  Everything that is known
   // about the picture being assembled lives in ONE value, reset by assignment when a picture is opened (open_job).
   // FreeSeg: the slice segments as they arrived (one tile), kept beside the row bookkeeping of Kvazaar's forms, which is dropped the moment a segment turns up
@@ -280,7 +292,7 @@ class Decoder {
   void bind_job(PicJob &job);
   // launch_gpu and its stages (decoder.hip), in the order they run; the `batched` / second-chain decisions between them are launch_gpu's own
   struct ChainSet; int launch_gpu(PicJob &job);
-  int fill_concealed(PicJob &job); uint8_t *input_buffer(PicJob &job, int ib);
+  int fill_concealed(PicJob &job); int fill_missing(PicJob &job); uint8_t *input_buffer(PicJob &job, int ib);
   DecFrame picture_frame(PicJob &job, const DecInputLayout &lay, const ChainSet &cs, uint8_t *d_in) const;
   bool upload(PicJob &job, const DecInputLayout &lay, uint8_t *d_in, int ib, bool batched);
   int post_to_batcher(PicJob &job, const DecFrame &f, uint8_t *d_in, int ib); int launch_self(PicJob &job, const DecFrame &f, uint8_t *d_in, int ib, bool alt);
@@ -330,7 +342,7 @@ class Decoder {
   bool queue_current_output();
   std::unique_ptr<FrameWorkers> workers_;
   // decoded picture buffer: slot = device planes + what reference marking needs
-  struct DpbPic { uint8_t *plane[3] = {nullptr, nullptr, nullptr}; int poc = 0; bool is_ref = false, used = false, is_lt = false;      // is_lt: marked "used for long-term reference" (8.3.2)
+  struct DpbPic { uint8_t *plane[3] = {nullptr, nullptr, nullptr}; int poc = 0; bool is_ref = false, used = false, is_lt = false, standin = false;      // is_lt: marked "used for long-term reference" (8.3.2)
                   long decode_idx = -1000; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion;      // (cmotion: concealment v3's record, NULL in mode 2 and for a stand-in)
                   hipEvent_t last_dl = nullptr;
                   hipEvent_t last_use = nullptr; bool last_use_alt = false; };      // (two chains, below: the last picture that read or wrote the buffer, and the stream it ran on)     // download mode: the copy of the picture last reconstructed here (a later picture's kernels wait for it before they write the buffer)
@@ -402,6 +414,38 @@ class Decoder {
   int16_t *d_standin_tab_ = nullptr; size_t standin_tab_cap_ = 0;      // the table on the device, allocated with the first stand-in of mode 3
   int standin_slot_ = -1; std::vector<int16_t> standin_tab_;          // debug_copy "standin" / "standin_mv": the stand-in filled last and its table
   float standin_ms_ = -1;                                              // debug_copy "standin_ms": time of the last stand-in's fill (either mode; set_profiling only)
+  // Partial pictures v1 (set_partial_pictures; off by default, and with it off nothing below exists).  The statement of record; tests/partial_model.py restates it on
+  // tests/pyhevc.py, the product is held to that model (the checker stays at today's behaviour).  One-tile pictures; total = the picture's coding tree blocks, next = where
+  // the decoded part ends so far (0 at first).
+  //  1. Segments are taken in arrival order inside an access unit; a = the segment's address.  a < next: ignored.  Independent: decoded; a > next leaves [next, a) missing.
+  //     Dependent: decoded only if a == next, next > 0 and block a - 1 was decoded -- else its predecessor is gone, with its CABAC state (9.3.1), header and neighbours: the
+  //     segment is dropped, next stays; a lost segment takes every following dependent one with it, up to the next independent one.  After a decoded segment next = a + the
+  //     blocks it coded.  The picture ends when next == total or when something arrives that can only belong to the next access unit; then [next, total) is missing.  A
+  //     picture none of whose segments was decoded is a lost picture (v2 / v3 as ever); a segment that arrives and does not parse is corruption: the picture is dropped as ever.
+  //  2. A non-first segment joins the open picture if nal_unit_type and PPS match (an independent one: slice_pic_order_cnt_lsb too) and a >= next.
+  //  3. A missing block has no coding units, is available (6.4.1) to nothing, files no motion (a collocated block there gives no temporal candidate; ConcealMotion: none), has
+  //     no edges, and its boundary is closed to both loop filters exactly as slice_loop_filter_across_slices_enabled_flag = 0 closes one (DecFrame::ctu_nb): no received
+  //     sample depends on a concealed one, the seam is unfiltered on purpose.
+  //  4. Its samples, three planes, clipped to the coded picture: S = v2's choice for the damaged picture's OWN order count among the reference pictures the DPB held when the
+  //     picture arrived (no stand-in made for this picture; nearest, of two the earlier); an IRAP picture that starts a coded video sequence: the held picture decoded last;
+  //     none: 128.  Mode 2: S's samples at the same place.  Mode 3: per 16x16 block v3's steps 1-3 scaled to the damaged picture's order count, the neighbour test over S's
+  //     whole grid, zero where S is a stand-in or S's own block was missing.
+  //  5. The damaged picture is output in its turn and kept as a reference; its hash SEI is neither compared nor counted; damage is reported beside it (DecodedPicture).
+  // BUILT in v1, two forms.  (a) What a Kvazaar peer's slices=wpp sends -- WPP, a dependent segment per CTB row: a lost row's segment takes every later row with it, the rows
+  // before it stay (append_segment drops what rule 1 drops, close_open_picture lays the tail out as missing; PicJob::missing is set before the parse).  (b) One-tile pictures
+  // in any other cut (Kvazaar's rows without WPP, free slices with or without WPP): gaps anywhere -- a first segment lost with an independent one behind it (slice_front: the segment opens the picture
+  // from its own header), a middle independent or dependent one, two gaps, the tail.  The picture is put together like a picture of free slices when its access unit ends
+  // (close_free_picture) and the PARSER finds the gaps (PicJob::scan_gaps, parse_substream): a segment that ends before the next one's address
+  // leaves what lies between missing, a dependent successor is skipped with its bytes, an independent one takes up decoding; a missing block gets the slice byte 255, which
+  // no decoded slice has (255 slices at most then).  With WPP a row thread learns from the row above whether it begins inside a gap and publishes its progress over skipped
+  // blocks too (parse_substream says how).  Pictures with tiles keep today's behaviour -- dropped whole, then concealed (DESIGN.md section 9.3 "Not covered").
+  // Where: parse_job gives the missing rows their records (nothing waits on them, their progress and ColMotion rows are published), fill_missing runs k_dec_fill_ctbs into the
+  // picture's buffer BEHIND the picture's last kernel and before anything later is launched, on a drained device like fill_concealed -- whoever launched the picture (batch.h).
+  bool partial_ = false; int cur_fill_src_ = -1, avoid_slot_ = -1;      // (cur_fill_src_: S of the picture whose first segment is being read; avoid_slot_: alloc_slot leaves S's buffer alone for it)
+  void choose_fill_source(int poc, bool last_decoded, const std::vector<int> &fresh);
+  std::vector<int32_t> damage_log_;
+  uint32_t *d_fill_ctbs_ = nullptr; size_t fill_ctbs_cap_ = 0; int16_t *d_fill_tab_ = nullptr; size_t fill_tab_cap_ = 0;      // the list and the table on the device, allocated with the first damaged picture
+  std::vector<int16_t> fill_tab_;                                       // debug_copy "fill_mv": the table used last
   bool cur_discard_ = false;     // the picture whose headers are being read empties the buffer without output (decided with its first segment)
   bool cur_no_rasl_ = false;     // NoRaslOutputFlag of the picture whose slice headers are being read (decided with its first segment)
   bool skip_rasl_ = false;       // NoRaslOutputFlag of the last IRAP picture: the RASL pictures that belong to it refer to pictures that are not there -- their NAL units are dropped

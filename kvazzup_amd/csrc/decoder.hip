@@ -107,6 +107,7 @@ void Decoder::free_buffers()
 {
   for (auto &j : jobs_) { if (j.h_in) hipHostFree(j.h_in); j.h_in = nullptr; j.h_in_cap = 0; j.col.reset(); j.own.reset(); j.cown.reset(); }
   hipFree(d_standin_tab_); d_standin_tab_ = nullptr; standin_tab_cap_ = 0; standin_slot_ = -1; standin_tab_.clear();
+  hipFree(d_fill_ctbs_); d_fill_ctbs_ = nullptr; fill_ctbs_cap_ = 0; hipFree(d_fill_tab_); d_fill_tab_ = nullptr; fill_tab_cap_ = 0; fill_tab_.clear();
   if (stream_dl_) hipStreamSynchronize(stream_dl_);
   for (auto &p : h_out_) { if (p) retired_out_.emplace_back(nal_calls_, p); p = nullptr; }      // (freed kOutHold calls later: free_retired)
   for (auto &p : d_in_) { hipFree(p); p = nullptr; } for (auto &c : d_in_cap_) c = 0;
@@ -220,7 +221,7 @@ int Decoder::conceal_ref(int poc, bool is_lt)
   const int s = alloc_slot();
   if (s < 0) return -1;
   DpbPic &d = dpb_[s];
-  d.poc = poc; d.is_ref = true; d.used = true; d.is_lt = is_lt; d.motion.reset(); d.cmotion.reset();      // (decode_idx stays: the buffer was old enough to be taken and is no picture anybody waits for -- free again the moment no set names it)
+  d.poc = poc; d.is_ref = true; d.used = true; d.is_lt = is_lt; d.standin = true; d.motion.reset(); d.cmotion.reset();      // (decode_idx stays: the buffer was old enough to be taken and is no picture anybody waits for -- free again the moment no set names it)
   pending_conceal_.emplace_back(s, -2);                           // (-2: the source is chosen once the reference picture set has been applied, decode_slice)
   if (concealed_++ < 3) fprintf(stderr, "kvazzup_amd: decoder: reference picture with POC %d never arrived -- the nearest reference picture (or a grey one) stands in\n", poc);
   return s;
@@ -253,7 +254,7 @@ int Decoder::alloc_slot()
 {
   for (int s = 0; s < KVZ_DEC_MAX_REFS; s++) {
     DpbPic &p = dpb_[s];
-    if (p.is_ref || job_head_ - p.decode_idx <= output_hold_ + (gpu_depth_ - 1)) continue;      // (pictures queued on the GPU behind the one handed out may already write their buffers)
+    if (p.is_ref || s == avoid_slot_ || job_head_ - p.decode_idx <= output_hold_ + (gpu_depth_ - 1)) continue;      // (pictures queued on the GPU behind the one handed out may already write their buffers)
     if (!p.plane[0] && parse_only_) p.plane[0] = (uint8_t *)(uintptr_t)64;
     if (!p.plane[0]) { if (hipSetDevice(device_) != hipSuccess || !alloc_picture(p)) return -1; hipDeviceSynchronize(); }      // (a buffer is added at most ten times)
     return s;
@@ -494,7 +495,9 @@ int Decoder::decode_nal_inner(const uint8_t *data, size_t len, int64_t pts)
   if (nal_type < 32 && cur_tid_ > max_tid_) return 0;            // (set_max_temporal_id: a sub-layer the caller does not want)
   const size_t n = unescape(data, len);
   BitReader r(rbsp_.data(), n);
-  if (asm_.active && (asm_.guessed_one_row || asm_.free) && nal_type >= 32 && nal_type <= 40 && nal_type != 38) { const int rc = close_open_picture(); if (rc < 0) return rc; }   // (what can only open the next access unit, or end the sequence)
+  // (partial pictures: a picture in the row form that is built -- one tile, WPP -- is closed here too, with what it has)
+  const bool open_rows = partial_ && asm_.active && !jobs_.empty() && jobs_[(size_t)(job_head_ % jobs_.size())].pps.wpp && jobs_[(size_t)(job_head_ % jobs_.size())].pps.tile_rows == 1 && jobs_[(size_t)(job_head_ % jobs_.size())].pps.tile_cols == 1;
+  if (asm_.active && (asm_.guessed_one_row || asm_.free || open_rows) && nal_type >= 32 && nal_type <= 40 && nal_type != 38) { const int rc = close_open_picture(); if (rc < 0) return rc; }   // (what can only open the next access unit, or end the sequence)
   if (nal_type >= 32 && nal_type <= 34) return decode_parameter_set(nal_type, r);
   if (nal_type == 36 || nal_type == 37) { after_eos_ = true; vwait_.clear(); int rc = finish_oldest(); if (rc < 0) last_error_ = rc; return rc; }   // EOS / EOB: drain one delayed picture; whatever picture follows starts a sequence
   if (nal_type == 40 && check_hash_) return hash_sei(rbsp_.data(), n);       // suffix SEI: decoded picture hash (libOpenHevcSetCheckMD5)
@@ -524,6 +527,7 @@ int Decoder::hash_sei(const uint8_t *rbsp, size_t len)
     if (job_head_ == 0) continue;
     PicJob &job = jobs_[(size_t)((job_head_ - 1) % (long)jobs_.size())];
     if (parse_only_) continue;
+    if (!job.missing.empty()) continue;                     // (partial pictures: a damaged picture's hash is neither compared nor counted)
     if (frame_threads_ > 1 || band_nrows_ > 0) { job.expect_hash = std::move(want); continue; }
     const int rc = verify_hash(job, want);
     if (rc < 0) return last_error_ = rc;
@@ -562,9 +566,10 @@ int Decoder::close_free_picture(PicJob &job)
 {
   const int wc = ctbs_in(w_, ctbl_), hc = ctbs_in(h_, ctbl_), total = wc * hc, n = (int)asm_.segs.size();
   const bool wpp = job.pps.wpp != 0;
-  if (n < 1 || asm_.segs[0].address != 0 || asm_.segs[0].dependent) return DEC_ERR_INVALID;
-  if (n == 1 && frame_threads_ == 1) free_stream_ = false;      // (one segment: the stream may be back to whole pictures -- the synchronous decoder can afford to find out, submit_job take_back)
-  if (n == 1) {
+  const bool headless = partial_ && n >= 1 && asm_.segs[0].address != 0 && !asm_.segs[0].dependent;      // (partial pictures: the picture's first segment never arrived)
+  if (n < 1 || (asm_.segs[0].address != 0 && !headless) || asm_.segs[0].dependent) return DEC_ERR_INVALID;
+  if (n == 1 && frame_threads_ == 1 && !headless) free_stream_ = false;      // (one segment: the stream may be back to whole pictures -- the synchronous decoder can afford to find out, submit_job take_back)
+  if (n == 1 && !headless && !(partial_ && wpp && (int)asm_.segs[0].subs.size() < hc)) {      // (partial pictures with WPP: a single segment that holds fewer rows than the picture has lost its tail)
     // the whole picture in one segment: the layout of Kvazaar's forms -- nothing per coding tree block, the parser's availability tests as they were
     if ((int)asm_.segs[0].subs.size() != (wpp ? hc : 1)) return DEC_ERR_INVALID;
     job.ctb_cut.clear(); job.ctb_slice.clear(); job.ctb_data.clear(); job.slice_qps.clear();
@@ -576,24 +581,34 @@ int Decoder::close_free_picture(PicJob &job)
   job.ctb_cut.assign((size_t)total, 0); job.ctb_slice.assign((size_t)total, 0); job.ctb_data.assign((size_t)total, SIZE_MAX); job.slice_qps.clear();
   job.sub_start.assign(wpp ? (size_t)hc : 1, SIZE_MAX);
   job.seg_end_row.assign((size_t)hc, 0); job.row_restart.assign((size_t)hc, SIZE_MAX);
+  job.row_seg_start.assign((size_t)hc, -1);
   int slice = -1;
   for (int k = 0; k < n; k++) {
     const FreeSeg &sg = asm_.segs[(size_t)k];
-    const int a = sg.address, e = k + 1 < n ? asm_.segs[(size_t)k + 1].address : total;
+    const int a = sg.address; int e = k + 1 < n ? asm_.segs[(size_t)k + 1].address : total;
+    // (partial pictures with WPP: the entry points say how many rows the segment goes into -- it ends in the last of them at the latest; what lies between that row's end
+    // and the next segment that arrived is missing whatever the parser finds)
+    if (partial_ && wpp && a >= 0 && !sg.subs.empty() && (long)(a / wc + (int)sg.subs.size()) * wc < e) e = (a / wc + (int)sg.subs.size()) * wc;
     if (a < 0 || e <= a || e > total || sg.subs.empty()) return DEC_ERR_INVALID;
-    if (!sg.dependent) { if (++slice > 255) return DEC_ERR_UNSUPPORTED; job.slice_qps.push_back((int8_t)sg.slice_qp); }      // (the kernels tell slices apart by a byte per block)
+    if (!sg.dependent) { if (++slice > (partial_ ? 254 : 255)) return DEC_ERR_UNSUPPORTED; job.slice_qps.push_back((int8_t)sg.slice_qp); }      // (the kernels tell slices apart by a byte per block)
     job.ctb_cut[(size_t)a] |= sg.dependent ? 2 : 1; job.ctb_cut[(size_t)e - 1] |= 4; job.ctb_data[(size_t)a] = sg.subs[0];
     memset(job.ctb_slice.data() + a, slice, (size_t)(e - a));
     const int rows = (e - 1) / wc - a / wc + 1;
     if (wpp) {
       if ((int)sg.subs.size() != rows) return DEC_ERR_INVALID;      // (an entry point per CTB row the segment goes on into)
-      for (int q = 0; q < rows; q++) if (q > 0 || a % wc == 0) job.sub_start[(size_t)(a / wc + q)] = sg.subs[(size_t)q];
+      for (int q = 0; q < rows; q++) if (q > 0 || a % wc == 0) { job.sub_start[(size_t)(a / wc + q)] = sg.subs[(size_t)q]; if (q > 0) job.row_seg_start[(size_t)(a / wc + q)] = a; }
     } else {
       if (sg.subs.size() != 1) return DEC_ERR_INVALID;
       if (k == 0) job.sub_start[0] = sg.subs[0];
     }
   }
-  for (size_t q = 0; q < job.sub_start.size(); q++) if (job.sub_start[q] == SIZE_MAX || (q > 0 && job.sub_start[q] <= job.sub_start[q - 1])) return DEC_ERR_INVALID;
+  { size_t last = SIZE_MAX;      // (partial pictures with WPP: a row that lies in a gap has no bytes)
+    for (size_t q = 0; q < job.sub_start.size(); q++) {
+      if (job.sub_start[q] == SIZE_MAX) { if (partial_ && wpp) continue; return DEC_ERR_INVALID; }
+      if (last != SIZE_MAX && job.sub_start[q] <= last) return DEC_ERR_INVALID;
+      last = job.sub_start[q];
+    }
+    if (last == SIZE_MAX && !(partial_ && wpp)) return DEC_ERR_INVALID; }
   if (wpp) job.ds_saved.assign((size_t)hc * CTX_COUNT, 0);
   for (int cy = 0; cy < hc; cy++) memcpy(job.ctu_tile + (size_t)cy * wc, job.ctb_slice.data() + (size_t)cy * wc, (size_t)wc);      // (one tile: the byte the kernels compare between adjacent blocks is the slice's)
   job.sh.slice_qp = job.slice_qps[0];
@@ -628,6 +643,14 @@ int Decoder::close_open_picture()
     old.seg_end_row[0] = 0; old.seg_end_row[(size_t)(old_hc - 1)] = 1;
     return submit_closed(old, 0);
   }
+  if (partial_ && old.pps.wpp && old.pps.tile_rows == 1 && old.pps.tile_cols == 1 && band_nrows_ == 0 && asm_.rows > 0 && asm_.rows < old_hc) {
+    // partial pictures v1 (decoder.h), Kvazaar's row form: with WPP the entry points say how many rows every segment holds -- rows [0, asm_.rows) arrived, the segment
+    // of row asm_.rows was lost and took the dependent ones behind it along (append_segment dropped them): the tail is missing, the picture is kept
+    const int wc = ctbs_in(w_, ctbl_);
+    old.missing.assign(1, std::make_pair(asm_.rows * wc, (old_hc - asm_.rows) * wc));
+    old.ambiguous_end = false;
+    return submit_closed(old, 0);
+  }
   if (old.pps.tile_rows == 1 && old.pps.tile_cols == 1 && band_nrows_ == 0 && asm_.segs.size() > 1) {
     // One tile, and the rows counted so far do not make the picture: they were counted on guesses -- without WPP no header says how far a segment reaches, a
     // dependent segment at a row's start was taken for that one row (the form Kvazaar's slices=wpp has WITH WPP).  The stream cuts its pictures as it likes after
@@ -648,7 +671,7 @@ int Decoder::close_open_picture()
 // what decode_slice's steps hand on to each other: the reader and the NAL unit, the header as far as it is read, the lists apply_rps_and_build_lists builds
 struct Decoder::SliceCtx {
   BitReader r; const uint8_t *rbsp; size_t len; int nal_type; int64_t pts; bool idr, irap;
-  bool first_seg = false, prior_flag = false, dependent = false; int pps_id = 0, seg_address = 0;      // prior_flag: no_output_of_prior_pics_flag
+  bool first_seg = false, opens = false, prior_flag = false, dependent = false; int pps_id = 0, seg_address = 0;      // prior_flag: no_output_of_prior_pics_flag
   const DecPps *p = nullptr; std::shared_ptr<const DecSps> sps; PicJob *open = nullptr;                  // open: the picture under way a further segment joins
   SliceHdr sh; StRps rps; LtRefs lt; bool across_slices = true;
   int nref = 0, ref_poc[16]; uint8_t ref_slot[16], ref_lt[16] = {};
@@ -699,6 +722,16 @@ bool Decoder::slice_front(SliceCtx &c, int &rc)
       // together from its segments when its access unit ends (append_segment, close_free_picture); this one is lost.
       free_stream_ = true;
     }
+    if (asm_.active && partial_ && !c.dependent && p.tile_cols == 1 && p.tile_rows == 1 && band_nrows_ == 0 && (c.pps_id != asm_.pps_id || c.nal_type != asm_.nal_type)) {
+      // (rule 2: an independent segment of ANOTHER picture -- the open one is closed with what it has)
+      if ((rc = close_open_picture()) < 0) return false;
+    }
+    if (!asm_.active && partial_ && !c.dependent && p.tile_cols == 1 && p.tile_rows == 1 && band_nrows_ == 0) {
+      // partial pictures v1, rule 2: an independent segment with no picture open opens one from its own header -- everything a first segment does; what lies in front of
+      // its address is missing
+      c.opens = true; c.open = nullptr;
+      return true;
+    }
     if (!asm_.active || c.pps_id != asm_.pps_id || c.nal_type != asm_.nal_type) { rc = DEC_ERR_INVALID; return false; }      // a segment without its picture's first one (lost), or of another picture
   } else if (asm_.active) {
     // the previous picture never got its last segment: close_open_picture() submits or drops it; this NAL unit -- a new picture -- is decoded normally
@@ -726,6 +759,8 @@ void Decoder::sequence_state(const SliceCtx &c)
 int Decoder::apply_rps_and_build_lists(SliceCtx &c)
 {
   const SliceHdr &sh = c.sh; const StRps &rps = c.rps; const DecSps &s = *c.sps;
+  cur_fill_src_ = avoid_slot_ = -1;
+  if (partial_ && cur_no_rasl_) choose_fill_source(sh.poc, true, std::vector<int>());      // (before the sequence before lets go of its pictures)
   if (cur_no_rasl_) for (auto &d : dpb_) d.is_ref = false;         // (8.3.2; what a CRA or BLA picture's set names is for its RASL pictures)
   if (!c.idr) {
     int cand_slot[32], nc = 0, nbefore = 0;             // the used pictures: those before the current one in output order (nearest first), then those after it, then the long-term ones
@@ -763,6 +798,7 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
     // same picture is a source.  (The source may be dropped by the set and become this picture's own buffer: the copy runs before the picture's kernels.)
     std::vector<int> fresh;
     for (const auto &pc : pending_conceal_) if (pc.second == -2) fresh.push_back(pc.first);
+    if (partial_ && !cur_no_rasl_) choose_fill_source(sh.poc, false, fresh);
     for (auto &pc : pending_conceal_) if (pc.second == -2) {
       int best = -1;
       for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) {
@@ -817,6 +853,8 @@ Decoder::PicJob &Decoder::open_job(const SliceCtx &c, const DecPps &pp, int slot
   for (int k = 0; k < 16; k++) { job.ref_poc[k] = k < c.nref ? c.ref_poc[k] : sh.poc; job.ref_slot[k] = k < c.nref ? c.ref_slot[k] : 0; job.ref_lt[k] = k < c.nref ? c.ref_lt[k] : 0; job.ref_lt1[k] = k < c.nref1 ? c.ref_lt1[k] : 0; }
   if (cur_no_rasl_) cvs_++;
   job.starts_cvs = cur_no_rasl_; job.discard_prior = cur_discard_;
+  job.missing.clear(); job.fill_src = cur_fill_src_; job.fill_motion.reset();
+  if (cur_fill_src_ >= 0) { job.fill_src_poc = dpb_[cur_fill_src_].poc; if (conceal_mode_ == 3) job.fill_motion = dpb_[cur_fill_src_].cmotion; }
   job.conceal = std::move(pending_conceal_); pending_conceal_.clear();                     // a new coded video sequence: its pictures follow ALL of the last one's in output order
   job.cvs = cvs_;
   job.nref1 = c.nref1; job.no_backward = c.no_backward;
@@ -868,7 +906,7 @@ Decoder::PicJob &Decoder::open_job(const SliceCtx &c, const DecPps &pp, int slot
   job.ambiguous_end = false; job.lf_restricted = false; job.lf_slices.clear();
   job.ctb_cut.clear(); job.ctb_slice.clear(); job.ctb_data.clear(); job.slice_qps.clear();
   asm_ = OpenPicture();
-  asm_.active = true; asm_.pps_id = c.pps_id; asm_.nal_type = c.nal_type; asm_.irap = c.irap; asm_.cur_qp = sh.slice_qp; asm_.lf.push_back(LfSlice{0, c.across_slices});
+  asm_.active = true; asm_.pps_id = c.pps_id; asm_.nal_type = c.nal_type; asm_.irap = c.irap; asm_.cur_qp = sh.slice_qp; asm_.lf.push_back(LfSlice{c.opens ? c.seg_address : 0, c.across_slices});
   return job;
 }
 
@@ -887,11 +925,16 @@ int Decoder::decode_slice(const uint8_t *rbsp, size_t len, int nal_type, int64_t
   const int slice_type = c.r.ue();
   if (slice_type < 0 || slice_type > 2) return DEC_ERR_INVALID;
   sh.is_intra = slice_type == 2; sh.is_b = slice_type == 0;
-  if (c.first_seg) sequence_state(c);                            // (an open picture has been closed by slice_front: seen_irap_ is current)
+  if (c.first_seg || c.opens) sequence_state(c);                            // (an open picture has been closed by slice_front: seen_irap_ is current)
   if ((rc = parse_slice_header_rest(c.r, s, p, c.idr, prev_poc_, cur_no_rasl_, sh, c.rps, c.lt, c.across_slices))) return rc;
   DecPps pp = p;                                                 // the picture's copy: tile boundaries for this picture size
   if ((rc = tile_boundaries(pp, s.wc(), s.hc()))) return rc;
-  if (!c.first_seg) {
+  if (!c.first_seg && !c.opens && partial_ && pp.tile_cols == 1 && pp.tile_rows == 1 && sh.poc != c.open->sh.poc) {
+    // partial pictures v1, rule 2: another picture's segment (its order count differs) -- the open picture is closed with what it has, this segment opens its own
+    if ((rc = close_open_picture()) < 0) return rc;
+    c.opens = true; c.open = nullptr; free_stream_ = true;
+  }
+  if (!c.first_seg && !c.opens) {
     // an independent slice of a picture under way
     if (!same_slice_params(sh, c.open->sh, pp.tile_cols > 1 || pp.tile_rows > 1)) return DEC_ERR_UNSUPPORTED;
     asm_.cur_dependent = false; asm_.cur_qp = sh.slice_qp;      // (inside one tile a slice may have its own SliceQpY: free slices, close_free_picture)
@@ -903,9 +946,10 @@ int Decoder::decode_slice(const uint8_t *rbsp, size_t len, int nal_type, int64_t
   if (p.cu_qp_delta && p.qp_delta_depth > s.ctb_log2 - s.min_cb_log2) return DEC_ERR_INVALID;      // (7.4.3.3.1: a quantisation group is no smaller than the minimum coding block)
   if (!ensure_buffers(s.width, s.height, s.ctb_log2)) return DEC_ERR_GPU;
   if ((rc = apply_rps_and_build_lists(c))) return rc;
-  const int slot = alloc_slot();
+  const int slot = alloc_slot();                                 // (partial pictures: not S's buffer, avoid_slot_ -- the fill reads it behind the picture's kernels)
+  avoid_slot_ = -1;
   if (slot < 0) return DEC_ERR_GPU;
-  return append_segment(open_job(c, pp, slot), c, pp, 0);
+  return append_segment(open_job(c, pp, slot), c, pp, c.opens ? c.seg_address : 0);
 }
 
 // The slice data of one segment joins the picture's job: entry points (the segment's substreams: whole CTU rows with WPP, else whole
@@ -931,8 +975,11 @@ int Decoder::append_segment(PicJob &job, const SliceCtx &c, const DecPps &pp, in
     asm_.free = true;
     if (!wait_always) free_stream_ = true;
   }
+  if (partial_ && !asm_.free && one_tile && p.wpp && asm_.cur_dependent && address % wc == 0 && address != asm_.rows * wc && address < wc * hc)
+    return 0;      // partial pictures v1, rule 1: a dependent segment behind a gap (its predecessor is gone) or before `next` (a duplicate) is dropped, the picture stays open
   if (!asm_.free && address != asm_.rows * wc) return fail(address % wc ? DEC_ERR_UNSUPPORTED : DEC_ERR_INVALID);     // whole CTU rows, in order
-  if (asm_.free && (address >= wc * hc || (asm_.segs.empty() ? address != 0 : address <= asm_.segs.back().address))) return fail(DEC_ERR_INVALID);
+  if (asm_.free && partial_ && !asm_.segs.empty() && address <= asm_.segs.back().address && address < wc * hc) return 0;      // (partial pictures, rule 1: a duplicate, or out of order -- ignored)
+  if (asm_.free && (address >= wc * hc || (asm_.segs.empty() ? (address != 0 && !partial_) : address <= asm_.segs.back().address))) return fail(DEC_ERR_INVALID);
   std::vector<uint32_t> entry; size_t hdr = 0;
   if (const int rc = parse_segment_tail(r, p.wpp || p.tile_rows > 1, p.header_extension != 0, entry, hdr)) return fail(rc);
   // CTU rows the segment covers
@@ -1006,12 +1053,36 @@ int Decoder::append_segment_tiles(PicJob &job, const SliceCtx &c, int address)
   return submit_job(job, asm_.nal_type, asm_.irap);
 }
 
+// partial pictures: four bytes per coding tree block of a parsed picture -- missing, its ctu_tile byte, its ctu_nb byte (0xff: no map), min(255, transform blocks)
+std::vector<uint8_t> Decoder::layout_of(const PicJob &job) const
+{
+  const int n = ctbs_in(w_, ctbl_) * ctbs_in(h_, ctbl_);
+  std::vector<uint8_t> o((size_t)n * 4);
+  for (int a = 0; a < n; a++) {
+    bool miss = false; for (const auto &m : job.missing) miss |= a >= m.first && a < m.first + m.second;
+    const uint32_t k = job.ctu[a].count & 0xffffffu;
+    o[4 * (size_t)a] = miss; o[4 * (size_t)a + 1] = job.ctu_tile[a]; o[4 * (size_t)a + 2] = job.lf_restricted ? job.h_in[job.lay.nb_off + (size_t)a] : 0xff; o[4 * (size_t)a + 3] = (uint8_t)(k > 255 ? 255 : k);
+  }
+  return o;
+}
+// ... a damaged picture that has parsed: its runs join the log, in decoding order, and its layout is kept for debug_copy "partial_layout"
+void Decoder::file_damage(const PicJob &job)
+{
+  if (job.missing.empty()) return;
+  for (const auto &m : job.missing) { damage_log_.push_back(job.sh.poc); damage_log_.push_back(m.first); damage_log_.push_back(m.second); }
+  damaged_layout_ = layout_of(job);
+}
+
 void Decoder::take_back_job(PicJob &job)
 {
   DpbPic &d = dpb_[job.slot];
   d.poc = job.undo.poc; d.is_ref = job.undo.is_ref; d.used = job.undo.used; d.decode_idx = job.undo.decode_idx; d.motion = job.undo.motion; d.cmotion = job.undo.cmotion; prev_poc_ = job.undo.prev_poc; seen_irap_ = job.undo.seen_irap;
-  vwait_ = std::move(job.undo.vwait);
+  vwait_ = std::move(job.undo.vwait); d.standin = job.undo.standin; take_backs_++;
   job.undo.motion.reset(); job.undo.cmotion.reset();
+  // the parse that ended early has released every row of the picture's ColMotion (parse_job release_all) and counted its columns: the picture is parsed AGAIN when its
+  // access unit has ended, and under frame threads the next picture's parser must wait for THAT parse, row by row -- the rows are closed again here (nobody holds the
+  // ColMotion but this job: the buffer's entry has just gone back to what it was, and no later picture has been opened)
+  if (job.own) for (int r = 0; r < job.own->hc; r++) { job.own->row_done[(size_t)r].store(0, std::memory_order_relaxed); if (job.own->row_cols) job.own->row_cols[(size_t)r].store(0, std::memory_order_relaxed); }
   job_head_--; job.state.store(0, std::memory_order_relaxed); job.rc = 0; job.early_dst = nullptr;
   asm_.active = true; asm_.free = free_stream_ = true;
 }
@@ -1022,6 +1093,7 @@ void Decoder::note_lf_restrictions(PicJob &job)
 {
   bool closed = (job.pps.tile_rows > 1 || job.pps.tile_cols > 1) && !job.pps.across_tiles;
   if (asm_.lf.size() > 1) for (const LfSlice &s : asm_.lf) closed |= !s.across;
+  closed |= !job.missing.empty();                                // (partial pictures: the boundary of what is missing is closed)
   job.lf_restricted = closed && band_nrows_ == 0;
   job.lf_slices.clear();
   if (job.lf_restricted) for (const LfSlice &s : asm_.lf) job.lf_slices.emplace_back(s.address, (uint8_t)s.across);
@@ -1036,9 +1108,10 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
   // (PicJob::ambiguous_end: when the picture's last segment ends before the picture does, more segments are to come -- everything is put back as it was before
   // the call and the picture is open again, as one of free slices; append_segment collects the rest, the end of the access unit closes it.  The synchronous decoder
   // knows at once; with frame threads the worker finds out and decode_slice looks when the next segment arrives.)
-  job.undo.poc = d.poc; job.undo.prev_poc = prev_poc_; job.undo.is_ref = d.is_ref; job.undo.used = d.used; job.undo.seen_irap = seen_irap_; job.undo.decode_idx = d.decode_idx; job.undo.motion = d.motion; job.undo.cmotion = d.cmotion;
+  job.undo.poc = d.poc; job.undo.prev_poc = prev_poc_; job.undo.is_ref = d.is_ref; job.undo.used = d.used; job.undo.seen_irap = seen_irap_; job.undo.decode_idx = d.decode_idx; job.undo.motion = d.motion; job.undo.cmotion = d.cmotion; job.undo.standin = d.standin;
   auto take_back = [&] { take_back_job(job); return 0; };
-  d.poc = sh.poc; d.is_ref = true; d.used = true; d.is_lt = false; d.decode_idx = job_head_; d.motion = job.own; d.cmotion = job.cown;
+  job.scan_gaps = partial_ && band_nrows_ == 0 && (!job.pps.wpp || !job.ctb_cut.empty()) && job.pps.tile_rows == 1 && job.pps.tile_cols == 1;      // (one tile, without WPP or as free slices: the parser finds the gaps, parse_substream)
+  d.poc = sh.poc; d.is_ref = true; d.used = true; d.is_lt = false; d.standin = false; d.decode_idx = job_head_; d.motion = job.own; d.cmotion = job.cown;
   if (cur_tid_ == 0 && (nal_type > 9 || ((nal_type & 1) && nal_type < 6))) prev_poc_ = sh.poc;   // prevTid0Pic (8.3.1): TemporalId 0, not RASL / RADL / sub-layer non-reference
   if (irap) seen_irap_ = true;
   {
@@ -1068,6 +1141,7 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
     job_tail_ = job_head_;
     if (job.rc < 0) return job.rc;
     probe_book(job, ms);
+    file_damage(job);      // (once the picture has parsed: rule 1, what does not parse is corruption and no damaged picture)
     return 0;
   }
   if (frame_threads_ == 1) {
@@ -1077,7 +1151,7 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
       // (decoder.h PicJob::early_dst; the buffer is the one launch_gpu will pick -- nothing is launched between here and there)
       static const bool early_off = [] { const char *e = getenv("KVAZZUP_AMD_DEC_EARLY_UP"); return e && atoi(e) == 0; }();
       const int ib = (int)(launched_ % (gpu_depth_ + 1));
-      if (!early_off && gpu_depth_ == 1 && band_nrows_ == 0 && job.pps.tile_cols == 1 && !job.lf_restricted && !(batch_attached_ && DecBatcher::get(device_).active()) && d_in_[ib] && d_in_cap_[ib] >= job.lay.fixed_bytes()) job.early_dst = d_in_[ib];      // (lf_restricted: parse_job's last step still changes records)
+      if (!early_off && gpu_depth_ == 1 && band_nrows_ == 0 && job.pps.tile_cols == 1 && !job.lf_restricted && !job.scan_gaps && !(batch_attached_ && DecBatcher::get(device_).active()) && d_in_[ib] && d_in_cap_[ib] >= job.lay.fixed_bytes()) job.early_dst = d_in_[ib];      // (lf_restricted: parse_job's last step still changes records)
     }
     job.rc = parse_job(job, true);
     if (job.rc == DEC_SEG_ENDS_EARLY) { if (job.early_dst) hipStreamSynchronize(stream_up_); return take_back(); }
@@ -1147,6 +1221,7 @@ int Decoder::finish_oldest()
     rc_launch = job.rc < 0 ? (job.rc == DEC_SEG_ENDS_EARLY ? DEC_ERR_UNSUPPORTED : job.rc) : launch_gpu(job);      // (a picture whose last segment ended early and whose rest never came)
     // a picture that could not be parsed (damaged on the way) is never reconstructed: its buffer is no reference picture -- the pictures that name it find it
     // missing and get a stand-in (conceal_ref) instead of whatever the buffer held.  (Frame threads: pictures submitted before this was known keep the buffer.)
+    if (job.rc >= 0) file_damage(job);      // (partial pictures: in decoding order, once the picture has parsed)
     if (job.rc < 0 && dpb_[job.slot].is_ref && dpb_[job.slot].poc == job.sh.poc && dpb_[job.slot].decode_idx == job_tail_ - 1) dpb_[job.slot].is_ref = false;
     tl("dlaunch1", job.pts);
     launched = rc_launch >= 0;
@@ -1178,6 +1253,8 @@ void Decoder::describe_output(const PicJob &job, DecodedPicture &o, int buf) con
   o.width = w_ - job.crop[0] - job.crop[1]; o.height = h_ - job.crop[2] - job.crop[3];
   o.poc = job.sh.poc; o.pts = job.pts; o.is_intra = job.sh.is_intra; o.cvs = job.cvs; o.num_reorder = job.sps->num_reorder; o.serial = job.serial;
   o.fps_num = job.fps_num; o.fps_den = job.fps_den;
+  for (const auto &m : job.missing) o.missing_ctbs += m.second;
+  o.total_ctbs = ctbs_in(w_, ctbl_) * ctbs_in(h_, ctbl_);
   for (int c = 0; c < 3; c++) {
     const int pw = c ? pw_ / 2 : pw_, ox = c ? job.crop[0] / 2 : job.crop[0], oy = c ? job.crop[2] / 2 : job.crop[2];
     const size_t off = (size_t)oy * pw + ox;
@@ -1241,7 +1318,7 @@ int Decoder::complete_gpu(PicJob &job)
     t_sync_ += tk.ms();
   }
   if (*h_err_) { fprintf(stderr, "kvazzup_amd: decoder device error flags 0x%x\n", *h_err_); return DEC_ERR_GPU; }
-  if (!job.expect_hash.empty()) {                  // libOpenHevcSetCheckMD5: the picture's hash SEI arrived while it was in the ring
+  if (!job.expect_hash.empty() && job.missing.empty()) {                  // libOpenHevcSetCheckMD5: the picture's hash SEI arrived while it was in the ring
     const std::vector<uint8_t> want = std::move(job.expect_hash); job.expect_hash.clear();
     const int rc = verify_hash(job, want);
     if (rc < 0) last_error_ = rc;                   // (the picture is still handed out: the application decides, as with OpenHEVC)
@@ -1331,6 +1408,56 @@ int Decoder::fill_concealed(PicJob &job)
   for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
   job.conceal.clear(); return 0;
 }
+// Partial pictures v1, rule 4 (decoder.h): S for the picture whose first segment is being read -- conceal_ref's selection (apply_rps_and_build_lists) for the picture's own
+// order count; last_decoded: an IRAP picture that starts a coded video sequence -- order counts of the sequence before do not compare, the held picture decoded last
+void Decoder::choose_fill_source(int poc, bool last_decoded, const std::vector<int> &fresh)
+{
+  int best = -1;
+  for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) {
+    if (!dpb_[q].is_ref || !dpb_[q].used || std::find(fresh.begin(), fresh.end(), q) != fresh.end()) continue;
+    if (last_decoded) { if (!dpb_[q].standin && (best < 0 || dpb_[q].decode_idx > dpb_[best].decode_idx)) best = q; continue; }
+    const long long dq = llabs((long long)dpb_[q].poc - poc), db = best < 0 ? 0 : llabs((long long)dpb_[best].poc - poc);
+    if (best < 0 || dq < db || (dq == db && dpb_[q].poc < dpb_[best].poc)) best = q;
+  }
+  cur_fill_src_ = avoid_slot_ = best;      // (from here to the picture's own alloc_slot nothing takes S's buffer: not a stand-in made for this picture either -- conceal_ref)
+}
+// ... and its samples: the missing coding tree blocks of `job` from S into the picture's buffer (DecFrame::out), BEHIND the picture's last kernel -- k_dec_inter writes whole
+// 32x32 regions, the SAO pass whole tiles, so nothing put there earlier would last -- and before any later picture is launched: the picture has been launched just now, by this
+// decoder or by the submission layer (batch.h; its `launched` flag is waited for), the device is drained -- the picture and S are complete --, the kernel runs, and only then
+// does launch_gpu return.  What the drain costs is what a lost picture's costs (fill_concealed): the GPU queue runs empty once -- the calling thread waits for the pictures in
+// flight and for this one instead of going on parsing headers; a damaged picture is rare.
+int Decoder::fill_missing(PicJob &job)
+{
+  while (!job.launched.load(std::memory_order_acquire)) futex_wait(job.launched, 0);
+  if (hipDeviceSynchronize() != hipSuccess) return DEC_ERR_GPU;
+  const int wc = ctbs_in(w_, ctbl_), total = wc * ctbs_in(h_, ctbl_);
+  std::vector<uint32_t> list;
+  for (const auto &m : job.missing) for (int k = 0; k < m.second; k++) if (m.first + k >= 0 && m.first + k < total) list.push_back((uint32_t)(m.first + k));
+  if (list.empty()) return 0;
+  if (list.size() * sizeof(uint32_t) > fill_ctbs_cap_) { hipFree(d_fill_ctbs_); fill_ctbs_cap_ = 0; if (hipMalloc(&d_fill_ctbs_, (size_t)total * sizeof(uint32_t)) != hipSuccess) { d_fill_ctbs_ = nullptr; return DEC_ERR_GPU; } fill_ctbs_cap_ = (size_t)total * sizeof(uint32_t); }
+  if (hipMemcpy(d_fill_ctbs_, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return DEC_ERR_GPU;
+  uint8_t *const *dst = dpb_[job.slot].plane;
+  uint8_t *const *src = job.fill_src >= 0 && job.fill_src != job.slot && dpb_[job.fill_src].plane[0] ? dpb_[job.fill_src].plane : nullptr;
+  const int16_t *d_tab = nullptr;
+  const int w16 = (w_ + 15) / 16, h16 = (h_ + 15) / 16;
+  fill_tab_.assign((size_t)w16 * h16 * 4, 0);
+  if (conceal_mode_ == 3 && src) {
+    fill_tab_ = conceal_displacements(job.fill_motion.get(), w16, h16, job.sh.poc, job.fill_src_poc);
+    const size_t bytes = fill_tab_.size() * sizeof(int16_t);
+    if (bytes > fill_tab_cap_) { hipFree(d_fill_tab_); fill_tab_cap_ = 0; if (hipMalloc(&d_fill_tab_, bytes) != hipSuccess) { d_fill_tab_ = nullptr; return DEC_ERR_GPU; } fill_tab_cap_ = bytes; }
+    if (hipMemcpy(d_fill_tab_, fill_tab_.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) return DEC_ERR_GPU;
+    d_tab = d_fill_tab_;
+  }
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  if (profiling_) for (auto &e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+  if (ev[0]) hipEventRecord(ev[0], stream_);
+  launch_dec_fill_ctbs(dst, src, d_tab, d_fill_ctbs_, (int)list.size(), ctbl_, w_, h_, pw_, stream_);
+  if (ev[1]) hipEventRecord(ev[1], stream_);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) return DEC_ERR_GPU;
+  if (ev[0] && ev[1]) { float ms = 0; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) standin_ms_ = ms; }      // (debug_copy "standin_ms": the last fill of either kind)
+  for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
+  return 0;
+}
 // The input block goes up on its own stream into one of gpu_depth_ + 1 device buffers: the gpu_depth_ pictures launched before this one may still be running
 // (finish_oldest launches before it completes the oldest of them) and read the other buffers; the one before those has been completed, so this buffer is free.
 // -> buffer `ib`, grown to hold this picture's block; NULL: no memory
@@ -1364,8 +1491,8 @@ DecFrame Decoder::picture_frame(PicJob &job, const DecInputLayout &lay, const Ch
   if (job.any_intra) f.chain_gen = chain_gen_;
   f.cb_qp_offset = (int8_t)job.pps.cb_qp_offset; f.cr_qp_offset = (int8_t)job.pps.cr_qp_offset; f.beta_offset = (int8_t)(2 * job.sh.beta_offset_div2); f.tc_offset = (int8_t)(2 * job.sh.tc_offset_div2);
   f.intra_direct = job.any_inter ? 1 : 0;                 // (a picture with inter blocks: few (CTU, plane) pairs hold intra blocks)
-  f.strong_intra = (uint8_t)job.sps->strong_intra; f.tiles = job.pps.tile_rows > 1 || job.pps.tile_cols > 1 || job.slice_qps.size() > 1;
-  f.general = (uint8_t)(job.pps.tile_rows > 1 || job.pps.tile_cols > 1 || job.slice_qps.size() > 1 || job.sps->pcm_depth[0] != 0);
+  f.strong_intra = (uint8_t)job.sps->strong_intra; f.tiles = job.pps.tile_rows > 1 || job.pps.tile_cols > 1 || job.slice_qps.size() > 1 || !job.missing.empty();      // (missing blocks: a slice byte of their own -- no received block takes them for neighbours or waits for them)
+  f.general = (uint8_t)(job.pps.tile_rows > 1 || job.pps.tile_cols > 1 || job.slice_qps.size() > 1 || !job.missing.empty() || job.sps->pcm_depth[0] != 0);
   f.cip = (uint8_t)(job.pps.cip && job.any_inter);      // (a picture without inter blocks: every neighbour is intra)
   f.tq_bypass = (uint8_t)(job.pps.tq_bypass || (job.sps->pcm_depth[0] && job.sps->pcm_no_filter));      // (units the loop filters keep out of: B4_BYPASS records)
   // scaling lists: the picture's factors (the PPS's lists when it carries any, else the SPS's) ride in the input block
@@ -1454,6 +1581,7 @@ int Decoder::launch_gpu(PicJob &job)
   if (!upload(job, job.lay, d_in, ib, batched)) return DEC_ERR_GPU;
   job.dl_buf = -1; job.launch_idx = launched_;
   if (const int rc = batched ? post_to_batcher(job, f, d_in, ib) : launch_self(job, f, d_in, ib, alt); rc < 0) return rc;
+  if (!job.missing.empty()) { const int rc = fill_missing(job); if (rc < 0) return rc; }      // (partial pictures: behind the picture's last kernel, before anything later is launched)
   t_api_ += tk_api.ms(); launched_++;
   if (band_nrows_ > 0) gpu_job_ = &job; else gpu_q_.push_back(&job);
   return 0;
@@ -1515,6 +1643,22 @@ bool Decoder::debug_copy(const char *what, void *dst, size_t bytes)
   // concealment v3: the stand-in filled last (its buffer as it lies in memory: Y | Cb | Cr, pitch = the padded width) and its table of displacements
   if (w == "standin") { if (standin_slot_ < 0 || bytes > npx * 3 / 2) return false; return hipDeviceSynchronize() == hipSuccess && hipMemcpy(dst, dpb_[standin_slot_].plane[0], bytes, hipMemcpyDeviceToHost) == hipSuccess; }
   if (w == "standin_ms") { if (bytes != sizeof(float) || standin_ms_ < 0) return false; memcpy(dst, &standin_ms_, sizeof(float)); return true; }      // (either mode, with set_profiling: the last stand-in's fill, ms)
+  if (w == "take_backs") { if (bytes != sizeof(uint32_t)) return false; memcpy(dst, &take_backs_, sizeof(uint32_t)); return true; }      // pictures taken back so far (take_back_job): what the tests of that path assert
+  if (w == "fill_mv") { if (fill_tab_.empty() || bytes > fill_tab_.size() * sizeof(int16_t)) return false; memcpy(dst, fill_tab_.data(), bytes); return true; }      // partial pictures: the table used last
+  if (w == "partial_layout") {
+    // partial pictures: the layout (layout_of) of the damaged picture filed last; before the first one, of the picture parsed last (the synchronous and the parse-only
+    // decoder: its parse has ended)
+    std::vector<uint8_t> lay = damaged_layout_;
+    if (lay.empty()) {
+      if (job_head_ < 1) return false;
+      const PicJob &job = jobs_[(size_t)((job_head_ - 1) % (long)jobs_.size())];
+      if (job.state.load(std::memory_order_acquire) == 1 || !job.h_in) return false;
+      lay = layout_of(job);
+    }
+    if (bytes != lay.size()) return false;
+    memcpy(dst, lay.data(), bytes);
+    return true;
+  }
   if (w == "standin_mv") { if (standin_slot_ < 0 || bytes > standin_tab_.size() * sizeof(int16_t)) return false; memcpy(dst, standin_tab_.data(), bytes); return true; }
   for (int c = 0; c < 3; c++) {
     size_t n = c ? npx / 4 : npx;

@@ -233,11 +233,16 @@ class WireAdapter : public Filter {
   // harness setting uvgx/wireLossEvery = n > 0: every n-th access unit is lost on the way (never one with parameter sets or an IRAP picture) -- what a UDP path does;
   // the decoder conceals (csrc/decoder.h; harness setting uvgx/concealment = 2 | 3 picks the rule, OpenHEVCFilter::init) and the chain keeps delivering.  lost(): how many went.
   void setLossEvery(int n) { lossEvery_ = n; }
+  // harness setting uvgx/wireLossSegmentEvery = n > 0: every n-th VCL NAL unit -- a slice segment, one packet -- is lost, never one of an IRAP picture: what video/Slices is
+  // switched on for.  With uvgx/partialPictures = 1 the decoder keeps the rest of the picture (csrc/decoder.h "Partial pictures v1").
+  void setLossSegmentEvery(int n) { lossSegmentEvery_ = n; }
+  uint64_t lostSegments() const { return lostSegments_.load(); }
   uint64_t lost() const { return lost_.load(); }
  protected:
   void process() override;
  private:
   int lossEvery_ = 0; uint64_t seen_ = 0; std::atomic<uint64_t> lost_{0};
+  int lossSegmentEvery_ = 0; uint64_t seenSegments_ = 0; std::atomic<uint64_t> lostSegments_{0};
 };
 
 }  // namespace uvgx

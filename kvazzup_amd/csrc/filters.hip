@@ -494,6 +494,9 @@ bool OpenHEVCFilter::init()                                // openhevcfilter.cpp
   // harness setting uvgx/concealment = 2 | 3 (kvazzup_amd.h kvzx_decoder_set_concealment): what stands in for a picture lost on the way; absent = 2
   const std::string conceal = get("uvgx/concealment", "");
   if (!conceal.empty() && !kvzx_decoder_set_concealment(handle_, atoi(conceal.c_str()))) { fprintf(stderr, "OpenHEVCFilter: invalid uvgx/concealment %s\n", conceal.c_str()); return false; }
+  // harness setting uvgx/partialPictures = 0 | 1 (kvazzup_amd.h kvzx_decoder_set_partial_pictures): a picture that lost slice segments keeps what arrived; absent = 0
+  const std::string partial = get("uvgx/partialPictures", "");
+  if (!partial.empty() && !kvzx_decoder_set_partial_pictures(handle_, atoi(partial.c_str()))) { fprintf(stderr, "OpenHEVCFilter: invalid uvgx/partialPictures %s\n", partial.c_str()); return false; }
   if (libOpenHevcStartDecoder(handle_) == -1) { fprintf(stderr, "OpenHEVCFilter: failed to start decoder\n"); return false; }
   libOpenHevcSetTemporalLayer_id(handle_, 0);
   libOpenHevcSetActiveDecoders(handle_, 0);
@@ -686,7 +689,10 @@ void WireAdapter::process()
       for (size_t k = 0; k + 1 < starts.size(); k++) { const int t = (p[starts[k] + 4] >> 1) & 0x3f; precious |= (t >= 16 && t <= 23) || (t >= 32 && t <= 34); }
       if (!precious && ++seen_ % (uint64_t)lossEvery_ == 0) { lost_.fetch_add(1); input = getInput(); continue; }
     }
+    bool irap = false;
+    if (lossSegmentEvery_ > 0) for (size_t k = 0; k + 1 < starts.size(); k++) { const int t = (p[starts[k] + 4] >> 1) & 0x3f; irap |= t >= 16 && t <= 23; }
     for (size_t k = 0; k + 1 < starts.size(); k++) {
+      if (lossSegmentEvery_ > 0 && !irap && ((p[starts[k] + 4] >> 1) & 0x3f) < 32 && ++seenSegments_ % (uint64_t)lossSegmentEvery_ == 0) { lostSegments_.fetch_add(1); continue; }      // (one packet, one slice segment)
       std::unique_ptr<Data> nal(new Data);
       nal->source = DS_REMOTE; nal->type = DT_HEVCVIDEO;
       nal->data_size = starts[k + 1] - starts[k];
@@ -787,6 +793,7 @@ KVZ_PUBLIC void *uvgx_pipeline_create(const char *settings_text, int loopback_de
   if (p->loopback) {
     p->wire.reset(new WireAdapter("uvgx", &p->stats));
     { auto it = p->settings.find("uvgx/wireLossEvery"); if (it != p->settings.end()) p->wire->setLossEvery(atoi(it->second.c_str())); }
+    { auto it = p->settings.find("uvgx/wireLossSegmentEvery"); if (it != p->settings.end()) p->wire->setLossSegmentEvery(atoi(it->second.c_str())); }
     p->dec.reset(new OpenHEVCFilter(1, &p->stats, &p->settings));
     if (!p->dec->init()) { delete p; return nullptr; }
     p->enc->addOutConnection(p->wire.get());

@@ -111,10 +111,10 @@ int kvzx_decoder_set_device(OpenHevc_Handle hh, int device)
 {
   Handle *h = H(hh);
   if (!h || h->started || device < 0) return 0;
-  int ft = h->dec->frame_threads(), cm = h->dec->concealment();
+  int ft = h->dec->frame_threads(), cm = h->dec->concealment(); const bool pp = h->dec->partial_pictures();
   delete h->dec;
   h->dec = new Decoder(device);
-  h->dec->set_frame_threads(ft); h->dec->set_concealment(cm);
+  h->dec->set_frame_threads(ft); h->dec->set_concealment(cm); h->dec->set_partial_pictures(pp);
   return 1;
 }
 void kvzx_decoder_hash_stats(OpenHevc_Handle hh, int *checked, int *mismatch) { Handle *h = H(hh); if (h) h->dec->hash_stats(checked, mismatch); }
@@ -138,6 +138,17 @@ int kvzx_decoder_parse_probe_stats(OpenHevc_Handle hh, uint64_t *out5, double *p
 }
 // what stands in for a lost reference picture (decoder.h "Concealment v2" / "v3"): before the first picture
 int kvzx_decoder_set_concealment(OpenHevc_Handle hh, int mode) { Handle *h = H(hh); return h && h->dec->set_concealment(mode) ? 1 : 0; }
+// partial pictures v1 (decoder.h): a picture that lost slice segments keeps what arrived; before the first picture, not on a band decoder
+int kvzx_decoder_set_partial_pictures(OpenHevc_Handle hh, int on) { Handle *h = H(hh); return h && h->dec->set_partial_pictures(on != 0) ? 1 : 0; }
+int kvzx_decoder_damage(OpenHevc_Handle hh, int *missing_ctbs, int *total_ctbs)
+{
+  Handle *h = H(hh);
+  if (!h || !h->have_pic) return 0;
+  if (missing_ctbs) *missing_ctbs = h->pic.missing_ctbs;
+  if (total_ctbs) *total_ctbs = h->pic.total_ctbs;
+  return 1;
+}
+int kvzx_decoder_damage_log(OpenHevc_Handle hh, int32_t *triples, int cap) { Handle *h = H(hh); return h ? h->dec->damage_log(triples, cap < 0 ? 0 : cap) : 0; }
 int kvzx_decoder_last_error(OpenHevc_Handle hh) { Handle *h = H(hh); return h ? h->dec->last_error() : -1; }
 int kvzx_decoder_output_device(OpenHevc_Handle hh, const void **planes, int *pitches)
 {

@@ -50,11 +50,13 @@ PACKED_TYPES = {"rgb32": 1 << 10, "rgb32-sse41": 1 << 10, "yuyv": 1 << 4}      #
 
 
 class Pipeline:
-    def __init__(self, width, height, fps=(30, 1), settings=None, custom=(), loopback=True, keep_outputs=True, concealment=None):
+    def __init__(self, width, height, fps=(30, 1), settings=None, custom=(), loopback=True, keep_outputs=True, concealment=None, partial_pictures=None):
         """settings: uvgComm's keys and the uvgx/* extensions (csrc/filters.h), e.g. uvgx/wireLossEvery; concealment = 2 | 3 is short for the setting
         uvgx/concealment (what the decoder puts in a lost picture's place, kvazzup_amd.h kvzx_decoder_set_concealment)"""
         if concealment is not None:
             settings = dict(settings or {}, **{"uvgx/concealment": int(concealment)})
+        if partial_pictures is not None:                            # (short for uvgx/partialPictures: a picture that lost slice segments keeps what arrived)
+            settings = dict(settings or {}, **{"uvgx/partialPictures": int(bool(partial_pictures))})
         self.lib = N.load_library()
         _bind(self.lib)
         s = dict(DEFAULT_SETTINGS)

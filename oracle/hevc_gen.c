@@ -43,6 +43,7 @@ struct orc_gen {
   int cu_qp_delta_coded, log2_qg;
   int cu_pred_mode, part_mode, intra_split, max_trafo_depth, cu_bypass;
   int intra_modes[4], chroma_mode;
+  uint64_t ctu_bins0; int ctu_raw_bits;   /* sat_levels: the coder's bin count when the coding tree unit began, the bits it has written raw (PCM samples) since */
 };
 
 /* ------------------------------------------------------------------ random numbers */
@@ -130,6 +131,9 @@ orc_gen *orc_gen_open(const orc_gen_config *cfg)
   if (c->tq_bypass < 0) c->tq_bypass = 0;
   if (c->scaling_lists < 0 || c->scaling_lists > 4) c->scaling_lists = 0;
   if (c->b_slices < 0) c->b_slices = 0;
+  if (c->sat_levels < 0) c->sat_levels = 0;                             /* (never drawn, as the two below) */
+  if (c->edge_mvd < 0) c->edge_mvd = 0;
+  if (c->edge_weights != 1) c->edge_weights = 0;
   if (c->weighted < 0) c->weighted = 0;
   if (c->list_mod < 0) c->list_mod = 0;
   if (c->gop != 2 && c->gop != 4 && c->gop != 8) c->gop = 0;
@@ -309,6 +313,27 @@ static int draw_abs_level(orc_gen *g)
   return rrange(g, 401, 20000);                       /* long escape codes */
 }
 
+/* sat_levels.  A coding tree unit may take 5/3 of its raw size at most (7.4.9.x: the bits of coding_tree_unit()); RawCtuBits is 12 bits per luma sample here.  The
+ * estimate of what the unit has spent is kept by the arithmetic coder itself: its count of bins since the unit began, every bin -- context-coded or bypass -- taken
+ * as one bit, plus the bits written raw (PCM samples).  A saturating coefficient costs 36 bins at most (significance, greater-1, greater-2, sign, and an escape code
+ * of 4 + 13 + 1 + 14 bins).  Saturating levels are admitted only while estimate + 36 per coefficient + 64 stays within the RAW size, three fifths of the limit: the
+ * other two fifths (8 bits per luma sample) are left to the ordinary syntax that may still follow in the unit and to context-coded bins that cost more than a
+ * bit.  That margin is EMPIRICAL, not derived: the ordinary draw's largest coding tree unit measures 3.9 bits per luma sample at CTB 16, 2.0 at 32 and 1.5 at 64 (density
+ * 90, twice what any test stream uses), and tests/test_bounds_streams.py holds both halves -- the ordinary draw to the margin, saturating units to the limit -- on
+ * pictures one coding tree block wide, where the entry points state each unit's size.  What does not fit is drawn the ordinary way. */
+static int sat_fits(const orc_gen *g, int ncoef)
+{
+  const int64_t raw = 12ll << (2 * g->cfg.ctb_log2);
+  return (int64_t)(g->c.bins - g->ctu_bins0) + g->ctu_raw_bits + 36ll * ncoef + 64 <= raw;
+}
+static int draw_sat_level(orc_gen *g, int negative)      /* 32768 only where the level is negative: TransCoeffLevel is -32768 .. 32767 */
+{
+  const int r = (int)(rnd(g) % 100u);
+  if (r < 35) return (negative && rpct(g, 50)) ? 32768 : 32767;
+  if (r < 55) return 32766;
+  return rrange(g, 20001, 32767);
+}
+
 static void gen_residual(orc_gen *g, int log2, int cidx, int scan_idx)
 {
   orc_cabac_enc *c = &g->c;
@@ -317,9 +342,18 @@ static void gen_residual(orc_gen *g, int log2, int cidx, int scan_idx)
   const uint8_t *px = orc_scan_x[scan_idx][2], *py = orc_scan_y[scan_idx][2];
   uint8_t csbf[8][8]; memset(csbf, 0, sizeof(csbf));
   if (g->pps.transform_skip_enabled && !g->cu_bypass && log2 <= 2) orc_cenc_bin(c, CTX_TS_FLAG + (cidx ? 1 : 0), rpct(g, 30));
+  /* sat_levels: 1 = a saturating block (everything coded, every level at the bound), 2 = one or two such levels among ordinary ones; the sign pattern of a
+   * saturating block: 0 all positive, 1 all negative, 2 alternating along the scan, 3 aligned with the inverse transform's basis at the sample (sat_x, sat_y) */
+  int sat = 0, sat_pat = 0, sat_x = 0, sat_y = 0, sat_flip = 0, sat_left = 0;
+  if (g->cfg.sat_levels > 0 && rpct(g, g->cfg.sat_levels)) {
+    if (rpct(g, 25)) { if (sat_fits(g, 2)) { sat = 2; sat_left = rrange(g, 1, 2); } }
+    else if (sat_fits(g, n * n)) { sat = 1; sat_pat = rrange(g, 0, 3); sat_x = rrange(g, 0, n - 1); sat_y = rrange(g, 0, n - 1); sat_flip = (int)(rnd(g) & 1u); }
+  }
+  const int sat_dst = g->cu_pred_mode == MODE_INTRA && log2 == 2 && cidx == 0;
   /* the last significant coefficient: mostly in the low-frequency corner */
   int last_sb, last_pos;
-  if (rpct(g, 60) || nsb == 1) { last_sb = 0; last_pos = rrange(g, 0, 15); }
+  if (sat == 1) { last_sb = nsb * nsb - 1; last_pos = 15; }
+  else if (rpct(g, 60) || nsb == 1) { last_sb = 0; last_pos = rrange(g, 0, 15); }
   else if (rpct(g, 70)) { last_sb = rrange(g, 0, ORC_MIN(3, nsb * nsb - 1)); last_pos = rrange(g, 0, 15); }
   else { last_sb = rrange(g, 0, nsb * nsb - 1); last_pos = rrange(g, 0, 15); }
   int lx = (sbx[last_sb] << 2) + px[last_pos], ly = (sby[last_sb] << 2) + py[last_pos];
@@ -337,7 +371,7 @@ static void gen_residual(orc_gen *g, int log2, int cidx, int scan_idx)
     int xs = sbx[i], ys = sby[i], infer_dc = 0;
     int right = (xs < nsb - 1) ? csbf[ys][xs + 1] : 0, below = (ys < nsb - 1) ? csbf[ys + 1][xs] : 0;
     if (i < last_sb && i > 0) {
-      csbf[ys][xs] = (uint8_t)rpct(g, 40);
+      csbf[ys][xs] = (uint8_t)(sat == 1 ? 1 : rpct(g, 40));
       orc_cenc_bin(c, CTX_CSBF + ((right | below) ? 1 : 0) + (cidx ? 2 : 0), csbf[ys][xs]);
       infer_dc = 1;
     } else csbf[ys][xs] = 1;
@@ -360,14 +394,30 @@ static void gen_residual(orc_gen *g, int log2, int cidx, int scan_idx)
           if (cidx == 0) { if (i > 0) sc += 3; sc += (log2 == 3) ? ((scan_idx == 0) ? 9 : 15) : 21; }
           else sc += (log2 == 3) ? 9 : 12;
         }
-        sig[k] = (uint8_t)rpct(g, dens);
+        sig[k] = (uint8_t)(sat == 1 ? 1 : rpct(g, dens));
         orc_cenc_bin(c, CTX_SIG + (cidx ? 27 : 0) + sc, sig[k]);
         if (sig[k]) infer_dc = 0;
       } else sig[0] = 1;                                /* inferred: a coded sub-block whose other flags are all zero */
     }
     int nsig = 0; for (int k = 0; k < 16; k++) nsig += sig[k];
     if (!nsig) continue;
-    int absv[16]; for (int k = 0; k < 16; k++) absv[k] = sig[k] ? draw_abs_level(g) : 0;
+    int absv[16], sgn[16];
+    if (sat == 1) {
+      /* signs first (32768 needs a negative one), then the levels; a hidden sign is the parity of the sum (9.3.4.3 / 7.3.8.11): where it comes out wrong the
+       * sub-block's last level in scan order moves by one, staying inside the set and off 32768 */
+      int lo = 16, hi = -1, sum = 0;
+      for (int k = 0; k < 16; k++) {
+        const int xc = (xs << 2) + px[k], yc = (ys << 2) + py[k];
+        const int tv = sat_dst ? orc_dst_mat[yc][sat_y] : orc_dct_mat[yc << (5 - log2)][sat_y], th = sat_dst ? orc_dst_mat[xc][sat_x] : orc_dct_mat[xc << (5 - log2)][sat_x];
+        sgn[k] = sat_pat == 0 ? 0 : sat_pat == 1 ? 1 : sat_pat == 2 ? (k & 1) : ((tv < 0) ^ (th < 0) ^ sat_flip);
+        absv[k] = sig[k] ? draw_sat_level(g, sgn[k]) : 0;
+        if (sig[k]) { if (lo > k) lo = k; hi = k; sum += absv[k]; }
+      }
+      if (g->pps.sign_data_hiding && !g->cu_bypass && hi - lo > 3 && (sum & 1) != sgn[lo]) absv[hi] += absv[hi] > 20001 ? -1 : 1;
+    } else {
+      for (int k = 0; k < 16; k++) absv[k] = sig[k] ? draw_abs_level(g) : 0;
+      for (int k = 0; k < 16 && sat_left > 0; k++) if (sig[k] && rpct(g, 15)) { absv[k] = draw_sat_level(g, 0); sat_left--; }      /* (sat == 2; the signs stay drawn) */
+    }
     int ctx_set = (i > 0 && cidx == 0) ? 2 : 0;
     if (c1 == 0) ctx_set++;
     c1 = 1;
@@ -385,7 +435,7 @@ static void gen_residual(orc_gen *g, int log2, int cidx, int scan_idx)
     }
     if (last_g1_pos != -1) orc_cenc_bin(c, CTX_GT2 + (cidx ? 4 : 0) + ctx_set, absv[last_g1_pos] > 2);
     int sign_hidden = g->pps.sign_data_hiding && !g->cu_bypass && (last_sig - first_sig > 3);
-    for (int k = 15; k >= 0; k--) if (sig[k] && (!sign_hidden || k != first_sig)) orc_cenc_bypass(c, (int)(rnd(g) & 1u));
+    for (int k = 15; k >= 0; k--) if (sig[k] && (!sign_hidden || k != first_sig)) orc_cenc_bypass(c, sat == 1 ? sgn[k] : (int)(rnd(g) & 1u));
     int num_sig = 0, rice = 0;
     for (int k = 15; k >= 0; k--) if (sig[k]) {
       int base = (num_sig < 8) ? ((k == last_g1_pos) ? 3 : 2) : 1;
@@ -478,6 +528,7 @@ static void put_mvd_comp_rest(orc_cabac_enc *c, int a)       /* abs_mvd_minus2 (
 }
 static int draw_mvd(orc_gen *g)
 {
+  if (g->cfg.edge_mvd > 0 && rpct(g, g->cfg.edge_mvd)) { static const int ends[4] = { -32768, -32767, 32766, 32767 }; return ends[rnd(g) & 3u]; }      /* the ends of mvd's range */
   int r = (int)(rnd(g) % 100u), v;
   if (r < 30) v = 0;
   else if (r < 60) v = rrange(g, 1, 6);
@@ -609,6 +660,7 @@ static void gen_coding_unit(orc_gen *g, int x0, int y0, int log2cb, int ct_depth
         for (int i = 0; i < n * n; i++) orc_bw_put(c->bw, rnd(g) & ((1u << s->pcm_bit_depth_luma) - 1), s->pcm_bit_depth_luma);
         for (int i = 0; i < n * n / 2; i++) orc_bw_put(c->bw, rnd(g) & ((1u << s->pcm_bit_depth_chroma) - 1), s->pcm_bit_depth_chroma);
         orc_cenc_start(c, c->bw);
+        g->ctu_raw_bits += n * n * s->pcm_bit_depth_luma + n * n / 2 * s->pcm_bit_depth_chroma + 8;
         fill4(pic, pic->intra_mode, x0, y0, n, n, 1);
         return;
       }
@@ -691,6 +743,7 @@ static void gen_coding_quadtree(orc_gen *g, int x0, int y0, int log2cb, int dept
   const orc_sps *s = &g->sps;
   const int n = 1 << log2cb;
   int split;
+  if (depth == 0) { g->ctu_bins0 = c->bins; g->ctu_raw_bits = 0; }
   if (x0 + n <= s->width && y0 + n <= s->height && log2cb > s->log2_min_cb) {
     int l = orc_available(&g->av, x0, y0, x0 - 1, y0) && pic->ct_depth[b4(pic, x0 - 1, y0)] > depth;
     int a = orc_available(&g->av, x0, y0, x0, y0 - 1) && pic->ct_depth[b4(pic, x0, y0 - 1)] > depth;
@@ -1015,20 +1068,28 @@ static void write_picture(orc_gen *g, int idr, int write_ps)
     /* pred_weight_table(): denominators 0 .. 7, weights and offsets over their whole ranges now and then, mostly near the defaults (a fade) */
     sh->weighted = 1;
     memset(sh->luma_weight_flag, 0, sizeof(sh->luma_weight_flag)); memset(sh->chroma_weight_flag, 0, sizeof(sh->chroma_weight_flag));
+    const int ew = g->cfg.edge_weights;         /* the ends of every range and their neighbours in place of the uniform wide draw */
+    static const int e8[4] = { -128, -127, 126, 127 }, e10[4] = { -512, -511, 510, 511 };
     sh->luma_log2_weight_denom = rrange(g, 0, 7);
     sh->delta_chroma_log2_weight_denom = rrange(g, 0, 7) - sh->luma_log2_weight_denom;
+    if (ew) {
+      int cd = sh->luma_log2_weight_denom + sh->delta_chroma_log2_weight_denom;
+      if (rpct(g, 50)) sh->luma_log2_weight_denom = rpct(g, 50) ? 0 : 7;
+      if (rpct(g, 50)) cd = rpct(g, 50) ? 0 : 7;
+      sh->delta_chroma_log2_weight_denom = cd - sh->luma_log2_weight_denom;
+    }
     for (int l = 0; l < (g->slice_is_b ? 2 : 1); l++) for (int i = 0; i < (l ? sh->num_ref_idx_l1 : sh->num_ref_idx_l0); i++) {
-      const int wide = rpct(g, 15);
+      const int wide = rpct(g, ew ? 60 : 15);
       if (rpct(g, g->cfg.weighted)) {
         sh->luma_weight_flag[l][i] = 1;
-        sh->delta_luma_weight[l][i] = (int16_t)(wide ? rrange(g, -128, 127) : rrange(g, -6, 6));
-        sh->luma_offset[l][i] = (int16_t)(wide ? rrange(g, -128, 127) : rrange(g, -10, 10));
+        sh->delta_luma_weight[l][i] = (int16_t)(wide ? (ew ? e8[rnd(g) & 3u] : rrange(g, -128, 127)) : rrange(g, -6, 6));
+        sh->luma_offset[l][i] = (int16_t)(wide ? (ew ? e8[rnd(g) & 3u] : rrange(g, -128, 127)) : rrange(g, -10, 10));
       }
       if (rpct(g, g->cfg.weighted)) {
         sh->chroma_weight_flag[l][i] = 1;
         for (int j = 0; j < 2; j++) {
-          sh->delta_chroma_weight[l][i][j] = (int16_t)(wide ? rrange(g, -128, 127) : rrange(g, -6, 6));
-          sh->delta_chroma_offset[l][i][j] = (int16_t)(wide ? rrange(g, -512, 511) : rrange(g, -20, 20));
+          sh->delta_chroma_weight[l][i][j] = (int16_t)(wide ? (ew ? e8[rnd(g) & 3u] : rrange(g, -128, 127)) : rrange(g, -6, 6));
+          sh->delta_chroma_offset[l][i][j] = (int16_t)(wide ? (ew ? e10[rnd(g) & 3u] : rrange(g, -512, 511)) : rrange(g, -20, 20));
         }
       }
     }
@@ -1036,6 +1097,7 @@ static void write_picture(orc_gen *g, int idr, int write_ps)
   }
   sh->max_num_merge_cand = rrange(g, 1, 5);
   sh->slice_qp_delta = rrange(g, -4, 4);
+  sh->slice_qp_delta = orc_clip3(0, 51, p->init_qp + sh->slice_qp_delta) - p->init_qp;      /* (SliceQpY stays in 0 .. 51: a stream at init_qp 0 or 51 has slices at that very end) */
   sh->slice_qp = p->init_qp + sh->slice_qp_delta;
   if (p->slice_chroma_qp_offsets_present) { sh->slice_cb_qp_offset = rrange(g, -2, 2); sh->slice_cr_qp_offset = rrange(g, -2, 2); }
   sh->slice_deblocking_disabled = p->pps_deblocking_disabled; sh->beta_offset_div2 = p->pps_beta_offset_div2; sh->tc_offset_div2 = p->pps_tc_offset_div2;

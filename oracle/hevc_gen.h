@@ -83,6 +83,16 @@ typedef struct {
                                * configurations do -- 0 (also -1): always explicit in the slice header, as Kvazaar writes */
   int hdr_extras;             /* 1: what a decoder has to step over -- slice_reserved_flag bits (num_extra_slice_header_bits), slice segment header extension bytes, SPS / PPS
                                * extension data, access unit delimiters, prefix and suffix SEI messages a decoder does not know, filler data NAL units -- 0 (also -1): none */
+  /* the bounds of the syntax (never drawn: -1 and 0 are off and take nothing from the random sequence, every earlier stream stays what it was) */
+  int sat_levels;             /* probability (%) that a residual block is written SATURATING: every sub-block coded, every position significant, absolute levels out of
+                               * { 32767, 32766, 20001..32767, 32768 where the sign is negative }, the signs all positive / all negative / alternating / aligned with the
+                               * transform's basis at one sample (both inverse stages then add terms of one sign there) -- or, a smaller share, one or two such levels
+                               * among ordinary ones (single longest escape codes at every Rice parameter).  Every block size, luma and chroma, transform-skip and
+                               * transquant-bypass blocks; TransCoeffLevel stays in -32768..32767 and the coding tree unit within its size limit (see sat_fits) */
+  int edge_mvd;               /* probability (%) that a vector difference component is one of -32768, -32767, 32766, 32767 (the predictor is not known here: vectors that cross
+                               * +-2^15 come from the fold of 8.5.3.2.6 on predictors that neighbours with such vectors hand on) */
+  int edge_weights;           /* 1: the wide draw of pred_weight_table() (taken more often) takes the ends of each range and their neighbours -- -128, -127, 126, 127 for
+                               * the weight deltas and offsets, -512, -511, 510, 511 for the chroma offset deltas -- and both denominators are 0 or 7 half of the time */
 } orc_gen_config;
 
 void orc_gen_default_config(orc_gen_config *c);    /* everything random, 416x240 */

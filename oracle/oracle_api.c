@@ -179,7 +179,8 @@ long orc_api_cabac_roundtrip(const uint8_t *kinds, const uint8_t *ci, const uint
   return (term == 1 && consumed == len) ? len : -len;
 }
 
-/* ---- stream synthesiser (hevc_gen.c): cfg = the orc_gen_config fields as a flat int array ---- */
+/* ---- stream synthesiser (hevc_gen.c): cfg = the orc_gen_config fields as a flat int array (a shorter array leaves the later fields -- sat_levels, edge_mvd,
+ * edge_weights are the last -- at -1, off) ---- */
 orc_gen *orc_api_gen_open(const int *cfg, int n)
 {
   orc_gen_config c; orc_gen_default_config(&c);

@@ -5,12 +5,16 @@ merge and AMVP candidate derivation, cu_qp_delta and the QpY predictor, intra mo
 syntax, deblocking decisions.  tests/test_python_decoder.py decodes the checker's and the generator's streams with it and
 compares reconstructed pictures with oracle/hevc_dec.c bit for bit.
 
-Scope: 8-bit 4:2:0, CTB 16..64, one slice per picture, I, P and B slices (bi-prediction, output in POC order), tile rows and columns, WPP, every CU size and
-partitioning, transform trees, several reference pictures (short-term RPS), TMVP, cu_qp_delta, sign data hiding, transform
-skip, deblocking with offsets, SAO, scaling lists (default / SPS / PPS), cu_transquant_bypass, explicit weighted prediction.  No PCM, long-term pictures.
+Scope: 8-bit 4:2:0, CTB 16..64, pictures of 16 samples a side upward, any number of slices and slice segments per picture (independent and dependent, beginning at
+any coding tree block), I, P and B slices (bi-prediction, output in POC order), tile rows and columns, WPP, every CU size and partitioning, transform trees, several
+reference pictures (short-term RPS in every coded form, long-term pictures), TMVP, cu_qp_delta, sign data hiding, transform skip, deblocking with offsets, SAO,
+scaling lists (default / SPS / PPS), cu_transquant_bypass, PCM units, explicit weighted prediction.  Python integers (int64 arrays far from their ends) make it the
+unbounded-precision statement of scaling, transformation (8.6.2 - 8.6.4) and weighted prediction (8.5.3.3.4); Decoder.seen counts what a stream held at those bounds.
 Normative tables are typed here per syntax element (initValue: Tables 9-5 .. 9-37); rangeTabLps and the state transition
 tables, the transform matrices and the interpolation filters are passed in by the caller (tests take them from the KAT-checked
 oracle tables: tests/test_oracle_kat.py), so that this file holds logic rather than 400 more typed constants."""
+import collections
+
 import numpy as np
 
 # ----------------------------------------------------------------------------------------------- bit reader
@@ -554,6 +558,8 @@ class Decoder:
         self.skipping = False   # inside a dropped picture: its further slice segments go the same way
         self.waiting = []       # decoded pictures that wait for their turn in output order (C.5.2.2 "needed for output")
         self.trace = None       # optional list: ("cu", x, y, log2, pred_mode, part), ("tu", cidx, x, y, log2, [levels...]) ...
+        self.raw_levels = None  # optional list: every TransCoeffLevel as parsed, before any clip
+        self.seen = collections.Counter()   # what the streams held at the bounds of the syntax (tests/bounds_cases.py names the counters): tests assert a stream carries what it is there for
 
     # ------------------------------------------------------------------------------------------- NAL level
     def decode(self, stream):
@@ -731,6 +737,7 @@ class Decoder:
                 sh["wp"] = (ld, cd, wp)
             sh["max_merge"] = 5 - r.ue()
         sh["qp"] = pps["init_qp"] + r.se()
+        self.seen["slice_qp_%d" % sh["qp"]] += 1
         sh["cb_off"] = sh["cr_off"] = 0
         if pps["slice_chroma_off"]:
             sh["cb_off"] = r.se()
@@ -781,6 +788,7 @@ class Decoder:
             for e in entry:
                 acc += e
                 starts.append(rbsp_before[acc] - hdr)
+        self.seen["substream_bytes_max"] = max([self.seen["substream_bytes_max"]] + [e - s for s, e in zip(starts, starts[1:] + [len(data)])])
         if not first:
             # a further segment of the picture under way (one tile): an independent slice brings its own header (its SliceQpY), the picture's state goes on
             sl = self.cur
@@ -1452,6 +1460,10 @@ class SliceDecoder:
                 dx, dy = (0, 0) if (X == 1 and sh["mvd_l1_zero"] and idc == 2) else mvd()
                 mvp = c.bin("mvp")
                 px, py = self.amvp_candidates(xcb, ycb, ncb, xpb, ypb, pw, ph, part_idx, X, ref)[mvp]
+                self.dec.seen["mv_wrap"] += sum(1 for v in (px + dx, py + dy) if not -32768 <= v <= 32767)
+                self.dec.seen["mv_wrap_near"] += sum(1 for v in (px + dx, py + dy) if 32768 <= v <= 32771 or -32772 <= v <= -32769)      # a fold by one to four: the off-by-one case
+                self.dec.seen["mv_at_end"] += sum(1 for v in (px + dx, py + dy) if 32764 <= v <= 32767 or -32768 <= v <= -32765)         # ... and its neighbour that must NOT fold
+                self.dec.seen["mvd_end"] += sum(1 for v in (dx, dy) if v in (-32768, -32767, 32766, 32767))
                 m[3 * X:3 * X + 3] = [wrap(px + dx), wrap(py + dy), ref]
             m = tuple(m)
         pic = self.pic
@@ -1464,6 +1476,20 @@ class SliceDecoder:
             pic.ref_lt[ys, xs, X] = 1 if ref >= 0 and self.refs[X][ref].is_lt else 0
         preds = [self.motion_compensate(xpb, ypb, pw, ph, m[3 * X], m[3 * X + 1], self.refs[X][m[3 * X + 2]]) for X in (0, 1) if m[3 * X + 2] >= 0]
         wp = self.sh.get("wp")
+        seen = self.dec.seen
+        for X in (0, 1):
+            if m[3 * X + 2] >= 0:                                   # a prediction block that lies wholly outside the reference picture: every sample is padding
+                xr, yr = xpb + (m[3 * X] >> 2), ypb + (m[3 * X + 1] >> 2)
+                if xr + pw <= 0 or yr + ph <= 0 or xr >= pic.w or yr >= pic.h:
+                    seen["pb_outside"] += 1
+                if wp:
+                    kind = "bi" if len(preds) == 2 else "uni"
+                    for ci in range(3):                             # luma and chroma counted apart (chroma: a leading "c"): the derived chroma offset is clipped and lands on an end easily
+                        denom = wp[1] if ci else wp[0]
+                        w, o = wp[2][X][m[3 * X + 2]][ci]
+                        for name, hit in (("w_lo", w - (1 << denom) == -128), ("w_hi", w - (1 << denom) == 127), ("o_lo", o == -128), ("o_hi", o == 127),
+                                          ("denom_lo", denom == 0), ("denom_hi", denom == 7)):
+                            seen[("c" if ci else "") + name + "_" + kind] += int(hit)
         for ci in range(3):
             sx = 1 if ci else 0
             if wp:                                                 # 8.5.3.3.4.3: explicit weights on the 14-bit predictions (shift1 = 6 at 8 bits)
@@ -1752,6 +1778,7 @@ class SliceDecoder:
                 scan_idx = 2 if 6 <= mode <= 14 else (1 if 22 <= mode <= 30 else 0)
             res = self.residual(0, log2, scan_idx, qp, self.cu_intra and log2 == 2)
             blk_ = self.pic.planes[0][y0:y0 + n, x0:x0 + n]
+            self.count_clips(blk_ + res[:blk_.shape[0], :blk_.shape[1]])
             blk_[:] = np.clip(blk_ + res[:blk_.shape[0], :blk_.shape[1]], 0, 255)
             self.tu_nz[y0 >> 2:(y0 + n) >> 2, x0 >> 2:(x0 + n) >> 2] = 1
         self.decoded4[y0 >> 2:(y0 + n) >> 2, x0 >> 2:(x0 + n) >> 2] = 1
@@ -1768,7 +1795,12 @@ class SliceDecoder:
                         scan_idx = 2 if 6 <= mode <= 14 else (1 if 22 <= mode <= 30 else 0)
                     res = self.residual(ci, cl2, scan_idx, chroma_qp(qp + off), False)
                     b = self.pic.planes[ci][yc:yc + cn, xc:xc + cn]
+                    self.count_clips(b + res[:b.shape[0], :b.shape[1]])
                     b[:] = np.clip(b + res[:b.shape[0], :b.shape[1]], 0, 255)
+
+    def count_clips(self, v):
+        self.dec.seen["rec_clip0"] += int((v < 0).sum())
+        self.dec.seen["rec_clip255"] += int((v > 255).sum())
 
     # ------------------------------------------------------------------------------------------- residual coding (7.3.8.11)
     def residual(self, cidx, log2, scan_idx, qp, dst):
@@ -1888,6 +1920,8 @@ class SliceDecoder:
                         rem = (p << rice) + c.bypass_bits(rice)
                     else:
                         rem = (((1 << (p - 3)) + 3 - 1) << rice) + c.bypass_bits(p - 3 + rice)
+                        if p - 3 + rice >= 14:
+                            self.dec.seen["esc14_rice%d" % rice] += 1
                     absv[j] = base + rem
                     if absv[j] > 3 * (1 << rice):
                         rice = min(rice + 1, 4)
@@ -1897,9 +1931,19 @@ class SliceDecoder:
             for j, k in enumerate(positions):
                 xp, yp = pos_scan[k]
                 v = -absv[j] if signs[j] else absv[j]
+                if self.dec.raw_levels is not None:
+                    self.dec.raw_levels.append(v)
                 coef[(ys << 2) + yp, (xs << 2) + xp] = min(max(v, -32768), 32767)
         if self.dec.trace is not None:
             self.dec.trace.append(("tu", cidx, log2, [int(v) for v in coef.reshape(-1)]))
+        seen = self.dec.seen
+        big = int((np.abs(coef) >= 32766).sum())
+        seen["level_big"] += big
+        seen["level_m32768"] += int((coef == -32768).sum())
+        if big and not self.cu_bypass:
+            seen["level_big_%s_qp%d" % ("chroma" if cidx else "luma", qp)] += big      # the QP such levels are scaled at
+        seen["level_big_bypass"] += big if self.cu_bypass else 0
+        seen["level_big_tskip"] += big if tskip else 0
         if self.cu_bypass:                   # 8.6.2: the residual is the level array itself
             return coef
         # ---- scaling (8.6.4.2: m = 16, or the scaling factors of the active lists) and transformation (8.6.4.2 / 8.6.2)
@@ -1908,11 +1952,15 @@ class SliceDecoder:
         if self.scaling is not None:
             inter = 0 if self.cu_intra else 1
             mfac = scaling_factor(self.scaling, log2 - 2, (inter if log2 == 5 else 3 * inter + cidx))
-        d = np.clip((coef * mfac * (LEVEL_SCALE[qp % 6] << (qp // 6)) + (1 << (bd - 1))) >> bd, -32768, 32767)
+        d = (coef * mfac * (LEVEL_SCALE[qp % 6] << (qp // 6)) + (1 << (bd - 1))) >> bd
+        seen["dequant_clip_lists" if self.scaling is not None else "dequant_clip_flat"] += int(((d < -32768) | (d > 32767)).sum())
+        d = np.clip(d, -32768, 32767)
         if tskip:
             return ((d << 7) + 2048) >> 12
         m = np.array(self.t["dst"], np.int64) if dst else np.array(self.t["dct"], np.int64)[::(32 >> log2), :n][:n]
-        e = np.clip((m.T @ d + 64) >> 7, -32768, 32767)          # columns first
+        e = (m.T @ d + 64) >> 7                                  # columns first
+        seen["stage1_clip_dst" if dst else "stage1_clip_%d" % n] += int(((e < -32768) | (e > 32767)).sum())
+        e = np.clip(e, -32768, 32767)
         return ((e @ m) + 2048) >> 12
 
     # ------------------------------------------------------------------------------------------- intra prediction (8.4.4.2)

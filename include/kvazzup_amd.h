@@ -96,8 +96,12 @@ KVZ_PUBLIC int kvzx_decoder_output_device(OpenHevc_Handle h, const void **planes
 /* when 0, libOpenHevcDecode leaves the picture in HBM and libOpenHevcGetOutput returns NULL planes */
 KVZ_PUBLIC void kvzx_decoder_set_download(OpenHevc_Handle h, int on);
 /* Lifetime of the device planes of kvzx_decoder_output_device (download off): they belong to the decoder's picture buffer and stay
- * untouched -- read as a reference picture at most -- while the next `pictures` pictures are decoded (default 2, 1..8); after that the
- * buffer may be reused.  A consumer that lags further must copy, or raise this. */
+ * untouched -- read as a reference picture at most -- while the next `pictures` pictures are begun (default 2, 1..8; values outside are
+ * clamped): from the libOpenHevcDecode call that handed the picture out until the call that takes the first NAL unit of the
+ * (`pictures` + 1)-th picture after that call -- with any number of frame threads, whatever other NAL units come between.  At the end of a
+ * stream every end-of-sequence / end-of-bitstream NAL unit counts like a picture's first: it moves the frame threads' ring on by one
+ * picture.  After that the buffer may be reused.  A consumer that lags further must copy, or raise this.  A stream that reorders its
+ * pictures for output is handed out as dense copies (pitch = width) with the same lifetime. */
 KVZ_PUBLIC void kvzx_decoder_set_output_hold(OpenHevc_Handle h, int pictures);
 KVZ_PUBLIC void kvzx_decoder_set_profiling(OpenHevc_Handle h, int every);
 KVZ_PUBLIC int kvzx_decoder_kernel_times(OpenHevc_Handle h, double *ms, uint64_t *launches, int reset);

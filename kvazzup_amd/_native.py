@@ -161,6 +161,9 @@ def load_library():
         L.kvzx_decoder_hash_stats.restype = None
         L.kvzx_decoder_output_device.argtypes = [C.c_void_p, _P(C.c_void_p), _P(C.c_int)]
         L.kvzx_decoder_set_download.argtypes = [C.c_void_p, C.c_int]
+        L.kvzx_decoder_set_output_hold.argtypes = [C.c_void_p, C.c_int]
+        L.kvzx_decoder_set_output_hold.restype = None
+        L.kvzx_decoder_output_rgb32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.kvzx_decoder_set_band.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.kvzx_decoder_band_halo_bytes.restype = C.c_size_t
         L.kvzx_decoder_band_halo_bytes.argtypes = [C.c_void_p]

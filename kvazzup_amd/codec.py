@@ -368,6 +368,14 @@ class Decoder:
             return None
         return list(planes), list(pitches)
 
+    def set_output_hold(self, pictures):
+        """download=False: the planes of output_device() stay untouched while this many further pictures are begun (kvzx_decoder_set_output_hold: 1..8, default 2)"""
+        self.lib.kvzx_decoder_set_output_hold(self.h, int(pictures))
+
+    def output_rgb32_device(self, d_rgb32, variant=0):
+        """the picture handed out last, converted where it lies into width * height * 4 bytes at the device address d_rgb32"""
+        return bool(self.lib.kvzx_decoder_output_rgb32_device(self.h, d_rgb32, int(variant)))
+
     def set_profiling(self, on):
         self.lib.kvzx_decoder_set_profiling(self.h, int(on))
 

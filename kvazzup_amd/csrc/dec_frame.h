@@ -20,7 +20,7 @@ struct B4Rec {
                            // slot are those of list 0 when it is used, else list 1's (a uni-predicted block is the same to the kernels either way)
   uint8_t flags;           // B4_*
   int8_t qp_y;             // QpY of the coding unit (8.6.1)
-  uint8_t slot;            // picture buffer of the reference picture: two indices naming one picture share it (8.7.2.4 compares pictures)
+  uint8_t slot;            // picture buffer of the reference picture (entry of DecFrame::ref): two indices naming one picture share it (8.7.2.4 compares pictures)
 };
 // the SECOND motion of a bi-predicted block (B4_BI; B slices): the list-1 vector and its picture buffer.  An array of its own beside b4[], present
 // only in pictures that hold such a block -- P pictures, every picture of a default Kvazaar peer, never pay for it
@@ -72,7 +72,7 @@ struct DecFrame {
   const uint8_t *ctu_tile;  // per CTB (raster, pitch cwc): (tile row mod 16) << 4 | (tile column mod 16) -- distinct for adjacent tiles, which is all the kernels compare
   uint8_t *rec[3];          // the picture being reconstructed (and deblocked in place)
   uint8_t *out[3];          // SAO output (== rec planes of the picture buffer when SAO runs from a work picture)
-  const uint8_t *ref[KVZ_DEC_MAX_REFS][3];   // picture buffers by slot
+  const uint8_t *ref[KVZ_DEC_MAX_REFS][3];   // picture buffers by slot (the decoder's ring may hold more buffers: decoder.h PicJob::ref_buf)
   const SaoParams *sao;     // per CTB (raster, pitch cwc); NULL = off
   const uint8_t *ctu_nb;    // per CTB (raster, pitch cwc), NULL = no boundary inside the picture is closed to the in-loop filters: bit k = the samples of the neighbouring CTB k
                             // (NW N NE W E SW S SE = 0 .. 7) may be used -- a slice with slice_loop_filter_across_slices_enabled_flag = 0, tiles with

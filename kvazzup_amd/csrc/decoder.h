@@ -139,8 +139,8 @@ class Decoder {
   bool set_parse_only() { if (jobs_.empty() && !started_) parse_only_ = true; return parse_only_; }      // (false: declined -- the decoder has been started)
   struct ProbeStats { uint64_t pictures = 0, tus = 0, levels = 0, digest = 0xcbf29ce484222325ull, bins = 0; double parse_ms = 0; };
   ProbeStats parse_probe_stats() const { return probe_; }
-  // device-resident output (set_download(false)): the planes handed out stay untouched while the next `n` pictures are decoded
-  // (they may be read as reference pictures, never written); default 2
+  // device-resident output (set_download(false)): the planes handed out stay untouched while the next `n` pictures are begun
+  // (they may be read as reference pictures, never written); default 2.  alloc_slot keeps the promise for the ring's buffers, free_retired for owned copies
   void set_output_hold(int n) { output_hold_ = n < 1 ? 1 : (n > 8 ? 8 : n); }
   void set_profiling(int every) { profiling_ = every > 0; prof_every_ = every > 0 ? every : 1; }   // n: every n-th picture
   void set_parse_threads(int n) { if (!pool_) parse_threads_ = n < 1 ? 1 : n; }
@@ -205,6 +205,7 @@ class Decoder {
     bool starts_cvs = false, discard_prior = false;              // NoRaslOutputFlag (8.1.3); ... and no_output_of_prior_pics_flag in force (C.5.2.2)
     int nref = 0; int ref_poc[16]; uint8_t ref_slot[16];        // RefPicList0
     int nref1 = 0; int ref_poc1[16]; uint8_t ref_slot1[16];     // RefPicList1 (B slices)
+    uint8_t ref_buf[KVZ_DEC_MAX_REFS] = {};                     // ref_slot / ref_slot1 name entries of the kernels' table (B4Rec::slot, DecFrame::ref); ref_buf: the picture buffer (dpb_) behind each entry
     uint8_t ref_lt[16] = {}, ref_lt1[16] = {};                  // the entry is a long-term reference picture (8.3.2: no vector scaling, 8.5.3.2.7 / 8.5.3.2.9)
     bool no_backward = true;                                     // NoBackwardPredFlag (8.5.3.2.9): no entry of either list follows the picture in output order
     // B slices: the two-list motion of every 4x4 block as the parser's own derivations read it (merge, AMVP); what the kernels need of it goes
@@ -331,8 +332,13 @@ class Decoder {
   // retires are only freed kOutHold calls later.
   static constexpr int kOutHold = 8;
   long nal_calls_ = 0;
+  // kvzx_decoder_set_output_hold counts pictures, not NAL units (an access unit may bring parameter sets, SEI messages, a delimiter): the calls that began a picture,
+  // and the end-of-sequence / end-of-bitstream calls, which move the ring on by one picture like them.  An owned picture's device copy goes back to the pool only
+  // after output_hold_ of those as well.
+  long hold_clock_ = 0;
   std::deque<std::pair<long, uint8_t *>> retired_out_;      // (call count at retirement, page-locked buffer)
-  std::deque<std::pair<long, OwnedPic>> retired_owned_;
+  struct Retired { long calls, clock; OwnedPic pic; };
+  std::deque<Retired> retired_owned_;
   // device buffers of OwnedPic copies, kept for the next picture of the same size (queue_current_output)
   static constexpr size_t kOwnedPoolMax = 24;
   std::vector<std::pair<size_t, uint8_t *>> owned_pool_; std::map<const uint8_t *, size_t> owned_bytes_; hipEvent_t owned_ev_ = nullptr;
@@ -346,7 +352,12 @@ class Decoder {
                   long decode_idx = -1000; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion;      // (cmotion: concealment v3's record, NULL in mode 2 and for a stand-in)
                   hipEvent_t last_dl = nullptr;
                   hipEvent_t last_use = nullptr; bool last_use_alt = false; };      // (two chains, below: the last picture that read or wrote the buffer, and the stream it ran on)     // download mode: the copy of the picture last reconstructed here (a later picture's kernels wait for it before they write the buffer)
-  DpbPic dpb_[KVZ_DEC_MAX_REFS];
+  // More buffers than a picture can have reference pictures: beside those (15 at most, 7.4.3.2.1) the ring holds the pictures handed out and still promised
+  // untouched (kvzx_decoder_set_output_hold: up to 8), the pictures launched behind them (kMaxGpuDepth), the picture at hand and the one a fill reads (avoid_slot_).
+  // Buffers past the first six are allocated when first taken.  The kernels' table (DecFrame::ref) has KVZ_DEC_MAX_REFS entries: entry k is buffer k, and a
+  // reference picture that lies in a buffer past those takes, for that picture, an entry whose own buffer the picture does not refer to (PicJob::ref_buf).
+  static constexpr int kMaxPics = 15 + 8 + 8 + 2 + 1;
+  DpbPic dpb_[kMaxPics];
   // device side
   // Frame-threaded mode keeps up to gpu_depth_ pictures queued on the GPU (launched, not yet completed): a picture's way through upload, kernels
   // and the copy back to the host is ~0.2 ms at 1080p, and with only one picture launched ahead of the one being waited for the calling thread

@@ -252,11 +252,16 @@ bool Decoder::prepare_jobs(int w, int h, int ctb_log2)
 
 int Decoder::alloc_slot()
 {
-  for (int s = 0; s < KVZ_DEC_MAX_REFS; s++) {
+  // A picture handed out stays untouched while output_hold_ further pictures are begun (kvzx_decoder_set_output_hold).  The synchronous decoder launches picture q
+  // in the call that begins it and hands picture p out in the call that began it: q may take p's buffer when q - p > output_hold_.  With frame threads the call that
+  // begins picture k hands out picture k - frame_threads_ and launches picture k - frame_threads_ + gpu_depth_: picture q is launched gpu_depth_ calls after the one
+  // that handed out q - gpu_depth_, so it may take p's buffer when q - p > output_hold_ + gpu_depth_.
+  const long margin = output_hold_ + (frame_threads_ > 1 ? gpu_depth_ : 0);
+  for (int s = 0; s < kMaxPics; s++) {
     DpbPic &p = dpb_[s];
-    if (p.is_ref || s == avoid_slot_ || job_head_ - p.decode_idx <= output_hold_ + (gpu_depth_ - 1)) continue;      // (pictures queued on the GPU behind the one handed out may already write their buffers)
+    if (p.is_ref || s == avoid_slot_ || job_head_ - p.decode_idx <= margin) continue;
     if (!p.plane[0] && parse_only_) p.plane[0] = (uint8_t *)(uintptr_t)64;
-    if (!p.plane[0]) { if (hipSetDevice(device_) != hipSuccess || !alloc_picture(p)) return -1; hipDeviceSynchronize(); }      // (a buffer is added at most ten times)
+    if (!p.plane[0]) { if (hipSetDevice(device_) != hipSuccess || !alloc_picture(p)) return -1; hipDeviceSynchronize(); }      // (a buffer is added kMaxPics - 6 times at most)
     return s;
   }
   return -1;
@@ -307,7 +312,10 @@ void Decoder::get_kernel_times(double *ms, uint64_t *launches, bool reset)
 void Decoder::free_retired(bool all)
 {
   while (!retired_out_.empty() && (all || nal_calls_ - retired_out_.front().first > kOutHold)) { hipHostFree(retired_out_.front().second); retired_out_.pop_front(); }
-  while (!retired_owned_.empty() && (all || nal_calls_ - retired_owned_.front().first > kOutHold)) { if (all) owned_free(retired_owned_.front().second.dev); else owned_release(retired_owned_.front().second.dev); retired_owned_.pop_front(); }
+  while (!retired_owned_.empty() && (all || (nal_calls_ - retired_owned_.front().calls > kOutHold && hold_clock_ - retired_owned_.front().clock > output_hold_))) {      // (the host copy's promise and the device copy's: decoder.h hold_clock_)
+    if (all) owned_free(retired_owned_.front().pic.dev); else owned_release(retired_owned_.front().pic.dev);
+    retired_owned_.pop_front();
+  }
 }
 
 int Decoder::decode_nal(const uint8_t *data, size_t len, int64_t pts)
@@ -337,7 +345,7 @@ int Decoder::decode_nal(const uint8_t *data, size_t len, int64_t pts)
   if (rc < 0) return rc;
   if (pic_ready_ && !queue_current_output()) return last_error_ = DEC_ERR_GPU;
   }
-  if (cur_owned_.dev || !cur_owned_.host.empty()) retired_owned_.emplace_back(nal_calls_, std::move(cur_owned_));      // (the caller may still be copying it out)
+  if (cur_owned_.dev || !cur_owned_.host.empty()) retired_owned_.push_back(Retired{nal_calls_, hold_clock_, std::move(cur_owned_)});      // (the caller may still be copying it out)
   cur_owned_ = OwnedPic();
   cur_owned_ = std::move(ready_q_.front());
   ready_q_.pop_front();
@@ -499,7 +507,7 @@ int Decoder::decode_nal_inner(const uint8_t *data, size_t len, int64_t pts)
   const bool open_rows = partial_ && asm_.active && !jobs_.empty() && jobs_[(size_t)(job_head_ % jobs_.size())].pps.wpp && jobs_[(size_t)(job_head_ % jobs_.size())].pps.tile_rows == 1 && jobs_[(size_t)(job_head_ % jobs_.size())].pps.tile_cols == 1;
   if (asm_.active && (asm_.guessed_one_row || asm_.free || open_rows) && nal_type >= 32 && nal_type <= 40 && nal_type != 38) { const int rc = close_open_picture(); if (rc < 0) return rc; }   // (what can only open the next access unit, or end the sequence)
   if (nal_type >= 32 && nal_type <= 34) return decode_parameter_set(nal_type, r);
-  if (nal_type == 36 || nal_type == 37) { after_eos_ = true; vwait_.clear(); int rc = finish_oldest(); if (rc < 0) last_error_ = rc; return rc; }   // EOS / EOB: drain one delayed picture; whatever picture follows starts a sequence
+  if (nal_type == 36 || nal_type == 37) { hold_clock_++; after_eos_ = true; vwait_.clear(); int rc = finish_oldest(); if (rc < 0) last_error_ = rc; return rc; }   // EOS / EOB: drain one delayed picture; whatever picture follows starts a sequence
   if (nal_type == 40 && check_hash_) return hash_sei(rbsp_.data(), n);       // suffix SEI: decoded picture hash (libOpenHevcSetCheckMD5)
   if (nal_type > 31) return 0;                                    // AUD / other SEI / ...
   if (!(nal_type <= 9 || (nal_type >= 16 && nal_type <= 21))) return last_error_ = DEC_ERR_UNSUPPORTED;      // (reserved types)
@@ -764,7 +772,7 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
   if (cur_no_rasl_) for (auto &d : dpb_) d.is_ref = false;         // (8.3.2; what a CRA or BLA picture's set names is for its RASL pictures)
   if (!c.idr) {
     int cand_slot[32], nc = 0, nbefore = 0;             // the used pictures: those before the current one in output order (nearest first), then those after it, then the long-term ones
-    bool keep[KVZ_DEC_MAX_REFS] = {false};
+    bool keep[kMaxPics] = {false};
     // the long-term entries first, among all reference pictures (8.3.2): by the POC's LSBs, or by the whole POC when delta_poc_msb_present_flag says how many LSB
     // cycles back -- what they name is a long-term reference picture from now on; the short-term entries name pictures among the rest
     int lt_slot[16], nl = 0;
@@ -772,7 +780,7 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
     for (int k = 0; k < c.lt.n; k++) {
       const long long full = (long long)sh.poc - (long long)c.lt.cycle[k] * max_lsb - (sh.poc & (max_lsb - 1)) + c.lt.lsb[k];      // (64 bits: a hostile cycle count must not wrap into a POC that exists)
       int found = -1;
-      for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) if (dpb_[q].is_ref && dpb_[q].used && (c.lt.msb[k] ? dpb_[q].poc == full : (dpb_[q].poc & (max_lsb - 1)) == c.lt.lsb[k])) found = q;
+      for (int q = 0; q < kMaxPics; q++) if (dpb_[q].is_ref && dpb_[q].used && (c.lt.msb[k] ? dpb_[q].poc == full : (dpb_[q].poc & (max_lsb - 1)) == c.lt.lsb[k])) found = q;
       if (found < 0 && c.lt.used[k] && !sh.is_intra) {               // lost on the way: a grey picture stands in (known by its LSBs alone: the nearest POC before the current one that has them)
         long long at = full; if (!c.lt.msb[k]) { at = (long long)sh.poc - (sh.poc & (max_lsb - 1)) + c.lt.lsb[k]; if (at >= sh.poc) at -= max_lsb; }
         found = conceal_ref((int)at, true);
@@ -784,10 +792,10 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
     for (int k = 0; k < rps.n_neg + rps.n_pos; k++) {
       const int poc = sh.poc + rps.dpoc[k];
       int found = -1;
-      for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) if (dpb_[q].is_ref && dpb_[q].used && !dpb_[q].is_lt && dpb_[q].poc == poc) found = q;
+      for (int q = 0; q < kMaxPics; q++) if (dpb_[q].is_ref && dpb_[q].used && !dpb_[q].is_lt && dpb_[q].poc == poc) found = q;
       if (found < 0 && rps.used[k] && !sh.is_intra) {
         bool lt_has_it = false;                                  // (a long-term picture of that POC is no short-term entry's picture: that stays an error)
-        for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) lt_has_it |= dpb_[q].is_ref && dpb_[q].used && dpb_[q].is_lt && dpb_[q].poc == poc;
+        for (int q = 0; q < kMaxPics; q++) lt_has_it |= dpb_[q].is_ref && dpb_[q].used && dpb_[q].is_lt && dpb_[q].poc == poc;
         if (!lt_has_it) found = conceal_ref(poc, false);
       }
       if (found >= 0) keep[found] = true;
@@ -801,7 +809,7 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
     if (partial_ && !cur_no_rasl_) choose_fill_source(sh.poc, false, fresh);
     for (auto &pc : pending_conceal_) if (pc.second == -2) {
       int best = -1;
-      for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) {
+      for (int q = 0; q < kMaxPics; q++) {
         if (!dpb_[q].is_ref || !dpb_[q].used || std::find(fresh.begin(), fresh.end(), q) != fresh.end()) continue;
         const long long dq = llabs((long long)dpb_[q].poc - dpb_[pc.first].poc), db = best < 0 ? 0 : llabs((long long)dpb_[best].poc - dpb_[pc.first].poc);
         if (best < 0 || dq < db || (dq == db && dpb_[q].poc < dpb_[best].poc)) best = q;
@@ -809,7 +817,7 @@ int Decoder::apply_rps_and_build_lists(SliceCtx &c)
       pc.second = best;                                            // (-1: none -- grey)
       if (conceal_mode_ == 3 && best >= 0) { pc.poc = dpb_[pc.first].poc; pc.src_poc = dpb_[best].poc; pc.motion = dpb_[best].cmotion; }      // (v3: the source's motion goes with the entry -- the buffer may be another picture's by the time it is filled; NULL: the source is a stand-in)
     }
-    for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) if (!keep[q]) dpb_[q].is_ref = false;
+    for (int q = 0; q < kMaxPics; q++) if (!keep[q]) dpb_[q].is_ref = false;
     if (!sh.is_intra) {
       const int nst = nc;                                 // (the short-term part of the temporary lists)
       for (int k = 0; k < nl && nc < 32; k++) cand_slot[nc++] = lt_slot[k];
@@ -850,7 +858,25 @@ Decoder::PicJob &Decoder::open_job(const SliceCtx &c, const DecPps &pp, int slot
   if (no_crop_) job.crop[0] = job.crop[1] = job.crop[2] = job.crop[3] = 0;
   job.fps_num = s.fps_num ? s.fps_num : vps_fps_num_; job.fps_den = s.fps_num ? s.fps_den : vps_fps_den_;
   job.slot = slot; job.nref = c.nref;
-  for (int k = 0; k < 16; k++) { job.ref_poc[k] = k < c.nref ? c.ref_poc[k] : sh.poc; job.ref_slot[k] = k < c.nref ? c.ref_slot[k] : 0; job.ref_lt[k] = k < c.nref ? c.ref_lt[k] : 0; job.ref_lt1[k] = k < c.nref1 ? c.ref_lt1[k] : 0; }
+  hold_clock_++;                                                 // (a picture has begun: decoder.h)
+  // the kernels' table of picture buffers (decoder.h dpb_): entry k is buffer k; a reference picture in a buffer past the table's end takes an entry whose own
+  // buffer neither list names (the lists name 16 distinct pictures at most, apply_rps_and_build_lists) -- the records then name the picture by that entry
+  uint8_t entry_of[kMaxPics];
+  {
+    bool taken[KVZ_DEC_MAX_REFS] = {false};
+    for (int k = 0; k < KVZ_DEC_MAX_REFS; k++) job.ref_buf[k] = (uint8_t)k;
+    for (int b = 0; b < kMaxPics; b++) entry_of[b] = (uint8_t)(b < KVZ_DEC_MAX_REFS ? b : 0xff);
+    for (int k = 0; k < c.nref; k++) if (c.ref_slot[k] < KVZ_DEC_MAX_REFS) taken[c.ref_slot[k]] = true;
+    for (int k = 0; k < c.nref1; k++) if (c.ref_slot1[k] < KVZ_DEC_MAX_REFS) taken[c.ref_slot1[k]] = true;
+    auto place = [&](uint8_t buf) {
+      if (entry_of[buf] != 0xff) return;
+      int e = 0; while (e < KVZ_DEC_MAX_REFS - 1 && taken[e]) e++;
+      taken[e] = true; entry_of[buf] = (uint8_t)e; job.ref_buf[e] = buf;
+    };
+    for (int k = 0; k < c.nref; k++) place(c.ref_slot[k]);
+    for (int k = 0; k < c.nref1; k++) place(c.ref_slot1[k]);
+  }
+  for (int k = 0; k < 16; k++) { job.ref_poc[k] = k < c.nref ? c.ref_poc[k] : sh.poc; job.ref_slot[k] = k < c.nref ? entry_of[c.ref_slot[k]] : 0; job.ref_lt[k] = k < c.nref ? c.ref_lt[k] : 0; job.ref_lt1[k] = k < c.nref1 ? c.ref_lt1[k] : 0; }
   if (cur_no_rasl_) cvs_++;
   job.starts_cvs = cur_no_rasl_; job.discard_prior = cur_discard_;
   job.missing.clear(); job.fill_src = cur_fill_src_; job.fill_motion.reset();
@@ -858,7 +884,7 @@ Decoder::PicJob &Decoder::open_job(const SliceCtx &c, const DecPps &pp, int slot
   job.conceal = std::move(pending_conceal_); pending_conceal_.clear();                     // a new coded video sequence: its pictures follow ALL of the last one's in output order
   job.cvs = cvs_;
   job.nref1 = c.nref1; job.no_backward = c.no_backward;
-  for (int k = 0; k < 16; k++) { job.ref_poc1[k] = k < c.nref1 ? c.ref_poc1[k] : sh.poc; job.ref_slot1[k] = k < c.nref1 ? c.ref_slot1[k] : 0; }
+  for (int k = 0; k < 16; k++) { job.ref_poc1[k] = k < c.nref1 ? c.ref_poc1[k] : sh.poc; job.ref_slot1[k] = k < c.nref1 ? entry_of[c.ref_slot1[k]] : 0; }
   job.col.reset();
   if (sh.tmvp && !sh.is_intra) job.col = dpb_[(sh.is_b && !sh.collocated_from_l0) ? c.ref_slot1[sh.collocated_ref_idx] : c.ref_slot[sh.collocated_ref_idx]].motion;      // 8.5.3.2.8
   job.any_bi.store(0, std::memory_order_relaxed);
@@ -1413,7 +1439,7 @@ int Decoder::fill_concealed(PicJob &job)
 void Decoder::choose_fill_source(int poc, bool last_decoded, const std::vector<int> &fresh)
 {
   int best = -1;
-  for (int q = 0; q < KVZ_DEC_MAX_REFS; q++) {
+  for (int q = 0; q < kMaxPics; q++) {
     if (!dpb_[q].is_ref || !dpb_[q].used || std::find(fresh.begin(), fresh.end(), q) != fresh.end()) continue;
     if (last_decoded) { if (!dpb_[q].standin && (best < 0 || dpb_[q].decode_idx > dpb_[best].decode_idx)) best = q; continue; }
     const long long dq = llabs((long long)dpb_[q].poc - poc), db = best < 0 ? 0 : llabs((long long)dpb_[best].poc - poc);
@@ -1483,7 +1509,7 @@ DecFrame Decoder::picture_frame(PicJob &job, const DecInputLayout &lay, const Ch
   f.ctu_tile = d_in + lay.tile_off; f.tus = (const DecTu *)(d_in + lay.tu_off); f.lev = (const uint32_t *)(d_in + lay.lev_off); f.ntu = (int)lay.ntu;
   const bool sao = job.sh.sao_luma || job.sh.sao_chroma;      // the picture is then built in the chain's work planes and filtered into its buffer
   for (int c = 0; c < 3; c++) { f.resid[c] = cs.resid[c]; f.rec[c] = sao ? cs.work[c] : dpb_[job.slot].plane[c]; f.out[c] = dpb_[job.slot].plane[c]; }
-  for (int k = 0; k < KVZ_DEC_MAX_REFS; k++) for (int c = 0; c < 3; c++) f.ref[k][c] = dpb_[k].plane[c];
+  for (int k = 0; k < KVZ_DEC_MAX_REFS; k++) for (int c = 0; c < 3; c++) f.ref[k][c] = dpb_[job.ref_buf[k]].plane[c];      // (entry k: buffer k, or a reference picture from past the table's end -- open_job)
   f.sao = sao ? (const SaoParams *)(d_in + lay.sao_off) : nullptr; f.ctu_nb = job.lf_restricted ? d_in + lay.nb_off : nullptr;
   { f.progress = cs.progress; f.intra_order = intra_order_; f.err = err_; const size_t nctu = (size_t)f.cwc * f.chc, S = (size_t)1 << ctbl_;
     f.edge_col[0] = cs.edge_col; f.edge_col[1] = cs.edge_col + nctu * S; f.edge_col[2] = cs.edge_col + nctu * (S + S / 2);      // per CTB: S words (luma), S / 2 (Cb), S / 2 (Cr)
@@ -1525,8 +1551,8 @@ int Decoder::post_to_batcher(PicJob &job, const DecFrame &f, uint8_t *d_in, int 
 template <class F> bool Decoder::each_buffer_used(const PicJob &job, F &&visit)
 {
   bool ok = visit(dpb_[job.slot]);
-  for (int k = 0; ok && k < job.nref; k++) ok = visit(dpb_[job.ref_slot[k]]);
-  for (int k = 0; ok && k < job.nref1; k++) ok = visit(dpb_[job.ref_slot1[k]]);
+  for (int k = 0; ok && k < job.nref; k++) ok = visit(dpb_[job.ref_buf[job.ref_slot[k]]]);
+  for (int k = 0; ok && k < job.nref1; k++) ok = visit(dpb_[job.ref_buf[job.ref_slot1[k]]]);
   return ok;
 }
 // One decoder: it launches for itself, frame by value, on the chain's stream.

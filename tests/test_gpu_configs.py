@@ -48,7 +48,9 @@ def test_config1_long_run_two_idrs(gpu, owf, threads):
     owf 6 with 32: all eight working sets of the encoder in rotation, pictures queued behind the intra pictures' chains):
     three IDRs; EVERY access unit is decoded by the checker's decoder and every picture the pipelined HIP decoder delivered equals the
     checker's (second and third IDR, the rotation of the encoder's eight working sets and the owf queueing included); the first
-    pictures' access units also equal the checker encoder's"""
+    pictures' access units also equal the checker encoder's -- three of them: at 1080p the checker's encoder makes 4.5 pictures a second.  The comparison
+    of EVERY access unit of two whole periods with the checker encoder's, at the benchmark's settings (owf 6, 32 frame threads, held device pictures in,
+    device-resident pictures out), is tests/test_gpu_bench_path.py at 416x240"""
     from kvazzup_amd import synth
     from kvazzup_amd.codec import Decoder
     from kvazzup_amd.pipeline import Pipeline

@@ -1,9 +1,10 @@
 // kvazzup_amd/csrc/decoder.h -- host engine of the HIP decoder behind libOpenHevc*
 // (/root/reference/src/media/processing/openhevcfilter.cpp:36-56,145-146,195-199).
 //
-// Three translation units share this class: dec_syntax.{h,hip} turns header bits into plain structs (parameter sets, slice header parts; knows no Decoder),
-// dec_parse.hip is the slice-data parser (parse_job / parse_substream), decoder.hip is everything between them -- NAL dispatch, picture assembly, reference
-// management, the job ring, buffers, launches, output.
+// Four parts: dec_syntax.{h,hip} turns header bits into plain structs (parameter sets, slice header parts; knows no Decoder), dec_parse.hip is the slice-data
+// parser (parse_job / parse_substream), dec_output.h (over dec_order.h; knows no Decoder either) owns the output side -- the order pictures leave in, the copies that
+// are handed out and how long they stay valid --, decoder.hip is everything between them: NAL dispatch, picture assembly, reference management, the job ring,
+// buffers, launches, the ring's own output buffers.
 //
 // Division of labour: the host parses NAL units and runs CABAC decoding (bit-serial, one substream per CTU row or tile),
 // which yields per-4x4 records (motion, edges, QpY), the transform blocks in decoding order and their non-zero levels
@@ -21,7 +22,7 @@
 // independent slice per tile) and -- one-tile pictures -- segments that begin at ANY coding tree block, independent slices (own SliceQpY) and dependent
 // segments mixed (an MTU per slice, N row groups: PicJob::ctb_cut).  Random access (8.1.3, C.5.2.2): decoding may begin at a CRA picture -- its RASL pictures are
 // dropped, its RADL pictures decoded --, BLA pictures and end of sequence NAL units start a coded video sequence, pic_output_flag = 0 keeps a picture in,
-// no_output_of_prior_pics_flag discards what still waits (Decoder::vwait_).  Rejected with a negative return value (kvzx_decoder_last_error): several slices
+// no_output_of_prior_pics_flag discards what still waits (dec_order.h).  Rejected with a negative return value (kvzx_decoder_last_error): several slices
 // inside a tile of a picture with tiles, slices of one picture that differ in more than SliceQpY and the loop filter flag,
 // > 255 slices in a picture.
 #pragma once
@@ -33,13 +34,13 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
 #include "hevc_core.h"
 #include "dec_syntax.h"
+#include "dec_output.h"
 #include "host_pool.h"
 #include "dec_frame.h"
 #include "dec_kernels.h"
@@ -50,25 +51,6 @@ namespace kvzx {
 // DK_HOST_PARSE is not a kernel: wall time of the host CABAC parsing stage
 enum { PM_INTER = 0, PM_INTRA = 1, PM_SKIP = 2, PM_NONE = 255 };      // PicJob::pred_mode
 enum DecKernelId { DK_INTER = 0, DK_INTRA, DK_DEBLOCK, DK_HOST_PARSE, DK_SAO, DK_INTRA_P, DK_COUNT };      // (DK_INTRA_P: the intra blocks of a picture that also has inter blocks)
-
-struct DecodedPicture {
-  int width = 0, height = 0;          // cropped
-  int coded_w = 0, coded_h = 0;
-  const uint8_t *host[3] = {nullptr, nullptr, nullptr}; int host_pitch[3] = {0, 0, 0};
-  const uint8_t *dev[3] = {nullptr, nullptr, nullptr}; int dev_pitch[3] = {0, 0, 0};
-  int poc = 0; int64_t pts = 0; uint32_t fps_num = 0, fps_den = 0; bool is_intra = false;
-  int cvs = 0, num_reorder = 0;       // coded video sequence the picture belongs to (a running count); its SPS's sps_max_num_reorder_pics
-  uint64_t serial = 0;                // the picture's number in decoding order (Decoder::vwait_: which waiting pictures an IDR / BLA picture discards)
-  int missing_ctbs = 0, total_ctbs = 0;      // partial pictures: coding tree blocks of the picture that never arrived and were filled in (0: the picture is whole)
-};
-
-// a finished picture that owns its samples: what is still in the frame-threaded ring when the stream changes its resolution is
-// completed and kept like this until the following calls have handed it out (the decoder's own buffers are re-sized meanwhile)
-struct OwnedPic {
-  DecodedPicture pic;
-  std::vector<uint8_t> host;          // download mode: the three planes, pitches as in pic.host_pitch
-  uint8_t *dev = nullptr;             // device-resident mode: one allocation holding the three planes
-};
 
 // worker threads that parse whole pictures concurrently (frame threading)
 class FrameWorkers {
@@ -111,7 +93,7 @@ struct ConcealMotion {
 
 class Decoder {
  public:
-  explicit Decoder(int device) : device_(device) {}
+  explicit Decoder(int device) : device_(device), outp_(device) {}
   // what stands in for a reference picture that never arrived: 2 = a copy of the nearest reference picture (default), 3 = that picture moved along its own motion
   // ("Concealment v2" / "v3" below); before the first picture, and 3 not in band mode.  false: refused
   bool set_concealment(int mode) { if ((mode != 2 && mode != 3) || !jobs_.empty() || (mode == 3 && band_nrows_ > 0)) return false; conceal_mode_ = mode; return true; }
@@ -140,8 +122,8 @@ class Decoder {
   struct ProbeStats { uint64_t pictures = 0, tus = 0, levels = 0, digest = 0xcbf29ce484222325ull, bins = 0; double parse_ms = 0; };
   ProbeStats parse_probe_stats() const { return probe_; }
   // device-resident output (set_download(false)): the planes handed out stay untouched while the next `n` pictures are begun
-  // (they may be read as reference pictures, never written); default 2.  alloc_slot keeps the promise for the ring's buffers, free_retired for owned copies
-  void set_output_hold(int n) { output_hold_ = n < 1 ? 1 : (n > 8 ? 8 : n); }
+  // (they may be read as reference pictures, never written); default 2.  alloc_slot keeps the promise for the ring's buffers, DecOutput for owned copies
+  void set_output_hold(int n) { outp_.set_hold(n < 1 ? 1 : (n > 8 ? 8 : n)); }
   void set_profiling(int every) { profiling_ = every > 0; prof_every_ = every > 0 ? every : 1; }   // n: every n-th picture
   void set_parse_threads(int n) { if (!pool_) parse_threads_ = n < 1 ? 1 : n; }
   void get_kernel_times(double *ms, uint64_t *launches, bool reset);
@@ -188,7 +170,7 @@ class Decoder {
     // some boundary inside the picture is closed to the in-loop filters (loop_filter_across_tiles_enabled_flag = 0 with tiles; a slice with
     // slice_loop_filter_across_slices_enabled_flag = 0): lf_slices = the picture's independent slices (first block, flag)
     bool lf_restricted = false; std::vector<std::pair<int, uint8_t>> lf_slices;
-    struct Undo { int poc = 0, prev_poc = 0; bool is_ref = false, used = false, seen_irap = false; long decode_idx = 0; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion; std::vector<std::pair<uint64_t, int>> vwait; bool standin = false; } undo;      // what submit_job changed
+    struct Undo { int poc = 0, prev_poc = 0; bool is_ref = false, used = false, seen_irap = false; long decode_idx = 0; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion; OrderMark order; bool standin = false; } undo;      // what submit_job changed
     SliceHdr sh; std::shared_ptr<const DecSps> sps; DecPps pps;  // (a later SPS / PPS NAL may replace the table entry while this picture is still being parsed: the job keeps the SPS it was coded with alive, the PPS by value)
     int64_t pts = 0; int crop[4] = {0, 0, 0, 0}; uint32_t fps_num = 0, fps_den = 0;
     int slot = 0;                                                // picture buffer this picture is reconstructed into
@@ -320,38 +302,16 @@ class Decoder {
   PicJob &open_job(const SliceCtx &c, const DecPps &pp, int slot);
   int append_segment_tiles(PicJob &job, const SliceCtx &c, int address);
   int append_segment(PicJob &job, const SliceCtx &c, const DecPps &pp, int address);
-  std::deque<OwnedPic> ready_q_; OwnedPic cur_owned_;       // pictures completed ahead of their turn (resolution change), the one last handed out
-  // Output order (C.5.2): a stream whose SPS allows reordering (sps_max_num_reorder_pics > 0: B pictures in groups, Kvazaar gop=8) has its pictures
-  // copied out as they are completed and handed on by POC -- the smallest of those waiting once more than the SPS's count wait, all of a coded
-  // video sequence before the next one's first, the rest one per call when the stream ends.  A low-delay stream (the count is 0) never enters this.
-  struct Waiting { OwnedPic pic; int cvs; };
-  std::deque<Waiting> reorder_q_; int cvs_ = 0, reorder_ = 0;
-  bool pop_reordered(bool flush);
-  // Frame memory handed out by get_picture stays valid while kOutHold further NAL units are decoded -- a caller may copy it out on a stage of its
-  // own (OpenHEVCFilter's output thread) -- also across a resolution change: the host output buffers and the owned pictures that such a change
-  // retires are only freed kOutHold calls later.
-  static constexpr int kOutHold = 8;
-  long nal_calls_ = 0;
-  // kvzx_decoder_set_output_hold counts pictures, not NAL units (an access unit may bring parameter sets, SEI messages, a delimiter): the calls that began a picture,
-  // and the end-of-sequence / end-of-bitstream calls, which move the ring on by one picture like them.  An owned picture's device copy goes back to the pool only
-  // after output_hold_ of those as well.
-  long hold_clock_ = 0;
-  std::deque<std::pair<long, uint8_t *>> retired_out_;      // (call count at retirement, page-locked buffer)
-  struct Retired { long calls, clock; OwnedPic pic; };
-  std::deque<Retired> retired_owned_;
-  // device buffers of OwnedPic copies, kept for the next picture of the same size (queue_current_output)
-  static constexpr size_t kOwnedPoolMax = 24;
-  std::vector<std::pair<size_t, uint8_t *>> owned_pool_; std::map<const uint8_t *, size_t> owned_bytes_; hipEvent_t owned_ev_ = nullptr;
-  uint8_t *owned_alloc(size_t bytes); void owned_release(uint8_t *p); void owned_free(uint8_t *p); bool stash_current_output();
-  void free_retired(bool all);
-  int decode_nal_inner(const uint8_t *data, size_t len, int64_t pts);
-  bool queue_current_output();
+  // the output side (dec_output.h): what decode_nal does not hand out where it lies in the ring (out_) is offered -- copied -- and comes back in its turn
+  DecOutput outp_; int cvs_ = 0;
+  bool offer_output(bool in_turn) { if (!outp_.completed(out_, in_turn, download_, stream_dl_ ? stream_dl_ : stream_)) return false; pic_ready_ = false; return true; }
+  int decode_nal_inner(const uint8_t *data, size_t len, int64_t pts, int &nal_type);
   std::unique_ptr<FrameWorkers> workers_;
   // decoded picture buffer: slot = device planes + what reference marking needs
   struct DpbPic { uint8_t *plane[3] = {nullptr, nullptr, nullptr}; int poc = 0; bool is_ref = false, used = false, is_lt = false, standin = false;      // is_lt: marked "used for long-term reference" (8.3.2)
                   long decode_idx = -1000; std::shared_ptr<ColMotion> motion; std::shared_ptr<ConcealMotion> cmotion;      // (cmotion: concealment v3's record, NULL in mode 2 and for a stand-in)
-                  hipEvent_t last_dl = nullptr;
-                  hipEvent_t last_use = nullptr; bool last_use_alt = false; };      // (two chains, below: the last picture that read or wrote the buffer, and the stream it ran on)     // download mode: the copy of the picture last reconstructed here (a later picture's kernels wait for it before they write the buffer)
+                  hipEvent_t last_dl = nullptr;      // download mode: the copy of the picture last reconstructed here (a later picture's kernels wait for it before they write the buffer)
+                  hipEvent_t last_use = nullptr; bool last_use_alt = false; };      // (two chains, below: the last picture that read or wrote the buffer, and the stream it ran on)
   // More buffers than a picture can have reference pictures: beside those (15 at most, 7.4.3.2.1) the ring holds the pictures handed out and still promised
   // untouched (kvzx_decoder_set_output_hold: up to 8), the pictures launched behind them (kMaxGpuDepth), the picture at hand and the one a fill reads (avoid_slot_).
   // Buffers past the first six are allocated when first taken.  The kernels' table (DecFrame::ref) has KVZ_DEC_MAX_REFS entries: entry k is buffer k, and a
@@ -388,7 +348,7 @@ class Decoder {
   void describe_output(const PicJob &job, DecodedPicture &o, int buf) const;
   int queue_download(PicJob &job);
   int start_ready_downloads();
-  long launched_ = 0; int out_slot_ = 0; int output_hold_ = 2;
+  long launched_ = 0; int out_slot_ = 0;
   char prio_dl_ = 'n', prio_up_ = 'n';
   char prio_ = 'n';                                       // priority level of the main stream (stream_pool.h key)
   int band_row0_ = 0, band_nrows_ = 0; uint8_t *band_din_ = nullptr; DecFrame band_f_{};      // band mode: the picture between its reconstruction and band_finish
@@ -398,10 +358,6 @@ class Decoder {
   int prev_poc_ = 0, cur_tid_ = 0; bool seen_irap_ = false;
   int max_tid_ = 7; bool no_crop_ = false;
   bool after_eos_ = false;       // an end of sequence / end of bitstream NAL unit came: the next picture starts a coded video sequence (a CRA picture then has NoRaslOutputFlag = 1, 8.1.3)
-  // C.5.2.2's bookkeeping in DECODING order, kept at submit time: the pictures that are "needed for output" and have not had their turn -- (serial, POC).  The pictures
-  // themselves complete later (frame threads) and leave through reorder_q_ by the same counting rule; this list exists so that an IDR / BLA picture with
-  // no_output_of_prior_pics_flag discards exactly the pictures the standard's process would still hold at that instant, whatever the threads' timing.
-  std::vector<std::pair<uint64_t, int>> vwait_; std::vector<uint64_t> discarded_; uint64_t pic_serial_ = 0;
   // Concealment v2: a picture the reference picture set says the current one predicts from is not there (its access unit was lost on the way): a buffer with its
   // picture order count stands in -- no motion, never output -- and decoding goes on.  Its samples: a copy of the reference picture nearest in output order among
   // those the DPB held when the current picture arrived (of two equally near the earlier one), mid-grey when there is none (libavcodec's generate_missing_ref always takes grey).

@@ -51,13 +51,7 @@ Decoder::~Decoder()
   if (h_err_ && *h_err_) fprintf(stderr, "kvazzup_amd: decoder device error flags 0x%x (last picture)\n", *h_err_);
   for (auto &j : jobs_) { for (auto &e : j.ev) { hipEventDestroy(e.a); hipEventDestroy(e.b); } if (j.done) hipEventDestroy(j.done); if (j.dl_done) hipEventDestroy(j.dl_done); }
   free_buffers();
-  free_retired(true);
-  for (auto &o : ready_q_) owned_free(o.dev);
-  for (auto &w : reorder_q_) owned_free(w.pic.dev);
-  owned_free(cur_owned_.dev);
-  for (auto &b : owned_pool_) owned_free(b.second);
-  owned_pool_.clear();
-  if (owned_ev_) hipEventDestroy(owned_ev_);
+  outp_.release();                                           // (before the streams go; the member's own destructor runs it once more and finds nothing)
   if (stream_dl_ != stream_up_) stream_release(stream_dl_, device_, 'L', 'l');
   stream_release(stream_up_, device_, 'U', prio_up_);
   for (auto &e : up_done_) if (e) hipEventDestroy(e);
@@ -109,7 +103,7 @@ void Decoder::free_buffers()
   hipFree(d_standin_tab_); d_standin_tab_ = nullptr; standin_tab_cap_ = 0; standin_slot_ = -1; standin_tab_.clear();
   hipFree(d_fill_ctbs_); d_fill_ctbs_ = nullptr; fill_ctbs_cap_ = 0; hipFree(d_fill_tab_); d_fill_tab_ = nullptr; fill_tab_cap_ = 0; fill_tab_.clear();
   if (stream_dl_) hipStreamSynchronize(stream_dl_);
-  for (auto &p : h_out_) { if (p) retired_out_.emplace_back(nal_calls_, p); p = nullptr; }      // (freed kOutHold calls later: free_retired)
+  for (auto &p : h_out_) { if (p) outp_.retire_host(p); p = nullptr; }      // (freed kOutHold calls later)
   for (auto &p : d_in_) { hipFree(p); p = nullptr; } for (auto &c : d_in_cap_) c = 0;
   free_chain(chain_[0]); hipFree(intra_order_); intra_order_ = nullptr;
   if (chain_[1].stream) { hipStreamSynchronize(chain_[1].stream); free_chain(chain_[1]); stream_release(chain_[1].stream, device_, 'E', alt_prio_); chain_[1].stream = nullptr; }
@@ -170,9 +164,9 @@ bool Decoder::ensure_buffers(int w, int h, int ctb_log2)
   // following calls hand it out one picture at a time, as a software decoder's bumping process would -- before the buffers go
   while (!parse_only_ && w_ && (!gpu_q_.empty() || job_tail_ != job_head_)) {      // (a band decoder's picture between its reconstruction and band_finish -- gpu_job_ -- is not finish_oldest's to complete: drop_pending below lets it go)
     const int rc = finish_oldest();
-    if (rc < 0 || (rc > 0 && pic_ready_ && !stash_current_output())) { drop_pending(); break; }
+    if (rc < 0 || (rc > 0 && pic_ready_ && !offer_output(false))) { drop_pending(); break; }
   }
-  while (!parse_only_ && w_ && pop_reordered(true)) {}                     // a new sequence follows: what waited for later pictures of the old one leaves in POC order, one picture per call
+  if (!parse_only_ && w_) outp_.drain();                                   // a new sequence follows: what waited for later pictures of the old one leaves in POC order, one picture per call
   if (parse_only_) {
     for (auto &j : jobs_) { free(j.h_in); j.h_in = nullptr; j.h_in_cap = 0; }
     if (jobs_.empty()) jobs_ = std::vector<PicJob>(3);
@@ -252,11 +246,11 @@ bool Decoder::prepare_jobs(int w, int h, int ctb_log2)
 
 int Decoder::alloc_slot()
 {
-  // A picture handed out stays untouched while output_hold_ further pictures are begun (kvzx_decoder_set_output_hold).  The synchronous decoder launches picture q
-  // in the call that begins it and hands picture p out in the call that began it: q may take p's buffer when q - p > output_hold_.  With frame threads the call that
+  // A picture handed out stays untouched while `hold` further pictures are begun (kvzx_decoder_set_output_hold; dec_output.h).  The synchronous decoder launches picture q
+  // in the call that begins it and hands picture p out in the call that began it: q may take p's buffer when q - p > hold.  With frame threads the call that
   // begins picture k hands out picture k - frame_threads_ and launches picture k - frame_threads_ + gpu_depth_: picture q is launched gpu_depth_ calls after the one
-  // that handed out q - gpu_depth_, so it may take p's buffer when q - p > output_hold_ + gpu_depth_.
-  const long margin = output_hold_ + (frame_threads_ > 1 ? gpu_depth_ : 0);
+  // that handed out q - gpu_depth_, so it may take p's buffer when q - p > hold + gpu_depth_.
+  const long margin = outp_.hold() + (frame_threads_ > 1 ? gpu_depth_ : 0);
   for (int s = 0; s < kMaxPics; s++) {
     DpbPic &p = dpb_[s];
     if (p.is_ref || s == avoid_slot_ || job_head_ - p.decode_idx <= margin) continue;
@@ -306,146 +300,18 @@ void Decoder::get_kernel_times(double *ms, uint64_t *launches, bool reset)
 }
 
 // ------------------------------------------------------------------------------------------ NAL units
-// One picture out per call at most (the libOpenHevcDecode contract).  Pictures that were completed ahead of their turn -- the ring's
-// contents at a resolution change -- are handed out first, one per call, in order; a picture this call itself completes meanwhile joins
-// the end of that queue.
-void Decoder::free_retired(bool all)
-{
-  while (!retired_out_.empty() && (all || nal_calls_ - retired_out_.front().first > kOutHold)) { hipHostFree(retired_out_.front().second); retired_out_.pop_front(); }
-  while (!retired_owned_.empty() && (all || (nal_calls_ - retired_owned_.front().calls > kOutHold && hold_clock_ - retired_owned_.front().clock > output_hold_))) {      // (the host copy's promise and the device copy's: decoder.h hold_clock_)
-    if (all) owned_free(retired_owned_.front().pic.dev); else owned_release(retired_owned_.front().pic.dev);
-    retired_owned_.pop_front();
-  }
-}
-
+// One picture out per call at most (the libOpenHevcDecode contract).  The fast path -- a sequence that does not reorder, nothing completed ahead of its turn -- hands
+// out the ring's own buffer as complete_gpu described it: no copy, no event, no allocation.  Everything else goes through DecOutput (dec_output.h): the picture this
+// call completed is copied and takes its place, and the next one in output order, if its turn has come, is handed out.
 int Decoder::decode_nal(const uint8_t *data, size_t len, int64_t pts)
 {
-  nal_calls_++;
-  if (!retired_out_.empty() || !retired_owned_.empty()) free_retired(false);
-  const int rc = decode_nal_inner(data, len, pts);
-  // ---- output order (C.5.2).  A picture of a stream that may reorder (its SPS says how many pictures may overtake one) is copied out of the ring as
-  // it completes and waits in reorder_q_; the smallest POC of the oldest coded video sequence goes out once more pictures wait than may overtake it,
-  // or a later sequence has begun, or the stream has ended (EOS / EOB with nothing left in the pipeline).  One picture per call, as ever.
-  if (rc >= 0 && ((pic_ready_ && out_.num_reorder > 0) || !reorder_q_.empty())) {
-    if (pic_ready_ && out_.num_reorder == 0) {
-      // a sequence that does not reorder behind one that did: everything still waiting precedes this picture -- all of it moves to ready_q_ at once
-      // (in order), the picture behind it; every later call, parameter sets included, hands one out, so the lag the old sequence needed drains
-      // instead of staying until the end of the stream
-      while (pop_reordered(true)) {}
-      if (!queue_current_output()) return last_error_ = DEC_ERR_GPU;
-    } else if (pic_ready_) {
-      const int cvs = out_.cvs; reorder_ = out_.num_reorder;
-      if (!queue_current_output()) return last_error_ = DEC_ERR_GPU;
-      reorder_q_.push_back(Waiting{std::move(ready_q_.back()), cvs}); ready_q_.pop_back();
-    }
-    const bool eos = len >= 2 && [&] { size_t i = 0; while (i + 2 < len && data[i] == 0) i++; const uint8_t *q = (i >= 2 && i < len && data[i] == 1) ? data + i + 1 : data; const int t = (q[0] >> 1) & 0x3f; return t == 36 || t == 37; }();
-    if (ready_q_.empty() && !pop_reordered(eos && pending() == 0)) return 0;
-  } else {
-  if (ready_q_.empty()) return rc;
-  if (rc < 0) return rc;
-  if (pic_ready_ && !queue_current_output()) return last_error_ = DEC_ERR_GPU;
-  }
-  if (cur_owned_.dev || !cur_owned_.host.empty()) retired_owned_.push_back(Retired{nal_calls_, hold_clock_, std::move(cur_owned_)});      // (the caller may still be copying it out)
-  cur_owned_ = OwnedPic();
-  cur_owned_ = std::move(ready_q_.front());
-  ready_q_.pop_front();
-  out_ = cur_owned_.pic;
-  size_t off = 0;
-  for (int c = 0; c < 3; c++) {
-    const int h = c ? out_.height / 2 : out_.height;
-    if (!cur_owned_.host.empty()) { out_.host[c] = cur_owned_.host.data() + off; off += (size_t)out_.host_pitch[c] * h; }
-  }
-  pic_ready_ = true;
-  return 1;
-}
-
-// C.5.2.4: of the waiting pictures of the oldest coded video sequence the one with the smallest POC becomes the next of ready_q_ -- when more of
-// them wait than may overtake a picture, when a later sequence has begun, or when the stream is over
-bool Decoder::pop_reordered(bool flush)
-{
-  if (reorder_q_.empty()) return false;
-  int first_cvs = reorder_q_.front().cvs, n = 0; size_t best = 0;
-  for (const Waiting &w : reorder_q_) if (w.cvs < first_cvs) first_cvs = w.cvs;
-  bool later = false;
-  for (size_t i = 0; i < reorder_q_.size(); i++) {
-    const Waiting &w = reorder_q_[i];
-    if (w.cvs != first_cvs) { later = true; continue; }
-    if (n++ == 0 || w.pic.pic.poc < reorder_q_[best].pic.pic.poc) best = i;
-  }
-  if (!(flush || later || n > reorder_)) return false;
-  ready_q_.push_back(std::move(reorder_q_[best].pic));
-  reorder_q_.erase(reorder_q_.begin() + (long)best);
-  return true;
-}
-
-// the picture complete_gpu() just made the output, copied into storage of its own at the end of the queue.  The device copy comes from a small pool
-// of buffers (a hipMalloc / hipFree per picture of a reordering stream synchronised the whole device -- every other encoder and decoder of the
-// process with it) and is made by the download stream, which this thread waits for by event.
-uint8_t *Decoder::owned_alloc(size_t bytes)
-{
-  for (size_t i = 0; i < owned_pool_.size(); i++) if (owned_pool_[i].first == bytes) { uint8_t *p = owned_pool_[i].second; owned_pool_.erase(owned_pool_.begin() + (long)i); return p; }
-  for (auto &b : owned_pool_) owned_free(b.second);      // (another size: the stream changed its resolution -- every pooled buffer of the old size goes at once: at 4K two dozen of them are 288 MB)
-  owned_pool_.clear();
-  uint8_t *p = nullptr;
-  if (hipSetDevice(device_) != hipSuccess || hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-  owned_bytes_[p] = bytes;
-  return p;
-}
-void Decoder::owned_release(uint8_t *p)
-{
-  if (!p) return;
-  auto it = owned_bytes_.find(p);
-  if (it != owned_bytes_.end() && owned_pool_.size() < kOwnedPoolMax && (owned_pool_.empty() || owned_pool_.front().first == it->second)) { owned_pool_.emplace_back(it->second, p); return; }      // (the pool holds ONE size: owned_alloc empties it when another one is asked for)
-  owned_free(p);
-}
-// every hipFree of an owned buffer comes through here: the address leaves the size map with it (a stale entry would pool a later allocation at the same
-// address under the wrong size)
-void Decoder::owned_free(uint8_t *p)
-{
-  if (!p) return;
-  owned_bytes_.erase(p);
-  hipFree(p);
-}
-bool Decoder::queue_current_output()
-{
-  OwnedPic o;
-  o.pic = out_;
-  if (download_) {
-    for (int c = 0; c < 3; c++) {                                 // plane after plane, pitch x rows each (decode_nal rebuilds the pointers the same way)
-      const uint8_t *p = out_.host[c];
-      o.host.insert(o.host.end(), p, p + (size_t)out_.host_pitch[c] * (c ? out_.height / 2 : out_.height));
-    }
-  }
-  {
-    // the device view: a dense copy (pitch = width), so that device-resident consumers keep working across the re-allocation
-    const size_t ny = (size_t)out_.width * out_.height;
-    o.dev = owned_alloc(ny * 3 / 2);
-    if (!o.dev) return false;
-    size_t off = 0;
-    hipStream_t st = stream_dl_ ? stream_dl_ : stream_;
-    for (int c = 0; c < 3; c++) {
-      const int w = c ? out_.width / 2 : out_.width, h = c ? out_.height / 2 : out_.height;
-      if (hipMemcpy2DAsync(o.dev + off, (size_t)w, out_.dev[c], (size_t)out_.dev_pitch[c], (size_t)w, (size_t)h, hipMemcpyDeviceToDevice, st) != hipSuccess) { owned_release(o.dev); return false; }
-      o.pic.dev[c] = o.dev + off; o.pic.dev_pitch[c] = w;
-      off += (size_t)w * h;
-    }
-    // (the picture's kernels are complete -- complete_gpu saw its event --, so the copies depend on nothing in another stream)
-    if (!owned_ev_ && hipEventCreateWithFlags(&owned_ev_, hipEventDisableTiming) != hipSuccess) { owned_release(o.dev); return false; }
-    if (hipEventRecord(owned_ev_, st) != hipSuccess || hipEventSynchronize(owned_ev_) != hipSuccess) { owned_release(o.dev); return false; }
-  }
-  ready_q_.push_back(std::move(o));
-  pic_ready_ = false;
-  return true;
-}
-
-// queue_current_output() for a picture completed AHEAD of its turn (the ring emptied at a resolution change, a picture closed by the next one's first
-// NAL unit): a stream that reorders keeps its output order -- the picture joins reorder_q_ with its sequence and POC like any other.
-bool Decoder::stash_current_output()
-{
-  const int cvs = out_.cvs, nr = out_.num_reorder;
-  if (!queue_current_output()) return false;
-  if (nr > 0 || !reorder_q_.empty()) { if (nr > 0) reorder_ = nr; reorder_q_.push_back(Waiting{std::move(ready_q_.back()), cvs}); ready_q_.pop_back(); }
-  return true;
+  outp_.begin_call();
+  int nal_type = -1;
+  const int rc = decode_nal_inner(data, len, pts, nal_type);
+  if (rc < 0 || (outp_.idle() && !(pic_ready_ && out_.num_reorder > 0))) return rc;
+  if (pic_ready_ && !offer_output(true)) return last_error_ = DEC_ERR_GPU;
+  pic_ready_ = outp_.next((nal_type == 36 || nal_type == 37) && pending() == 0, out_);      // (EOS / EOB with nothing left in the pipeline: what still waits leaves, one per call)
+  return pic_ready_ ? 1 : 0;
 }
 
 // emulation prevention bytes out (7.4.2; hevc_headers.h append_nal is the inverse): the bytes between zero bytes in one piece.  The payload behind the two
@@ -487,7 +353,7 @@ int Decoder::decode_parameter_set(int nal_type, BitReader &r)
   return rc ? (last_error_ = rc) : 0;
 }
 
-int Decoder::decode_nal_inner(const uint8_t *data, size_t len, int64_t pts)
+int Decoder::decode_nal_inner(const uint8_t *data, size_t len, int64_t pts, int &nal_type)
 {
   Tick tk_nal;
   struct Acc { double &d; Tick &t; double &w, &s, &a, &y; double w0, s0, a0, y0; ~Acc() { d += t.ms() - ((w - w0) + (s - s0) + (a - a0) + (y - y0)); } } acc_{t_nal_, tk_nal, t_wait_, t_stage_, t_api_, t_sync_, t_wait_, t_stage_, t_api_, t_sync_};
@@ -497,7 +363,7 @@ int Decoder::decode_nal_inner(const uint8_t *data, size_t len, int64_t pts)
   while (i + 2 < len && data[i] == 0) i++;
   if (i >= 2 && i < len && data[i] == 1) { data += i + 1; len -= i + 1; }
   if (len < 2 || (data[0] & 0x80)) return last_error_ = DEC_ERR_INVALID;      // EOS / EOB are header-only
-  const int nal_type = (data[0] >> 1) & 0x3f, layer = ((data[0] & 1) << 5) | (data[1] >> 3);
+  nal_type = (data[0] >> 1) & 0x3f; const int layer = ((data[0] & 1) << 5) | (data[1] >> 3);
   if (layer != 0) return 0;
   cur_tid_ = (data[1] & 7) - 1;
   if (nal_type < 32 && cur_tid_ > max_tid_) return 0;            // (set_max_temporal_id: a sub-layer the caller does not want)
@@ -507,7 +373,7 @@ int Decoder::decode_nal_inner(const uint8_t *data, size_t len, int64_t pts)
   const bool open_rows = partial_ && asm_.active && !jobs_.empty() && jobs_[(size_t)(job_head_ % jobs_.size())].pps.wpp && jobs_[(size_t)(job_head_ % jobs_.size())].pps.tile_rows == 1 && jobs_[(size_t)(job_head_ % jobs_.size())].pps.tile_cols == 1;
   if (asm_.active && (asm_.guessed_one_row || asm_.free || open_rows) && nal_type >= 32 && nal_type <= 40 && nal_type != 38) { const int rc = close_open_picture(); if (rc < 0) return rc; }   // (what can only open the next access unit, or end the sequence)
   if (nal_type >= 32 && nal_type <= 34) return decode_parameter_set(nal_type, r);
-  if (nal_type == 36 || nal_type == 37) { hold_clock_++; after_eos_ = true; vwait_.clear(); int rc = finish_oldest(); if (rc < 0) last_error_ = rc; return rc; }   // EOS / EOB: drain one delayed picture; whatever picture follows starts a sequence
+  if (nal_type == 36 || nal_type == 37) { outp_.begin_picture(); after_eos_ = true; outp_.sequence_ended(); int rc = finish_oldest(); if (rc < 0) last_error_ = rc; return rc; }   // EOS / EOB: drain one delayed picture; whatever picture follows starts a sequence
   if (nal_type == 40 && check_hash_) return hash_sei(rbsp_.data(), n);       // suffix SEI: decoded picture hash (libOpenHevcSetCheckMD5)
   if (nal_type > 31) return 0;                                    // AUD / other SEI / ...
   if (!(nal_type <= 9 || (nal_type >= 16 && nal_type <= 21))) return last_error_ = DEC_ERR_UNSUPPORTED;      // (reserved types)
@@ -630,7 +496,7 @@ int Decoder::submit_closed(PicJob &job, int rc)
 {
   if (rc >= 0) rc = submit_job(job, asm_.nal_type, asm_.irap);
   if (rc < 0) { last_error_ = rc; return 0; }
-  if (rc > 0 && pic_ready_ && !stash_current_output()) return last_error_ = DEC_ERR_GPU;
+  if (rc > 0 && pic_ready_ && !offer_output(false)) return last_error_ = DEC_ERR_GPU;
   return 0;
 }
 
@@ -858,7 +724,7 @@ Decoder::PicJob &Decoder::open_job(const SliceCtx &c, const DecPps &pp, int slot
   if (no_crop_) job.crop[0] = job.crop[1] = job.crop[2] = job.crop[3] = 0;
   job.fps_num = s.fps_num ? s.fps_num : vps_fps_num_; job.fps_den = s.fps_num ? s.fps_den : vps_fps_den_;
   job.slot = slot; job.nref = c.nref;
-  hold_clock_++;                                                 // (a picture has begun: decoder.h)
+  outp_.begin_picture();                                         // (a picture has begun: dec_output.h)
   // the kernels' table of picture buffers (decoder.h dpb_): entry k is buffer k; a reference picture in a buffer past the table's end takes an entry whose own
   // buffer neither list names (the lists name 16 distinct pictures at most, apply_rps_and_build_lists) -- the records then name the picture by that entry
   uint8_t entry_of[kMaxPics];
@@ -1103,7 +969,7 @@ void Decoder::take_back_job(PicJob &job)
 {
   DpbPic &d = dpb_[job.slot];
   d.poc = job.undo.poc; d.is_ref = job.undo.is_ref; d.used = job.undo.used; d.decode_idx = job.undo.decode_idx; d.motion = job.undo.motion; d.cmotion = job.undo.cmotion; prev_poc_ = job.undo.prev_poc; seen_irap_ = job.undo.seen_irap;
-  vwait_ = std::move(job.undo.vwait); d.standin = job.undo.standin; take_backs_++;
+  outp_.restore(std::move(job.undo.order)); d.standin = job.undo.standin; take_backs_++;
   job.undo.motion.reset(); job.undo.cmotion.reset();
   // the parse that ended early has released every row of the picture's ColMotion (parse_job release_all) and counted its columns: the picture is parsed AGAIN when its
   // access unit has ended, and under frame threads the next picture's parser must wait for THAT parse, row by row -- the rows are closed again here (nobody holds the
@@ -1140,24 +1006,7 @@ int Decoder::submit_job(PicJob &job, int nal_type, bool irap)
   d.poc = sh.poc; d.is_ref = true; d.used = true; d.is_lt = false; d.standin = false; d.decode_idx = job_head_; d.motion = job.own; d.cmotion = job.cown;
   if (cur_tid_ == 0 && (nal_type > 9 || ((nal_type & 1) && nal_type < 6))) prev_poc_ = sh.poc;   // prevTid0Pic (8.3.1): TemporalId 0, not RASL / RADL / sub-layer non-reference
   if (irap) seen_irap_ = true;
-  {
-    // output bookkeeping in decoding order (C.5.2.2, C.5.2.3; Decoder::vwait_)
-    job.undo.vwait = vwait_; job.serial = ++pic_serial_;
-    const int nr = job.sps->num_reorder;
-    auto bump = [&] { size_t b = 0; for (size_t i = 1; i < vwait_.size(); i++) if (vwait_[i].second < vwait_[b].second) b = i; vwait_.erase(vwait_.begin() + (long)b); };
-    if (job.starts_cvs) {
-      if (job.discard_prior && !vwait_.empty()) {
-        for (const auto &v : vwait_) discarded_.push_back(v.first);
-        for (size_t i = 0; i < reorder_q_.size();) {             // (the ones that have completed wait here; the others find their number in discarded_ when they complete)
-          if (std::find(discarded_.begin(), discarded_.end(), reorder_q_[i].pic.pic.serial) != discarded_.end()) { owned_release(reorder_q_[i].pic.dev); reorder_q_.erase(reorder_q_.begin() + (long)i); }
-          else i++;
-        }
-        if (discarded_.size() > 64) discarded_.erase(discarded_.begin(), discarded_.end() - 64);
-      }
-      vwait_.clear();
-    } else while ((int)vwait_.size() > nr) bump();
-    if (!sh.no_output) { vwait_.emplace_back(job.serial, sh.poc); while ((int)vwait_.size() > nr) bump(); }
-  }
+  job.undo.order = outp_.mark(); job.serial = outp_.submitted(sh.poc, job.sps->num_reorder, job.starts_cvs, job.discard_prior, sh.no_output);      // output bookkeeping in decoding order (C.5.2.2, C.5.2.3; dec_order.h)
   job_head_++;
   if (parse_only_) {
     auto t0 = std::chrono::steady_clock::now();
@@ -1354,7 +1203,7 @@ int Decoder::complete_gpu(PicJob &job)
     job.ev_used = 0;
   }
   if (job.sh.no_output) { job.dl_buf = -1; return 0; }      // pic_output_flag = 0 (7.4.7.1): reconstructed -- later pictures predict from it -- and never handed out
-  if (!discarded_.empty() && std::find(discarded_.begin(), discarded_.end(), job.serial) != discarded_.end()) { job.dl_buf = -1; return 0; }      // (an IDR / BLA picture behind it said so: C.5.2.2)
+  if (outp_.discarded(job.serial)) { job.dl_buf = -1; return 0; }      // (an IDR / BLA picture behind it said so: C.5.2.2)
   describe_output(job, out_, download_ ? job.dl_buf : -1);
   out_slot_ = job.slot;
   job.dl_buf = -1;

@@ -547,7 +547,7 @@ void OpenHEVCFilter::process()                             // openhevcfilter.cpp
         discardedFrames_ = 0;
         kvzx::tl("dec0", (long)input->presentationTimestamp);
         if (asyncOut_) {
-          // A picture's memory stays valid for a number of further decode CALLS (Decoder::kOutHold / kOutRing), whether or not they return pictures -- and at the
+          // A picture's memory stays valid for a number of further decode CALLS (DecOutput::kOutHold / Decoder::kOutRing), whether or not they return pictures -- and at the
           // end of a stream many do not (end-of-sequence units while the frame threads finish).  So a call waits while the oldest copy still pending is of a
           // picture handed out five calls ago: the output stage may lag by pictures, never by calls.  (Found as 27 wrong bytes at the start of one picture of a
           // reordered stream under a loaded host: the copy read a buffer the allocator had taken back.)

@@ -47,6 +47,9 @@ def _declare(L):
         # coder.cpp
         "hcr_play": (I, [I, P, P, P, I, P, P, I, P, P]), "hcr_code_picture": (I, [I, I, P, P, P] + [I] * 7 + [P, I, P, I, P]),
         "hcr_code_band": (I, [I, I, P, P, P] + [I] * 8 + [P, I, P, I, P]), "hcr_bench": (D, [P, LONG, I, I, I]),
+        # order.cpp
+        "ho_new": (P, []), "ho_free": (None, [P]), "ho_submitted": (U64, [P] + [I] * 5 + [P, I, P]), "ho_mark": (None, [P]), "ho_restore": (None, [P]), "ho_discarded": (I, [P, U64]),
+        "ho_sequence_ended": (None, [P]), "ho_idle": (I, [P]), "ho_completed": (None, [P, U64] + [I] * 4), "ho_next": (I, [P, I, P]), "ho_drain": (None, [P]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -126,6 +126,18 @@ KVZ_PUBLIC void kvzx_batch_hold(int device, int on);
 /* delta-QP map for the pictures submitted through the device entry point (the host entry point takes it from kvz_picture.roi,
  * kvazaarfilter.cpp:423-431): w x h int8 cells over the picture, w == 0 removes it; needs "set-qp-in-cu" = 1 */
 KVZ_PUBLIC void kvzx_encoder_set_roi(kvz_encoder *enc, int w, int h, const int8_t *map);
+/* "loss-feedback" = H ("uvgx loss feedback v1"): the receiver's loss report, the triples of kvzx_decoder_damage_log handed over unchanged.
+ * poc names the MOST RECENTLY CODED picture with that POC; first_ctb and count are 64x64 coding tree blocks in raster order of the coded picture; count <= 0:
+ * the whole picture -- an access unit that never arrived, or an application's "refresh now".  Returns
+ *   1  accepted: the first picture handed in after the call returns is the heal picture -- a P picture with intra units where the error may have travelled,
+ *      starting with a recovery point SEI; from it on the receiver has the encoder's pictures exactly.  Several reports before one picture fold into one heal
+ *      picture; a report older than H pictures is accepted and treated as "everything damaged" (every quarter of the heal picture is intra);
+ *   2  void: an IDR picture has been coded since the reported picture, there is nothing to heal and the stream is unchanged;
+ *   0  refused: the option is off (a band encoder cannot have it on), or the range lies outside the picture.
+ * A stale report whose POC collides with a newer picture of the same POC (behind a later IDR picture) is taken for that newer picture: it over-heals and never
+ * under-heals.  Call it from the thread that hands pictures in, between any two of its calls; with owf >= 2 it waits until the encoder's submitter thread has
+ * planned every picture handed in so far, and is safe against that thread. */
+KVZ_PUBLIC int kvzx_encoder_report_damage(kvz_encoder *enc, int32_t poc, int first_ctb, int count);
 /* Rate control ("bitrate" > 0) in band mode: every band's encoder runs the same picture-level controller, which books the size of access
  * unit t - 3 before picture t; the caller tells EVERY encoder the size of each assembled access unit (picture = 0, 1, ...) before
  * picture + 3 is started.  kvazzup_amd/tilesplit.py passes the sizes along with the substream headers it gathers anyway. */

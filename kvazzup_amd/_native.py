@@ -39,7 +39,7 @@ class KvzConfig(C.Structure):
                 ("pu_depth_inter_min", C.c_int32), ("pu_depth_inter_max", C.c_int32), ("pu_depth_intra_min", C.c_int32), ("pu_depth_intra_max", C.c_int32),
                 ("me_range", C.c_int32), ("gpu_device", C.c_int32), ("recon_output", C.c_int32), ("intra_satd", C.c_int32),
                 ("band_row0", C.c_int32), ("band_rows", C.c_int32), ("input_hold", C.c_int32), ("null_input_poll", C.c_int32), ("intra_in_p", C.c_int32), ("gpu_entropy", C.c_int32), ("intra_chain", C.c_int32), ("me_source", C.c_int32),
-                ("lp_refs", C.c_int32), ("me_coarse", C.c_int32), ("lp_gop", C.c_int32), ("weightp", C.c_int32), ("intra_refresh", C.c_int32), ("scenecut", C.c_int32), ("input_format", C.c_int32)]
+                ("lp_refs", C.c_int32), ("me_coarse", C.c_int32), ("lp_gop", C.c_int32), ("weightp", C.c_int32), ("intra_refresh", C.c_int32), ("scenecut", C.c_int32), ("input_format", C.c_int32), ("loss_feedback", C.c_int32)]
 
 
 class KvzRoi(C.Structure):
@@ -102,7 +102,7 @@ class OpenHevcFrame(C.Structure):
 
 ENCODER_EXPORTS = ["kvz_api_get", "kvzx_version", "kvzx_rgb32_to_yuv420", "kvzx_rgb32_to_yuv420_device", "kvzx_yuv420_to_rgb32", "kvzx_yuv420_to_rgb32_device", "uvgx_pipeline_flush", "kvzx_device_count", "kvzx_encoder_encode_device", "kvzx_encoder_encode_host", "kvzx_encoder_encode_packed_host", "kvzx_encoder_encode_packed_device",
                    "kvzx_encoder_coded_size", "kvzx_encoder_download_recon", "kvzx_encoder_recon_device", "kvzx_encoder_debug_copy",
-                   "kvzx_encoder_set_profiling", "kvzx_encoder_kernel_times", "kvzx_encoder_kernel_name", "kvzx_encoder_last_bins", "kvzx_encoder_pending"]
+                   "kvzx_encoder_set_profiling", "kvzx_encoder_kernel_times", "kvzx_encoder_kernel_name", "kvzx_encoder_last_bins", "kvzx_encoder_pending", "kvzx_encoder_report_damage"]
 DECODER_EXPORTS = ["libOpenHevcInit", "libOpenHevcStartDecoder", "libOpenHevcDecode", "libOpenHevcGetPictureInfo",
                    "libOpenHevcGetPictureSize2", "libOpenHevcGetOutput", "libOpenHevcGetOutputCpy", "libOpenHevcSetCheckMD5",
                    "libOpenHevcSetDebugMode", "libOpenHevcSetTemporalLayer_id", "libOpenHevcSetNoCropping", "libOpenHevcSetActiveDecoders",
@@ -139,6 +139,7 @@ def load_library():
     L.kvzx_encoder_last_bins.restype = C.c_uint64
     L.kvzx_encoder_last_bins.argtypes = [C.c_void_p]
     L.kvzx_encoder_pending.argtypes = [C.c_void_p]
+    L.kvzx_encoder_report_damage.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_int]
     if hasattr(L, "libOpenHevcInit"):
         L.libOpenHevcInit.restype = C.c_void_p
         L.libOpenHevcInit.argtypes = [C.c_int, C.c_int]

@@ -141,6 +141,10 @@ class Encoder:
         ok = self.lib.kvzx_encoder_encode_packed_device(self.enc, dptr, self._au.ctypes.data, len(self._au), C.byref(n), C.byref(info))
         return self._packed_out(ok, n, info, want_recon, "kvzx_encoder_encode_packed_device")
 
+    def report_damage(self, poc, first_ctb, count):
+        """"loss-feedback": the receiver's loss report (a triple of Decoder.damage_log()); 1 accepted -- the next picture is the heal picture --, 2 void, 0 refused"""
+        return int(self.lib.kvzx_encoder_report_damage(self.enc, int(poc), int(first_ctb), int(count)))
+
     def coded_size(self):
         a, b = C.c_int(), C.c_int()
         self.lib.kvzx_encoder_coded_size(self.enc, C.byref(a), C.byref(b))
@@ -175,6 +179,11 @@ class Encoder:
         # intra-refresh: position in the cycle, the band's first and end column, the cycle's length -- a key of its own only with the option on
         if int(self.cfg.contents.intra_refresh):
             d["ir"] = [int(v) for v in self.debug("ir", np.int32, (4,))]
+        # loss-feedback: the delivered picture's record, and the map and block records of the heal picture last submitted -- keys of their own only with the option on
+        if int(self.cfg.contents.loss_feedback):
+            d["fb"] = dict(zip(("heal", "reports", "cells", "forced"), (int(v) for v in self.debug("fb", np.int32, (4,)))))
+            d["fb_map"] = self.debug("fb_map", np.uint8, b8)
+            d["fb_blk"] = self.debug("fb_blk", np.uint8, (ch // 32, cw // 32, 2))
         # scenecut: the delivered picture's record, and (S, A) of every block of the picture last examined -- keys of their own only with the option on
         if int(self.cfg.contents.scenecut):
             d["scenecut"] = dict(zip(("examined", "n_new", "n_b", "d", "cut"), (int(v) for v in self.debug("scenecut", np.int32, (5,)))))

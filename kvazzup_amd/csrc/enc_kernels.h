@@ -53,6 +53,20 @@ struct ScArgs {
 void launch_sc_sum(const ScArgs &a, hipStream_t st);      // every picture: sum_c (zero before the launch) += the visible samples of qc
 void launch_sc_blocks(const ScArgs &a, hipStream_t st);   // an examined picture: (S, A) of every block, n_new
 void launch_sc_decide(const ScArgs &a, hipStream_t st);   // ... and its record
+// "loss-feedback" (fb_kernels.hip)
+struct FbArgs {
+  int gw, gh;                                        // the cell grid: coded width / 8, coded height / 8
+  const int16_t *cu_mv; const uint8_t *cu_intra, *cu_log2;   // k_fb_record: the working set's final arrays; clean: the record of an IDR picture, KVZ_FB_CLEAN (the statement's; the engine files none, it never steps through one)
+  int clean;
+  int16_t *rec_mv; uint8_t *rec_info;                // one picture's record in the ring: [cell][2] vectors, [cell] fb_info (written by k_fb_record, read by k_fb_step)
+  uint8_t *map, *tmp;                                // the map being taken to the heal picture, and a step's scratch, one byte a cell
+  int first, count, dilate;                          // k_fb_seed: the reported coding tree blocks; dilate: deblocking or SAO is on
+  int me_range; uint8_t *blk; int32_t *stat;         // k_fb_blocks: the block records [32x32 block][2] and the slot's host-mapped record {heal, reports, cells, forced quarters}
+};
+void launch_fb_record(const FbArgs &a, hipStream_t st);   // every P picture with the option on, behind its chain
+void launch_fb_seed(const FbArgs &a, hipStream_t st);     // a heal picture: one report into the map
+void launch_fb_step(const FbArgs &a, hipStream_t st);     // ... the map through one picture's record
+void launch_fb_blocks(const FbArgs &a, hipStream_t st);   // ... the block records and the counts
 // k_cabac_rows (cabac_kernels.hip): the arithmetic coder proper on the GPU, one wave per substream
 struct CabacRowsArgs {
   const uint16_t *tok; const int32_t *count; const uint32_t *off;   // dense tokens (device): CTU i has count[i] tokens at tok + off[i]

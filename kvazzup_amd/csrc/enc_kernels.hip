@@ -51,9 +51,13 @@ namespace kvzx {
 // band is not searched -- its quarters go to k_intra_analyse<true, true> with the cost 0xffffffff, which passes the gate and beats every intra price; the block
 // whose left quarters alone are forced is searched as ever (never left early) and joins the list as well; a clean block (left of the band, position >= 1)
 // drops the candidates beyond ir_mvx_max.  A form of its own: the launches without the option run the code of before.
-template <bool MR, bool CO = false, bool IR = false>
+// FB (loss-feedback; one reference, no coarse stage): a heal picture's block reads its record (f.fb_blk, fb_block_record) where the IR form
+// computes the band -- the forced quarters take the IR form's path, and every candidate beyond the record's reach in x or y is dropped (the zero vector never is).
+// A form of its own as well.
+template <bool MR, bool CO = false, bool IR = false, bool FB = false>
 __global__ __launch_bounds__(256) void k_me(EncFrame f)
 {
+  constexpr bool FQ = IR || FB;                                        // the block may have forced quarters
   using Key = typename std::conditional<MR || CO, unsigned long long, uint32_t>::type;
   constexpr int KS = CO ? 17 : (MR ? 16 : 13);                         // cost field's shift
   constexpr Key KMAX = ~(Key)0;
@@ -74,6 +78,13 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
   if constexpr (IR) {
     ir_forced = ir_forced_quarters(x0, f.ir_s, f.ir_e);
     if (ir_clean_block(x0, f.ir_s, f.ir_j)) ir_dx = ir_mvx_max(x0, f.ir_s) >> 2;
+  }
+  int fb_r = 0;                                                        // FB: the block's reach in full samples
+  if constexpr (FB) {
+    const uint8_t *r = f.fb_blk + 2 * ((size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
+    ir_forced = r[0]; fb_r = fb_reach(r[1]);
+  }
+  if constexpr (FQ) {
     if (ir_forced == 15) {                                             // (the same for every thread, in front of the first barrier)
       if (tid < 16) {
         const int i = b8idx(f, x0 + (tid & 3) * 8, y0 + (tid >> 2) * 8);
@@ -97,7 +108,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     if (f.me_early) { s0 = wave_sum_u32(s0); if ((tid & 63) == 0) atomicAdd(&red[0], (Key)s0); }
   }
   __syncthreads();
-  if (f.me_early && !(IR && ir_forced) && red[0] <= 64u * lam) {
+  if (f.me_early && !(FQ && ir_forced) && red[0] <= 64u * lam) {
     if (tid < 16) {
       const int i = b8idx(f, x0 + (tid & 3) * 8, y0 + (tid >> 2) * 8);
       f.cu_log2[i] = 5; f.cu_intra[i] = 0; f.cu_mv[i * 2] = 0; f.cu_mv[i * 2 + 1] = 0;
@@ -189,6 +200,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
       if (dyi >= W) continue;
       { const int dy = oy + dyi - R, m = (dy & 1) ? 4 : 0; if ((ty0 > 0 && y0 + dy - m < ty0) || (ty1 < f.ch && y0 + dy + 32 + m > ty1)) continue; }
       if (f.mv_frame) { const int dy = oy + dyi - R, my = (f.mv_frame == 2 && (dy & 1)) ? 4 : 0; if (y0 + dy - my < 0 || y0 + dy + 32 + my > f.ch) continue; }
+      if constexpr (FB) { const int dy = oy + dyi - R; if (dy > fb_r || dy < -fb_r) continue; }      // within the record's reach
       const int ry = mvd_bits((oy + dyi - R) * 4);
 #pragma unroll
       for (int k4 = 0; k4 < 4; k4++) {
@@ -197,6 +209,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
         { const int dx = ox + dxi - R, m = (dx & 1) ? 4 : 0; if ((tx0 > 0 && x0 + dx - m < tx0) || (tx1 < f.cw && x0 + dx + 32 + m > tx1)) continue; }
         if (f.mv_frame) { const int dx = ox + dxi - R, mx = (f.mv_frame == 2 && (dx & 1)) ? 4 : 0; if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > f.cw) continue; }
         if constexpr (IR) { if (ox + dxi - R > ir_dx) continue; }     // a clean block stays out of what the reference has not cleaned
+        if constexpr (FB) { const int dx = ox + dxi - R; if (dx > fb_r || dx < -fb_r) continue; }
         const Key cand = CO ? (Key)me_fine_key(0u, rf, win, dyi * W + dxi) : ((Key)(dyi * W + dxi) | ((Key)rf << 13));
         const uint32_t rate = (lam * (uint32_t)(mvd_bits((ox + dxi - R) * 4) + ry + rbins)) >> 4;
         uint32_t sq[4];
@@ -240,7 +253,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     f.cu_mv[i * 2] = (int16_t)((cx + (int)(ci % W) - R) * 4);
     f.cu_mv[i * 2 + 1] = (int16_t)((cy + (int)(ci / W) - R) * 4);
     // intra-in-P: the inter cost of the block's 16x16 quarters -- what the search found for a quarter, or a quarter of the 32x32 block's cost
-    if constexpr (IR) {                                  // a forced quarter: past the gate whatever the search found; ir_free 0 (intra-in-p 0): no other quarter is priced
+    if constexpr (FQ) {                                  // a forced quarter: past the gate whatever the search found; ir_free 0 (intra-in-p 0): no other quarter is priced
       if (tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] =
         ((ir_forced >> tid) & 1) ? 0xffffffffu : (!f.ir_free ? 0u : (split ? (uint32_t)(red[tid] >> KS) : ((uint32_t)(red[4] >> KS) + 2) >> 2));
       if (tid == 0) {
@@ -939,6 +952,7 @@ void launch_me(const EncFrame &f, hipStream_t st)
     else hipLaunchKernelGGL((k_me<false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
   }
   else if (f.cu_ref) hipLaunchKernelGGL(k_me<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // lp-refs
+  else if (f.fb_heal) hipLaunchKernelGGL((k_me<false, false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);      // loss-feedback: a heal picture (one reference, no coarse stage)
   else if (f.ir_e) hipLaunchKernelGGL((k_me<false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // intra-refresh (one reference, no coarse stage)
   else hipLaunchKernelGGL(k_me<false>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
 }

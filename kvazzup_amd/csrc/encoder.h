@@ -85,6 +85,11 @@ struct EncoderConfig {
   int input_format = 0;       // "input-format" (extension; enum kvz_input_format): 0 = I420 pictures (the encoder of before); rgb32 / rgb32-sse41 / yuyv = PACKED pictures
                               // (encode_packed_host / _device), converted with the reference's arithmetic in the input stage -- k_input_rgb32 / k_input_yuyv (input_kernels.hip)
                               // write the working set's padded planes in k_pad_input's place, and everything behind them is as ever.  Not with input-hold, not in band mode
+  int loss_feedback = 0;      // "loss-feedback" H (extension, "uvgx loss feedback v1"; statement of record: tests/fb_model.py): 0 = off; 1 .. 64 = the encoder
+                              // keeps the motion records of its last H pictures and takes the receiver's loss reports (report_damage): the picture behind a report is a
+                              // HEAL PICTURE -- a P picture whose 16x16 quarters are intra units wherever the reported error may have travelled along the motion since,
+                              // and whose other blocks keep their vectors out of it; it carries a recovery point SEI.  Without a report no picture changes.  Not with
+                              // lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless, intra-chain=0 or intra-refresh
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -98,6 +103,7 @@ struct EncodedPicture {
   int32_t wp[3 * KVZ_MAX_LP_REFS] = {0, 64, 0, 0, 64, 0, 0, 64, 0, 0, 64, 0};   // weightp: the picture's record [reference][flag, w, o]
   int32_t sc[5] = {0, 0, 0, 0, 0};  // scenecut: the picture's record {examined, n_new, n_b, d, cut}
   int32_t ir[4] = {-1, 0, 0, 0};  // intra-refresh: position j in the cycle (-1: an IDR picture, or the option is off), the band [s_j, e_j), the cycle's length n
+  int32_t fb[4] = {0, 0, 0, 0};   // loss-feedback: {heal picture, reports folded into it, damaged cells of its map, forced quarters}
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
 };
@@ -127,6 +133,11 @@ class Encoder {
   // delta-QP map for the following pictures (kvz_picture.roi, kvazaarfilter.cpp:423-431): w x h int8 cells spread uniformly over
   // the picture, clamped to [-12, 12]; w == 0 removes it.  Needs cfg.qp_in_cu.  Statement: roi_targets() in oracle/hevc_enc.c.
   void set_roi(int w, int h, const int8_t *map);
+  // loss-feedback: the receiver lost `count` coding tree blocks (64x64, raster order of the coded picture) from `first_ctb` of the most recently coded picture
+  // with this POC; count <= 0: the whole picture.  1: accepted -- the next picture handed in is the heal picture (several reports fold into one); 2: void, an
+  // IDR picture has been coded since; 0: refused (option off, range outside the picture).  A report older than H pictures counts as "everything damaged".
+  // May be called from the thread that calls encode_*, between any two of its calls.
+  int report_damage(int32_t poc, int first_ctb, int count);
   // ---- band mode (cfg.band_rows > 0); every call is synchronous.  Per picture: band_phase1, export the halos, exchange them
   // with the neighbouring bands' encoders (rank - 1 gets `up`, rank + 1 gets `down`), import theirs, band_phase2.
   void band_report_au(long picture, uint32_t bytes);              // rate control in band mode: size of the assembled access unit of picture `picture` (every band's encoder is told; needed before picture + 3 starts)
@@ -158,6 +169,8 @@ class Encoder {
   //   "ir" (intra-refresh; host values, 4 int32: position j in the cycle, the band's s_j and e_j, the cycle's length n -- an IDR picture: -1, 0, 0, n),
   //   "scenecut" (scenecut; 5 int32: the record {examined, n_new, n_b, d, cut} of the picture last output -- a picture that was not examined: 0, 0, n_b, 0, 0),
   //   "sc_blocks" (scenecut; n_b pairs of uint32: (S, A) of every block of the picture last EXAMINED, raster order),
+  //   "fb" (loss-feedback; host values, 4 int32: {heal picture, reports folded, damaged cells, forced quarters} of the picture last output),
+  //   "fb_map" (loss-feedback; the map D' of the heal picture last submitted, one byte a cell), "fb_blk" (... its block records, two bytes per 32x32 block),
   //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
   int coded_width() const { return cw_; }
@@ -180,7 +193,8 @@ class Encoder {
   // side: the chain on stream_idr_; ahead: me-source search on the input stream; ms: the chain's stream; qp: the picture's QP (rate control's, plus the layer with
   // lp-gop); nref / dist: its references in list 0 order, dist[k] pictures back (k + 1 without lp-gop); layer: lp-gop's QP layer of a P picture, else 0
   struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; int qp = 0, layer = 0, nref = 1; int8_t dist[KVZ_MAX_LP_REFS] = {1, 2, 3, 4};
-                int ir_j = -1, ir_s = 0, ir_e = 0; };   // intra-refresh: the P picture's position in the cycle and its band (ir_e 0: none)
+                int ir_j = -1, ir_s = 0, ir_e = 0;      // intra-refresh: the P picture's position in the cycle and its band (ir_e 0: none)
+                bool fb = false; };                     // loss-feedback: a heal picture (fb_heal_ has its reports)
   bool gop_on() const { return cfg_.lp_gop && cfg_.gop_g >= 1; }
   bool sl_gop_timeline(const Plan &p) const { return gop_on() && !p.intra && Timeline::get().path; }
   Plan plan(int set);
@@ -234,6 +248,14 @@ class Encoder {
   int32_t out_gop_[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // debug_copy("lp_gop") of the picture last output
   int32_t out_ir_[4] = {-1, 0, 0, 0};               // debug_copy("ir") of the picture last output
   bool ir_free_ = true;                             // intra-refresh with intra-in-p=0: false -- the intra-in-P stages run for the band alone
+  // loss-feedback (fb_kernels.hip): the ring of the last H pictures' records (picture i in place i % H), the map and its scratch, the heal picture's block
+  // records; the reports wait in fb_q_ (under fbm_) until plan() takes them for the next P picture (fb_heal_) or an IDR picture voids them
+  struct FbReport { int32_t poc; int first, count; };
+  int16_t *fb_rec_mv_ = nullptr; uint8_t *fb_rec_info_ = nullptr, *fb_map_ = nullptr, *fb_tmp_ = nullptr, *fb_blk_ = nullptr;
+  std::mutex fbm_; std::vector<FbReport> fb_q_, fb_heal_;
+  hipEvent_t ev_fb_me_ = nullptr;                   // me-source: behind a heal picture's search on the main stream, which reads the previous input picture; the input stream waits for it
+  int32_t out_fb_[4] = {0, 0, 0, 0};                // debug_copy("fb") of the picture last output
+  bool fb_stage(const EncFrame &f, const Plan &p, Slot &sl);   // main stream, in front of a heal picture's search: seeds, steps, block records
   // weightp (wp_kernels.hip): per working set the input picture's partial sums, its moments {m, v} and the picture's record; one set of scratch (candidates, the
   // check's sums) and of search planes -- their writers and readers follow one another on one stream (the input stream; the planes without me-source: the main stream)
   unsigned long long *wp_partial_[kSets] = {}; int64_t *wp_stat_[kSets] = {}; int32_t *wp_rec_[kSets] = {};
@@ -303,6 +325,7 @@ class Encoder {
     hipEvent_t done = nullptr, rec_done = nullptr;       // tokens / substreams delivered (stream_tok_ / ent_stream) / reconstruction final (stream_)
     hipEvent_t sink_done = nullptr; bool has_sink = false; // set_recon_sink: the reconstruction's copy into the caller's picture (stream_rec_)
     int poc = 0, rec_idx = 0, set = 0, qp = 0; bool intra = false, write_ps = false; long pic_idx = 0;
+    int32_t *h_fb = nullptr, *d_fb = nullptr;            // loss-feedback: the picture's record {heal, reports, cells, forced quarters} (host-mapped: k_fb_blocks writes the counts)
     int32_t ir[4] = {-1, 0, 0, 0};                         // intra-refresh: what debug_copy("ir") says of the picture; ir[0] == 0: its access unit starts with the recovery point SEI
     int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop (nref 0: off): what the slice header's reference picture set and debug_copy("lp_gop") say
     std::vector<EvPair> ev; size_t ev_used = 0;

@@ -97,6 +97,20 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     ir_free_ = cfg.intra_in_p != 0;
     if (!cfg.intra_in_p) cfg.intra_in_p = 1;
   }
+  if (cfg.loss_feedback) {                                 // "uvgx loss feedback v1" ("refused")
+    const char *why = nullptr;
+    if (cfg.loss_feedback < 0 || cfg.loss_feedback > 64) why = "loss-feedback must be 0 .. 64";
+    else if (cfg.lp_refs >= 2) why = "loss-feedback is not available with lp-refs >= 2 (the map follows one reference)";
+    else if (cfg.lp_gop) why = "loss-feedback is not available with lp-gop";
+    else if (cfg.tmvp) why = "loss-feedback is not available with tmvp (a temporal candidate is read from a picture the decoder may have got wrong)";
+    else if (cfg.me_coarse) why = "loss-feedback is not available with me-coarse";
+    else if (cfg.tile_rows != 1 || cfg.tile_cols != 1) why = "loss-feedback is not available with tiles";
+    else if (cfg.band_rows > 0) why = "loss-feedback is not available in band mode";
+    else if (cfg.lossless) why = "loss-feedback is not available with lossless";
+    else if (!cfg.intra_chain) why = "loss-feedback is not available with intra-chain=0";
+    else if (cfg.intra_refresh) why = "loss-feedback is not available with intra-refresh (both own the forced quarters)";
+    if (why) { if (error) *error = why; return false; }
+  }
 
   const char *prio = getenv("KVAZZUP_AMD_PRIO"); if (!prio || strlen(prio) < 4) prio = "hnnn";   // main, tokenizer, input, decoder: the chain the next picture waits for is the urgent one (+6 % at 1080p; any explicit priority also gives the stream a hardware queue of its own)
 
@@ -224,6 +238,10 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
       HIP_OK(mem_.pinned(&sl.h_wp, 3 * KVZ_MAX_LP_REFS, hipHostMallocMapped, &sl.d_wp));
       for (int r = 0; r < KVZ_MAX_LP_REFS; r++) { sl.h_wp[3 * r] = 0; sl.h_wp[3 * r + 1] = 64; sl.h_wp[3 * r + 2] = 0; }
     }
+    if (cfg.loss_feedback) {
+      HIP_OK(mem_.pinned(&sl.h_fb, 4, hipHostMallocMapped, &sl.d_fb));
+      for (int i = 0; i < 4; i++) sl.h_fb[i] = 0;
+    }
     if (cfg.scenecut) {
       HIP_OK(mem_.pinned(&sl.h_sc, 5, hipHostMallocMapped, &sl.d_sc));
       for (int i = 0; i < 5; i++) sl.h_sc[i] = 0;
@@ -231,7 +249,12 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     HIP_OK(mem_.event(&sl.done, hipEventDisableTiming)); HIP_OK(mem_.event(&sl.rec_done, hipEventDisableTiming));
   }
   HIP_OK(mem_.event(&in_done_, kDeviceEvent));
-  if (cfg.intra_in_p) HIP_OK(mem_.dev(&me_cost16_, L.me_block, true));      // k_me's inter cost per 16x16 block (intra-in-P)
+  if (cfg.intra_in_p || cfg.loss_feedback) HIP_OK(mem_.dev(&me_cost16_, L.me_block, true));      // k_me's inter cost per 16x16 block (intra-in-P; loss-feedback with intra-in-p=0: the heal pictures')
+  if (cfg.loss_feedback) {                                 // (encoder.h fb_rec_mv_)
+    HIP_OK(mem_.dev(&fb_rec_mv_, (size_t)cfg.loss_feedback * L.nb8 * 2, true)); HIP_OK(mem_.dev(&fb_rec_info_, (size_t)cfg.loss_feedback * L.nb8, true));
+    HIP_OK(mem_.event(&ev_fb_me_, kDeviceEvent));
+    HIP_OK(mem_.dev(&fb_map_, L.nb8, true)); HIP_OK(mem_.dev(&fb_tmp_, L.nb8, true)); HIP_OK(mem_.dev(&fb_blk_, L.nb8 / 16 * 2, true));
+  }
   me_ahead_ = cfg.me_source != 0;
   if (me_ahead_ && cfg.intra_in_p)                         // (encoder.h me_block_: one block of these and one array of progress counters per working set)
     for (int k = 0; k < kSets; k++) { HIP_OK(mem_.dev(&me_block_[k], L.me_block, true)); HIP_OK(mem_.dev(&sync_set_[k], L.sync, true)); }
@@ -265,7 +288,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   b.row0 = cfg.band_rows > 0 ? cfg.band_row0 : 0; b.nrows = cfg.band_rows > 0 ? cfg.band_rows : 0;
   b.range = cfg.me_range; b.scaling = d_scaling_; b.intra_chain = cfg.intra_chain;
   b.lossless = cfg.lossless; b.rdoq = cfg.rdoq; b.signhide = cfg.signhide; b.intra_p = cfg.intra_in_p;
-  if (me_cost16_) point_me_block(b, L, me_cost16_);
+  if (cfg.intra_in_p) point_me_block(b, L, me_cost16_);      // (loss-feedback with intra-in-p=0: a heal picture's frame alone points at it)
   b.wpp = cfg.wpp; b.mv_frame = cfg.mv_frame; b.me_early = cfg.me_early; b.satd = cfg.satd; b.subme = cfg.subme; b.slices = cfg.slices;
   uint8_t *p = intra_scratch_;
   b.ic8 = (uint32_t *)p; b.ic16 = (uint32_t *)(p + L.ic16_off); b.ic32 = (uint32_t *)(p + L.ic32_off); b.im8 = p + L.im8_off; b.im16 = p + L.im16_off; b.im32 = p + L.im32_off;
@@ -620,6 +643,15 @@ Encoder::Plan Encoder::plan(int set)
     p.ir_s = ir_band_start(cw_, cfg_.intra_refresh, p.ir_j); p.ir_e = ir_band_end(cw_, cfg_.intra_refresh, p.ir_j);
   }
   p.ahead = me_ahead_ && !p.intra;
+  if (cfg_.loss_feedback) {
+    // loss-feedback: the reports made since the last picture was planned turn this P picture into their heal picture; an IDR picture heals everything and
+    // voids them.  Under me-source the heal picture's search waits for the picture before it on the main stream (the map comes from that picture's record)
+    // and still reads the previous input picture; no other picture changes its place
+    std::lock_guard<std::mutex> l(fbm_);
+    fb_heal_.clear();
+    if (p.intra) fb_q_.clear();
+    else if (!fb_q_.empty()) { fb_heal_.swap(fb_q_); p.fb = true; p.ahead = false; }
+  }
   // the stream this picture's chain runs on: an intra picture's own (encoder.h stream_idr_), else the main stream -- behind the last intra picture's chain
   p.side = p.intra && (idr_side_ || (all_intra_alt_ && (frame_idx_ & 1)));
   p.ms = p.side ? stream_idr_ : stream_;
@@ -645,7 +677,7 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   for (int c = 0; c < 3; c++) { f.rec[c] = cfg_.sao ? chain_.work[c] : rec_[cur_idx_][c]; f.sao_out[c] = rec_[cur_idx_][c]; f.ref[c] = rec_[ref_idx_][c]; }
   // me-source: the search looks at the previous input picture (still in its working set: the set is not padded into again before kSets - 1 more pictures have
   // gone through the input stream, behind this picture's k_me), and what the search and the intra pricing behind it write is the set's own
-  f.me_ref = p.ahead ? src_[prev_set_][0] : f.ref[0];
+  f.me_ref = me_ahead_ && !p.intra ? src_[prev_set_][0] : f.ref[0];      // (a heal picture is not ahead and searches the previous input picture all the same)
   // lp-refs: reference r is the picture p.dist[r] before this one (the plan: r + 1, or lp-gop's table) -- ring slot cur_idx_ - p.dist[r]; the search
   // looks at its reconstruction or (me-source) at its input picture, which is still in the working set it was padded into (set_ - p.dist[r]: a set is padded
   // into again kSets pictures later, behind this picture's search on the input stream)
@@ -668,6 +700,10 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
     for (int r = 0; r < KVZ_MAX_LP_REFS; r++) f.mc_qrefs[r] = mc_q_[(k + kSets - (r < nr ? p.dist[r] : 1)) % kSets];
   }
   if (p.ir_e) { f.ir_j = p.ir_j; f.ir_s = p.ir_s; f.ir_e = p.ir_e; f.ir_free = ir_free_ ? 1 : 0; }      // intra-refresh: the picture's band
+  if (p.fb) {                                          // loss-feedback: a heal picture -- its block records; intra-in-p = 0: the intra-in-P stages for the forced quarters alone
+    f.fb_heal = 1; f.fb_blk = fb_blk_; f.ir_free = cfg_.intra_in_p ? 1 : 0;
+    if (!cfg_.intra_in_p) { f.intra_p = 1; point_me_block(f, lay_, me_cost16_); }
+  }
   if (wp_rec_[k] && !p.intra) f.wp = wp_rec_[k];       // weightp: the record k_wp_decide writes on the input stream, in front of everything that reads it
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
   if (p.ahead && me_block_[k]) { point_me_block(f, lay_, me_block_[k]); f.sync = sync_set_[k]; }
@@ -778,7 +814,7 @@ bool Encoder::input_stage(const EncFrame &f, const Plan &p, const uint8_t *d_i42
     // 1080p leave the chain the next picture waits for; the head of the chain, when there is one, is a launch of its own on the main stream)
     const EncFrame fs = f.wp ? wp_search_frame(f, p, stream_in_) : f;      // weightp: the search reads the references' weighted planes
     timed(K_ME, stream_in_, [&] { launch_me(fs, stream_in_); });
-    if (cfg_.intra_in_p) timed(K_INTRA_ANALYSE_P, stream_in_, [&] { launch_intra_analyse(f, stream_in_); });
+    if (f.intra_p) timed(K_INTRA_ANALYSE_P, stream_in_, [&] { launch_intra_analyse(f, stream_in_); });
   }
   if (!stage_roi(stream_in_)) return false;
   HIP_CHECK(hipEventRecord(in_done_, stream_in_)); in_pending_ = true;
@@ -796,9 +832,13 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
   if (p.intra) {
     timed(K_INTRA_RECON, ms, [&] { launch_intra_recon(f, ms); });
   } else {
+    if (p.fb && !fb_stage(f, p, *cur_slot_)) return false;        // loss-feedback: the heal picture's map and block records, behind the chain of the picture before
     if (!p.ahead) { const EncFrame fs = f.wp ? wp_search_frame(fm, p, stream_) : fm; timed(K_ME, stream_, [&] { launch_me(fs, stream_); }); }      // (weightp: the planes are made of reconstructions here, so on this stream)
+    // loss-feedback under me-source: the one search that reads an input picture (t - 1's, in its working set) from the MAIN stream.  That set's free event was
+    // recorded behind t - 1's chain, in front of this read, so the input stream -- which pads a later picture into the set -- waits for the search itself
+    if (p.fb && me_ahead_) { HIP_CHECK(hipEventRecord(ev_fb_me_, stream_)); HIP_CHECK(hipStreamWaitEvent(stream_in_, ev_fb_me_, 0)); }
     // intra-in-P: quarters whose inter cost is high are priced as intra blocks and may become intra units (the launch leaves at once where none is)
-    if (cfg_.intra_in_p && !p.ahead) timed(K_INTRA_ANALYSE_P, stream_, [&] { launch_intra_analyse(f, stream_); });
+    if (f.intra_p && !p.ahead) timed(K_INTRA_ANALYSE_P, stream_, [&] { launch_intra_analyse(f, stream_); });
     if (cfg_.subme > 0) timed(K_SUBPEL, stream_, [&] { launch_subpel(p.ahead ? fm : f, stream_); });
     if (rc_state_) {
       // rate control v2: the CTU rows in groups inside the one launch, the next group's QP decided on the device from the levels of the groups before
@@ -809,8 +849,8 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
     } else
     timed(K_INTER_RECON, stream_, [&] { launch_inter_recon(f, stream_); });
     // ... and are reconstructed behind every inter unit (their reference samples may lie in inter units anywhere around them)
-    if (cfg_.intra_in_p) timed(K_INTRA_RECON_P, stream_, [&] { launch_intra_recon(f, stream_); });
-    if (cfg_.intra_in_p && !cfg_.deblock) { HIP_CHECK(hipMemsetAsync(f.me_cand, 0, sizeof(uint32_t), stream_)); HIP_CHECK(hipMemsetAsync(f.sync + rows_ * (cw_ / 64) * 3 + 1, 0, sizeof(uint32_t), stream_)); }      // (k_deblock_tile does it otherwise)
+    if (f.intra_p) timed(K_INTRA_RECON_P, stream_, [&] { launch_intra_recon(f, stream_); });
+    if (f.intra_p && !cfg_.deblock) { HIP_CHECK(hipMemsetAsync(f.me_cand, 0, sizeof(uint32_t), stream_)); HIP_CHECK(hipMemsetAsync(f.sync + rows_ * (cw_ / 64) * 3 + 1, 0, sizeof(uint32_t), stream_)); }      // (k_deblock_tile does it otherwise)
   }
   launch_qp_resolve(f, ms);                                      // per-CTU QP: which CU carries the delta, QpY for deblocking
   // levels, cbf and motion of the picture are final: the tokenizer's stream may start.  With SAO it waits for the filter anyway (the CTUs' SAO parameters
@@ -818,11 +858,60 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
   if (!cfg_.sao) HIP_CHECK(hipEventRecord(ev_signalled_, ms));
   if (cfg_.deblock) timed(K_DEBLOCK, ms, [&] { launch_deblock(f, ms); });
   if (cfg_.sao) timed(K_SAO, ms, [&] { launch_sao(f, ms); });      // (ONE event behind the chain's last kernel says "SAO done" and "the set is free": every record in the chain is a packet the next picture waits behind)
+  // loss-feedback: a P picture's record into its place in the ring -- vectors and intra decisions are final.  An IDR picture files none: fb_stage never steps
+  // through one (a report from in front of it is void), and its chain may run on the side stream, beside a heal picture that still reads the ring
+  if (cfg_.loss_feedback && !p.intra) {
+    FbArgs a{};
+    a.gw = cw_ / 8; a.gh = ch_ / 8; a.cu_mv = f.cu_mv; a.cu_intra = f.cu_intra; a.cu_log2 = f.cu_log2; a.clean = 0;
+    const size_t place = (size_t)(frame_idx_ % cfg_.loss_feedback);
+    a.rec_mv = fb_rec_mv_ + place * lay_.nb8 * 2; a.rec_info = fb_rec_info_ + place * lay_.nb8;
+    launch_fb_record(a, ms);
+  }
   // Last reader of this set on the main stream: k_sao reads the source picture for its statistics, deblocking the CU records.
   // Input padding and intra analysis of the next picture with this set (input stream) overwrite both and wait for this event.
   HIP_CHECK(hipEventRecord(ev_src_free_[set_], ms)); src_busy_[set_] = true;
   if (p.side) { HIP_CHECK(hipEventRecord(ev_idr_done_, ms)); idr_pending_ = true; }
   return true;
+}
+
+// loss-feedback, the main stream, in front of the heal picture's search: the map starts empty at the oldest reported picture, takes that picture's reports
+// (k_fb_seed), then goes through the record of every picture up to the one before the heal picture (k_fb_step), taking the later pictures' reports on the way;
+// a report from further back than the ring reaches makes the map full.  Then the block records.  The pictures since the last IDR picture have the POCs
+// 0 .. poc_ one after the other, so the picture with POC k lies poc_ - k pictures back.
+bool Encoder::fb_stage(const EncFrame &f, const Plan &p, Slot &sl)
+{
+  (void)p;
+  const int H = cfg_.loss_feedback, t = poc_;
+  FbArgs a{};
+  a.gw = cw_ / 8; a.gh = ch_ / 8; a.map = fb_map_; a.tmp = fb_tmp_; a.dilate = cfg_.deblock || cfg_.sao ? 1 : 0;
+  a.me_range = f.range; a.blk = fb_blk_; a.stat = sl.d_fb;
+  int oldest = t;
+  for (const FbReport &r : fb_heal_) oldest = r.poc < oldest ? r.poc : oldest;
+  if (t - oldest > H) HIP_CHECK(hipMemsetAsync(fb_map_, 1, lay_.nb8, stream_));
+  else {
+    HIP_CHECK(hipMemsetAsync(fb_map_, 0, lay_.nb8, stream_));
+    for (int k = oldest; k < t; k++) {
+      if (k > oldest) {
+        const size_t place = (size_t)((frame_idx_ - (t - k)) % H);
+        a.rec_mv = fb_rec_mv_ + place * lay_.nb8 * 2; a.rec_info = fb_rec_info_ + place * lay_.nb8;
+        launch_fb_step(a, stream_);
+      }
+      for (const FbReport &r : fb_heal_) if (r.poc == k) { a.first = r.first; a.count = r.count; launch_fb_seed(a, stream_); }
+    }
+  }
+  launch_fb_blocks(a, stream_);
+  return true;
+}
+
+int Encoder::report_damage(int32_t poc, int first_ctb, int count)
+{
+  if (!cfg_.loss_feedback || poc < 0) return 0;
+  if (count > 0 && (first_ctb < 0 || (long long)first_ctb + count > (long long)lay_.nctu)) return 0;
+  drain_submitter();                                        // (owf >= 2: everything handed in so far has been planned -- the next picture is the heal picture)
+  if (frame_idx_ == 0 || poc > poc_) return 2;              // the picture lies in front of the last IDR picture (or nothing has been coded): nothing to heal
+  std::lock_guard<std::mutex> l(fbm_);
+  fb_q_.push_back(FbReport{poc, first_ctb, count});
+  return 1;
 }
 
 // weightp, the input stream: the picture's statistics; a P picture: candidate weights against every reference's input picture (the set it was padded into, as
@@ -901,6 +990,7 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
   sink_sub_[0] = sink_sub_[1] = sink_sub_[2] = nullptr;
   sl.pic_idx = submitted_; sl.poc = poc_; sl.intra = p.intra; sl.rec_idx = cur_idx_; sl.qp = f.qp; sl.write_ps = false;
   if (sl_gop_timeline(p)) { char w[12]; snprintf(w, sizeof(w), "g%dq%02dd%d%d%d%d", p.layer, f.qp, p.nref > 0 ? p.dist[0] : 0, p.nref > 1 ? p.dist[1] : 0, p.nref > 2 ? p.dist[2] : 0, p.nref > 3 ? p.dist[3] : 0); tl(w, submitted_); }      // KVAZZUP_AMD_TIMELINE, lp-gop: a P picture's layer, QP and reference distances as a record "g<layer>q<QP>d<four distances, 0 = none>"
+  if (sl.h_fb) { sl.h_fb[0] = p.fb ? 1 : 0; sl.h_fb[1] = p.fb ? (int32_t)fb_heal_.size() : 0; if (!p.fb) { sl.h_fb[2] = 0; sl.h_fb[3] = 0; } }      // (a heal picture's counts: k_fb_blocks)
   sl.ir[0] = p.ir_j; sl.ir[1] = p.ir_s; sl.ir[2] = p.ir_e; sl.ir[3] = cfg_.intra_refresh ? ir_cycle(cw_, cfg_.intra_refresh) : 0;
   sl.layer = p.layer; sl.nref = gop_on() && !p.intra ? p.nref : 0; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) sl.dist[r] = r < sl.nref ? p.dist[r] : 0;
   if (p.intra) {
@@ -973,6 +1063,7 @@ bool Encoder::collect(EncodedPicture *out)
   memcpy(out_wp_, out->wp, sizeof(out_wp_));
   memcpy(out_ir_, out->ir, sizeof(out_ir_));
   memcpy(out_sc_, out->sc, sizeof(out_sc_));
+  memcpy(out_fb_, out->fb, sizeof(out_fb_));
   rc_bytes_[(collected_ - 1) & 7] = (uint32_t)out->au.size();   // (collected_ - 1 = index of this picture)
   return ok;
 }
@@ -1046,7 +1137,9 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
   PicRefs pr; pr.n = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
   memcpy(out->ir, sl.ir, sizeof(out->ir));
   if (sl.h_sc) memcpy(out->sc, sl.h_sc, sizeof(out->sc));      // scenecut: the record, final since the picture was submitted
-  const int recovery = cfg_.intra_refresh && !sl.intra && sl.ir[0] == 0 ? sl.ir[3] - 1 : -1;      // intra-refresh: a cycle's first picture says when the pass is complete
+  if (sl.h_fb) for (int i = 0; i < 4; i++) out->fb[i] = sl.h_fb[i];      // loss-feedback: the record, final with the picture's chain
+  int recovery = cfg_.intra_refresh && !sl.intra && sl.ir[0] == 0 ? sl.ir[3] - 1 : -1;      // intra-refresh: a cycle's first picture says when the pass is complete
+  if (sl.h_fb && sl.h_fb[0]) recovery = 0;                 // loss-feedback: the heal picture is itself the recovery point
   PicWeights pw{};                                         // weightp: the record k_wp_decide left in the slot (final long before the tokens are)
   for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
     const bool on = cfg_.weightp && !sl.intra && sl.h_wp[3 * r] != 0;
@@ -1242,6 +1335,9 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   if (w == "ir") { if (!cfg_.intra_refresh || bytes > sizeof(out_ir_)) return false; memcpy(dst, out_ir_, bytes); return true; }      // (host values)
   if (w == "wp") { if (!cfg_.weightp || bytes > sizeof(out_wp_)) return false; memcpy(dst, out_wp_, bytes); return true; }      // (host values, as the slice headers said them)
   if (w == "scenecut") { if (!cfg_.scenecut || bytes > sizeof(out_sc_)) return false; memcpy(dst, out_sc_, bytes); return true; }      // (host values, as submit() read or wrote them)
+  if (w == "fb") { if (!cfg_.loss_feedback || bytes > sizeof(out_fb_)) return false; memcpy(dst, out_fb_, bytes); return true; }      // (host values)
+  if (w == "fb_map" && fb_map_) { src = fb_map_; have = lay_.nb8; }      // (the heal picture last submitted: a synchronous copy, behind its kernels)
+  if (w == "fb_blk" && fb_blk_) { src = fb_blk_; have = lay_.nb8 / 16 * 2; }
   if (w == "sc_blocks" && sc_blocks_) { src = sc_blocks_; have = lay_.sc_blocks * sizeof(uint32_t); }      // (the picture last examined: its kernels are done, submit() waited for them)
   if (w == "cu_mv") { src = cu_mv_[out_set_]; have = lay_.cu_mv * sizeof(int16_t); }
   if (w == "cu_mvd") { src = cu_mvd_[out_set_]; have = lay_.cu_mv * sizeof(int16_t); }

@@ -146,9 +146,15 @@ struct EncFrame {
   // mc_q = the quarter picture of this picture's input (cw / 4 x ch / 4, written by k_luma_quarter), mc_qrefs[k] = that of input picture t - 1 - k;
   // mc_centres = [reference][32x32 block, raster] the centres (x, y) in full samples, written by k_me_coarse, read by k_me<.., true>
   int mc_rq;
+  // "loss-feedback" (fb_heal 0: not a heal picture, and a P picture's kernels run the forms of before): 1 -- fb_blk is the heal picture's
+  // record per 32x32 block in raster order, two bytes, the forced-quarter nibble and the reach (fb_block_record), written by k_fb_blocks in front of the
+  // picture's search.  The forced quarters are coded as intra units as intra-refresh's are (k_me<.., FB>, cost 0xffffffff to k_intra_analyse<true>; ir_free as
+  // below), the other blocks keep every vector within the reach (k_me<.., FB>, k_subpel<.., FB>).  (The flag in the four bytes that padded mc_rq, the pointer in
+  // mc_centres' place -- the encoder refuses me-coarse beside loss-feedback: the frame keeps its size and every other field its place in the kernels' argument block)
+  int fb_heal;
   uint8_t *mc_q;
   const uint8_t *mc_qrefs[KVZ_MAX_LP_REFS];
-  int16_t *mc_centres;
+  union { int16_t *mc_centres; const uint8_t *fb_blk; };
   // "weightp" (NULL: off, and a P picture's kernels run the forms of before): the picture's record [reference][flag, w, o] in device memory,
   // written by k_wp_decide on the input stream.  k_subpel and k_inter_recon predict luma from reference k as wp_pred14(.., w, o); me_ref / me_refs then point at
   // the references' search planes (k_wp_plane), which k_me reads as it reads any reference
@@ -178,6 +184,77 @@ KVZ_HD bool ir_clean_block(int x0, int s, int j) { return j >= 1 && x0 + 32 <= s
 KVZ_HD int ir_mvx_max(int x0, int s) { return 4 * (s - x0 - 32); }
 // a forced unit of size nb at xb on the band's last unit column (beyond it lies what the reference picture has not cleaned): no mode that reads above-right samples
 KVZ_HD bool ir_last_column(int xb, int nb, int e, int cw) { return xb + nb == e && e < cw; }
+
+// ---------------------------------------------------------------------------------------------
+// "uvgx loss feedback v1" (loss-feedback=H; statement of record: tests/fb_model.py).  All integer.  A CELL is an 8x8 luma block of the
+// coded picture, gw = cw / 8 by gh = ch / 8 of them in raster order; a map holds one byte a cell, non-zero where a decoder's picture may differ from the
+// encoder's reconstruction.  A picture's record holds per cell its final vector (quarter samples) and fb_info().
+// ---------------------------------------------------------------------------------------------
+#define KVZ_FB_CLEAN 0x80      // a record's info byte of an IDR picture: whatever went before, the picture is clean
+#define KVZ_FB_ZERO_ONLY 0xff  // a block record's reach byte: the zero vector only, no refinement
+KVZ_HD uint8_t fb_info(int intra, int log2) { return (uint8_t)((intra ? 1 : 0) | (log2 << 1)); }      // bit 0: an intra unit; bits 1 .. 3: log2 of the unit's size
+// is a cell of the map set inside the sample rectangle [x0, x1] x [y0, y1] (inclusive, inside the picture)
+KVZ_HD bool fb_hit(const uint8_t *map, int gw, int x0, int y0, int x1, int y1)
+{
+  for (int cy = y0 >> 3; cy <= (y1 >> 3); cy++) for (int cx = x0 >> 3; cx <= (x1 >> 3); cx++) if (map[cy * gw + cx]) return true;
+  return false;
+}
+// seed: is cell (cx, cy) in the reported coding tree blocks [first, first + count) -- 64x64 blocks in raster order; count <= 0: the whole picture
+KVZ_HD bool fb_seed_cell(int cw, int cx, int cy, int first, int count)
+{
+  if (count <= 0) return true;
+  const int ctb = (cy >> 3) * (cw >> 6) + (cx >> 3);
+  return ctb >= first && ctb < first + count;
+}
+// step, an inter cell with the vector (mx, my): does the rectangle it reads meet a cell of the previous picture's map -- the cell moved by the integer part,
+// widened by 4 samples on both sides where the component is not a multiple of 8 (the 8-tap luma filter, the 4-tap chroma filter on half a chroma sample:
+// k_me's tile margin), every coordinate clamped to the picture as the interpolation clamps it
+KVZ_HD bool fb_inter_cell(const uint8_t *prev, int cw, int ch, int cx, int cy, int mx, int my)
+{
+  const int ix = mx >> 2, iy = my >> 2, wx = (mx & 7) ? 4 : 0, wy = (my & 7) ? 4 : 0;
+  const int x0 = clip3(0, cw - 1, cx * 8 + ix - wx), x1 = clip3(0, cw - 1, cx * 8 + 7 + ix + wx);
+  const int y0 = clip3(0, ch - 1, cy * 8 + iy - wy), y1 = clip3(0, ch - 1, cy * 8 + 7 + iy + wy);
+  return fb_hit(prev, cw >> 3, x0, y0, x1, y1);
+}
+// step, a cell of an intra unit of size 1 << log2: is a cell that holds the unit's reference samples in the set s -- the row above from the above-left sample
+// to 2 nb samples along, the column to the left likewise, what lies outside the picture left out (its samples are substituted from the others)
+KVZ_HD bool fb_intra_cell(const uint8_t *s, int cw, int ch, int cx, int cy, int log2)
+{
+  const int nb = 1 << log2, x = (cx * 8) & ~(nb - 1), y = (cy * 8) & ~(nb - 1), gw = cw >> 3;
+  if (y > 0 && fb_hit(s, gw, imax(x - 1, 0), y - 1, imin(x + 2 * nb - 1, cw - 1), y - 1)) return true;
+  if (x > 0 && fb_hit(s, gw, x - 1, imax(y - 1, 0), x - 1, imin(y + 2 * nb - 1, ch - 1))) return true;
+  return false;
+}
+// a cell or one of its eight neighbours is set: what deblocking and SAO can carry an error across (DESIGN.md section 9i has the count of samples)
+KVZ_HD bool fb_dilated(const uint8_t *s, int gw, int gh, int cx, int cy)
+{
+  return fb_hit(s, gw, imax(cx - 1, 0) * 8, imax(cy - 1, 0) * 8, imin(cx + 1, gw - 1) * 8, imin(cy + 1, gh - 1) * 8);
+}
+// heal picture: the record of the 32x32 block (bx, by) against the map d -- out[0]: bit k set where the 16x16 quarter k (raster of 2 x 2) holds a cell of d and
+// is forced intra; out[1]: the reach of the block's vectors in full samples, the least over its free quarters of min(me_range, dist - 4), where dist is the
+// Chebyshev distance in samples from the quarter to the nearest cell of d (a multiple of 8) -- KVZ_FB_ZERO_ONLY where a free quarter touches a cell of d
+// (dist 0) or the block has no free quarter
+KVZ_HD void fb_block_record(const uint8_t *d, int gw, int gh, int bx, int by, int me_range, uint8_t *out)
+{
+  const int K = (me_range + 4 + 7) / 8 + 1;                 // cells around a quarter that can matter: dist <= me_range + 4
+  int forced = 0, reach = me_range; bool zero = false;
+  for (int k = 0; k < 4; k++) {
+    const int c0 = bx * 4 + (k & 1) * 2, r0 = by * 4 + (k >> 1) * 2;
+    int best = K + 1;                                        // least Chebyshev distance in cells (0: inside the quarter)
+    for (int cy = imax(r0 - K, 0); cy <= imin(r0 + 1 + K, gh - 1); cy++) for (int cx = imax(c0 - K, 0); cx <= imin(c0 + 1 + K, gw - 1); cx++) {
+      if (!d[cy * gw + cx]) continue;
+      const int dx = imax(imax(c0 - cx, cx - (c0 + 1)), 0), dy = imax(imax(r0 - cy, cy - (r0 + 1)), 0);
+      best = imin(best, imax(dx, dy));
+    }
+    if (best == 0) forced |= 1 << k;
+    else if (best == 1) zero = true;
+    else if (best <= K) reach = imin(reach, 8 * (best - 1) - 4);
+  }
+  out[0] = (uint8_t)forced;
+  out[1] = (uint8_t)(zero || forced == 15 ? KVZ_FB_ZERO_ONLY : reach);
+}
+// the reach byte as a bound: |dx|, |dy| <= fb_reach() in full samples, 4 times that in quarter samples
+KVZ_HD int fb_reach(uint8_t code) { return code == KVZ_FB_ZERO_ONLY ? 0 : (int)code; }
 
 // ---------------------------------------------------------------------------------------------
 // "uvgx weighted prediction v1" (weightp; restated in tests/wp_model.py).  All integer.

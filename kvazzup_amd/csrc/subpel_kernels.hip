@@ -159,7 +159,9 @@ __device__ __forceinline__ bool allowed(const EncFrame &f, int x0, int y0, int n
 // launches without the option run the code of before.
 // IR (intra-refresh): in a clean block -- left of the picture's band, position >= 1 -- a candidate whose horizontal component lies beyond
 // ir_mvx_max is dropped, next to the mv_frame test; the centre is k_me's vector, which kept the bound.  Forms of their own as well.
-template <bool WP, bool IR = false>
+// FB (loss-feedback): in a heal picture a candidate with a component beyond four times the block's reach (f.fb_blk, quarter samples) is
+// dropped; the centre is k_me<.., FB>'s vector, which kept the reach in full samples.  Forms of their own as well.
+template <bool WP, bool IR = false, bool FB = false>
 __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
 {
   __shared__ SubpelLds s;
@@ -195,6 +197,8 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
   }
   int ir_max = 0x7fffffff;
   if constexpr (IR) { if (ir_clean_block(x0, f.ir_s, f.ir_j)) ir_max = ir_mvx_max(x0, f.ir_s); }
+  int fb_q = 0x7fffffff;
+  if constexpr (FB) fb_q = 4 * fb_reach(f.fb_blk[2 * ((size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5)) + 1]);
   uint8_t *win = s.win[w];
   {
     // the 24 x 24 window (both waves of the quadrant load half of it): six dwords per row when it lies inside the picture (any
@@ -261,7 +265,7 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
     if (lane <= ncand && ncand) {
       const int k = lane - 1, mx = k < 0 ? cx : cx + offx[k & 7] * scale, my = k < 0 ? cy : cy + offy[k & 7] * scale;
       if (k < 0) key = step == 0 ? (unit_satd(0) + ((lam * (uint32_t)(mvd_bits_fast(cx) + mvd_bits_fast(cy))) >> 4)) << 4 : best;
-      else if ((!IR || mx <= ir_max) && allowed(f, ux, uy, un, mx, my, ty0, ty1, tx0, tx1)) key = ((unit_satd(lane) + ((lam * (uint32_t)(mvd_bits_fast(mx) + mvd_bits_fast(my))) >> 4)) << 4) | (uint32_t)lane;
+      else if ((!IR || mx <= ir_max) && (!FB || (mx <= fb_q && mx >= -fb_q && my <= fb_q && my >= -fb_q)) && allowed(f, ux, uy, un, mx, my, ty0, ty1, tx0, tx1)) key = ((unit_satd(lane) + ((lam * (uint32_t)(mvd_bits_fast(mx) + mvd_bits_fast(my))) >> 4)) << 4) | (uint32_t)lane;
     }
     // minimum over lanes 0 .. 8 (two rows of the DPP network: lanes 0-7 by quad / half-row steps, lane 8 read directly)
     uint32_t m = key;
@@ -282,7 +286,11 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
 
 void launch_subpel(const EncFrame &f, hipStream_t st)
 {
-  if (f.ir_e) {
+  if (f.fb_heal) {                                           // loss-feedback: a heal picture
+    if (f.wp) hipLaunchKernelGGL((k_subpel<true, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
+    else hipLaunchKernelGGL((k_subpel<false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
+  }
+  else if (f.ir_e) {
     if (f.wp) hipLaunchKernelGGL((k_subpel<true, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
     else hipLaunchKernelGGL((k_subpel<false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
   }

@@ -137,6 +137,7 @@ typedef struct kvz_config {
   int32_t scenecut;           /* "scenecut" 0 / 1..255 (extension, "uvgx scene cut v1"; restated in tests/scenecut_model.py): N = the least distance in pictures between an IDR picture and a scene-cut IDR picture behind it.  An input picture at least N pictures behind the last IDR picture (and not an IDR picture by "period" anyway) is compared with the previous INPUT picture on their quarter-resolution pictures: the previous one is shifted by the difference of the two means, every visible 8x8 block (32x32 samples) looks for its best match within +-max(8, me-coarse / 4) quarter samples, and a block whose best SAD exceeds its own activity (sum |c - mean|) by more than 128 is new; when more than half of the blocks are new the picture is coded as an IDR picture (POC 0, parameter sets as "vps-period" says) and "period" counts from it -- slide changes, window and camera switches.  Brightness steps, fades and pans within reach are not cuts.  encoder_encode of an examined picture waits for that verdict on the GPU before the picture is planned (DESIGN.md section 9g has the cost); pictures that are not examined wait for nothing.  0 (default, also at every preset): the streams of before byte for byte.  uvgComm users pass it as a custom parameter, e.g. "scenecut=8".  encoder_open fails with it in band mode */
   int32_t input_format;       /* "input-format" i420 / rgb32 / rgb32-sse41 / yuyv (extension; enum kvz_input_format): what the pictures handed to the encoder are.  i420 (default, also at every preset): planar pictures as ever, the encoder of before byte for byte.  Otherwise the encoder takes PACKED pictures through kvzx_encoder_encode_packed_host / _device (kvazzup_amd.h) -- rgb32: width * height * 4 bytes, rows top to bottom, converted with the arithmetic of uvgComm's rgb_to_yuv420_i_c; rgb32-sse41: the same bytes with the arithmetic of rgb_to_yuv420_i_sse41, which turns the picture upside down; yuyv: width * height * 2 bytes Y0 U Y1 V, converted as yuyv_to_yuv420_c does -- and converts them in its input stage on the GPU, in the pass that pads the picture: the stream and the reconstructions are those of an i420 encoder fed the converted pictures, byte for byte.  The format is fixed per encoder; encoder_encode (a kvz_picture carries planes) and the I420 entry points return 0 on such an encoder.  encoder_open fails with it beside input-hold and in band mode, and for rgb32 / rgb32-sse41 when the width is no multiple of 4 */
   int32_t loss_feedback;      /* "loss-feedback" 0 / 1..64 (extension, "uvgx loss feedback v1"; statement of record: tests/fb_model.py): H = how many coded pictures back a loss report may reach -- the encoder keeps that many pictures' motion records on the device.  The application hands the receiver's reports (kvzx_decoder_damage_log's triples) to kvzx_encoder_report_damage (kvazzup_amd.h); the next picture is then a HEAL PICTURE: a P picture that codes as intra units the 16x16 quarters the reported error may have reached along the encoder's own motion since, keeps every other block's vectors out of them, and carries a recovery point SEI (recovery_poc_cnt 0, exact_match_flag 1).  From it on a decoder that handled the loss in any way has the encoder's pictures exactly -- no IDR picture, no parameter sets.  With "intra-in-p=0" the forced quarters are the only intra units.  Without a report no picture changes; 0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with it beside lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless, intra-chain=0 and intra-refresh */
+  int32_t fb_anchor;          /* "fb-anchor" 0 / 2..7 (extension, "uvgx loss feedback v2"; statement of record: tests/fb_anchor_model.py): K = how many pictures the encoder and every decoder keep behind the current one.  Beside "loss-feedback" = H >= K.  Every P picture's slice header then lists the K pictures before it (used_by_curr_pic_s0_flag 1 for the previous picture alone), the parameter sets say a picture buffer of K + 1, and the slice data of a picture without a report is that of fb-anchor = 0 bit for bit.  A heal picture whose oldest report names picture n0 is a V2 HEAL PICTURE when the ANCHOR a = n0 - 1 -- the last picture the receiver holds whole -- lies at most K pictures back and not in front of the last IDR or heal picture: it has two references, the previous picture and the anchor; the quarters the error may have reached are searched in the anchor and coded as inter units, where v1 codes them as intra units, so the heal picture is a P picture of roughly ordinary size (reference invalidation).  A report that comes later than that gets v1's heal picture.  kvz_frame_info.ref_list of a v2 heal picture names {t - 1, a}.  0 (default, also at every preset): the streams of before byte for byte.  encoder_open fails with 1, with K > 7, K > H, without loss-feedback, with weightp, where K + 1 exceeds MaxDpbSize of the coded size (1920x1088 and 3840x2176: K <= 5), and with whatever loss-feedback refuses */
 } kvz_config;
 
 /* Picture.  y/u/v are planar 8-bit with stride == width (chroma width/2), as uvgComm assumes

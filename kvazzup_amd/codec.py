@@ -184,6 +184,9 @@ class Encoder:
             d["fb"] = dict(zip(("heal", "reports", "cells", "forced"), (int(v) for v in self.debug("fb", np.int32, (4,)))))
             d["fb_map"] = self.debug("fb_map", np.uint8, b8)
             d["fb_blk"] = self.debug("fb_blk", np.uint8, (ch // 32, cw // 32, 2))
+        # fb-anchor: the delivered picture's record -- a key of its own only with the option on ("cu_ref" above: a v2 heal picture's references, zero in every other picture)
+        if int(self.cfg.contents.fb_anchor):
+            d["fb_anchor"] = dict(zip(("v2", "anchor", "da", "ref1_quarters"), (int(v) for v in self.debug("fb_anchor", np.int32, (4,)))))
         # scenecut: the delivered picture's record, and (S, A) of every block of the picture last examined -- keys of their own only with the option on
         if int(self.cfg.contents.scenecut):
             d["scenecut"] = dict(zip(("examined", "n_new", "n_b", "d", "cut"), (int(v) for v in self.debug("scenecut", np.int32, (5,)))))

@@ -63,10 +63,17 @@ struct FbArgs {
   int first, count, dilate;                          // k_fb_seed: the reported coding tree blocks; dilate: deblocking or SAO is on
   int me_range; uint8_t *blk; int32_t *stat;         // k_fb_blocks: the block records [32x32 block][2] and the slot's host-mapped record {heal, reports, cells, forced quarters}
 };
+// "fb-anchor" (DESIGN.md section 9j): what the kernels of a v2 heal picture's record take on top -- an argument block of their own, so that the kernels of before
+// keep theirs.  cu_ref: k_fb_record_ref files the cell's reference index into the info byte (KVZ_FB_REF1), k_fb_refs counts; anchor_bad: k_fb_step_ref -- the
+// record's reference-1 cells are in S (the report reaches that picture's anchor) or never are
+struct FbRefArgs : FbArgs { const uint8_t *cu_ref; int anchor_bad; };
 void launch_fb_record(const FbArgs &a, hipStream_t st);   // every P picture with the option on, behind its chain
 void launch_fb_seed(const FbArgs &a, hipStream_t st);     // a heal picture: one report into the map
 void launch_fb_step(const FbArgs &a, hipStream_t st);     // ... the map through one picture's record
 void launch_fb_blocks(const FbArgs &a, hipStream_t st);   // ... the block records and the counts
+void launch_fb_record_ref(const FbRefArgs &a, hipStream_t st);   // fb-anchor, a v2 heal picture: its record with the reference bit
+void launch_fb_step_ref(const FbRefArgs &a, hipStream_t st);     // ... a later heal picture: the map through that record
+void launch_fb_refs(const FbRefArgs &a, hipStream_t st);         // ... behind its decisions: the quarters coded from reference 1 into stat[7]
 // k_cabac_rows (cabac_kernels.hip): the arithmetic coder proper on the GPU, one wave per substream
 struct CabacRowsArgs {
   const uint16_t *tok; const int32_t *count; const uint32_t *off;   // dense tokens (device): CTU i has count[i] tokens at tok + off[i]

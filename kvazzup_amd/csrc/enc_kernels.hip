@@ -54,10 +54,16 @@ namespace kvzx {
 // FB (loss-feedback; one reference, no coarse stage): a heal picture's block reads its record (f.fb_blk, fb_block_record) where the IR form
 // computes the band -- the forced quarters take the IR form's path, and every candidate beyond the record's reach in x or y is dropped (the zero vector never is).
 // A form of its own as well.
+// MR and FB together (fb-anchor, "uvgx loss feedback v2"; two references, 0 = the previous picture, 1 = the anchor): a v2 heal picture.  A
+// quarter whose bit of the record's nibble is set is searched in reference 1 alone, over the whole window; a free quarter in reference 0 alone, within the
+// record's reach.  The 32x32 key is admissible in reference 0 where the nibble is 0 and in reference 1 where it is 15; a mixed block is coded as its four
+// quarters.  Early termination: nibble 0 as the FB form, nibble 15 against the anchor's co-located block (reference 1, zero vector), mixed none.  No quarter is
+// sent to the intra path: the ordinary gate prices what the search found.  A form of its own as well.
 template <bool MR, bool CO = false, bool IR = false, bool FB = false>
 __global__ __launch_bounds__(256) void k_me(EncFrame f)
 {
-  constexpr bool FQ = IR || FB;                                        // the block may have forced quarters
+  constexpr bool FA = MR && FB;                                        // a v2 heal picture: forced quarters go to the anchor
+  constexpr bool FQ = IR || (FB && !FA);                               // the block may have quarters forced intra
   using Key = typename std::conditional<MR || CO, unsigned long long, uint32_t>::type;
   constexpr int KS = CO ? 17 : (MR ? 16 : 13);                         // cost field's shift
   constexpr Key KMAX = ~(Key)0;
@@ -83,7 +89,9 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
   if constexpr (FB) {
     const uint8_t *r = f.fb_blk + 2 * ((size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5));
     ir_forced = r[0]; fb_r = fb_reach(r[1]);
+    if constexpr (FA) { if (ir_forced == 15) ref = f.me_refs[1]; }     // (early termination looks at the anchor's co-located block)
   }
+  const int it0 = FA && ir_forced == 15 ? 1 : 0, it1 = FA && ir_forced == 0 ? 1 : 2;      // FA: the references the block's quarters are searched in
   if constexpr (FQ) {
     if (ir_forced == 15) {                                             // (the same for every thread, in front of the first barrier)
       if (tid < 16) {
@@ -108,12 +116,12 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     if (f.me_early) { s0 = wave_sum_u32(s0); if ((tid & 63) == 0) atomicAdd(&red[0], (Key)s0); }
   }
   __syncthreads();
-  if (f.me_early && !(FQ && ir_forced) && red[0] <= 64u * lam) {
+  if (f.me_early && !(FQ && ir_forced) && !(FA && ir_forced != 0 && ir_forced != 15) && red[0] <= 64u * lam) {
     if (tid < 16) {
       const int i = b8idx(f, x0 + (tid & 3) * 8, y0 + (tid >> 2) * 8);
       f.cu_log2[i] = 5; f.cu_intra[i] = 0; f.cu_mv[i * 2] = 0; f.cu_mv[i * 2 + 1] = 0;
       f.cu_mvp_idx[i] = 0;                               // mark for k_subpel: not searched (k_inter_signal writes the real value later)
-      if (MR) f.cu_ref[i] = 0;                           // (the co-located block of reference 0)
+      if (MR) f.cu_ref[i] = FA && ir_forced == 15 ? 1 : 0;      // (the co-located block of reference 0; FA, every quarter forced: of the anchor)
     }
     if (f.intra_p && tid < 4) f.me_cost16[((y0 >> 4) + (tid >> 1)) * (f.cw >> 4) + (x0 >> 4) + (tid & 1)] = 0;      // never an intra candidate
     return;
@@ -121,7 +129,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
   Key best[5] = {KMAX, KMAX, KMAX, KMAX, KMAX};
   const int nr = MR ? f.nref : 1;
 #pragma unroll 1
-  for (int it = 0; it < (CO ? 2 * nr : nr); it++) {                    // (MR: one reference after the other through the same LDS window; CO: each reference's two windows)
+  for (int it = FA ? it0 : 0; it < (FA ? it1 : (CO ? 2 * nr : nr)); it++) {                    // (MR: one reference after the other through the same LDS window; CO: each reference's two windows)
   const int rf = CO ? it >> 1 : it, win = CO ? it & 1 : 0;
   int ox = 0, oy = 0;                                                  // the window's centre (CO, second window: k_me_coarse's)
   if constexpr (CO) {
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     }
     *(uint32_t *)&wbuf[wy * ME_WPITCH + wx] = v;
   }
-  if (it == 0 && tid < 5) red[tid] = KMAX;
+  if (it == (FA ? it0 : 0) && tid < 5) red[tid] = KMAX;
   __syncthreads();
   const uint32_t rbins = MR ? (uint32_t)ref_bins(rf, nr) : 0u;
   // tile constraint (statement: me_block32() in oracle/hevc_enc.c): the displaced 32x32 block, plus 4 rows each side for
@@ -200,7 +208,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
       if (dyi >= W) continue;
       { const int dy = oy + dyi - R, m = (dy & 1) ? 4 : 0; if ((ty0 > 0 && y0 + dy - m < ty0) || (ty1 < f.ch && y0 + dy + 32 + m > ty1)) continue; }
       if (f.mv_frame) { const int dy = oy + dyi - R, my = (f.mv_frame == 2 && (dy & 1)) ? 4 : 0; if (y0 + dy - my < 0 || y0 + dy + 32 + my > f.ch) continue; }
-      if constexpr (FB) { const int dy = oy + dyi - R; if (dy > fb_r || dy < -fb_r) continue; }      // within the record's reach
+      if constexpr (FB) { const int dy = oy + dyi - R; if ((!FA || rf == 0) && (dy > fb_r || dy < -fb_r)) continue; }      // within the record's reach (FA: reference 0)
       const int ry = mvd_bits((oy + dyi - R) * 4);
 #pragma unroll
       for (int k4 = 0; k4 < 4; k4++) {
@@ -209,15 +217,15 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
         { const int dx = ox + dxi - R, m = (dx & 1) ? 4 : 0; if ((tx0 > 0 && x0 + dx - m < tx0) || (tx1 < f.cw && x0 + dx + 32 + m > tx1)) continue; }
         if (f.mv_frame) { const int dx = ox + dxi - R, mx = (f.mv_frame == 2 && (dx & 1)) ? 4 : 0; if (x0 + dx - mx < 0 || x0 + dx + 32 + mx > f.cw) continue; }
         if constexpr (IR) { if (ox + dxi - R > ir_dx) continue; }     // a clean block stays out of what the reference has not cleaned
-        if constexpr (FB) { const int dx = ox + dxi - R; if (dx > fb_r || dx < -fb_r) continue; }
+        if constexpr (FB) { const int dx = ox + dxi - R; if ((!FA || rf == 0) && (dx > fb_r || dx < -fb_r)) continue; }
         const Key cand = CO ? (Key)me_fine_key(0u, rf, win, dyi * W + dxi) : ((Key)(dyi * W + dxi) | ((Key)rf << 13));
         const uint32_t rate = (lam * (uint32_t)(mvd_bits((ox + dxi - R) * 4) + ry + rbins)) >> 4;
         uint32_t sq[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) sq[k] = (uint32_t)(acc[e][k] >> (16 * k4)) & 0xffffu;
 #pragma unroll
-        for (int k = 0; k < 4; k++) best[k] = min(best[k], ((Key)(sq[k] + rate) << KS) | cand);
-        best[4] = min(best[4], ((Key)(sq[0] + sq[1] + sq[2] + sq[3] + rate) << KS) | cand);
+        for (int k = 0; k < 4; k++) { if (FA && ((ir_forced >> k) & 1) != rf) continue; best[k] = min(best[k], ((Key)(sq[k] + rate) << KS) | cand); }      // (FA: a quarter has one reference)
+        best[4] = min(best[4], ((Key)(sq[0] + sq[1] + sq[2] + sq[3] + rate) << KS) | cand);      // (FA: one reference is searched where the nibble is 0 or 15; a mixed block never reads it)
       }
     }
   }
@@ -234,6 +242,7 @@ __global__ __launch_bounds__(256) void k_me(EncFrame f)
     uint32_t pen = (lam * SPLIT_BITS) >> 4;
     uint32_t csplit = pen + (uint32_t)(red[0] >> KS) + (uint32_t)(red[1] >> KS) + (uint32_t)(red[2] >> KS) + (uint32_t)(red[3] >> KS);
     bool split = csplit < (uint32_t)(red[4] >> KS);
+    if constexpr (FA) split = split || (ir_forced != 0 && ir_forced != 15);
     int bx = tid & 3, by = tid >> 2;                     // 8x8 block inside the 32x32 block
     int k = (by >> 1) * 2 + (bx >> 1);
     uint32_t ci = (uint32_t)(split ? red[k] : red[4]) & 0x1fff;
@@ -951,6 +960,7 @@ void launch_me(const EncFrame &f, hipStream_t st)
     if (f.cu_ref) hipLaunchKernelGGL((k_me<true, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
     else hipLaunchKernelGGL((k_me<false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);
   }
+  else if (f.cu_ref && f.fb_heal) hipLaunchKernelGGL((k_me<true, false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);      // fb-anchor: a v2 heal picture (references: the previous picture and the anchor)
   else if (f.cu_ref) hipLaunchKernelGGL(k_me<true>, dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // lp-refs
   else if (f.fb_heal) hipLaunchKernelGGL((k_me<false, false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);      // loss-feedback: a heal picture (one reference, no coarse stage)
   else if (f.ir_e) hipLaunchKernelGGL((k_me<false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(threads), 0, st, f);     // intra-refresh (one reference, no coarse stage)

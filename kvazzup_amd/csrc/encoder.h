@@ -90,6 +90,12 @@ struct EncoderConfig {
                               // HEAL PICTURE -- a P picture whose 16x16 quarters are intra units wherever the reported error may have travelled along the motion since,
                               // and whose other blocks keep their vectors out of it; it carries a recovery point SEI.  Without a report no picture changes.  Not with
                               // lp-refs >= 2, lp-gop, tmvp, me-coarse, tiles, band mode, lossless, intra-chain=0 or intra-refresh
+  int fb_anchor = 0;          // "fb-anchor" K (extension, "uvgx loss feedback v2"; statement of record: tests/fb_anchor_model.py): 0 = off; 2 .. 7 beside
+                              // loss-feedback = H >= K: every P picture's slice header lists the K pictures before it, so that every decoder keeps them, and the ring of
+                              // reconstructions keeps them too; a heal picture whose oldest report names picture n0 is then a V2 HEAL PICTURE when the anchor a = n0 - 1
+                              // is at most K pictures back and not in front of the last IDR or heal picture: two references, the previous picture and the anchor, the
+                              // quarters the error may have reached predicted from the anchor where v1 codes them as intra units.  Otherwise the heal picture is v1's.
+                              // Not with weightp, K + 1 > MaxDpbSize of the coded size, and whatever loss-feedback refuses
   int owf = 0;                // kvazaar "owf": 0 = encode() returns its own picture; 1 = output lags one picture and the host
                               // coding of picture t overlaps the kernels of t + 1; >= 2 = output lags two pictures and the host
                               // coding runs on a background thread, so the calling thread only launches kernels
@@ -104,6 +110,7 @@ struct EncodedPicture {
   int32_t sc[5] = {0, 0, 0, 0, 0};  // scenecut: the picture's record {examined, n_new, n_b, d, cut}
   int32_t ir[4] = {-1, 0, 0, 0};  // intra-refresh: position j in the cycle (-1: an IDR picture, or the option is off), the band [s_j, e_j), the cycle's length n
   int32_t fb[4] = {0, 0, 0, 0};   // loss-feedback: {heal picture, reports folded into it, damaged cells of its map, forced quarters}
+  int32_t fba[4] = {0, 0, 0, 0};  // fb-anchor: {v2 heal picture, the anchor's POC, its distance da, quarters coded from reference 1}
   uint64_t bins = 0;
   bool recon_delivered = false;   // the reconstruction has been copied into the planes given to set_recon_sink
 };
@@ -170,6 +177,7 @@ class Encoder {
   //   "scenecut" (scenecut; 5 int32: the record {examined, n_new, n_b, d, cut} of the picture last output -- a picture that was not examined: 0, 0, n_b, 0, 0),
   //   "sc_blocks" (scenecut; n_b pairs of uint32: (S, A) of every block of the picture last EXAMINED, raster order),
   //   "fb" (loss-feedback; host values, 4 int32: {heal picture, reports folded, damaged cells, forced quarters} of the picture last output),
+  //   "fb_anchor" (fb-anchor; host values, 4 int32: {v2 heal picture, the anchor's POC, its distance da, quarters coded from reference 1} of the picture last output),
   //   "fb_map" (loss-feedback; the map D' of the heal picture last submitted, one byte a cell), "fb_blk" (... its block records, two bytes per 32x32 block),
   //   "cu_mv" (b8 * 2 int16), "coef0..2" (int16 planes), "rec0..2" (coded planes), "src0..2", "col" (tmvp, a P picture: its collocated record, ColMv per 16x16), "me_coarse" (me-coarse, a P picture: the centres, int16 pairs [reference][32x32 block])
   bool debug_copy(const char *what, void *dst, size_t bytes);
@@ -194,7 +202,8 @@ class Encoder {
   // lp-gop); nref / dist: its references in list 0 order, dist[k] pictures back (k + 1 without lp-gop); layer: lp-gop's QP layer of a P picture, else 0
   struct Plan { bool intra = false, side = false, ahead = false; hipStream_t ms = nullptr; int qp = 0, layer = 0, nref = 1; int8_t dist[KVZ_MAX_LP_REFS] = {1, 2, 3, 4};
                 int ir_j = -1, ir_s = 0, ir_e = 0;      // intra-refresh: the P picture's position in the cycle and its band (ir_e 0: none)
-                bool fb = false; };                     // loss-feedback: a heal picture (fb_heal_ has its reports)
+                bool fb = false;                        // loss-feedback: a heal picture (fb_heal_ has its reports)
+                int fb_da = 0; };                       // fb-anchor: a v2 heal picture -- its anchor lies fb_da pictures back and is reference 1 (0: not one)
   bool gop_on() const { return cfg_.lp_gop && cfg_.gop_g >= 1; }
   bool sl_gop_timeline(const Plan &p) const { return gop_on() && !p.intra && Timeline::get().path; }
   Plan plan(int set);
@@ -255,6 +264,10 @@ class Encoder {
   std::mutex fbm_; std::vector<FbReport> fb_q_, fb_heal_;
   hipEvent_t ev_fb_me_ = nullptr;                   // me-source: behind a heal picture's search on the main stream, which reads the previous input picture; the input stream waits for it
   int32_t out_fb_[4] = {0, 0, 0, 0};                // debug_copy("fb") of the picture last output
+  // fb-anchor: the clean point c -- the POC of the most recent IDR or heal picture --, and per place of the ring the anchor's POC of the v2 heal picture filed
+  // there (-1: the record holds no reference-1 cell)
+  int fb_clean_ = 0; std::vector<int> fb_rec_anchor_;
+  int32_t out_fba_[4] = {0, 0, 0, 0};               // debug_copy("fb_anchor") of the picture last output
   bool fb_stage(const EncFrame &f, const Plan &p, Slot &sl);   // main stream, in front of a heal picture's search: seeds, steps, block records
   // weightp (wp_kernels.hip): per working set the input picture's partial sums, its moments {m, v} and the picture's record; one set of scratch (candidates, the
   // check's sums) and of search planes -- their writers and readers follow one another on one stream (the input stream; the planes without me-source: the main stream)
@@ -325,7 +338,8 @@ class Encoder {
     hipEvent_t done = nullptr, rec_done = nullptr;       // tokens / substreams delivered (stream_tok_ / ent_stream) / reconstruction final (stream_)
     hipEvent_t sink_done = nullptr; bool has_sink = false; // set_recon_sink: the reconstruction's copy into the caller's picture (stream_rec_)
     int poc = 0, rec_idx = 0, set = 0, qp = 0; bool intra = false, write_ps = false; long pic_idx = 0;
-    int32_t *h_fb = nullptr, *d_fb = nullptr;            // loss-feedback: the picture's record {heal, reports, cells, forced quarters} (host-mapped: k_fb_blocks writes the counts)
+    int32_t *h_fb = nullptr, *d_fb = nullptr;            // loss-feedback: the picture's record {heal, reports, cells, forced quarters} (host-mapped: k_fb_blocks writes the counts); fb-anchor: four more words, {v2 heal, anchor POC, da, quarters from reference 1} (k_fb_refs writes the count)
+    int kept = 0;                                        // fb-anchor: entries of the P picture's reference picture set (nref of them used)
     int32_t ir[4] = {-1, 0, 0, 0};                         // intra-refresh: what debug_copy("ir") says of the picture; ir[0] == 0: its access unit starts with the recovery point SEI
     int layer = 0, nref = 0; int8_t dist[KVZ_MAX_LP_REFS] = {0, 0, 0, 0};   // lp-gop (nref 0: off): what the slice header's reference picture set and debug_copy("lp_gop") say
     std::vector<EvPair> ev; size_t ev_used = 0;

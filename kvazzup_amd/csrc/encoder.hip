@@ -109,6 +109,16 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
     else if (cfg.lossless) why = "loss-feedback is not available with lossless";
     else if (!cfg.intra_chain) why = "loss-feedback is not available with intra-chain=0";
     else if (cfg.intra_refresh) why = "loss-feedback is not available with intra-refresh (both own the forced quarters)";
+    if (why) { if (error) { *error = why; if (cfg.fb_anchor) *error += "; fb-anchor rests on loss-feedback"; } return false; }
+  }
+  if (cfg.fb_anchor) {                                     // "uvgx loss feedback v2" ("refused"; what loss-feedback refuses is refused above)
+    const char *why = nullptr;
+    const EncLayout sz(cfg.width, cfg.height, 0);
+    if (cfg.fb_anchor < 2 || cfg.fb_anchor > kMaxRefDist) why = "fb-anchor must be 0 or 2 .. 7";
+    else if (!cfg.loss_feedback) why = "fb-anchor needs loss-feedback (the anchor answers a loss report)";
+    else if (cfg.fb_anchor > cfg.loss_feedback) why = "fb-anchor must not exceed loss-feedback (a report the anchor answers lies within the ring of records)";
+    else if (cfg.fb_anchor + 1 > fb_anchor_max_dpb(sz.cw, sz.ch)) why = "fb-anchor: the kept pictures and the current one exceed MaxDpbSize of the coded size at its level (1920x1088, 3840x2176: at most 5)";
+    else if (cfg.weightp) why = "fb-anchor is not available with weightp";
     if (why) { if (error) *error = why; return false; }
   }
 
@@ -152,7 +162,8 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   // overwritten (the oldest, t - depth_, reads t - depth_ - lp_refs); + 1 (at least): an intra picture is written ahead of its turn, beside the P pictures
   // in front of it, which still read theirs
   // (lp-gop with several references: a key picture stays a reference for up to kMaxRefDist pictures)
-  const int keep = cfg.lp_gop && cfg.gop_g > 1 && cfg.lp_refs > 1 ? kMaxRefDist : cfg.lp_refs;
+  // (fb-anchor K: the K pictures behind the current one stay, as every decoder keeps them)
+  const int keep = cfg.fb_anchor ? cfg.fb_anchor : (cfg.lp_gop && cfg.gop_g > 1 && cfg.lp_refs > 1 ? kMaxRefDist : cfg.lp_refs);
   nrec_ = depth_ + 1 + keep < 2 + keep ? 2 + keep : depth_ + 1 + keep;
   prio_[0] = prio[0]; prio_[1] = prio[1]; prio_[2] = prio[2];
   HIP_OK(stream_acquire(&stream_, cfg.device, 'M', prio_[0]));
@@ -164,7 +175,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   for (int k = 0; k < kSets; k++) {
     HIP_OK(mem_.dev(&cu_bytes_[k], L.cu_bytes, true));
     HIP_OK(mem_.dev(&cu_mv_[k], L.cu_mv, true)); HIP_OK(mem_.dev(&cu_mvd_[k], L.cu_mv, true));
-    if (cfg.lp_refs > 1) HIP_OK(mem_.dev(&cu_ref_[k], L.nb8, true));
+    if (cfg.lp_refs > 1 || cfg.fb_anchor) HIP_OK(mem_.dev(&cu_ref_[k], L.nb8, true));      // (fb-anchor: a v2 heal picture's frame alone points at it)
     if (cfg.tmvp) HIP_OK(mem_.dev(&col_[k], L.col, true));
     if (cfg.me_coarse || cfg.scenecut) HIP_OK(mem_.dev(&mc_q_[k], L.mc_q, true));
     if (cfg.scenecut) HIP_OK(mem_.dev(&sc_sum_[k], 1, true));
@@ -239,8 +250,9 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
       for (int r = 0; r < KVZ_MAX_LP_REFS; r++) { sl.h_wp[3 * r] = 0; sl.h_wp[3 * r + 1] = 64; sl.h_wp[3 * r + 2] = 0; }
     }
     if (cfg.loss_feedback) {
-      HIP_OK(mem_.pinned(&sl.h_fb, 4, hipHostMallocMapped, &sl.d_fb));
-      for (int i = 0; i < 4; i++) sl.h_fb[i] = 0;
+      const int nfb = cfg.fb_anchor ? 8 : 4;
+      HIP_OK(mem_.pinned(&sl.h_fb, nfb, hipHostMallocMapped, &sl.d_fb));
+      for (int i = 0; i < nfb; i++) sl.h_fb[i] = 0;
     }
     if (cfg.scenecut) {
       HIP_OK(mem_.pinned(&sl.h_sc, 5, hipHostMallocMapped, &sl.d_sc));
@@ -253,6 +265,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   if (cfg.loss_feedback) {                                 // (encoder.h fb_rec_mv_)
     HIP_OK(mem_.dev(&fb_rec_mv_, (size_t)cfg.loss_feedback * L.nb8 * 2, true)); HIP_OK(mem_.dev(&fb_rec_info_, (size_t)cfg.loss_feedback * L.nb8, true));
     HIP_OK(mem_.event(&ev_fb_me_, kDeviceEvent));
+    if (cfg.fb_anchor) fb_rec_anchor_.assign((size_t)cfg.loss_feedback, -1);
     HIP_OK(mem_.dev(&fb_map_, L.nb8, true)); HIP_OK(mem_.dev(&fb_tmp_, L.nb8, true)); HIP_OK(mem_.dev(&fb_blk_, L.nb8 / 16 * 2, true));
   }
   me_ahead_ = cfg.me_source != 0;
@@ -306,6 +319,7 @@ bool Encoder::init(const EncoderConfig &cfg_in, std::string *error)
   sp_.lp_refs = cfg.lp_refs > 1 ? cfg.lp_refs : 0;
   sp_.tmvp = cfg.tmvp;
   sp_.weightp = cfg.weightp;
+  sp_.fb_anchor = cfg.fb_anchor;
   sp_.deblock = cfg.deblock; sp_.fps_num = cfg.fps_num; sp_.fps_den = cfg.fps_den;
   HIP_OK(hipStreamSynchronize(stream_));
   HIP_OK(hipDeviceSynchronize());
@@ -649,8 +663,19 @@ Encoder::Plan Encoder::plan(int set)
     // and still reads the previous input picture; no other picture changes its place
     std::lock_guard<std::mutex> l(fbm_);
     fb_heal_.clear();
-    if (p.intra) fb_q_.clear();
-    else if (!fb_q_.empty()) { fb_heal_.swap(fb_q_); p.fb = true; p.ahead = false; }
+    if (p.intra) { fb_q_.clear(); fb_clean_ = 0; }
+    else if (!fb_q_.empty()) {
+      fb_heal_.swap(fb_q_); p.fb = true; p.ahead = false;
+      // fb-anchor: the picture before the oldest reported one is the anchor when it is kept and not in front of the clean point (fb_anchor_pick) -- the heal
+      // picture's references are then the previous picture and the anchor; otherwise it is v1's heal picture in every decision
+      if (cfg_.fb_anchor) {
+        int n0 = poc_;
+        for (const FbReport &r : fb_heal_) n0 = r.poc < n0 ? r.poc : n0;
+        const int a = fb_anchor_pick(fb_clean_, n0, poc_, cfg_.fb_anchor, cfg_.loss_feedback);
+        if (a >= 0) { p.fb_da = poc_ - a; p.nref = 2; p.dist[0] = 1; p.dist[1] = (int8_t)p.fb_da; }
+      }
+      fb_clean_ = poc_;
+    }
   }
   // the stream this picture's chain runs on: an intra picture's own (encoder.h stream_idr_), else the main stream -- behind the last intra picture's chain
   p.side = p.intra && (idr_side_ || (all_intra_alt_ && (frame_idx_ & 1)));
@@ -669,7 +694,7 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   f.cu_log2 = cu; f.cu_intra = cu + lay_.cu_off(1); f.cu_flags = cu + lay_.cu_off(2); f.cu_merge_idx = cu + lay_.cu_off(3);
   f.cu_mvp_idx = cu + lay_.cu_off(4); f.cu_intra_mode = cu + lay_.cu_off(5); f.cu_cbf = cu + lay_.cu_off(6);
   f.cu_mv = cu_mv_[k]; f.cu_mvd = cu_mvd_[k];
-  f.cu_ref = cu_ref_[k];                              // NULL with one reference
+  f.cu_ref = cfg_.fb_anchor && !p.fb_da ? nullptr : cu_ref_[k];      // NULL with one reference (fb-anchor: every picture but a v2 heal picture)
   f.sao = sao_[k];                                    // NULL without SAO
   f.ctu_qt = ctu_qt_[k]; f.ctu_qy = ctu_qy_[k]; f.ctu_delta = ctu_delta_[k]; f.ctu_first = ctu_first_[k];     // all NULL without qp_in_cu
   f.qp = p.qp; f.qpc = kChromaQp[p.qp]; f.lambda_q4 = kLambdaQ4[p.qp];
@@ -686,10 +711,10 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
     for (int r = 0; r < KVZ_MAX_LP_REFS; r++) {
       const int back = r < f.nref ? p.dist[r] : 1, slot = (cur_idx_ + nrec_ - back) % nrec_;
       for (int c = 0; c < 3; c++) f.refs[r][c] = rec_[slot][c];
-      f.me_refs[r] = p.ahead ? src_[(k + kSets - back) % kSets][0] : f.refs[r][0];
+      f.me_refs[r] = p.ahead || (p.fb_da && me_ahead_) ? src_[(k + kSets - back) % kSets][0] : f.refs[r][0];      // (a v2 heal picture is not ahead and searches the input pictures all the same)
     }
   }
-  if (gop_on() && !p.intra) f.ref_dist = (uint32_t)(uint8_t)p.dist[0] | (uint32_t)(uint8_t)p.dist[1] << 8 | (uint32_t)(uint8_t)p.dist[2] << 16 | (uint32_t)(uint8_t)p.dist[3] << 24;
+  if ((gop_on() && !p.intra) || p.fb_da) f.ref_dist = (uint32_t)(uint8_t)p.dist[0] | (uint32_t)(uint8_t)p.dist[1] << 8 | (uint32_t)(uint8_t)p.dist[2] << 16 | (uint32_t)(uint8_t)p.dist[3] << 24;
   // tmvp: the previous picture -- set k - 1 -- filed its record on the tokenizer's stream, where this picture's k_inter_signal reads it; right after the IDR
   // picture (which files none) the slice says slice_temporal_mvp_enabled_flag = 0 (hevc_headers.h slice_tmvp) and nothing is read
   // me-coarse: the quarter picture of this set's input and of the sets that hold input pictures t - p.dist[r] (written on the input stream, where the coarse stage
@@ -702,7 +727,7 @@ EncFrame Encoder::picture_frame(const Plan &p, const Slot &sl, uint32_t chain_ge
   if (p.ir_e) { f.ir_j = p.ir_j; f.ir_s = p.ir_s; f.ir_e = p.ir_e; f.ir_free = ir_free_ ? 1 : 0; }      // intra-refresh: the picture's band
   if (p.fb) {                                          // loss-feedback: a heal picture -- its block records; intra-in-p = 0: the intra-in-P stages for the forced quarters alone
     f.fb_heal = 1; f.fb_blk = fb_blk_; f.ir_free = cfg_.intra_in_p ? 1 : 0;
-    if (!cfg_.intra_in_p) { f.intra_p = 1; point_me_block(f, lay_, me_cost16_); }
+    if (!cfg_.intra_in_p && !p.fb_da) { f.intra_p = 1; point_me_block(f, lay_, me_cost16_); }      // (a v2 heal picture forces no quarter intra: no intra stage is brought up for it)
   }
   if (wp_rec_[k] && !p.intra) f.wp = wp_rec_[k];       // weightp: the record k_wp_decide writes on the input stream, in front of everything that reads it
   if (col_[k] && !p.intra) { f.col_out = col_[k]; f.col_prev = poc_ >= 2 ? col_[(k + kSets - 1) % kSets] : nullptr; }
@@ -853,6 +878,12 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
     if (f.intra_p && !cfg_.deblock) { HIP_CHECK(hipMemsetAsync(f.me_cand, 0, sizeof(uint32_t), stream_)); HIP_CHECK(hipMemsetAsync(f.sync + rows_ * (cw_ / 64) * 3 + 1, 0, sizeof(uint32_t), stream_)); }      // (k_deblock_tile does it otherwise)
   }
   launch_qp_resolve(f, ms);                                      // per-CTU QP: which CU carries the delta, QpY for deblocking
+  if (cfg_.fb_anchor && !p.fb_da) HIP_CHECK(hipMemsetAsync(cu_ref_[set_], 0, lay_.nb8, ms));      // fb-anchor: one reference -- debug_copy("cu_ref") says so (no kernel of the picture reads the array)
+  if (p.fb_da) {                                                 // fb-anchor: the v2 heal picture's count of quarters on the anchor (the decisions are final)
+    FbRefArgs a{};
+    a.gw = cw_ / 8; a.gh = ch_ / 8; a.cu_intra = f.cu_intra; a.cu_ref = f.cu_ref; a.stat = cur_slot_->d_fb;
+    launch_fb_refs(a, ms);
+  }
   // levels, cbf and motion of the picture are final: the tokenizer's stream may start.  With SAO it waits for the filter anyway (the CTUs' SAO parameters
   // are coded) -- then no event is recorded in the middle of the chain (an event between two kernels of a stream costs the chain ~7 us)
   if (!cfg_.sao) HIP_CHECK(hipEventRecord(ev_signalled_, ms));
@@ -861,11 +892,13 @@ bool Encoder::chain_stage(const EncFrame &f, const Plan &p)
   // loss-feedback: a P picture's record into its place in the ring -- vectors and intra decisions are final.  An IDR picture files none: fb_stage never steps
   // through one (a report from in front of it is void), and its chain may run on the side stream, beside a heal picture that still reads the ring
   if (cfg_.loss_feedback && !p.intra) {
-    FbArgs a{};
+    FbRefArgs a{};
     a.gw = cw_ / 8; a.gh = ch_ / 8; a.cu_mv = f.cu_mv; a.cu_intra = f.cu_intra; a.cu_log2 = f.cu_log2; a.clean = 0;
     const size_t place = (size_t)(frame_idx_ % cfg_.loss_feedback);
     a.rec_mv = fb_rec_mv_ + place * lay_.nb8 * 2; a.rec_info = fb_rec_info_ + place * lay_.nb8;
-    launch_fb_record(a, ms);
+    if (cfg_.fb_anchor) fb_rec_anchor_[place] = p.fb_da ? poc_ - p.fb_da : -1;
+    if (p.fb_da) { a.cu_ref = f.cu_ref; launch_fb_record_ref(a, ms); }      // fb-anchor: a v2 heal picture's record carries the reference bit
+    else launch_fb_record(a, ms);
   }
   // Last reader of this set on the main stream: k_sao reads the source picture for its statistics, deblocking the CU records.
   // Input padding and intra analysis of the next picture with this set (input stream) overwrite both and wait for this event.
@@ -882,7 +915,7 @@ bool Encoder::fb_stage(const EncFrame &f, const Plan &p, Slot &sl)
 {
   (void)p;
   const int H = cfg_.loss_feedback, t = poc_;
-  FbArgs a{};
+  FbRefArgs a{};
   a.gw = cw_ / 8; a.gh = ch_ / 8; a.map = fb_map_; a.tmp = fb_tmp_; a.dilate = cfg_.deblock || cfg_.sao ? 1 : 0;
   a.me_range = f.range; a.blk = fb_blk_; a.stat = sl.d_fb;
   int oldest = t;
@@ -894,7 +927,9 @@ bool Encoder::fb_stage(const EncFrame &f, const Plan &p, Slot &sl)
       if (k > oldest) {
         const size_t place = (size_t)((frame_idx_ - (t - k)) % H);
         a.rec_mv = fb_rec_mv_ + place * lay_.nb8 * 2; a.rec_info = fb_rec_info_ + place * lay_.nb8;
-        launch_fb_step(a, stream_);
+        // fb-anchor: picture k was a v2 heal picture -- its reference-1 cells read its anchor, which is wrong only where the report reaches it
+        if (cfg_.fb_anchor && fb_rec_anchor_[place] >= 0) { a.anchor_bad = oldest <= fb_rec_anchor_[place] ? 1 : 0; launch_fb_step_ref(a, stream_); }
+        else launch_fb_step(a, stream_);
       }
       for (const FbReport &r : fb_heal_) if (r.poc == k) { a.first = r.first; a.count = r.count; launch_fb_seed(a, stream_); }
     }
@@ -992,7 +1027,9 @@ bool Encoder::hand_off(const EncFrame &f, const Plan &p, Slot &sl, int in_ring)
   if (sl_gop_timeline(p)) { char w[12]; snprintf(w, sizeof(w), "g%dq%02dd%d%d%d%d", p.layer, f.qp, p.nref > 0 ? p.dist[0] : 0, p.nref > 1 ? p.dist[1] : 0, p.nref > 2 ? p.dist[2] : 0, p.nref > 3 ? p.dist[3] : 0); tl(w, submitted_); }      // KVAZZUP_AMD_TIMELINE, lp-gop: a P picture's layer, QP and reference distances as a record "g<layer>q<QP>d<four distances, 0 = none>"
   if (sl.h_fb) { sl.h_fb[0] = p.fb ? 1 : 0; sl.h_fb[1] = p.fb ? (int32_t)fb_heal_.size() : 0; if (!p.fb) { sl.h_fb[2] = 0; sl.h_fb[3] = 0; } }      // (a heal picture's counts: k_fb_blocks)
   sl.ir[0] = p.ir_j; sl.ir[1] = p.ir_s; sl.ir[2] = p.ir_e; sl.ir[3] = cfg_.intra_refresh ? ir_cycle(cw_, cfg_.intra_refresh) : 0;
-  sl.layer = p.layer; sl.nref = gop_on() && !p.intra ? p.nref : 0; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) sl.dist[r] = r < sl.nref ? p.dist[r] : 0;
+  sl.layer = p.layer; sl.nref = (gop_on() || cfg_.fb_anchor) && !p.intra ? p.nref : 0; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) sl.dist[r] = r < sl.nref ? p.dist[r] : 0;
+  sl.kept = cfg_.fb_anchor && !p.intra ? fb_anchor_kept(poc_, cfg_.fb_anchor) : 0;      // fb-anchor: every P picture lists the pictures it keeps
+  if (sl.h_fb && cfg_.fb_anchor) { sl.h_fb[4] = p.fb_da ? 1 : 0; sl.h_fb[5] = p.fb_da ? poc_ - p.fb_da : 0; sl.h_fb[6] = p.fb_da; if (!p.fb_da) sl.h_fb[7] = 0; }      // (a v2 heal picture's count: k_fb_refs)
   if (p.intra) {
     sl.write_ps = (intra_count_ == 0) || (cfg_.vps_period > 0 && (intra_count_ % cfg_.vps_period) == 0);
     intra_count_++;
@@ -1064,6 +1101,7 @@ bool Encoder::collect(EncodedPicture *out)
   memcpy(out_ir_, out->ir, sizeof(out_ir_));
   memcpy(out_sc_, out->sc, sizeof(out_sc_));
   memcpy(out_fb_, out->fb, sizeof(out_fb_));
+  memcpy(out_fba_, out->fba, sizeof(out_fba_));
   rc_bytes_[(collected_ - 1) & 7] = (uint32_t)out->au.size();   // (collected_ - 1 = index of this picture)
   return ok;
 }
@@ -1134,10 +1172,11 @@ bool Encoder::finish_slot(Slot &sl, EncodedPicture *out, int worker)
   // ---- access unit assembly (host): parameter sets with IDR pictures, then the slice NAL
   out->valid = true; out->poc = sl.poc; out->qp = sl.qp; out->is_intra = sl.intra; out->bins = bins;
   out->layer = sl.layer; out->nref = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) out->dist[r] = sl.dist[r];
-  PicRefs pr; pr.n = sl.nref; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
+  PicRefs pr; pr.n = sl.nref; pr.kept = sl.kept; for (int r = 0; r < KVZ_MAX_LP_REFS; r++) pr.dist[r] = sl.dist[r];      // lp-gop: the slice headers carry the picture's reference picture set
   memcpy(out->ir, sl.ir, sizeof(out->ir));
   if (sl.h_sc) memcpy(out->sc, sl.h_sc, sizeof(out->sc));      // scenecut: the record, final since the picture was submitted
   if (sl.h_fb) for (int i = 0; i < 4; i++) out->fb[i] = sl.h_fb[i];      // loss-feedback: the record, final with the picture's chain
+  if (sl.h_fb && cfg_.fb_anchor) for (int i = 0; i < 4; i++) out->fba[i] = sl.h_fb[4 + i];
   int recovery = cfg_.intra_refresh && !sl.intra && sl.ir[0] == 0 ? sl.ir[3] - 1 : -1;      // intra-refresh: a cycle's first picture says when the pass is complete
   if (sl.h_fb && sl.h_fb[0]) recovery = 0;                 // loss-feedback: the heal picture is itself the recovery point
   PicWeights pw{};                                         // weightp: the record k_wp_decide left in the slot (final long before the tokens are)
@@ -1336,6 +1375,7 @@ bool Encoder::debug_copy(const char *what, void *dst, size_t bytes)
   if (w == "wp") { if (!cfg_.weightp || bytes > sizeof(out_wp_)) return false; memcpy(dst, out_wp_, bytes); return true; }      // (host values, as the slice headers said them)
   if (w == "scenecut") { if (!cfg_.scenecut || bytes > sizeof(out_sc_)) return false; memcpy(dst, out_sc_, bytes); return true; }      // (host values, as submit() read or wrote them)
   if (w == "fb") { if (!cfg_.loss_feedback || bytes > sizeof(out_fb_)) return false; memcpy(dst, out_fb_, bytes); return true; }      // (host values)
+  if (w == "fb_anchor") { if (!cfg_.fb_anchor || bytes > sizeof(out_fba_)) return false; memcpy(dst, out_fba_, bytes); return true; }      // (host values)
   if (w == "fb_map" && fb_map_) { src = fb_map_; have = lay_.nb8; }      // (the heal picture last submitted: a synchronous copy, behind its kernels)
   if (w == "fb_blk" && fb_blk_) { src = fb_blk_; have = lay_.nb8 / 16 * 2; }
   if (w == "sc_blocks" && sc_blocks_) { src = sc_blocks_; have = lay_.sc_blocks * sizeof(uint32_t); }      // (the picture last examined: its kernels are done, submit() waited for them)

@@ -257,6 +257,32 @@ KVZ_HD void fb_block_record(const uint8_t *d, int gw, int gh, int bx, int by, in
 KVZ_HD int fb_reach(uint8_t code) { return code == KVZ_FB_ZERO_ONLY ? 0 : (int)code; }
 
 // ---------------------------------------------------------------------------------------------
+// "uvgx loss feedback v2" (fb-anchor=K beside loss-feedback=H; statement of record: tests/fb_anchor_model.py).  All integer.  The encoder
+// and every decoder keep the K pictures before the current one; a heal picture whose oldest report names picture n0 predicts the quarters the error may have
+// reached from the ANCHOR a = n0 - 1, the last picture the receiver holds whole, as reference 1 -- where v1 codes them as intra units.
+// ---------------------------------------------------------------------------------------------
+#define KVZ_FB_REF1 0x10       // a record's info byte: the cell's vector refers to reference 1 of its picture (a v2 heal picture's anchor)
+// MaxDpbSize (A.4.2, maxDpbPicBuf 6) of a coded picture of cw x ch samples at the level hevc_headers.h level_idc_for() writes for it (4.1, 5.1, 6.1)
+KVZ_HD int fb_anchor_max_dpb(int cw, int ch)
+{
+  const long long px = (long long)cw * ch, ps = px <= 2228224 ? 2228224 : (px <= 8912896 ? 8912896 : 35651584);
+  return px <= (ps >> 2) ? 16 : (px <= (ps >> 1) ? 12 : (px <= ((3 * ps) >> 2) ? 8 : 6));
+}
+// the anchor's POC for the heal picture t, or -1: v1's heal picture.  c: the POC of the most recent IDR or heal picture (the clean point); n0: the least POC
+// among the pending reports.  The anchor lies at or behind the clean point, within the K kept pictures, and no report is older than the ring of H records
+KVZ_HD int fb_anchor_pick(int c, int n0, int t, int K, int H)
+{
+  const int a = n0 - 1;
+  return (K >= 2 && a >= c && a >= 0 && t - a <= K && t - n0 <= H) ? a : -1;
+}
+// the reference picture set of P picture t: entries (each one picture further back), and whether the entry `back` pictures back is used by the picture --
+// the previous picture, and the anchor da pictures back (da 0: no anchor)
+KVZ_HD int fb_anchor_kept(int t, int K) { return t < K ? t : K; }
+KVZ_HD bool fb_anchor_used(int back, int da) { return back == 1 || (da > 0 && back == da); }
+// step through the record of a picture: is a reference-1 cell in S -- only where the report reaches the anchor of that (v2 heal) picture or further back
+KVZ_HD bool fb_anchor_cell(uint8_t info, int anchor_bad) { return (info & KVZ_FB_REF1) && anchor_bad; }
+
+// ---------------------------------------------------------------------------------------------
 // "uvgx weighted prediction v1" (weightp; restated in tests/wp_model.py).  All integer.
 // ---------------------------------------------------------------------------------------------
 // floor(sqrt(v))

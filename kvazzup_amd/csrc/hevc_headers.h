@@ -39,17 +39,22 @@ struct StreamParams {
   int lp_refs = 0;          // "lp-refs" n >= 2: n short-term RPS sets (set i: pictures -1 .. -(i + 1)), n references by default, DPB of n + 1 pictures; 0 / 1: one reference
   int tmvp = 0;             // sps_temporal_mvp_enabled_flag; the slices: slice_temporal_mvp_enabled_flag (slice_tmvp), collocated_ref_idx 0
   int weightp = 0;          // "weightp" (DESIGN.md section 9e): PPS weighted_pred_flag; every independent P slice segment header carries pred_weight_table() (PicWeights)
+  int fb_anchor = 0;        // "fb-anchor" K >= 2: a DPB of K + 1 pictures; every P slice header carries its own reference picture set (PicRefs with kept > 0), one reference by default
 };
 
 // "lp-gop" (DESIGN.md section 9d): the references of one P picture -- n of them, dist[k] pictures back, by increasing distance (dist[0] = 1).  A slice header
 // given one writes the picture's reference picture set itself (short_term_ref_pic_set_sps_flag 0), all entries used by the current picture, and n active
-// references; the parameter sets are the ones of lp-refs
-struct PicRefs { int n; int8_t dist[4]; };
+// references; the parameter sets are the ones of lp-refs.
+// "fb-anchor" (DESIGN.md section 9j), kept > 0: the set holds the `kept` pictures before this one, each one picture further back; the n references are the
+// entries marked used_by_curr_pic_s0_flag, every other entry is only kept in the decoder's buffer
+struct PicRefs { int n; int8_t dist[4]; int kept = 0; };
 // "weightp": the luma weights of one P picture's references, list 0 order -- flag[k] 0: reference k is predicted from as ever (w 64, o 0)
 struct PicWeights { int8_t flag[4]; int16_t w[4], o[4]; };
 
 // pictures the DPB holds beside the current one: sps/vps_max_dec_pic_buffering_minus1
-inline int dpb_minus1(const StreamParams &s) { return s.lp_refs > 1 ? s.lp_refs : 1; }
+inline int dpb_minus1(const StreamParams &s) { return s.fb_anchor > 1 ? s.fb_anchor : (s.lp_refs > 1 ? s.lp_refs : 1); }
+// references active by default: the PPS's num_ref_idx_l0_default_active_minus1 + 1 (fb-anchor keeps pictures and leaves the default at one)
+inline int default_refs(const StreamParams &s) { return s.lp_refs > 1 ? s.lp_refs : 1; }
 // active references of a P picture `poc` pictures after its IDR picture
 inline int active_refs(const StreamParams &s, int poc) { const int n = s.lp_refs > 1 ? s.lp_refs : 1; return poc < n ? (poc < 1 ? 1 : poc) : n; }
 // slice_temporal_mvp_enabled_flag of the picture `poc` pictures after its IDR picture: 1 but where the collocated picture (ref_idx_l0 0, the previous
@@ -117,7 +122,7 @@ inline void write_pps(BitWriter &w, const StreamParams &s)
 {
   w.ue(0); w.ue(0);
   w.bit(s.slices == 1); w.bit(0); w.put(0, 3); w.bit(s.signhide != 0); w.bit(0);   // dependent_slice_segments_enabled_flag, output_flag_present, extra header bits, sign_data_hiding_enabled_flag, cabac_init_present
-  w.ue((uint32_t)dpb_minus1(s) - 1); w.ue(0);                   // num_ref_idx_l0 / l1_default_active_minus1
+  w.ue((uint32_t)default_refs(s) - 1); w.ue(0);                 // num_ref_idx_l0 / l1_default_active_minus1
   w.se(s.qp - 26);
   w.bit(0); w.bit(0); w.bit(s.qp_in_cu != 0);                    // constrained intra, transform skip, cu_qp_delta
   if (s.qp_in_cu) w.ue(0);                                       // diff_cu_qp_delta_depth
@@ -171,15 +176,19 @@ inline void write_slice_header(BitWriter &w, const StreamParams &s, bool idr, in
       w.put((uint32_t)poc & 255, 8);
       if (refs) {                                                  // st_ref_pic_set(num_short_term_ref_pic_sets) (7.3.7): the SPS carries sets, so the prediction flag is present
         w.bit(0); w.bit(0);                                        // short_term_ref_pic_set_sps_flag, inter_ref_pic_set_prediction_flag
-        w.ue((uint32_t)refs->n); w.ue(0);                          // num_negative_pics, num_positive_pics
-        for (int k = 0; k < refs->n; k++) { w.ue((uint32_t)(refs->dist[k] - (k ? refs->dist[k - 1] : 0) - 1)); w.bit(1); }      // delta_poc_s0_minus1, used_by_curr_pic_s0_flag
+        w.ue((uint32_t)(refs->kept ? refs->kept : refs->n)); w.ue(0);      // num_negative_pics, num_positive_pics
+        if (refs->kept) for (int j = 1; j <= refs->kept; j++) {     // fb-anchor: delta_poc_s0_minus1 0, used where the picture j back is one of the n references
+          bool used = false; for (int k = 0; k < refs->n; k++) used |= refs->dist[k] == j;
+          w.ue(0); w.bit(used);
+        }
+        else for (int k = 0; k < refs->n; k++) { w.ue((uint32_t)(refs->dist[k] - (k ? refs->dist[k - 1] : 0) - 1)); w.bit(1); }      // delta_poc_s0_minus1, used_by_curr_pic_s0_flag
       } else w.bit(1);
       if (!refs && s.lp_refs > 1) { int bits = 0; while ((1 << bits) < s.lp_refs) bits++; w.put((uint32_t)nact - 1, bits); }     // short_term_ref_pic_set_idx
       if (s.tmvp) w.bit(slice_tmvp(s, idr, poc));                  // slice_temporal_mvp_enabled_flag
     }
     if (s.sao) { w.bit(1); w.bit(1); }                             // slice_sao_luma_flag, slice_sao_chroma_flag
     if (!idr) {
-      const int ndef = dpb_minus1(s);
+      const int ndef = default_refs(s);
       w.bit(nact != ndef); if (nact != ndef) w.ue((uint32_t)nact - 1);   // num_ref_idx_active_override_flag (fewer pictures since the IDR picture than lp-refs)
       if (slice_tmvp(s, idr, poc) && nact > 1) w.ue(0);             // collocated_ref_idx: the previous picture (P slice: collocated_from_l0_flag inferred 1)
       if (s.weightp) {                                             // pred_weight_table() (7.3.6.3): denominators 6, chroma never weighted

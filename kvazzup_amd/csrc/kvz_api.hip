@@ -205,6 +205,7 @@ int config_parse(kvz_config *cfg, const char *name, const char *value)
   if (n == "scenecut") { if (!parse_int(value, &iv) || iv < 0 || iv > 255) return 0; cfg->scenecut = iv; return 1; }      // (extension: "uvgx scene cut v1", DESIGN.md section 9g -- an input picture at least N pictures behind the last IDR picture that shares nothing with the picture before it becomes an IDR picture; off by default and at every preset)
   if (n == "intra-refresh") { if (!parse_int(value, &iv) || (iv != 0 && (iv < 2 || iv > 255))) return 0; cfg->intra_refresh = iv; return 1; }      // (extension: "uvgx intra refresh v1", DESIGN.md section 9f -- a band of intra units walks across the P pictures, N pictures a pass at most; off by default and at every preset)
   if (n == "loss-feedback") { if (!parse_int(value, &iv) || iv < 0 || iv > 64) return 0; cfg->loss_feedback = iv; return 1; }      // (extension: "uvgx loss feedback v1", DESIGN.md section 9i -- H pictures of motion records, so that kvzx_encoder_report_damage can heal a reported loss in the next picture; off by default and at every preset)
+  if (n == "fb-anchor") { if (!parse_int(value, &iv) || (iv != 0 && (iv < 2 || iv > 7))) return 0; cfg->fb_anchor = iv; return 1; }      // (extension: "uvgx loss feedback v2", DESIGN.md section 9j -- K kept pictures, so that a heal picture can predict the damaged quarters from the last picture the receiver holds whole; off by default and at every preset)
   if (n == "input-format") {                     // (extension, DESIGN.md section 9h: packed RGB32 / YUYV pictures converted in the encoder's input stage; i420 by default and at every preset)
     static const char *formats[] = {"i420", "rgb32", "rgb32-sse41", "yuyv"};
     for (int i = 0; i < 4; i++) if (!strcmp(value, formats[i])) { cfg->input_format = i; return 1; }
@@ -372,6 +373,7 @@ kvz_encoder *encoder_open(const kvz_config *cfg)
   ec.scenecut = cfg->scenecut;
   ec.input_format = cfg->input_format;
   ec.loss_feedback = cfg->loss_feedback;
+  ec.fb_anchor = cfg->fb_anchor;
   ec.hash = cfg->hash == KVZ_HASH_MD5 ? 2 : (cfg->hash == KVZ_HASH_CHECKSUM ? 1 : 0);
   ec.vaq = cfg->vaq > 0 ? cfg->vaq : 0;
   ec.qp_in_cu = (cfg->set_qp_in_cu || ec.vaq > 0) ? 1 : 0;

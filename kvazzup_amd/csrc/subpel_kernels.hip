@@ -161,7 +161,9 @@ __device__ __forceinline__ bool allowed(const EncFrame &f, int x0, int y0, int n
 // ir_mvx_max is dropped, next to the mv_frame test; the centre is k_me's vector, which kept the bound.  Forms of their own as well.
 // FB (loss-feedback): in a heal picture a candidate with a component beyond four times the block's reach (f.fb_blk, quarter samples) is
 // dropped; the centre is k_me<.., FB>'s vector, which kept the reach in full samples.  Forms of their own as well.
-template <bool WP, bool IR = false, bool FB = false>
+// FA (fb-anchor; beside FB): a v2 heal picture -- the quadrant whose bit of the record's nibble is set refers to the anchor (reference 1)
+// and is refined without a bound; the others keep the reach.  A form of its own as well.
+template <bool WP, bool IR = false, bool FB = false, bool FA = false>
 __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
 {
   __shared__ SubpelLds s;
@@ -199,6 +201,7 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
   if constexpr (IR) { if (ir_clean_block(x0, f.ir_s, f.ir_j)) ir_max = ir_mvx_max(x0, f.ir_s); }
   int fb_q = 0x7fffffff;
   if constexpr (FB) fb_q = 4 * fb_reach(f.fb_blk[2 * ((size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5)) + 1]);
+  if constexpr (FA) { if ((f.fb_blk[2 * ((size_t)(y0 >> 5) * (f.cw >> 5) + (x0 >> 5))] >> w) & 1) fb_q = 0x7fffffff; }      // (an unsplit block's nibble is 0 or 15: its four waves agree)
   uint8_t *win = s.win[w];
   {
     // the 24 x 24 window (both waves of the quadrant load half of it): six dwords per row when it lies inside the picture (any
@@ -286,7 +289,8 @@ __global__ __launch_bounds__(512) void k_subpel(EncFrame f)
 
 void launch_subpel(const EncFrame &f, hipStream_t st)
 {
-  if (f.fb_heal) {                                           // loss-feedback: a heal picture
+  if (f.fb_heal && f.cu_ref) hipLaunchKernelGGL((k_subpel<false, false, true, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);      // fb-anchor: a v2 heal picture (the encoder refuses weightp beside it)
+  else if (f.fb_heal) {                                      // loss-feedback: a heal picture
     if (f.wp) hipLaunchKernelGGL((k_subpel<true, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
     else hipLaunchKernelGGL((k_subpel<false, false, true>), dim3(f.cw / 32, band_rows(f) * 2), dim3(512), 0, st, f);
   }

@@ -11,7 +11,11 @@ ultrafast and veryfast (slices=wpp, qp 32, me-range 16), the benchmark's synthet
   times    owf 0 with profiling on: the kernel times per picture kind (the record writer rides behind every chain; the map kernels run on heal pictures only and
            are read from a kernel-trace run of `--trace PRESET`, which encodes the heal clip once and nothing else)
 
-usage: python tools/measure/loss_feedback_ab.py [out.txt] [--pictures N]      (one JSON object per line, also appended to out.txt)"""
+With `--anchor K` the same case for fb-anchor=K ("uvgx loss feedback v2") and nothing else: the v2 heal picture and its run beside v1's,
+the never-told and the IDR one; the heal picture's kernel times beside v1's; pictures/s with the option on and no report against loss-feedback alone; and the
+memory the kept pictures take.
+
+usage: python tools/measure/loss_feedback_ab.py [out.txt] [--pictures N] [--anchor K]      (one JSON object per line, also appended to out.txt)"""
 import json
 import os
 import sys
@@ -29,6 +33,11 @@ NF = 64
 if "--pictures" in ARGV:
     i = ARGV.index("--pictures")
     NF = int(ARGV[i + 1])
+    del ARGV[i:i + 2]
+ANCHOR = 0
+if "--anchor" in ARGV:
+    i = ARGV.index("--anchor")
+    ANCHOR = int(ARGV[i + 1])
     del ARGV[i:i + 2]
 ARGS = [a for a in ARGV if not a.startswith("--")]
 OUT = ARGS[0] if ARGS and "--trace" not in ARGV else None
@@ -55,7 +64,7 @@ def psnr(a, b):
 
 
 def encode(frames, preset, extra, report=None):
-    """[(bytes, luma PSNR)] per picture, the heal picture's record"""
+    """[(bytes, luma PSNR)] per picture, the heal picture's record (fb-anchor: and its anchor record behind it)"""
     e = Encoder(W, H, options=opts(preset, 0, extra))
     assert not e.rejected, e.rejected
     out, fb = [], None
@@ -66,8 +75,56 @@ def encode(frames, preset, extra, report=None):
         out.append((len(au), psnr(rec, f)))
         if report and t == HEAL:
             fb = [int(v) for v in e.debug("fb", np.int32, (4,))]
+            if dict(extra).get("fb-anchor"):
+                fb += [int(v) for v in e.debug("fb_anchor", np.int32, (4,))]
     e.close()
     return out, fb
+
+
+def run_psnr(pics):
+    return round(sum(p for _, p in pics) / len(pics), 2)
+
+
+def anchor_heal(frames, preset):
+    """fb-anchor: the one-CTU-row case, v2 against v1, never told and IDR"""
+    report = (LOST, 8 * WC, (HC - 8) * WC)
+    plain, _ = encode(frames, preset, ())
+    idr, _ = encode(frames, preset, (("period", HEAL),))
+    v1, fb1 = encode(frames, preset, (("loss-feedback", HIST),), report)
+    v2, fb2 = encode(frames, preset, (("loss-feedback", HIST), ("fb-anchor", ANCHOR)), report)
+    row = lambda pics: {"heal_picture_bytes": pics[HEAL][0], "heal_picture_psnr_y": pics[HEAL][1], "run_bytes": sum(b for b, _ in pics), "run_psnr_y": run_psnr(pics)}
+    emit({"measure": "anchor heal", "preset": preset, "fb-anchor": ANCHOR, "report": list(report), "v2": row(v2), "v1": row(v1), "never_told": row(plain), "idr_at_heal": row(idr),
+          "v2_record": dict(zip(("heal", "reports", "cells", "forced_quarters", "v2", "anchor", "da", "quarters_on_the_anchor"), fb2)), "v1_forced_quarters": fb1[3], "quarters": (WC * 4) * (HC * 4)})
+
+
+def anchor_times(frames, preset):
+    for name, extra in (("v1", (("loss-feedback", HIST),)), ("v2", (("loss-feedback", HIST), ("fb-anchor", ANCHOR)))):
+        e = Encoder(W, H, options=opts(preset, 0, extra))
+        e.set_profiling(1)
+        for t, f in enumerate(frames[:HEAL + 1]):
+            if t == HEAL:
+                assert e.report_damage(LOST, 8 * WC, (HC - 8) * WC) == 1
+                e.kernel_times(reset=True)
+            e.encode(f, want_recon=False)
+        emit({"measure": "anchor times", "preset": preset, "picture": "heal, " + name, "ms": {k: round(v[0], 4) for k, v in e.kernel_times(reset=True).items() if v[1]}})
+        e.close()
+
+
+def anchor_rate(dev, preset):
+    for name, extra in (("loss-feedback alone", (("loss-feedback", HIST),)), ("fb-anchor=%d, no report" % ANCHOR, (("loss-feedback", HIST), ("fb-anchor", ANCHOR)))):
+        e = Encoder(W, H, options=opts(preset, 2, (("input-hold", 1),) + extra))
+        assert not e.rejected, e.rejected
+        best = 0.0
+        for rep in range(4):                             # (the first pass warms up)
+            t0 = time.perf_counter()
+            for d in dev:
+                e.encode_device(d)
+            for _ in range(3):
+                e.encode_device(None)
+            if rep:
+                best = max(best, len(dev) / (time.perf_counter() - t0))
+        e.close()
+        emit({"measure": "anchor rate", "preset": preset, "config": name, "pictures_per_s": round(best, 1)})
 
 
 def heal(frames, preset):
@@ -138,6 +195,15 @@ def main():
     frames = [orc.synth_frame(0, 0x5EED0000, W, H, t) for t in range(NF)]
     if "--trace" in ARGV:
         encode(frames[:32], ARGV[ARGV.index("--trace") + 1], (("loss-feedback", HIST),), (LOST, 8 * WC, WC))
+        return
+    if ANCHOR:
+        cw, ch = WC * 64, HC * 64
+        emit({"measure": "anchor memory", "fb-anchor": ANCHOR, "kept_reconstructions_bytes": (ANCHOR - 1) * cw * ch * 3 // 2, "cu_ref_bytes": 8 * (cw // 8) * (ch // 8)})
+        dev = upload(frames)
+        for preset in ("ultrafast", "veryfast"):
+            anchor_heal(frames, preset)
+            anchor_times(frames, preset)
+            anchor_rate(dev, preset)
         return
     dev = upload(frames)
     for preset in ("ultrafast", "veryfast"):
